@@ -26,7 +26,11 @@ max_iter sweeps per level whether they ran or not and is quoted beside it, never
 path; the only exchanges are one RCCL broadcast of the parameter block and one all-gather of
 two scalars per rank for the report.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the line (roofline figures from the timed steps and the
+committed profiles).  --full adds what takes runs of its own: scale_reference, the extras (the other stopping rule and
+arithmetic, batched, temporal, sync, compositor stages, config[3] and config[4] on one GPU) and cpu_baseline with its
+bit-for-bit parity check.  --dump-outputs DIR writes what the last timed step computed (dump_outputs).
 With N > 1 and no torch.distributed environment the script starts its N ranks itself (as
 child processes, before anything touches the GPU); under
 `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...` it is one rank.
@@ -128,6 +132,14 @@ def parse_args(argv=None):
                     help="config 2 on ONE GPU: solve the shard rank K of an --of G-rank job would get (static partition "
                          "study: per-rank load without the G GPUs)")
     ap.add_argument("--of", type=int, default=8)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: scale_reference, the extras (other semantics, "
+                         "arithmetic, sizes, stages and configurations) and the cpu_baseline leg with its parity check; "
+                         "--no-extras, --no-scale-ref, --no-cpu-baseline and --extras select among them")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / "
+                         "float64, at most 64 MB in all: a fixed, seeded sample of a larger output); rank k > 0 of an "
+                         "N > 1 run writes <name>_rank<k>.npy")
     return ap.parse_args(argv)
 
 
@@ -328,12 +340,22 @@ def main():
     # cause -- profiles/r05_scale_ref_bisect.txt: the TEMPORAL extra, and in it the video lanes' graded stream priorities: their
     # low-priority streams took hardware queues the runtime never handed back, so two of the job's three streams then shared
     # one.  Fixed in vm_video.cpp (the lanes run on plain streams); the order no longer matters: 836 ms either way.)
+    if args.dump_outputs:
+        # what a caller of vm_solve / vm_solve_batch receives from the last timed step: every pair's full-resolution halfway
+        # field and the sweeps each level executed (the timing fields of vm_progress are not outputs)
+        last = step_sets[-1]
+        dump_outputs(args.dump_outputs, {"v": np.stack([p[1].v for p in last]),
+                                         "iters_executed_per_level": np.array([[pr[i].iters_live for i in range(nlev - 1)]
+                                                                               for pr in progs[len(progs) - len(last):]], np.float64)},
+                     rank if world > 1 else None)
+
+    # everything below the headline (other workloads, configurations, the CPU leg) runs only with --full
     extras = {}
     scale_ref = None
-    want_scale_ref = rank == 0 and world == 1 and config == 1 and not args.size and not (args.no_extras or args.no_scale_ref)
+    want_scale_ref = args.full and rank == 0 and world == 1 and config == 1 and not args.size and not (args.no_extras or args.no_scale_ref)
     if want_scale_ref and not args.scale_ref_last:
         scale_ref = scale_reference(args, morph, blk, local_rank, frames, solve_group, sizes, nlev, FIXED)
-    if rank == 0 and not (args.no_extras or args.no_extras_but_scale_ref) and config != 2:
+    if args.full and rank == 0 and not (args.no_extras or args.no_extras_but_scale_ref) and config != 2:
         extras = run_extras(args, np, capi, morph, synth, L, blk, ctx, pyrs[0], w, h, nlev, FIXED, B, solve, solve_group, local_rank, frames)
     if want_scale_ref and args.scale_ref_last:
         scale_ref = scale_reference(args, morph, blk, local_rank, frames, solve_group, sizes, nlev, FIXED)
@@ -341,7 +363,7 @@ def main():
         extras["scale_reference"] = scale_ref
 
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not args.no_cpu_baseline:
         cpu = cpu_baseline(np, capi, L, blk, [p for p in pyrs[:3] if p._ctx is ctx], nlev, ctx)
 
     if rank == 0:
@@ -389,6 +411,11 @@ def config4_main(args, np, torch, dist, vdist, capi, morph, synth, blk, cons, ra
         runs = [job.step(group) for _ in range(args.steps)] if mine else []
         el = time.perf_counter() - t0
         barrier()
+        if args.dump_outputs and runs:
+            # the solve stage's result of the last timed step (every pair's halfway field) and the compositor's PCG
+            # iteration counts; the rendered frames stay on the device in the timed path
+            dump_outputs(args.dump_outputs, {"v": np.stack([q[1].v for q in group]), "pcg_iterations": np.array(runs[-1]["its"], np.float64)},
+                         rank if world > 1 else None)
         if args.digest and mine:       # one more, untimed step whose frames and fields are fingerprinted (tests)
             got = {}
             job.step(group, collect=got)
@@ -1463,6 +1490,42 @@ def sync_stage_extra(np, morph, ctx, w, h, d, blk):
     out["resample_ms_per_frame_both_videos"] = round(float(np.median(ms[1:])), 3)
     pyr.clear()
     return out
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SEED = 20240601
+
+
+def dump_plan(arrays, max_bytes=DUMP_MAX_BYTES):
+    """`--dump-outputs`: name -> array as written.  Floating arrays stay float32 / go to float64, anything else becomes
+    float64.  If everything together exceeds max_bytes, every array of more than 2^20 elements is replaced by
+    `<name>_sample`, a fixed, seeded sample of its flattened elements (the same positions for the same shape in every run),
+    with `<name>_sample_index` (float64 flat indices) beside it; the sample sizes are chosen so that the total fits."""
+    import numpy as np
+    conv = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        conv[name] = a.astype(np.float32 if a.dtype == np.float32 else np.float64, copy=False)
+    if sum(a.nbytes for a in conv.values()) <= max_bytes:
+        return conv
+    big = [n for n, a in conv.items() if a.size > (1 << 20)]
+    rest = sum(a.nbytes for n, a in conv.items() if n not in big)
+    frac = max(max_bytes - rest, 0) / float(sum(conv[n].size * (conv[n].itemsize + 8) for n in big))
+    out = {n: a for n, a in conv.items() if n not in big}
+    for n in big:
+        a = conv[n].ravel()
+        k = int(a.size * frac)
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, size=k, replace=False))
+        out[n + "_sample"] = a[idx]
+        out[n + "_sample_index"] = idx.astype(np.float64)
+    return out
+
+
+def dump_outputs(path, arrays, rank=None):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in dump_plan(arrays).items():
+        np.save(os.path.join(path, name + ("_rank%d" % rank if rank else "") + ".npy"), a)
 
 
 def effective_cpus():

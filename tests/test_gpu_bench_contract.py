@@ -15,7 +15,7 @@ SIZES = [(1920, 1080), (960, 540), (480, 270), (240, 135), (120, 68)]
 
 
 def test_bench_json_line():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-extras"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--no-extras"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -80,10 +80,37 @@ def test_bench_json_line():
     assert (d["ms_cycling_steps"] is None) == (n_cyc == 0) and (d["ms_converging_steps"] is None) == (n_cyc == 2)
 
 
+def test_bench_plain_line_is_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """a plain run (no --full) times the steps and prints the headline keys -- nothing that takes runs of its own --,
+    and --dump-outputs writes what its last timed step computed: the same arrays from two runs with the same arguments"""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        out = tmp_path / ("out%d" % k)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "0",
+                            "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        d = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline", "cpu_baseline"):
+            assert key in d, key
+        assert d["steps"] == 2 and d["warmup"] == 0 and d["unit"] == "Mpixel*iters/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert d["cpu_baseline"] is None and "scale_reference" not in d and "config3_4k" not in d and "pipeline_config4_30_frames" not in d
+        assert len(d["step_ms"]["each"]) == 2 and d["config"]["frame_ids"] == [0, 1]
+        assert abs(d["value"] * 1e6 * d["ms_per_step"] * 1e-3 * d["steps"] / d["executed_pixel_iters"] - 1.0) < 0.01
+        v, its = np.load(str(out / "v.npy")), np.load(str(out / "iters_executed_per_level.npy"))
+        assert v.dtype == np.float32 and v.shape == (1, 1080, 1920, 2) and np.isfinite(v).all() and np.abs(v).max() > 0
+        assert its.dtype == np.float64 and its.shape == (1, 5) and (its >= 1).all() and (its <= 500).all()
+        assert sum(f.stat().st_size for f in out.iterdir()) <= 64 << 20
+        dumps.append((v, its))
+    assert np.array_equal(dumps[0][0], dumps[1][0]) and np.array_equal(dumps[0][1], dumps[1][1])
+
+
 def test_bench_scale_reference_in_the_n1_line():
-    """the N = 1 line carries config[2]'s job -- what an N > 1 run shards -- on this one GPU (here: 6 pairs)"""
+    """the N = 1 line of `--full` carries config[2]'s job -- what an N > 1 run shards -- on this one GPU (here: 6 pairs)"""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0", "--no-cpu-baseline",
-                        "--no-extras-but-scale-ref", "--scale-ref-pairs", "6"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "--full", "--no-extras-but-scale-ref", "--scale-ref-pairs", "6"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.strip().startswith("{")][-1])
     sr = d["scale_reference"]
@@ -97,11 +124,11 @@ def test_bench_scale_reference_in_the_n1_line():
 
 
 def test_bench_extras_of_round_5():
-    """the driver's default line carries config[3] in one step, config[4] as stated (30 frames: solve with constraints,
+    """the `--full` line carries config[3] in one step, config[4] as stated (30 frames: solve with constraints,
     batched Poisson extension, render; round 6: three runs, fastest + median) with Metric 2 both ways, and the Poisson
     extension's own figures at the fixture-verified tolerances; here with the development switch that runs only those extras"""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0", "--no-cpu-baseline",
-                        "--no-scale-ref", "--extras", "render,poisson,pipeline30,config3"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                        "--full", "--no-scale-ref", "--extras", "render,poisson,pipeline30,config3"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.strip().startswith("{")][-1])
     c3 = d["config3_4k"]

@@ -239,3 +239,28 @@ def test_bench_times_the_poisson_stage_only_at_verified_tolerances():
     import re
     lits = re.findall(r"poisson_extend\w*\([^)]*tol=([0-9.e-]+)", src)
     assert set(lits) <= {"1e-3"}, lits
+
+
+def test_bench_options_plain_run_and_output_dump(tmp_path):
+    """a plain bench run measures the headline only (--full is off by default); --dump-outputs keeps floats in float32 /
+    float64, turns counts into float64, and past 64 MB writes a fixed, seeded sample of each large output with its flat
+    indices -- the same positions in every run"""
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and a.full is False and a.dump_outputs == ""
+    a = bench.parse_args(["--full", "--dump-outputs", str(tmp_path)])
+    assert a.full is True and a.dump_outputs == str(tmp_path)
+    small = {"v": np.ones((2, 3, 2), np.float32), "iters": np.arange(4)}
+    plan = bench.dump_plan(small)
+    assert set(plan) == {"v", "iters"} and plan["v"].dtype == np.float32 and plan["iters"].dtype == np.float64
+    big = np.random.default_rng(5).random((3, 1 << 20)).astype(np.float32)       # 12 MB, over a 4 MB limit
+    plan = bench.dump_plan({"v": big, "iters": np.arange(5)}, max_bytes=4 << 20)
+    assert set(plan) == {"v_sample", "v_sample_index", "iters"}
+    assert sum(x.nbytes for x in plan.values()) <= 4 << 20 and plan["v_sample"].size > 250000
+    idx = plan["v_sample_index"].astype(np.int64)
+    assert np.array_equal(big.ravel()[idx], plan["v_sample"]) and (np.diff(idx) > 0).all()
+    again = bench.dump_plan({"v": big * 2, "iters": np.arange(5)}, max_bytes=4 << 20)
+    assert np.array_equal(again["v_sample_index"], plan["v_sample_index"])
+    bench.dump_outputs(str(tmp_path / "d"), small)
+    bench.dump_outputs(str(tmp_path / "d"), small, rank=1)
+    assert sorted(os.listdir(str(tmp_path / "d"))) == ["iters.npy", "iters_rank1.npy", "v.npy", "v_rank1.npy"]
+    assert np.load(str(tmp_path / "d" / "v.npy")).dtype == np.float32

@@ -40,7 +40,7 @@ for w in n1:"$Q1" b8:"$Q2" c2:"$Q3"; do
 done
 find $O -name "*counter_collection.csv" -delete; find $O -name "*kernel_trace.csv" -delete
 if [ -z "$PMC_ONLY" ]; then
-timeout 600 python3 bench.py --config 3 --steps 3 --warmup 1 --no-extras > $O/config3_bench.json 2> $O/config3.err; echo "config3 rc=$?"
+timeout 600 python3 bench.py --config 3 --steps 3 --warmup 1 --full --no-extras > $O/config3_bench.json 2> $O/config3.err; echo "config3 rc=$?"
 timeout 600 python3 bench.py --config 2 --pairs 60 --gpus 1 --steps 2 --warmup 1 --no-extras --no-cpu-baseline > $O/config2_1gpu_bench.json 2> $O/config2.err; echo "config2 rc=$?"
 fi
 ls $O; du -sh $O
