@@ -99,3 +99,20 @@ def test_product_never_touches_the_oracle():
     assert not bad, bad
     out = subprocess.run(["ldd", capi.LIB_PATH], capture_output=True, text=True).stdout
     assert "oracle" not in out
+
+
+def test_device_memory_and_events_have_owners():
+    """the host code allocates, frees, creates and destroys through the owners of csrc/vm_devmem.h only: no raw
+    hipMalloc / hipFree / hipEventCreate / ... anywhere else under csrc/ (hipHostRegister pins the caller's memory,
+    not ours, and is not one of them)"""
+    csrc = os.path.join(ROOT, "videomorphing_amd", "csrc")
+    raw = re.compile(r"\b(hipMalloc|hipHostMalloc|hipFree|hipHostFree|hipEventCreate|hipEventCreateWithFlags|hipEventDestroy)\b")
+    bad = []
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".cpp", ".h")) or f == "vm_devmem.h":
+            continue
+        txt = open(os.path.join(csrc, f), errors="replace").read()
+        txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+        txt = re.sub(r"//[^\n]*", "", txt)
+        bad += ["%s: %s" % (f, m.group(1)) for m in raw.finditer(txt)]
+    assert not bad, bad

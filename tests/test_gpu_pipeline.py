@@ -415,3 +415,64 @@ def test_streams_overlap_probe_and_context_beside(gpu_ctx):
             gpu_ctx.runs_beside(gpu_ctx)
     finally:
         c1.close()
+
+
+def _touched(kind, ctx):
+    """an object of the given kind on ctx, used so that the buffers it makes on first use exist too; returns it and
+    its destroy function"""
+    if kind == "pyramid":                      # the sweeps make the levels' schedule workspaces
+        i0, i1 = synth.make_pair(192, 120)
+        pyr = morph.Pyramid(ctx)
+        pyr.build(i0, i1, 32)
+        morph.solve_batch([pyr], 8, 1.0)
+        return pyr, pyr.clear
+    if kind == "video":                        # the pipelined solve makes the lanes (contexts + accumulators)
+        levels = [(96, 64, 5), (48, 32, 5), (24, 16, 5), (12, 8, 5)]
+        vid = morph.VideoPyramid(ctx)
+        vid.build_levels(levels)
+        for t in range(5):
+            pyr = synth.build_pyramid(*synth.make_pair(96, 64, frame=t), len(levels))
+            for l in range(len(levels) - 1):
+                vid.upload_luma(l, t, *pyr[l])
+        capi.check(vid._L.vm_video_solve(vid._h, 4.0, 1.0, None, 0, None, 0, None))
+        return vid, vid.clear
+    if kind == "frame":                        # the extension makes the solver workspace
+        w, h, ex = 320, 200, 24
+        e0, e1, v = _frame_pair(w, h, ex, 3)
+        fr = morph.Frame(ctx, w, h, ex)
+        fr.upload(e0, e1, v, None)
+        fr.poisson_extend(1)
+        return fr, fr.close
+    w, h, d = 1920, 1080, 16                   # sync: the renderer's videos and flows, about 0.8 GB
+    syn = morph.SyncPyramid(ctx)
+    syn.build_levels(morph.sync_level_table(w, h, d, 8))
+    rgba, flow = np.zeros((h, w, 4), np.uint8), np.zeros((h, w, 2), np.float32)
+    for side in (0, 1):
+        for t in range(d):
+            syn.upload_frame(side, t, rgba)
+            syn.upload_flow(side, t, flow)
+    return syn, syn.clear
+
+
+def _device_free_bytes(vmlib):
+    """hipMemGetInfo of device 0 through the HIP runtime the product library is bound to: looked up through the
+    library's own handle, so that another runtime in the process (torch's) is neither asked nor initialised"""
+    import ctypes as C
+    free, total = C.c_size_t(0), C.c_size_t(0)
+    assert vmlib.hipSetDevice(0) == 0 and vmlib.hipMemGetInfo(C.byref(free), C.byref(total)) == 0
+    return free.value
+
+
+@pytest.mark.parametrize("kind", ["pyramid", "video", "frame", "sync"])
+def test_objects_destroyed_after_their_context_free_their_memory(vmlib, gpu_ctx, kind):
+    """a garbage-collected host may destroy a context before the objects made on it: the object's destroy then drains
+    the device and frees its buffers without the context -- no error, and no device memory left behind over repeated
+    rounds (the device's free memory counts every process on it, hence the wide margin)"""
+    free0 = _device_free_bytes(vmlib)
+    for _ in range(4):
+        ctx = morph.Context(0, capi.MATH_FAST)
+        _, destroy = _touched(kind, ctx)
+        ctx.close()
+        destroy()
+    free1 = _device_free_bytes(vmlib)
+    assert free1 > free0 - (1 << 30), (kind, (free0 - free1) / 2 ** 30)

@@ -138,12 +138,12 @@ static void build_tables(uint32_t *tab)
 // ---------------------------------------------------------------------------
 static void ctx_free(vm_ctx *c);
 
-// Live contexts.  Destroying a pyramid, video or frame after its context is a caller error; a
-// garbage-collected host language can produce that order.  The destroy functions check here and
-// then free the object's device buffers without the context (every object remembers its device;
-// hipFree needs neither the stream nor the context, after a device-wide synchronise nothing can
-// still be using them): no use-after-free and no leak.  Every other entry point refuses an object
-// whose context is gone.
+// Live contexts.  Destroying a pyramid, video, frame or sync object after its context is a caller
+// error; a garbage-collected host language can produce that order.  vm_destroy_object (vm_host.h)
+// checks here and then frees the object's device buffers without the context (every object
+// remembers its device; hipFree needs neither the stream nor the context, after a device-wide
+// synchronise nothing can still be using them): no use-after-free and no leak.  Every other entry
+// point refuses an object whose context is gone.
 #include <set>
 static std::mutex g_live_mu;
 static std::set<const vm_ctx *> g_live;
@@ -172,22 +172,22 @@ extern "C" int vm_ctx_create(int device, vm_ctx **out)
     // a context that cannot be completed is torn down again: nothing leaks on the error paths
     uint32_t tab[VM_TAB_WORDS];
     build_tables(tab);
-    c->flags_cap = 4096;
-    hipError_t e2 = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    if (e2 == hipSuccess) e2 = hipEventCreate(&c->ev0);
-    if (e2 == hipSuccess) e2 = hipEventCreate(&c->ev1);
-    if (e2 == hipSuccess) e2 = hipEventCreateWithFlags(&c->done_ev, hipEventDisableTiming);
-    if (e2 == hipSuccess) e2 = hipEventCreateWithFlags(&c->xfer_ev, hipEventDisableTiming);
-    if (e2 == hipSuccess) e2 = hipEventRecord(c->done_ev, c->stream);
-    if (e2 == hipSuccess) e2 = hipMalloc((void **)&c->tables, sizeof(tab));
-    if (e2 == hipSuccess) e2 = hipMemcpy(c->tables, tab, sizeof(tab), hipMemcpyHostToDevice);
-    if (e2 == hipSuccess) e2 = hipMalloc((void **)&c->flags, c->flags_cap * sizeof(uint32_t));
-    if (e2 == hipSuccess) e2 = hipHostMalloc((void **)&c->flags_host, c->flags_cap * sizeof(uint32_t), hipHostMallocDefault);
-    if (e2 == hipSuccess) e2 = hipMalloc((void **)&c->stats, c->flags_cap * VM_STAT_WORDS * sizeof(uint32_t));
-    if (e2 == hipSuccess) e2 = hipHostMalloc((void **)&c->stats_host, c->flags_cap * VM_STAT_WORDS * sizeof(uint32_t), hipHostMallocDefault);
-    if (e2 != hipSuccess) {
+    auto hip = [](hipError_t e) { return e == hipSuccess ? VM_OK : vm_fail(VM_E_DEVICE, "vm_ctx_create: %s", hipGetErrorString(e)); };
+    int rc = hip(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    if (rc == VM_OK) rc = c->ev0.create();
+    if (rc == VM_OK) rc = c->ev1.create();
+    if (rc == VM_OK) rc = c->done_ev.create(hipEventDisableTiming);
+    if (rc == VM_OK) rc = c->xfer_ev.create(hipEventDisableTiming);
+    if (rc == VM_OK) rc = hip(hipEventRecord(c->done_ev.get(), c->stream));
+    if (rc == VM_OK) rc = c->tables.reserve(VM_TAB_WORDS);
+    if (rc == VM_OK) rc = hip(hipMemcpy(c->tables.get(), tab, sizeof(tab), hipMemcpyHostToDevice));
+    if (rc == VM_OK) rc = c->flags.reserve(4096);
+    if (rc == VM_OK) rc = c->flags_host.reserve(4096);
+    if (rc == VM_OK) rc = c->stats.reserve(4096 * VM_STAT_WORDS);
+    if (rc == VM_OK) rc = c->stats_host.reserve(4096 * VM_STAT_WORDS);
+    if (rc != VM_OK) {
         ctx_free(c);
-        return vm_fail(VM_E_DEVICE, "vm_ctx_create: %s", hipGetErrorString(e2));
+        return rc;
     }
     {
         std::lock_guard<std::mutex> lock(g_live_mu);
@@ -199,32 +199,12 @@ extern "C" int vm_ctx_create(int device, vm_ctx **out)
 
 static void ctx_free(vm_ctx *c)
 {
-    if (c->stream) hipStreamSynchronize(c->stream);
-    hipFree(c->tables);
-    hipFree(c->flags);
-    hipHostFree(c->flags_host);
-    hipFree(c->stats);
-    hipHostFree(c->stats_host);
-    hipFree(c->step_slots);
-    hipFree(c->pass_bar);
-    hipFree(c->pass_err);
-    hipFree(c->pass_snap);
-    hipHostFree(c->pass_err_host);
-    hipFree(c->pass_dbg);
-    hipFree(c->cons_dev);
-    hipFree(c->views);
-    hipFree(c->iter_dev);
-    hipFree(c->tile_list);
-    hipFree(c->mgb_sys);
-    hipFree(c->mgb_shared);
+    hipStream_t s = c->stream;
+    if (s) hipStreamSynchronize(s);
     for (auto &g : c->graphs) hipGraphExecDestroy(g.exec);
-    if (c->ev0) hipEventDestroy(c->ev0);
-    if (c->ev1) hipEventDestroy(c->ev1);
-    if (c->done_ev) hipEventDestroy(c->done_ev);
-    if (c->xfer_ev) hipEventDestroy(c->xfer_ev);
-    if (c->stream) hipStreamDestroy(c->stream);
-    (void)hipGetLastError();
     delete c;
+    if (s) hipStreamDestroy(s);
+    (void)hipGetLastError();
 }
 
 extern "C" void vm_ctx_destroy(vm_ctx *c)
@@ -316,16 +296,16 @@ extern "C" int vm_dbg_pass_placement(vm_ctx *c, uint8_t *xcc_of_block, int n)
     if (!c || !xcc_of_block || n < 1 || n > 2048) return vm_fail(VM_E_INVALID, "vm_dbg_pass_placement: bad argument");
     std::lock_guard<std::recursive_mutex> lock(c->mu);
     VM_ON_DEVICE(c);
-    if (!c->pass_dbg) { // arm: the next PASS launches record where their workgroups run
-        VM_HIP(hipMalloc((void **)&c->pass_dbg, 2048 * sizeof(uint32_t)));
-        VM_HIP(hipMemsetAsync(c->pass_dbg, 0xFF, 2048 * sizeof(uint32_t), c->stream));
+    if (!c->pass_dbg.get()) { // arm: the next PASS launches record where their workgroups run
+        if (int rc = c->pass_dbg.reserve(2048)) return rc;
+        VM_HIP(hipMemsetAsync(c->pass_dbg.get(), 0xFF, 2048 * sizeof(uint32_t), c->stream));
         VM_HIP(hipStreamSynchronize(c->stream));
         memset(xcc_of_block, 0xFF, (size_t)n);
         return VM_OK;
     }
     std::vector<uint32_t> h(2048);
     VM_HIP(hipStreamSynchronize(c->stream));
-    VM_HIP(hipMemcpy(h.data(), c->pass_dbg, 2048 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    VM_HIP(hipMemcpy(h.data(), c->pass_dbg.get(), 2048 * sizeof(uint32_t), hipMemcpyDeviceToHost));
     for (int k = 0; k < n; ++k) xcc_of_block[k] = (uint8_t)(h[k] & 0xFFu);
     return VM_OK;
 }
@@ -353,51 +333,31 @@ extern "C" int vm_device_info(vm_ctx *c, char *name256, int *cus, uint64_t *hbm)
 }
 
 // ---------------------------------------------------------------------------
-void vm_level_free(vm_level &l)
-{
-    hipFree(l.slab);
-    hipFree(l.ws);
-    hipFree(l.sp_ws);
-    l.slab = l.ws = l.sp_ws = nullptr;
-    l.has_state = false;
-    VmLevelView &V = l.view;
-    V.rec_a = V.rec_b = V.rec_a2 = V.rec_b2 = nullptr;
-    V.rec_tag = V.rec_tag2 = nullptr;
-    V.mean2 = V.var2 = V.tps_b2 = nullptr;
-    V.cross2 = V.value2 = nullptr;
-    V.impmask2 = nullptr;
-    V.temp_ref = nullptr;
-    V.temp_mask = nullptr;
-    V.sp_wl = V.sp_cnt = V.sp_stamp = nullptr;
-}
-
 // one slab per level: every array starts on a 256-byte boundary
 int vm_level_alloc(vm_ctx *c, vm_level &l, bool with_images)
 {
     size_t n = (size_t)l.rs * l.h;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     size_t off = 0;
-    size_t o_v = off; off += al(n * 8);
+    size_t o_v = off; off += vm_align256(n * 8);
     size_t o_img0 = off, o_img1 = off, o_luma = off, o_mean = off, o_var = off, o_tpsb = off,
            o_uib = off, o_cross = off, o_value = off, o_uiaxy = off, o_imp = off;
     if (with_images) {
-        o_img0 = off; off += al(n * 4);
-        o_img1 = off; off += al(n * 4);
-        o_luma = off; off += al(n * 8);
-        o_mean = off; off += al(n * 8);
-        o_var = off; off += al(n * 8);
-        o_tpsb = off; off += al(n * 8);
-        o_uib = off; off += al(n * 8);
-        o_cross = off; off += al(n * 4);
-        o_value = off; off += al(n * 4);
-        o_uiaxy = off; off += al(n * 4);
-        o_imp = off; off += al((size_t)l.imp_rs * l.imp_rows * 4);
+        o_img0 = off; off += vm_align256(n * 4);
+        o_img1 = off; off += vm_align256(n * 4);
+        o_luma = off; off += vm_align256(n * 8);
+        o_mean = off; off += vm_align256(n * 8);
+        o_var = off; off += vm_align256(n * 8);
+        o_tpsb = off; off += vm_align256(n * 8);
+        o_uib = off; off += vm_align256(n * 8);
+        o_cross = off; off += vm_align256(n * 4);
+        o_value = off; off += vm_align256(n * 4);
+        o_uiaxy = off; off += vm_align256(n * 4);
+        o_imp = off; off += vm_align256((size_t)l.imp_rs * l.imp_rows * 4);
     }
-    VM_HIP(hipMalloc((void **)&l.slab, off));
+    if (int rc = l.slab.reserve(off)) return rc;
     // stream-ordered: the context's stream does not synchronise with the null stream
-    VM_HIP(hipMemsetAsync(l.slab, 0, off, c->stream));
-    l.slab_bytes = off;
-    char *b = (char *)l.slab;
+    VM_HIP(hipMemsetAsync(l.slab.get(), 0, off, c->stream));
+    char *b = l.slab.get();
     VmLevelView &V = l.view;
     V.w = l.w; V.h = l.h; V.rs = l.rs;
     V.inv_wh = 1.0f / (l.w * l.h);          // pyramid.cu:537
@@ -433,26 +393,25 @@ int vm_level_alloc(vm_ctx *c, vm_level &l, bool with_images)
 // a level is swept with one of them -- in practice the small levels only.
 static int level_ensure_ws(vm_ctx *c, vm_level &l)
 {
-    if (l.ws) return VM_OK;
+    if (l.ws.get()) return VM_OK;
     const size_t n = (size_t)l.rs * l.h, nimp = (size_t)l.imp_rs * l.imp_rows;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t total = 2 * al(n * 4) + 4 * al(n * 16) + 3 * al(n * 8) + 2 * al(n * 4) + al(nimp * 4);
-    VM_HIP(hipMalloc((void **)&l.ws, total));
-    VM_HIP(hipMemsetAsync(l.ws, 0, total, c->stream));
-    char *b = (char *)l.ws;
+    const size_t total = 2 * vm_align256(n * 4) + 4 * vm_align256(n * 16) + 3 * vm_align256(n * 8) + 2 * vm_align256(n * 4) + vm_align256(nimp * 4);
+    if (int rc = l.ws.reserve(total)) return rc;
+    char *b = l.ws.get();
     VmLevelView &V = l.view;
-    V.rec_tag = (uint32_t *)b; b += al(n * 4);
-    V.rec_tag2 = (uint32_t *)b; b += al(n * 4);
-    V.rec_a = (float4 *)b; b += al(n * 16);
-    V.rec_b = (float4 *)b; b += al(n * 16);
-    V.rec_a2 = (float4 *)b; b += al(n * 16);
-    V.rec_b2 = (float4 *)b; b += al(n * 16);
-    V.mean2 = (float2 *)b; b += al(n * 8);
-    V.var2 = (float2 *)b; b += al(n * 8);
-    V.tps_b2 = (float2 *)b; b += al(n * 8);
-    V.cross2 = (float *)b; b += al(n * 4);
-    V.value2 = (float *)b; b += al(n * 4);
+    V.rec_tag = (uint32_t *)b; b += vm_align256(n * 4);
+    V.rec_tag2 = (uint32_t *)b; b += vm_align256(n * 4);
+    V.rec_a = (float4 *)b; b += vm_align256(n * 16);
+    V.rec_b = (float4 *)b; b += vm_align256(n * 16);
+    V.rec_a2 = (float4 *)b; b += vm_align256(n * 16);
+    V.rec_b2 = (float4 *)b; b += vm_align256(n * 16);
+    V.mean2 = (float2 *)b; b += vm_align256(n * 8);
+    V.var2 = (float2 *)b; b += vm_align256(n * 8);
+    V.tps_b2 = (float2 *)b; b += vm_align256(n * 8);
+    V.cross2 = (float *)b; b += vm_align256(n * 4);
+    V.value2 = (float *)b; b += vm_align256(n * 4);
     V.impmask2 = (uint32_t *)b;
+    VM_HIP(hipMemsetAsync(l.ws.get(), 0, total, c->stream));
     return VM_OK;
 }
 
@@ -460,16 +419,15 @@ static int level_ensure_ws(vm_ctx *c, vm_level &l)
 // their lengths and a stamp per word -- 12 B per 5x5 block, allocated on first use.
 static int level_ensure_sparse(vm_ctx *c, vm_level &l)
 {
-    if (l.sp_ws) return VM_OK;
+    if (l.sp_ws.get()) return VM_OK;
     const size_t nw = (size_t)l.imp_rs * l.imp_rows;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t total = al(2 * nw * 4) + al(nw * 4) + 256;
-    VM_HIP(hipMalloc((void **)&l.sp_ws, total));
-    VM_HIP(hipMemsetAsync(l.sp_ws, 0, total, c->stream));
-    char *b = (char *)l.sp_ws;
-    l.view.sp_wl = (uint32_t *)b; b += al(2 * nw * 4);
-    l.view.sp_stamp = (uint32_t *)b; b += al(nw * 4);
+    const size_t total = vm_align256(2 * nw * 4) + vm_align256(nw * 4) + 256;
+    if (int rc = l.sp_ws.reserve(total)) return rc;
+    char *b = l.sp_ws.get();
+    l.view.sp_wl = (uint32_t *)b; b += vm_align256(2 * nw * 4);
+    l.view.sp_stamp = (uint32_t *)b; b += vm_align256(nw * 4);
     l.view.sp_cnt = (uint32_t *)b;
+    VM_HIP(hipMemsetAsync(l.sp_ws.get(), 0, total, c->stream));
     return VM_OK;
 }
 
@@ -498,24 +456,7 @@ extern "C" int vm_pyramid_create(vm_ctx *c, int nlevels, const int *w, const int
     return VM_OK;
 }
 
-extern "C" void vm_pyramid_destroy(vm_pyr *p)
-{
-    if (!p) return;
-    if (!vm_ctx_alive(p->ctx)) { // destroyed after its context: the buffers are freed without it
-        VmDeviceGuard g(p->device);
-        if (g.ok) {
-            hipDeviceSynchronize();
-            for (auto &l : p->lv) vm_level_free(l);
-            (void)hipGetLastError();
-        }
-        delete p;
-        return;
-    }
-    VM_ON_DEVICE_VOID(p->ctx);
-    hipStreamSynchronize(p->ctx->stream);
-    for (auto &l : p->lv) vm_level_free(l);
-    delete p;
-}
+extern "C" void vm_pyramid_destroy(vm_pyr *p) { vm_destroy_object(p); }
 
 extern "C" int vm_pyramid_levels(vm_pyr *p) { return p ? (int)p->lv.size() : 0; }
 
@@ -665,14 +606,8 @@ extern "C" int vm_level_clear(vm_pyr *p, int lvl)
 static int upload_constraints(vm_ctx *c, const vm_constraint *cons, int n)
 {
     if (n <= 0) return VM_OK;
-    if (n > c->cons_cap) {
-        hipFree(c->cons_dev);
-        c->cons_dev = nullptr;
-        c->cons_cap = 0;
-        VM_HIP(hipMalloc((void **)&c->cons_dev, (size_t)n * sizeof(vm_constraint)));
-        c->cons_cap = n;
-    }
-    VM_HIP(hipMemcpyAsync(c->cons_dev, cons, (size_t)n * sizeof(vm_constraint), hipMemcpyHostToDevice, c->stream));
+    if (int rc = c->cons_dev.reserve(n)) return rc;
+    VM_HIP(hipMemcpyAsync(c->cons_dev.get(), cons, (size_t)n * sizeof(vm_constraint), hipMemcpyHostToDevice, c->stream));
     VM_HIP(hipStreamSynchronize(c->stream)); // the host buffer belongs to the caller
     return VM_OK;
 }
@@ -724,17 +659,17 @@ int vm_level_init(vm_ctx *c, vm_level &l, int w0, int h0, const vm_constraint *c
     int rc = upload_constraints(c, cons, n);
     if (rc != VM_OK) return rc;
     if (c->math_mode == VM_MATH_REF_TEX8) {
-        vm_launch_init_level_tex8(l.view, c->kp.ssim_clamp, c->tables, c->stream);
-        if (n > 0) vm_launch_splat_exact(l.view, w0, h0, c->cons_dev, n, c->stream);
+        vm_launch_init_level_tex8(l.view, c->kp.ssim_clamp, c->tables.get(), c->stream);
+        if (n > 0) vm_launch_splat_exact(l.view, w0, h0, c->cons_dev.get(), n, c->stream);
     } else if (c->math_mode == VM_MATH_REF_TEX8_TRUNC) {
-        vm_launch_init_level_tex8t(l.view, c->kp.ssim_clamp, c->tables, c->stream);
-        if (n > 0) vm_launch_splat_exact(l.view, w0, h0, c->cons_dev, n, c->stream);
+        vm_launch_init_level_tex8t(l.view, c->kp.ssim_clamp, c->tables.get(), c->stream);
+        if (n > 0) vm_launch_splat_exact(l.view, w0, h0, c->cons_dev.get(), n, c->stream);
     } else if (c->math_mode != VM_MATH_FAST) {
-        vm_launch_init_level_exact(l.view, c->kp.ssim_clamp, c->tables, c->stream);
-        if (n > 0) vm_launch_splat_exact(l.view, w0, h0, c->cons_dev, n, c->stream);
+        vm_launch_init_level_exact(l.view, c->kp.ssim_clamp, c->tables.get(), c->stream);
+        if (n > 0) vm_launch_splat_exact(l.view, w0, h0, c->cons_dev.get(), n, c->stream);
     } else {
-        vm_launch_init_level_fast(l.view, c->kp.ssim_clamp, c->tables, c->stream);
-        if (n > 0) vm_launch_splat_fast(l.view, w0, h0, c->cons_dev, n, c->stream);
+        vm_launch_init_level_fast(l.view, c->kp.ssim_clamp, c->tables.get(), c->stream);
+        if (n > 0) vm_launch_splat_fast(l.view, w0, h0, c->cons_dev.get(), n, c->stream);
     }
     VM_HIP(hipGetLastError());
     l.has_state = true;
@@ -828,10 +763,10 @@ static hipGraphExec_t sweep_graph(vm_ctx *c, int math_mode, int n, int w, int h,
     if (!c->use_graphs) return nullptr;
     for (auto &g : c->graphs)
         if (g.math_mode == math_mode && g.n == n && g.w == w && g.h == h && g.cap == cap && g.fixed_work == fixed_work &&
-            g.threads == threads && g.dense == dense && g.order == c->commit_order && g.views == c->views && g.flags == c->flags && g.stats == c->stats && g.tile_list == tile_list &&
+            g.threads == threads && g.dense == dense && g.order == c->commit_order && g.views == c->views.get() && g.flags == c->flags.get() && g.stats == c->stats.get() && g.tile_list == tile_list &&
             memcmp(&g.kp, &c->kp, sizeof(c->kp)) == 0)
             return g.exec;
-    if (!c->iter_dev && hipMalloc((void **)&c->iter_dev, sizeof(int)) != hipSuccess) {
+    if (c->iter_dev.reserve(1) != VM_OK) {
         c->use_graphs = 0;
         return nullptr;
     }
@@ -843,10 +778,10 @@ static hipGraphExec_t sweep_graph(vm_ctx *c, int math_mode, int n, int w, int h,
     if (ok) {
         for (int it = 0; it < VM_GRAPH_ITERS; ++it) {
             for (int k = 0; k < 4; ++k) {
-                SL.optimize(c->views, n, cap, w, h, P, c->tables, offs[k][0], offs[k][1], c->flags, c->stats, it, fixed_work, threads, c->iter_dev, dense, tile_list, c->stream);
+                SL.optimize(c->views.get(), n, cap, w, h, P, c->tables.get(), offs[k][0], offs[k][1], c->flags.get(), c->stats.get(), it, fixed_work, threads, c->iter_dev.get(), dense, tile_list, c->stream);
             }
         }
-        SL.next_iter(c->iter_dev, 0, VM_GRAPH_ITERS, c->stream);
+        SL.next_iter(c->iter_dev.get(), 0, VM_GRAPH_ITERS, c->stream);
         ok = hipStreamEndCapture(c->stream, &graph) == hipSuccess && graph;
     }
     if (ok) ok = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess;
@@ -860,7 +795,7 @@ static hipGraphExec_t sweep_graph(vm_ctx *c, int math_mode, int n, int w, int h,
         for (auto &g : c->graphs) hipGraphExecDestroy(g.exec);
         c->graphs.clear();
     }
-    c->graphs.push_back({math_mode, n, w, h, cap, fixed_work, threads, dense, c->commit_order, c->views, c->flags, c->stats, tile_list, c->kp, exec});
+    c->graphs.push_back({math_mode, n, w, h, cap, fixed_work, threads, dense, c->commit_order, c->views.get(), c->flags.get(), c->stats.get(), tile_list, c->kp, exec});
     return exec;
 }
 
@@ -1001,24 +936,11 @@ int vm_optimize_levels(vm_ctx *c, vm_level **lv, int n, float max_iter, volatile
     int rc0 = vm_iteration_cap(max_iter, &cap);
     if (rc0 != VM_OK) return rc0;
     const size_t words = (size_t)cap * n;
-    if ((size_t)c->flags_cap < words) {
-        hipFree(c->flags); hipHostFree(c->flags_host);
-        hipFree(c->stats); hipHostFree(c->stats_host);
-        c->flags = c->flags_host = c->stats = c->stats_host = nullptr;
-        c->flags_cap = 0;
-        VM_HIP(hipMalloc((void **)&c->flags, words * 4));
-        VM_HIP(hipHostMalloc((void **)&c->flags_host, words * 4, hipHostMallocDefault));
-        VM_HIP(hipMalloc((void **)&c->stats, words * 4 * VM_STAT_WORDS));
-        VM_HIP(hipHostMalloc((void **)&c->stats_host, words * 4 * VM_STAT_WORDS, hipHostMallocDefault));
-        c->flags_cap = (int)words;
-    }
-    if (n > c->views_cap) {
-        hipFree(c->views);
-        c->views = nullptr;
-        c->views_cap = 0;
-        VM_HIP(hipMalloc((void **)&c->views, (size_t)n * sizeof(VmLevelView)));
-        c->views_cap = n;
-    }
+    if (int rc = c->flags.reserve(words)) return rc;
+    if (int rc = c->flags_host.reserve(words)) return rc;
+    if (int rc = c->stats.reserve(words * VM_STAT_WORDS)) return rc;
+    if (int rc = c->stats_host.reserve(words * VM_STAT_WORDS)) return rc;
+    if (int rc = c->views.reserve(n)) return rc;
     hipStream_t s = c->stream;
     const int ntiles_lvl = ((l0.w + VM_PITCH_X - 1) / VM_PITCH_X) * ((l0.h + VM_PITCH_Y - 1) / VM_PITCH_Y);
     // SPARSE: one workgroup per pair walks the few active tiles of a pruned level on the device
@@ -1042,11 +964,11 @@ int vm_optimize_levels(vm_ctx *c, vm_level **lv, int n, float max_iter, volatile
             }
         std::vector<VmLevelView> hv(n);
         for (int i = 0; i < n; ++i) hv[i] = lv[i]->view;
-        VM_HIP(hipMemcpyAsync(c->views, hv.data(), (size_t)n * sizeof(VmLevelView), hipMemcpyHostToDevice, s));
+        VM_HIP(hipMemcpyAsync(c->views.get(), hv.data(), (size_t)n * sizeof(VmLevelView), hipMemcpyHostToDevice, s));
         VM_HIP(hipStreamSynchronize(s)); // hv is a stack object
     }
-    VM_HIP(hipMemsetAsync(c->flags, 0, words * 4, s));
-    VM_HIP(hipMemsetAsync(c->stats, 0, words * 4 * VM_STAT_WORDS, s));
+    VM_HIP(hipMemsetAsync(c->flags.get(), 0, words * 4, s));
+    VM_HIP(hipMemsetAsync(c->stats.get(), 0, words * 4 * VM_STAT_WORDS, s));
     const bool exact = c->math_mode != VM_MATH_FAST; // EXACT and its FMA-contracted diagnostic build
     const SweepLaunchers &SL = sweep_launchers(c->math_mode);
     // FAST kernels are built for at most 512 threads (256-VGPR budget: the register-cached
@@ -1068,15 +990,8 @@ int vm_optimize_levels(vm_ctx *c, vm_level **lv, int n, float max_iter, volatile
                            tiles_per_pass <= 65535 && n <= 65535;
     if (listed_ok) {
         const size_t need = 4 * (size_t)cap + 2 * (size_t)tiles_per_pass * n; // counters per iteration and pass, stamps, entries
-        if (c->tile_list_words < need) {
-            VM_HIP(hipStreamSynchronize(s));
-            hipFree(c->tile_list);
-            c->tile_list = nullptr;
-            c->tile_list_words = 0;
-            VM_HIP(hipMalloc((void **)&c->tile_list, need * sizeof(uint32_t)));
-            c->tile_list_words = need;
-        }
-        VM_HIP(hipMemsetAsync(c->tile_list, 0, (4 * (size_t)cap + (size_t)tiles_per_pass * n) * sizeof(uint32_t), s));
+        if (int rc = c->tile_list.reserve(need, s)) return rc;
+        VM_HIP(hipMemsetAsync(c->tile_list.get(), 0, (4 * (size_t)cap + (size_t)tiles_per_pass * n) * sizeof(uint32_t), s));
     }
     // SPLIT / STEP schedules: workgroups per tile (every candidate gets 32 lanes, 16 candidates
     // per 512-thread workgroup)
@@ -1136,10 +1051,10 @@ int vm_optimize_levels(vm_ctx *c, vm_level **lv, int n, float max_iter, volatile
             want_pass = false;
         }
     }
-    if (want_pass && pass_token.try_acquire(c->device) && !c->pass_err) {
-        VM_HIP(hipMalloc((void **)&c->pass_err, 256));
-        VM_HIP(hipMemsetAsync(c->pass_err, 0, 256, s));
-        VM_HIP(hipHostMalloc((void **)&c->pass_err_host, 256, hipHostMallocDefault));
+    if (want_pass && pass_token.try_acquire(c->device) && !c->pass_err_host.get()) { // the error word and its mirror: made together, the mirror last
+        if (int rc = c->pass_err.reserve(64)) return rc;
+        VM_HIP(hipMemsetAsync(c->pass_err.get(), 0, 256, s));
+        if (int rc = c->pass_err_host.reserve(64)) return rc;
     }
     bool may_pass = want_pass && pass_token.owns;
     // diagnostic forms of a FORCED PASS schedule (vm_set_tuning(VM_SWEEP_PASS, 0, parts)): parts == 1 stores
@@ -1151,14 +1066,8 @@ int vm_optimize_levels(vm_ctx *c, vm_level **lv, int n, float max_iter, volatile
     const bool pass_guard = may_pass && c->sweep_mode == VM_SWEEP_AUTO;
     if (pass_guard) {
         size_t need = 0;
-        for (int i = 0; i < n; ++i) need += lv[i]->slab_bytes;
-        if (c->pass_snap_bytes < need) {
-            hipFree(c->pass_snap);
-            c->pass_snap = nullptr;
-            c->pass_snap_bytes = 0;
-            VM_HIP(hipMalloc(&c->pass_snap, need));
-            c->pass_snap_bytes = need;
-        }
+        for (int i = 0; i < n; ++i) need += lv[i]->slab.capacity();
+        if (int rc = c->pass_snap.reserve(need)) return rc;
     }
     const int offs[4][2] = {{0, 0}, {VM_TILE_W, 0}, {0, VM_TILE_H}, {VM_TILE_W, VM_TILE_H}}; // morph.cu:1382-1385
     std::vector<int> executed(n, cap), improving(n, 1), stopped(n, 0), live(n, -1);
@@ -1207,7 +1116,7 @@ int vm_optimize_levels(vm_ctx *c, vm_level **lv, int n, float max_iter, volatile
                             (c->sweep_mode == VM_SWEEP_SPARSE || tiles_prev <= (double)vm_sparse_tiles());
         const int sched = pass ? 4 : (split ? 2 : (sparse ? 3 : (dense ? 0 : 1)));
         const int launches_before = launches;
-        VM_HIP(hipEventRecord(c->ev0, s));
+        VM_HIP(hipEventRecord(c->ev0.get(), s));
         uint32_t last_epoch = 0;
         int sb = 0; // step index inside this batch: parity = which copy of the sums is read
         int slot_iter = -1; // iteration whose counts the previous STEP launch left in its slots
@@ -1215,35 +1124,22 @@ int vm_optimize_levels(vm_ctx *c, vm_level **lv, int n, float max_iter, volatile
         if (pass && pass_guard) {
             size_t off = 0;
             for (int i = 0; i < n; ++i) {
-                VM_HIP(hipMemcpyAsync((char *)c->pass_snap + off, lv[i]->slab, lv[i]->slab_bytes, hipMemcpyDeviceToDevice, s));
-                off += lv[i]->slab_bytes;
+                VM_HIP(hipMemcpyAsync(c->pass_snap.get() + off, lv[i]->slab.get(), lv[i]->slab.capacity(), hipMemcpyDeviceToDevice, s));
+                off += lv[i]->slab.capacity();
             }
         }
         if (pass) { // barrier counters of every launch of the batch, zeroed once
             const size_t need_bar = (size_t)nb * 4 * pass_groups * VM_PASS_SYNC_WORDS;
-            if (c->pass_bar_words < need_bar) {
-                VM_HIP(hipStreamSynchronize(s));
-                hipFree(c->pass_bar);
-                c->pass_bar = nullptr;
-                c->pass_bar_words = 0;
-                VM_HIP(hipMalloc((void **)&c->pass_bar, std::max(need_bar, (size_t)64 * 4 * 8 * VM_PASS_SYNC_WORDS) * sizeof(uint32_t)));
-                c->pass_bar_words = std::max(need_bar, (size_t)64 * 4 * 8 * VM_PASS_SYNC_WORDS);
-            }
-            VM_HIP(hipMemsetAsync(c->pass_bar, 0, need_bar * sizeof(uint32_t), s));
+            if (int rc = c->pass_bar.reserve(std::max(need_bar, (size_t)64 * 4 * 8 * VM_PASS_SYNC_WORDS), s)) return rc;
+            VM_HIP(hipMemsetAsync(c->pass_bar.get(), 0, need_bar * sizeof(uint32_t), s));
         }
         if (step || pass) {
             // per-workgroup count slots of the last two launches (k_step / k_pass fold them one launch late)
             const int gxs = (l0.w + VM_PITCH_X - 1) / VM_PITCH_X, gys = (l0.h + VM_PITCH_Y - 1) / VM_PITCH_Y;
             const size_t need = pass ? (size_t)pass_blocks * 4 : (size_t)gxs * gys * parts * n * 4;
-            if (c->step_slots_words < need) {
-                VM_HIP(hipStreamSynchronize(s));
-                hipFree(c->step_slots);
-                c->step_slots = nullptr;
-                c->step_slots_words = 0;
-                VM_HIP(hipMalloc((void **)&c->step_slots, 2 * need * sizeof(uint32_t)));
-                c->step_slots_words = need;
-            }
+            if (int rc = c->step_slots.reserve(2 * need, s)) return rc;
         }
+        uint32_t *const slots[2] = {c->step_slots.get(), c->step_slots.get() + c->step_slots.capacity() / 2}; // its two halves
         int it0 = done;
         if (sparse) {
             for (int i = 0; i < n; ++i)
@@ -1251,7 +1147,7 @@ int vm_optimize_levels(vm_ctx *c, vm_level **lv, int n, float max_iter, volatile
             // (forced SPARSE schedule with parts given: the LDS capacity of the word list, 0 < parts; parts = 1 is
             // "as good as none": the list then lives in memory from the first pass it holds two words -- tests)
             SL.sparse(
-                c->views, n, cap, l0.w, l0.h, P, c->tables, c->flags, c->stats, done, nb, fixed_work, threads, dense,
+                c->views.get(), n, cap, l0.w, l0.h, P, c->tables.get(), c->flags.get(), c->stats.get(), done, nb, fixed_work, threads, dense,
                 c->sweep_mode == VM_SWEEP_SPARSE && c->sweep_parts > 0 ? c->sweep_parts : 1 << 20, c->sparse_resident, s);
             launches += 2;
             it0 = done + nb;
@@ -1265,11 +1161,11 @@ int vm_optimize_levels(vm_ctx *c, vm_level **lv, int n, float max_iter, volatile
         const int tile_threads = small_dense.in_flight() >= VM_CORUN_MIN_WGS ? 256 : threads;
         // pruned TILE passes of a big batch: the listed form (k_tile_scan) -- dispatching tiles x pairs workgroups that
         // find nothing costs ~4.7 ns each, 118 us per pass over 30 1080p pairs
-        uint32_t *const tile_list = (listed_ok && dense == 0 && !split && !sparse) ? c->tile_list : nullptr;
+        uint32_t *const tile_list = (listed_ok && dense == 0 && !split && !sparse) ? c->tile_list.get() : nullptr;
         if (!split && !sparse && nb >= VM_GRAPH_ITERS) {
             // TILE batch: whole groups of VM_GRAPH_ITERS iterations are graph replays
             if (hipGraphExec_t ge = sweep_graph(c, c->math_mode, n, l0.w, l0.h, cap, fixed_work, tile_threads, dense, tile_list, P)) {
-                SL.next_iter(c->iter_dev, 1, done, s);
+                SL.next_iter(c->iter_dev.get(), 1, done, s);
                 for (; it0 + VM_GRAPH_ITERS <= done + nb; it0 += VM_GRAPH_ITERS) {
                     VM_HIP(hipGraphLaunch(ge, s));
                     launches += 4 * VM_GRAPH_ITERS;
@@ -1280,11 +1176,10 @@ int vm_optimize_levels(vm_ctx *c, vm_level **lv, int n, float max_iter, volatile
             for (int k = 0; k < 4; ++k) {
                 if (pass) {
                     SL.pass(
-                        c->views, n, cap, l0.w, l0.h, P, c->tables, offs[k][0], offs[k][1], 1u + (uint32_t)((it * 4 + k) * 4),
-                        c->pass_bar + (size_t)((it - done) * 4 + k) * pass_groups * VM_PASS_SYNC_WORDS, c->flags, c->stats, it, fixed_work,
-                        c->step_slots + (size_t)(sb & 1) * c->step_slots_words,
-                        c->step_slots + (size_t)((sb + 1) & 1) * c->step_slots_words, sb == 0 ? -1 : slot_iter, c->pass_err,
-                        c->pass_dbg, 1, pass_switches, s);
+                        c->views.get(), n, cap, l0.w, l0.h, P, c->tables.get(), offs[k][0], offs[k][1], 1u + (uint32_t)((it * 4 + k) * 4),
+                        c->pass_bar.get() + (size_t)((it - done) * 4 + k) * pass_groups * VM_PASS_SYNC_WORDS, c->flags.get(), c->stats.get(), it, fixed_work,
+                        slots[sb & 1], slots[(sb + 1) & 1], sb == 0 ? -1 : slot_iter, c->pass_err.get(),
+                        c->pass_dbg.get(), 1, pass_switches, s);
                     slot_iter = it;
                     ++sb;
                     ++launches;
@@ -1292,60 +1187,58 @@ int vm_optimize_levels(vm_ctx *c, vm_level **lv, int n, float max_iter, volatile
                     for (int ph = 0; ph < 4; ++ph, ++sb) {
                         const uint32_t epoch = 1u + (uint32_t)((it * 4 + k) * 4 + ph);
                         SL.step(
-                            c->views, n, cap, l0.w, l0.h, P, c->tables, offs[k][0], offs[k][1], ph >> 1, ph & 1, epoch,
-                            sb == 0 ? 0u : epoch - 1u, sb & 1, 1, c->flags, c->stats, it, fixed_work, threads, parts,
-                            c->step_slots + (size_t)(sb & 1) * c->step_slots_words,
-                            c->step_slots + (size_t)((sb + 1) & 1) * c->step_slots_words, sb == 0 ? -1 : slot_iter, s);
+                            c->views.get(), n, cap, l0.w, l0.h, P, c->tables.get(), offs[k][0], offs[k][1], ph >> 1, ph & 1, epoch,
+                            sb == 0 ? 0u : epoch - 1u, sb & 1, 1, c->flags.get(), c->stats.get(), it, fixed_work, threads, parts,
+                            slots[sb & 1], slots[(sb + 1) & 1], sb == 0 ? -1 : slot_iter, s);
                         slot_iter = it;
                         last_epoch = epoch;
                     }
                     launches += 4;
                 } else if (split) {
-                    SL.split(c->views, n, cap, l0.w, l0.h, P, c->tables, offs[k][0], offs[k][1], k, c->flags, c->stats, it, fixed_work, threads, parts, s);
+                    SL.split(c->views.get(), n, cap, l0.w, l0.h, P, c->tables.get(), offs[k][0], offs[k][1], k, c->flags.get(), c->stats.get(), it, fixed_work, threads, parts, s);
                     launches += 8;
                 } else {
-                    SL.optimize(c->views, n, cap, l0.w, l0.h, P, c->tables, offs[k][0], offs[k][1], c->flags, c->stats, it, fixed_work, tile_threads, nullptr, dense, tile_list, s);
+                    SL.optimize(c->views.get(), n, cap, l0.w, l0.h, P, c->tables.get(), offs[k][0], offs[k][1], c->flags.get(), c->stats.get(), it, fixed_work, tile_threads, nullptr, dense, tile_list, s);
                     ++launches;
                 }
             }
         if (step) { // fold the last phase's records in place: copy 0 is complete again
             SL.step(
-                c->views, n, cap, l0.w, l0.h, P, c->tables, 0, 0, 0, 0, 0u, last_epoch, 2, 0, c->flags, c->stats,
-                done + nb - 1, fixed_work, threads, parts, c->step_slots + (size_t)(sb & 1) * c->step_slots_words,
-                c->step_slots + (size_t)((sb + 1) & 1) * c->step_slots_words, sb == 0 ? -1 : slot_iter, s);
+                c->views.get(), n, cap, l0.w, l0.h, P, c->tables.get(), 0, 0, 0, 0, 0u, last_epoch, 2, 0, c->flags.get(), c->stats.get(),
+                done + nb - 1, fixed_work, threads, parts, slots[sb & 1], slots[(sb + 1) & 1], sb == 0 ? -1 : slot_iter, s);
             ++launches;
         }
         if (pass && sb > 0) { // the counts the last launch left in its slots
             SL.pass(
-                c->views, n, cap, l0.w, l0.h, P, c->tables, 0, 0, 0u, nullptr, c->flags, c->stats, done + nb - 1, fixed_work,
-                nullptr, c->step_slots + (size_t)((sb + 1) & 1) * c->step_slots_words, slot_iter, c->pass_err, nullptr, 0, pass_switches, s);
+                c->views.get(), n, cap, l0.w, l0.h, P, c->tables.get(), 0, 0, 0u, nullptr, c->flags.get(), c->stats.get(), done + nb - 1, fixed_work,
+                nullptr, slots[(sb + 1) & 1], slot_iter, c->pass_err.get(), nullptr, 0, pass_switches, s);
             ++launches;
         }
-        VM_HIP(hipEventRecord(c->ev1, s));
+        VM_HIP(hipEventRecord(c->ev1.get(), s));
         VM_HIP(hipGetLastError());
         if (pass)
-            VM_HIP(hipMemcpyAsync(c->pass_err_host, c->pass_err, 4, hipMemcpyDeviceToHost, s));
+            VM_HIP(hipMemcpyAsync(c->pass_err_host.get(), c->pass_err.get(), 4, hipMemcpyDeviceToHost, s));
         // (one strided copy per array instead of 2 n small ones was measured: 60 pairs 838 -> 836 ms, 8 pairs 328 -> 332: not kept)
         for (int i = 0; i < n; ++i) {
-            VM_HIP(hipMemcpyAsync(c->flags_host + (size_t)i * cap + done, c->flags + (size_t)i * cap + done, (size_t)nb * 4, hipMemcpyDeviceToHost, s));
-            VM_HIP(hipMemcpyAsync(c->stats_host + ((size_t)i * cap + done) * VM_STAT_WORDS, c->stats + ((size_t)i * cap + done) * VM_STAT_WORDS,
+            VM_HIP(hipMemcpyAsync(c->flags_host.get() + (size_t)i * cap + done, c->flags.get() + (size_t)i * cap + done, (size_t)nb * 4, hipMemcpyDeviceToHost, s));
+            VM_HIP(hipMemcpyAsync(c->stats_host.get() + ((size_t)i * cap + done) * VM_STAT_WORDS, c->stats.get() + ((size_t)i * cap + done) * VM_STAT_WORDS,
                                   (size_t)nb * 4 * VM_STAT_WORDS, hipMemcpyDeviceToHost, s));
         }
         VM_HIP(hipStreamSynchronize(s));
-        if (pass && c->pass_err_host[0]) {
-            VM_HIP(hipMemsetAsync(c->pass_err, 0, 4, s));
+        if (pass && c->pass_err_host.get()[0]) {
+            VM_HIP(hipMemsetAsync(c->pass_err.get(), 0, 4, s));
             if (!pass_guard)
                 return vm_fail(VM_E_DEVICE, "vm_optimize_level: a tile barrier of the PASS schedule timed out (are all of this device's "
                                             "compute units available to this process?  VM_SWEEP_AUTO falls back to the STEP schedule by itself)");
             // AUTO: the batch never happened -- state, records, flags and counters as before it -- and runs again with STEP
             size_t off = 0;
             for (int i = 0; i < n; ++i) {
-                VM_HIP(hipMemcpyAsync(lv[i]->slab, (char *)c->pass_snap + off, lv[i]->slab_bytes, hipMemcpyDeviceToDevice, s));
-                off += lv[i]->slab_bytes;
+                VM_HIP(hipMemcpyAsync(lv[i]->slab.get(), c->pass_snap.get() + off, lv[i]->slab.capacity(), hipMemcpyDeviceToDevice, s));
+                off += lv[i]->slab.capacity();
                 VM_HIP(hipMemsetAsync(lv[i]->view.rec_tag, 0, (size_t)l0.rs * l0.h * 4, s));
                 VM_HIP(hipMemsetAsync(lv[i]->view.rec_tag2, 0, (size_t)l0.rs * l0.h * 4, s));
-                VM_HIP(hipMemsetAsync(c->flags + (size_t)i * cap + done, 0, (size_t)nb * 4, s));
-                VM_HIP(hipMemsetAsync(c->stats + ((size_t)i * cap + done) * VM_STAT_WORDS, 0, (size_t)nb * 4 * VM_STAT_WORDS, s));
+                VM_HIP(hipMemsetAsync(c->flags.get() + (size_t)i * cap + done, 0, (size_t)nb * 4, s));
+                VM_HIP(hipMemsetAsync(c->stats.get() + ((size_t)i * cap + done) * VM_STAT_WORDS, 0, (size_t)nb * 4 * VM_STAT_WORDS, s));
             }
             launches = launches_before;
             may_pass = false;
@@ -1356,14 +1249,14 @@ int vm_optimize_levels(vm_ctx *c, vm_level **lv, int n, float max_iter, volatile
             continue;
         }
         float bms = 0;
-        VM_HIP(hipEventElapsedTime(&bms, c->ev0, c->ev1));
+        VM_HIP(hipEventElapsedTime(&bms, c->ev0.get(), c->ev1.get()));
         ms += bms;
         sched_ms[sched] += bms;
         sched_launches[sched] += launches - launches_before;
         bool all_stopped = true;
         double b_cand = 0, b_tiles = 0;
         for (int i = 0; i < n; ++i) {
-            const uint32_t *fl = c->flags_host + (size_t)i * cap, *st = c->stats_host + (size_t)i * cap * VM_STAT_WORDS;
+            const uint32_t *fl = c->flags_host.get() + (size_t)i * cap, *st = c->stats_host.get() + (size_t)i * cap * VM_STAT_WORDS;
             for (int it = done; it < done + nb && !stopped[i]; ++it) {
                 // [0] tile visits (TILE schedule), [3] tile-phases with records (SPLIT schedule)
                 st_tiles[i] += st[VM_STAT_WORDS * it] + 0.25 * st[VM_STAT_WORDS * it + 3];
@@ -1396,7 +1289,7 @@ int vm_optimize_levels(vm_ctx *c, vm_level **lv, int n, float max_iter, volatile
     }
     // everything this call wrote into the levels is enqueued: consumers on other streams wait on this event
     // (vm_frame_set_v_from_level across contexts) instead of draining this stream from the host
-    VM_HIP(hipEventRecord(c->done_ev, s));
+    VM_HIP(hipEventRecord(c->done_ev.get(), s));
     for (int i = 0; i < n && out; ++i) {
         out[i].iters = executed[i];
         out[i].iters_live = live[i] < 0 ? executed[i] : std::min(live[i], executed[i]);

@@ -23,37 +23,25 @@ extern "C" int vm_frame_create(vm_ctx *c, int w, int h, int ex, vm_frame **out)
     f->cw = w + 2 * ex; f->ch = h + 2 * ex;
     f->rs = (w + 31) / 32 * 32; // UI/RenderWidget.cpp:235
     size_t nc = (size_t)f->cw * f->ch, nv = (size_t)f->rs * h;
+    int rc = VM_OK;
+    for (int k = 0; k < 2 && rc == VM_OK; ++k) rc = f->ext[k].reserve(nc);
+    for (int k = 0; k < 2 && rc == VM_OK; ++k) rc = f->crop[k].reserve((size_t)w * h);
+    if (rc == VM_OK) rc = f->v.reserve(nv);
+    if (rc == VM_OK) rc = f->u.reserve(nv);
+    if (rc == VM_OK) rc = f->out.reserve((size_t)w * h * 3);
     hipError_t e = hipSuccess;
-    for (int k = 0; k < 2 && e == hipSuccess; ++k) e = hipMalloc((void **)&f->ext[k], nc * 4);
-    for (int k = 0; k < 2 && e == hipSuccess; ++k) e = hipMalloc((void **)&f->crop[k], (size_t)w * h * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&f->v, nv * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&f->u, nv * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&f->out, (size_t)w * h * 3);
-    if (e == hipSuccess) e = hipMemsetAsync(f->v, 0, nv * 8, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(f->u, 0, nv * 8, c->stream);
-    if (e != hipSuccess) {
+    if (rc == VM_OK && ((e = hipMemsetAsync(f->v.get(), 0, nv * 8, c->stream)) != hipSuccess ||
+                        (e = hipMemsetAsync(f->u.get(), 0, nv * 8, c->stream)) != hipSuccess))
+        rc = vm_fail(VM_E_DEVICE, "vm_frame_create: %s", hipGetErrorString(e));
+    if (rc != VM_OK) {
         vm_frame_destroy(f);
-        return vm_fail(VM_E_DEVICE, "vm_frame_create: %s", hipGetErrorString(e));
+        return rc;
     }
     *out = f;
     return VM_OK;
 }
 
-extern "C" void vm_frame_destroy(vm_frame *f)
-{
-    if (!f) return;
-    const bool alive = vm_ctx_alive(f->ctx); // destroyed after its context: freed without it (vm_api.cpp)
-    VmDeviceGuard g(f->device);
-    if (g.ok) {
-        if (alive) hipStreamSynchronize(f->ctx->stream);
-        else hipDeviceSynchronize();
-        hipFree(f->ext[0]); hipFree(f->ext[1]);
-        hipFree(f->crop[0]); hipFree(f->crop[1]);
-        hipFree(f->v); hipFree(f->u); hipFree(f->out); hipFree(f->rgb_stage); hipFree(f->pws2[0]); hipFree(f->pws2[1]);
-        (void)hipGetLastError();
-    }
-    delete f;
-}
+extern "C" void vm_frame_destroy(vm_frame *f) { vm_destroy_object(f); }
 
 extern "C" int vm_frame_upload(vm_frame *f, const uint8_t *e0, const uint8_t *e1, const float *v,
                                const float *q)
@@ -66,13 +54,13 @@ extern "C" int vm_frame_upload(vm_frame *f, const uint8_t *e0, const uint8_t *e1
     const uint8_t *e[2] = {e0, e1};
     for (int k = 0; k < 2; ++k)
         if (e[k]) {
-            VM_HIP(hipMemcpyAsync(f->ext[k], e[k], nc, hipMemcpyHostToDevice, s));
+            VM_HIP(hipMemcpyAsync(f->ext[k].get(), e[k], nc, hipMemcpyHostToDevice, s));
             // the originals both sides' fills sample from (cloned before any solve)
-            vm_poisson_launch_crop(f->crop[k], f->ext[k], f->w, f->h, f->ex, s);
+            vm_poisson_launch_crop(f->crop[k].get(), f->ext[k].get(), f->w, f->h, f->ex, s);
         }
-    if (v) VM_HIP(hipMemcpy2DAsync(f->v, (size_t)f->rs * 8, v, (size_t)f->w * 8, (size_t)f->w * 8, f->h, hipMemcpyHostToDevice, s));
-    if (q) VM_HIP(hipMemcpy2DAsync(f->u, (size_t)f->rs * 8, q, (size_t)f->w * 8, (size_t)f->w * 8, f->h, hipMemcpyHostToDevice, s));
-    else if (!f->u_zero) VM_HIP(hipMemsetAsync(f->u, 0, (size_t)f->rs * f->h * 8, s));
+    if (v) VM_HIP(hipMemcpy2DAsync(f->v.get(), (size_t)f->rs * 8, v, (size_t)f->w * 8, (size_t)f->w * 8, f->h, hipMemcpyHostToDevice, s));
+    if (q) VM_HIP(hipMemcpy2DAsync(f->u.get(), (size_t)f->rs * 8, q, (size_t)f->w * 8, (size_t)f->w * 8, f->h, hipMemcpyHostToDevice, s));
+    else if (!f->u_zero) VM_HIP(hipMemsetAsync(f->u.get(), 0, (size_t)f->rs * f->h * 8, s));
     f->u_zero = q == nullptr;
     VM_HIP(hipStreamSynchronize(s));
     return VM_OK;
@@ -90,11 +78,11 @@ extern "C" int vm_frame_upload_rgb(vm_frame *f, const uint8_t *rgb0, const uint8
     VM_ON_DEVICE(f->ctx);
     hipStream_t s = f->ctx->stream;
     const size_t one = (size_t)f->w * f->h * 3;
-    if (!f->rgb_stage) VM_HIP(hipMalloc((void **)&f->rgb_stage, 2 * one));
+    if (int rc = f->rgb_stage.reserve(2 * one)) return rc;
     const uint8_t *src[2] = {rgb0, rgb1};
     for (int k = 0; k < 2; ++k) {
-        VM_HIP(hipMemcpy2DAsync(f->rgb_stage + k * one, (size_t)3 * f->w, src[k], (size_t)pitch_bytes, (size_t)3 * f->w, f->h, hipMemcpyHostToDevice, s));
-        vm_poisson_launch_canvas(f->ext[k], f->crop[k], f->rgb_stage + k * one, f->w, f->h, f->ex, s);
+        VM_HIP(hipMemcpy2DAsync(f->rgb_stage.get() + k * one, (size_t)3 * f->w, src[k], (size_t)pitch_bytes, (size_t)3 * f->w, f->h, hipMemcpyHostToDevice, s));
+        vm_poisson_launch_canvas(f->ext[k].get(), f->crop[k].get(), f->rgb_stage.get() + k * one, f->w, f->h, f->ex, s);
     }
     VM_HIP(hipGetLastError());
     VM_HIP(hipStreamSynchronize(s));        // the host buffers belong to the caller
@@ -187,7 +175,7 @@ extern "C" int vm_frame_download_ext(vm_frame *f, int side, uint8_t *ext)
     if (!vm_ctx_alive(f->ctx)) return vm_fail(VM_E_INVALID, "%s: the context was destroyed", __func__);
     VM_ON_DEVICE(f->ctx);
     hipStream_t s = f->ctx->stream;
-    VM_HIP(hipMemcpyAsync(ext, f->ext[side - 1], (size_t)f->cw * f->ch * 4, hipMemcpyDeviceToHost, s));
+    VM_HIP(hipMemcpyAsync(ext, f->ext[side - 1].get(), (size_t)f->cw * f->ch * 4, hipMemcpyDeviceToHost, s));
     VM_HIP(hipStreamSynchronize(s));
     return VM_OK;
 }
@@ -210,16 +198,16 @@ extern "C" int vm_frame_set_v_from_level(vm_frame *f, vm_pyr *p, int lvl)
     if (p->ctx != f->ctx) {
         vm_ctx *pc = p->ctx;
         if (pc->mu.try_lock()) {
-            hipError_t e = hipEventRecord(pc->xfer_ev, pc->stream);
-            if (e == hipSuccess) e = hipStreamWaitEvent(f->ctx->stream, pc->xfer_ev, 0);
+            hipError_t e = hipEventRecord(pc->xfer_ev.get(), pc->stream);
+            if (e == hipSuccess) e = hipStreamWaitEvent(f->ctx->stream, pc->xfer_ev.get(), 0);
             pc->mu.unlock();
             if (e != hipSuccess) return vm_fail(VM_E_DEVICE, "vm_frame_set_v_from_level: %s", hipGetErrorString(e));
         } else {
-            VM_HIP(hipStreamWaitEvent(f->ctx->stream, pc->done_ev, 0));
+            VM_HIP(hipStreamWaitEvent(f->ctx->stream, pc->done_ev.get(), 0));
         }
     }
     vm_level &l = p->lv[lvl];
-    vm_launch_upscale(f->v, f->w, f->h, f->rs, l.view.v, l.w, l.h, l.rs, f->ctx->stream);
+    vm_launch_upscale(f->v.get(), f->w, f->h, f->rs, l.view.v, l.w, l.h, l.rs, f->ctx->stream);
     VM_HIP(hipGetLastError());
     return VM_OK;
 }
@@ -233,14 +221,13 @@ extern "C" int vm_upscale_result(vm_pyr *p, int lvl, int w0, int h0, float *out,
     VM_ON_DEVICE(p->ctx);
     vm_level &l = p->lv[lvl];
     hipStream_t s = p->ctx->stream;
-    float2 *tmp = nullptr;
-    VM_HIP(hipMalloc((void **)&tmp, (size_t)w0 * h0 * 8));
-    vm_launch_upscale(tmp, w0, h0, w0, l.view.v, l.w, l.h, l.rs, s);
+    VmDev<float2> tmp;
+    if (int rc = tmp.reserve((size_t)w0 * h0)) return rc;
+    vm_launch_upscale(tmp.get(), w0, h0, w0, l.view.v, l.w, l.h, l.rs, s);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess)
-        e = hipMemcpy2DAsync(out, (size_t)pitch * 4, tmp, (size_t)w0 * 8, (size_t)w0 * 8, h0, hipMemcpyDeviceToHost, s);
+        e = hipMemcpy2DAsync(out, (size_t)pitch * 4, tmp.get(), (size_t)w0 * 8, (size_t)w0 * 8, h0, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    hipFree(tmp);
     if (e != hipSuccess) return vm_fail(VM_E_DEVICE, "vm_upscale_result: %s", hipGetErrorString(e));
     return VM_OK;
 }
@@ -251,14 +238,14 @@ static int render_dev(vm_frame *f, float color_fa, float geo_fa, int color_from,
     if (color_from < 0 || color_from > 2) return vm_fail(VM_E_INVALID, "vm_render_halfway: color_from %d", color_from);
     vm_ctx *c = f->ctx;
     VM_ON_DEVICE(c);
-    if (ms) VM_HIP(hipEventRecord(c->ev0, c->stream));
-    vm_launch_render(f->out, f->w * 3, f->w, f->h, f->rs, f->ex, color_fa, geo_fa, color_from,
-                     f->ext[0], f->ext[1], f->v, f->u_zero ? nullptr : f->u, c->stream);
+    if (ms) VM_HIP(hipEventRecord(c->ev0.get(), c->stream));
+    vm_launch_render(f->out.get(), f->w * 3, f->w, f->h, f->rs, f->ex, color_fa, geo_fa, color_from,
+                     f->ext[0].get(), f->ext[1].get(), f->v.get(), f->u_zero ? nullptr : f->u.get(), c->stream);
     VM_HIP(hipGetLastError());
     if (ms) {
-        VM_HIP(hipEventRecord(c->ev1, c->stream));
-        VM_HIP(hipEventSynchronize(c->ev1));
-        VM_HIP(hipEventElapsedTime(ms, c->ev0, c->ev1));
+        VM_HIP(hipEventRecord(c->ev1.get(), c->stream));
+        VM_HIP(hipEventSynchronize(c->ev1.get()));
+        VM_HIP(hipEventElapsedTime(ms, c->ev0.get(), c->ev1.get()));
     }
     return VM_OK;
 }
@@ -279,7 +266,7 @@ extern "C" int vm_render_halfway(vm_frame *f, float color_fa, float geo_fa, int 
     if (!vm_ctx_alive(f->ctx)) return vm_fail(VM_E_INVALID, "%s: the context was destroyed", __func__);
     VM_ON_DEVICE(f->ctx);
     hipStream_t s = f->ctx->stream;
-    VM_HIP(hipMemcpy2DAsync(rgb, pitch, f->out, (size_t)f->w * 3, (size_t)f->w * 3, f->h, hipMemcpyDeviceToHost, s));
+    VM_HIP(hipMemcpy2DAsync(rgb, pitch, f->out.get(), (size_t)f->w * 3, (size_t)f->w * 3, f->h, hipMemcpyDeviceToHost, s));
     VM_HIP(hipStreamSynchronize(s));
     return VM_OK;
 }

@@ -3,10 +3,10 @@
 #define VM_HOST_H
 
 #include "vm_internal.h"
+#include "vm_devmem.h"
 #include <mutex>
 #include <vector>
 
-int vm_fail(int code, const char *fmt, ...);
 struct vm_ctx;
 bool vm_ctx_alive(const vm_ctx *c); // vm_api.cpp: is this context still alive?
 
@@ -56,33 +56,35 @@ struct VmDeviceGuard {
 // ... and in destructors / void functions (best effort)
 #define VM_ON_DEVICE_VOID(ctx) VmDeviceGuard VM_CAT(vm_device_guard_, __LINE__)((ctx)->device)
 
+struct VmMgbSys; // vm_mgb.h
+
 struct vm_ctx {
     std::recursive_mutex mu;         // a context is single-threaded by contract; this makes misuse safe
     int device = 0;
     int math_mode = VM_MATH_EXACT;
     vm_kern_params kp{};
+    // a plain handle, destroyed by ctx_free after every member (vm_api.cpp): ensure_lanes (vm_video.cpp) replaces a
+    // lane's stream
     hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    VmEvent ev0, ev1;
     // done_ev: recorded on `stream` (under `mu`, never inside a graph capture) whenever a solver call has enqueued its
     // last write of a level; xfer_ev: scratch for the same purpose in a consumer that holds `mu` itself.  Another
     // context's stream waits on one of them instead of the host draining this stream (vm_frame_set_v_from_level)
-    hipEvent_t done_ev = nullptr, xfer_ev = nullptr;
-    uint32_t *tables = nullptr;      // VM_TAB_WORDS words
-    uint32_t *flags = nullptr;       // per-iteration "improving" flags (device)
-    uint32_t *flags_host = nullptr;  // pinned mirror
-    uint32_t *stats = nullptr;       // per-iteration activity counters, 4 words each (device)
-    uint32_t *stats_host = nullptr;  // pinned mirror
-    uint32_t *step_slots = nullptr;  // STEP schedule: per-workgroup activity counts of the last two launches
-    size_t step_slots_words = 0;     // capacity of ONE of the two halves, in words
+    VmEvent done_ev, xfer_ev;
+    VmDev<uint32_t> tables;          // VM_TAB_WORDS words
+    VmDev<uint32_t> flags;           // per-iteration "improving" flags
+    VmPinned<uint32_t> flags_host;   // ... mirror
+    VmDev<uint32_t> stats;           // per-iteration activity counters, VM_STAT_WORDS words each
+    VmPinned<uint32_t> stats_host;   // ... mirror
+    VmDev<uint32_t> step_slots;      // STEP schedule: per-workgroup activity counts of the last two launches (two halves)
     // PASS schedule: tile-barrier counters (one per tile group and launch of a batch), the
     // error word a timed-out barrier raises (+ pinned mirror), optional XCD-placement record
-    uint32_t *pass_bar = nullptr;
-    size_t pass_bar_words = 0;
-    uint32_t *pass_err = nullptr, *pass_err_host = nullptr;
+    VmDev<uint32_t> pass_bar;
+    VmDev<uint32_t> pass_err;
+    VmPinned<uint32_t> pass_err_host;
     int pass_resident[8] = {-1, -1, -1, -1, -1, -1, -1, -1}; // co-resident k_pass workgroups on this device, per arithmetic build (math_mode); -1: not asked yet
-    uint32_t *pass_dbg = nullptr;    // vm_dbg_pass_xcd: 256 words, XCC id per workgroup of the last launch
-    void *pass_snap = nullptr;       // AUTO: the levels' slabs as they stood before the current PASS batch
-    size_t pass_snap_bytes = 0;
+    VmDev<uint32_t> pass_dbg;        // vm_dbg_pass_xcd: 256 words, XCC id per workgroup of the last launch
+    VmDev<char> pass_snap;           // AUTO: the levels' slabs as they stood before the current PASS batch
     bool pass_latched_off = false;   // AUTO: a tile barrier timed out once on this context: STEP from then on
     bool pass_latched_by_test = false; // ... and it was vm_dbg_pass_force_timeout's doing (only then the hook may lift it)
     int pass_fallbacks = 0;          // how often that happened (vm_dbg_pass_fallbacks)
@@ -90,13 +92,10 @@ struct vm_ctx {
     int sweep_threads = 0;           // 0 = automatic
     int sweep_mode = 0;              // VM_SWEEP_AUTO / TILE / SPLIT
     int sweep_parts = 0;             // workgroups per tile in the SPLIT schedule, 0 = automatic
-    int flags_cap = 0;
-    VmLevelView *views = nullptr;    // device copies of the level views of the current batch
-    int views_cap = 0;
-    vm_constraint *cons_dev = nullptr;
-    int cons_cap = 0;
+    VmDev<VmLevelView> views;        // device copies of the level views of the current batch
+    VmDev<vm_constraint> cons_dev;
     // hipGraph replay of launch-bound TILE sweeps (vm_api.cpp): 8 iterations per graph
-    int *iter_dev = nullptr;         // device iteration counter read by the replayed kernels
+    VmDev<int> iter_dev;             // device iteration counter read by the replayed kernels
     struct SweepGraph {
         int math_mode;
         int n, w, h, cap, fixed_work, threads, dense, order;
@@ -108,11 +107,10 @@ struct vm_ctx {
     int commit_order = 0;         // vm_set_commit_order (EXACT, diagnostic): order 0..3
     int sparse_resident = 0;      // vm_dbg_sparse_resident: 0 = automatic, 1 = never, 2 / 3 = tests (k_sparse, sv_phases)
     unsigned long long sparse_resident_visits = 0; // vm_dbg_sparse_resident_visits: tile visits served from the resident LDS copy
-    uint32_t *tile_list = nullptr;   // the listed form of pruned TILE passes over big batches (k_tile_scan): counters, stamps, entries
-    size_t tile_list_words = 0;
+    VmDev<uint32_t> tile_list;       // the listed form of pruned TILE passes over big batches (k_tile_scan): counters, stamps, entries
     int use_graphs = -1;             // -1: not decided yet, 0: off (VM_NO_GRAPH or a failed capture), 1: on
-    void *mgb_sys = nullptr;         // device descriptors of the systems of the current Poisson batch (vm_poisson_api.cpp)
-    void *mgb_shared = nullptr;      // ... and their PCG scalars + block / tile counts, contiguous: ONE clear and ONE read-back per check for the whole batch
+    VmDev<VmMgbSys> mgb_sys;         // device descriptors of the systems of the current Poisson batch (vm_poisson_api.cpp)
+    VmDev<char> mgb_shared;          // ... and their PCG scalars + block / tile counts, contiguous: ONE clear and ONE read-back per check for the whole batch
     // vm_dbg_poisson_profile: HIP-event time of the launch that carries the PCG update (k_mgb_update, or the level-0
     // restriction with the update fused in), summed over the launches of the solves since the probe was switched on,
     // and what those launches processed
@@ -123,10 +121,9 @@ struct vm_ctx {
 
 struct vm_level {
     int w = 0, h = 0, rs = 0, imp_rs = 0, imp_rows = 0;
-    void *slab = nullptr;
-    size_t slab_bytes = 0;
-    void *ws = nullptr;              // SPLIT / STEP workspace, allocated on first use (vm_api.cpp)
-    void *sp_ws = nullptr;           // SPARSE workspace (word lists, stamps), allocated on first use
+    VmDev<char> slab;
+    VmDev<char> ws;                  // SPLIT / STEP workspace, allocated on first use (vm_api.cpp)
+    VmDev<char> sp_ws;               // SPARSE workspace (word lists, stamps), allocated on first use
     bool has_state = false;
     VmLevelView view{};
     // pages of a video level: where lvl.temp.ref / lvl.temp.mask of the page live (the view
@@ -146,7 +143,7 @@ struct vm_pyr {
 // Pyramid.h:85-90, pitched float2 instead of cudaArray) and lvl.temp.ref / lvl.temp.mask.
 struct vm_video_page {
     vm_level lv;
-    void *tslab = nullptr;                                   // flows + temporal arrays
+    VmDev<char> tslab;                                       // flows + temporal arrays
     float2 *flow[4] = {nullptr, nullptr, nullptr, nullptr};  // f0, f1, b0, b1
     float2 *temp_ref = nullptr;
     float *temp_mask = nullptr;
@@ -159,7 +156,7 @@ struct vm_video_page {
 // step) tasks can run side by side (vm_video.cpp).
 struct vm_video_lane {
     vm_ctx *c = nullptr;
-    long long *acc = nullptr;
+    VmDev<long long> acc;
 };
 
 struct vm_video {
@@ -172,36 +169,54 @@ struct vm_video {
     float factor_d0 = 1.0f;
     std::vector<std::vector<vm_video_page>> pages;
     // scratch of the splat (sized for the finest level): fixed-point accumulators, v_cur, weight
-    long long *acc = nullptr;
-    float2 *vcur = nullptr;
-    float *weight = nullptr;
+    VmDev<long long> acc;
+    VmDev<float2> vcur;
+    VmDev<float> weight;
     std::vector<vm_video_lane> lanes;     // created by the first pipelined solve
-    float2 *result_tmp = nullptr;         // vm_frame_set_v_from_video: two full-resolution planes (blended frames)
-    size_t result_tmp_elems = 0;
+    VmDev<float2> result_tmp;             // vm_frame_set_v_from_video: two full-resolution planes (blended frames)
 };
 
 struct vm_frame {
     vm_ctx *ctx = nullptr;
     int device = 0;
     int w = 0, h = 0, ex = 0, cw = 0, ch = 0, rs = 0;
-    uchar4 *ext[2] = {nullptr, nullptr};  // (w+2ex) x (h+2ex) RGBA8 canvases
-    uchar4 *crop[2] = {nullptr, nullptr}; // w x h originals (CPoissonExt::_image1/_image2, PoissonExt.cpp:26-27)
-    float2 *v = nullptr, *u = nullptr;    // h x rs
+    VmDev<uchar4> ext[2];                 // (w+2ex) x (h+2ex) RGBA8 canvases
+    VmDev<uchar4> crop[2];                // w x h originals (CPoissonExt::_image1/_image2, PoissonExt.cpp:26-27)
+    VmDev<float2> v, u;                   // h x rs
     bool u_zero = true;                   // the quadratic path is all zeros (never uploaded / computed: the reference app's
                                           // state, UI/MdiEditor.cpp:1898-1903): vm_render_halfway then skips its 21 taps of u --
                                           // a zero path stays zero through the fixed-point steps, the bytes are the same
-    uint8_t *out = nullptr;               // h x w x 3
-    uint8_t *rgb_stage = nullptr;         // vm_frame_upload_rgb: the two RGB8 frames as they arrive (2 x h x w x 3), allocated on first use
+    VmDev<uint8_t> out;                   // h x w x 3
+    VmDev<uint8_t> rgb_stage;             // vm_frame_upload_rgb: the two RGB8 frames as they arrive (2 x h x w x 3), allocated on first use
     // solver workspace (allocated on first use), pws2[side - 1]: one per side (both sides of a frame are in flight
     // together); the quadratic path uses side 1's
-    void *pws2[2] = {nullptr, nullptr};
-    size_t pws2_bytes[2] = {0, 0};
+    VmDev<char> pws2[2];
 };
+
+// The one destroy path of the objects that live on a context's device (pyramid, video, frame, sync).  With the device
+// current and whatever may still use the object's buffers drained -- the context's stream, or the whole device once the
+// context is gone (a garbage-collected host language can destroy in that order; the object remembers its device) -- the
+// object is deleted and its members free themselves.  If the device cannot be made current, the object and its buffers
+// are leaked on purpose rather than freed on another device.
+template <class T> void vm_destroy_object(T *o)
+{
+    if (!o) return;
+    VmDeviceGuard g(o->device);
+    if (!g.ok) return;
+    if (vm_ctx_alive(o->ctx)) {
+        std::lock_guard<std::recursive_mutex> lock(o->ctx->mu);
+        (void)hipStreamSynchronize(o->ctx->stream);
+        delete o;
+    } else {
+        (void)hipDeviceSynchronize();
+        delete o;
+    }
+    (void)hipGetLastError();
+}
 
 // level-wise pieces of the solver shared by the frame-pair API (vm_api.cpp) and the video
 // API (vm_video.cpp); a "level" here is one page of one pyramid level
 int vm_level_alloc(vm_ctx *c, vm_level &l, bool with_images);
-void vm_level_free(vm_level &l);
 int vm_level_upsample(vm_ctx *c, vm_level &dst, const vm_level &src);
 int vm_level_init(vm_ctx *c, vm_level &l, int w0, int h0, const vm_constraint *cons, int n);
 int vm_level_read_field(vm_ctx *c, vm_level &l, int field, void *host);

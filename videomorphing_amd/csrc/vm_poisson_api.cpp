@@ -15,8 +15,6 @@
 
 namespace {
 
-size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // grid sizes: halve (rounding up) down to a grid of at most VM_MGB_COARSEST cells
 std::vector<std::pair<int, int>> mg_sizes(int w, int h)
 {
@@ -87,29 +85,29 @@ size_t mgb_bytes(int w, int h, bool with_best = false)
 {
     const auto sz = mg_sizes(w, h);
     const size_t N0 = (size_t)w * h;
-    size_t need = 2 * al256(N0) + al256(sizeof(VmMgbScalars)) + al256(2 * VM_MGB_MAXLEV * sizeof(int)) + 5 * al256(N0 * 12);
+    size_t need = 2 * vm_align256(N0) + vm_align256(sizeof(VmMgbScalars)) + vm_align256(2 * VM_MGB_MAXLEV * sizeof(int)) + 5 * vm_align256(N0 * 12);
     for (size_t l = 0; l < sz.size(); ++l) {
         const size_t N = (size_t)sz[l].first * sz[l].second;
         const size_t nb = (size_t)((sz[l].first + 63) / 64) * ((sz[l].second + 3) / 4);
-        need += (l ? 4 * al256(N * 4) : 0) + 2 * al256(N * 12) + al256((N + 1) / 2 * 12) + 3 * al256(nb * 4);
+        need += (l ? 4 * vm_align256(N * 4) : 0) + 2 * vm_align256(N * 12) + vm_align256((N + 1) / 2 * 12) + 3 * vm_align256(nb * 4);
     }
-    return need + (with_best ? al256(N0 * 12) : 0);
+    return need + (with_best ? vm_align256(N0 * 12) : 0);
 }
 
 void mgb_carve(MgbWork &W, int w, int h, char *b, bool qpath = false)
 {
     const auto sz = mg_sizes(w, h);
     const size_t N0 = (size_t)w * h;
-    W.type = (uint8_t *)b; b += al256(N0);
+    W.type = (uint8_t *)b; b += vm_align256(N0);
     W.S.type = W.type;
-    W.S.sc = (VmMgbScalars *)b; b += al256(sizeof(VmMgbScalars));
-    W.counts = (int *)b; b += al256(2 * VM_MGB_MAXLEV * sizeof(int));
+    W.S.sc = (VmMgbScalars *)b; b += vm_align256(sizeof(VmMgbScalars));
+    W.counts = (int *)b; b += vm_align256(2 * VM_MGB_MAXLEV * sizeof(int));
     W.tail = mg_tail_level(sz);
-    W.S.X = (VmV3 *)b; b += al256(N0 * 12);
-    W.S.P[0] = (VmV3 *)b; b += al256(N0 * 12);
-    W.S.P[1] = (VmV3 *)b; b += al256(N0 * 12);
-    W.S.Q = (VmV3 *)b; b += al256(N0 * 12);
-    VmV3 *const r1 = (VmV3 *)b; b += al256(N0 * 12);
+    W.S.X = (VmV3 *)b; b += vm_align256(N0 * 12);
+    W.S.P[0] = (VmV3 *)b; b += vm_align256(N0 * 12);
+    W.S.P[1] = (VmV3 *)b; b += vm_align256(N0 * 12);
+    W.S.Q = (VmV3 *)b; b += vm_align256(N0 * 12);
+    VmV3 *const r1 = (VmV3 *)b; b += vm_align256(N0 * 12);
     W.S.nlev = (int)sz.size();
     for (size_t l = 0; l < sz.size(); ++l) {
         VmMgbLevel &L = W.S.lv[l];
@@ -119,29 +117,29 @@ void mgb_carve(MgbWork &W, int w, int h, char *b, bool qpath = false)
         L.info = nullptr;
         L.we = L.ws = L.dg = L.k = nullptr;
         if (l == 0) {                       // one byte of operator per cell
-            L.info = (uint8_t *)b; b += al256(N);
+            L.info = (uint8_t *)b; b += vm_align256(N);
         } else {
-            L.we = (float *)b; b += al256(N * 4);
-            L.ws = (float *)b; b += al256(N * 4);
-            L.dg = (float *)b; b += al256(N * 4);
-            L.k = (float *)b; b += al256(N * 4);
+            L.we = (float *)b; b += vm_align256(N * 4);
+            L.ws = (float *)b; b += vm_align256(N * 4);
+            L.dg = (float *)b; b += vm_align256(N * 4);
+            L.k = (float *)b; b += vm_align256(N * 4);
         }
-        L.b = (VmV3 *)b; b += al256(N * 12);
+        L.b = (VmV3 *)b; b += vm_align256(N * 12);
         L.nu = mg_nu((int)l, (int)l >= W.tail, qpath);
-        L.xr = (VmV3 *)b; b += al256((N + 1) / 2 * 12);
-        L.flags = (uint32_t *)b; b += al256(nb * 4);
-        L.blocks = (uint32_t *)b; b += al256(nb * 4);
+        L.xr = (VmV3 *)b; b += vm_align256((N + 1) / 2 * 12);
+        L.flags = (uint32_t *)b; b += vm_align256(nb * 4);
+        L.blocks = (uint32_t *)b; b += vm_align256(nb * 4);
         L.nblocks = W.counts + l;
-        L.tiles = (uint32_t *)b; b += al256(nb * 4);
+        L.tiles = (uint32_t *)b; b += vm_align256(nb * 4);
         L.ntiles = W.counts + VM_MGB_MAXLEV + l;
     }
     // the x arrays last and together: level 0's (z), then the coarse ones, which are cleared per extension (a
     // fine cell may read the correction of a coarse cell that is no unknown and sits in a block nobody sweeps)
-    W.S.lv[0].x = (VmV3 *)b; b += al256(N0 * 12);
+    W.S.lv[0].x = (VmV3 *)b; b += vm_align256(N0 * 12);
     W.xcoarse = b;
     for (size_t l = 1; l < sz.size(); ++l) {
         W.S.lv[l].x = (VmV3 *)b;
-        b += al256((size_t)sz[l].first * sz[l].second * 12);
+        b += vm_align256((size_t)sz[l].first * sz[l].second * 12);
     }
     W.xcoarse_bytes = (size_t)(b - W.xcoarse);
     W.Xbest = qpath ? (VmV3 *)b : nullptr;     // (the quadratic path keeps the best iterate seen: mgb_solve)
@@ -195,20 +193,6 @@ double mgb_rel(const VmMgbScalars &h, int par)
 
 } // namespace
 
-// make sure *ws holds the batched solver's workspace of a w x h system
-static int mgb_reserve(void **ws, size_t *ws_bytes, int w, int h, size_t at_least = 0)
-{
-    const size_t need = std::max(mgb_bytes(w, h), at_least);
-    if (*ws_bytes < need) {
-        hipFree(*ws);
-        *ws = nullptr;
-        *ws_bytes = 0;
-        VM_HIP(hipMalloc(ws, need));
-        *ws_bytes = need;
-    }
-    return VM_OK;
-}
-
 // The batched PCG proper: nsys systems of one size whose workspaces are carved, whose type maps, right-hand sides
 // (lv[0].b) and initial guesses (X) are enqueued on the context's stream.  Leaves every system's solution in its X
 // (the iterate it stopped at; the best one seen near the tolerance if the workspace was carved with room for it), its
@@ -217,15 +201,15 @@ static int mgb_solve(vm_ctx *c, std::vector<MgbWork> &W, int nsys, float tol, in
 {
     hipStream_t s = c->stream;
     const size_t N0 = (size_t)W[0].S.lv[0].w * W[0].S.lv[0].h;
-    if (!c->mgb_sys) VM_HIP(hipMalloc((void **)&c->mgb_sys, VM_MGB_MAXSYS * sizeof(VmMgbSys)));
+    if (int rc = c->mgb_sys.reserve(VM_MGB_MAXSYS)) return rc;
     // the systems' PCG scalars and block / tile counts live side by side in one buffer of the context (the descriptors
     // handed to the kernels point there): one clear per solve, one read-back per residual check for the whole batch
     // instead of one per system
     const size_t cnt_bytes = (size_t)VM_MGB_MAXSYS * 2 * VM_MGB_MAXLEV * sizeof(int);
-    if (!c->mgb_shared) VM_HIP(hipMalloc(&c->mgb_shared, VM_MGB_MAXSYS * sizeof(VmMgbScalars) + cnt_bytes));
-    VmMgbScalars *sc_dev = (VmMgbScalars *)c->mgb_shared;
-    int *cnt_dev = (int *)((char *)c->mgb_shared + VM_MGB_MAXSYS * sizeof(VmMgbScalars));
-    VmMgbSys *dev = (VmMgbSys *)c->mgb_sys;
+    if (int rc = c->mgb_shared.reserve(VM_MGB_MAXSYS * sizeof(VmMgbScalars) + cnt_bytes)) return rc;
+    VmMgbScalars *sc_dev = (VmMgbScalars *)c->mgb_shared.get();
+    int *cnt_dev = (int *)(c->mgb_shared.get() + VM_MGB_MAXSYS * sizeof(VmMgbScalars));
+    VmMgbSys *dev = c->mgb_sys.get();
     std::vector<VmMgbSys> hs(nsys);
     const int nlev = W[0].S.nlev;
     // The PCG update rides in the level-0 restriction wherever the hierarchy allows it.  Measured on the 2304 x 1464 canvas
@@ -271,7 +255,7 @@ static int mgb_solve(vm_ctx *c, std::vector<MgbWork> &W, int nsys, float tol, in
     std::vector<VmMgbScalars> h(nsys);
     std::vector<double> best(nsys, 1e300);
     std::vector<int> best_it(nsys, 0), next_check(nsys, 0), saved(nsys, 0);
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev;
+    std::vector<std::pair<VmEvent, VmEvent>> prof_ev;
     std::vector<int> prof_sys;
     int it = 0;
     // A system's residual is looked at every 4 iterations (a read drains the stream) until it is within a factor 30
@@ -325,13 +309,13 @@ static int mgb_solve(vm_ctx *c, std::vector<MgbWork> &W, int nsys, float tol, in
     }
     while (active) {
         if (c->mgb_prof && it > 0) {     // the probe of vm_dbg_poisson_profile: events around the launch that carries the update
-            hipEvent_t e0 = nullptr, e1 = nullptr;
-            VM_HIP(hipEventCreate(&e0));
-            VM_HIP(hipEventCreate(&e1));
-            VM_HIP(hipEventRecord(e0, s));
+            prof_ev.emplace_back();
+            VmEvent &e0 = prof_ev.back().first, &e1 = prof_ev.back().second;
+            if (int rc = e0.create()) return rc;
+            if (int rc = e1.create()) return rc;
+            VM_HIP(hipEventRecord(e0.get(), s));
             mgb_iter_head(dev, nsys, fused, nb, nt, it, active, s);
-            VM_HIP(hipEventRecord(e1, s));
-            prof_ev.push_back({e0, e1});
+            VM_HIP(hipEventRecord(e1.get(), s));
             prof_sys.push_back(__builtin_popcountll(active));
         } else {
             mgb_iter_head(dev, nsys, fused, nb, nt, it, active, s);
@@ -353,14 +337,12 @@ static int mgb_solve(vm_ctx *c, std::vector<MgbWork> &W, int nsys, float tol, in
         VM_HIP(hipStreamSynchronize(s));
         for (size_t k = 0; k < prof_ev.size(); ++k) {
             float ms = 0;
-            if (hipEventElapsedTime(&ms, prof_ev[k].first, prof_ev[k].second) == hipSuccess) {
+            if (hipEventElapsedTime(&ms, prof_ev[k].first.get(), prof_ev[k].second.get()) == hipSuccess) {
                 c->mgb_prof_us += 1e3 * ms;
                 c->mgb_prof_launches += 1;
                 c->mgb_prof_fused += fused ? 1 : 0;
                 c->mgb_prof_unknown_launches += prof_sys[k];        // active systems of that launch (x unknowns per system: the caller's)
             }
-            hipEventDestroy(prof_ev[k].first);
-            hipEventDestroy(prof_ev[k].second);
         }
     }
     return VM_OK;
@@ -400,18 +382,17 @@ static int poisson_solve_batch(vm_ctx *c, vm_frame *const *frames, const int *si
     for (int i = 0; i < nsys; ++i) {
         vm_frame *f = frames[i];
         const int side = sides[i];
-        int rc = mgb_reserve(&f->pws2[side - 1], &f->pws2_bytes[side - 1], cw, ch);
-        if (rc != VM_OK) return rc;
-        mgb_carve(W[i], cw, ch, (char *)f->pws2[side - 1]);
-        uchar4 *ext = f->ext[side - 1];
-        const uchar4 *other = f->crop[side == 1 ? 1 : 0]; // PoissonExt.cpp:54-57
-        vm_poisson_launch_prepare(ext, W[i].type, other, f->v, f->w, f->h, f->rs, f->ex, side == 1 ? 1 : -1, s);
+        if (int rc = f->pws2[side - 1].reserve(mgb_bytes(cw, ch))) return rc;
+        mgb_carve(W[i], cw, ch, f->pws2[side - 1].get());
+        uchar4 *ext = f->ext[side - 1].get();
+        const uchar4 *other = f->crop[side == 1 ? 1 : 0].get(); // PoissonExt.cpp:54-57
+        vm_poisson_launch_prepare(ext, W[i].type, other, f->v.get(), f->w, f->h, f->rs, f->ex, side == 1 ? 1 : -1, s);
         vm_poisson_launch_setup3(ext, W[i].type, W[i].S.lv[0].b, W[i].S.X, cw, ch, s);
     }
     int rc = mgb_solve(c, W, nsys, tol, max_it, iters, rels);
     if (rc != VM_OK) return rc;
     for (int i = 0; i < nsys; ++i)
-        vm_poisson_launch_paste3(frames[i]->ext[sides[i] - 1], W[i].type, W[i].S.X, cw, ch, s);
+        vm_poisson_launch_paste3(frames[i]->ext[sides[i] - 1].get(), W[i].type, W[i].S.X, cw, ch, s);
     VM_HIP(hipGetLastError());
     return VM_OK;
 }
@@ -425,16 +406,16 @@ extern "C" int vm_poisson_extend(vm_frame *f, int side, float tol, int max_it, i
     VM_ON_DEVICE(c);
     std::lock_guard<std::recursive_mutex> lock(c->mu);
     hipStream_t s = c->stream;
-    VM_HIP(hipEventRecord(c->ev0, s));
+    VM_HIP(hipEventRecord(c->ev0.get(), s));
     int total_it = 0;
     double rel = 0;
     int rc = poisson_solve_batch(c, &f, &side, 1, tol, max_it, &total_it, &rel);
     if (rc != VM_OK) return rc;
     VM_HIP(hipGetLastError());
-    VM_HIP(hipEventRecord(c->ev1, s));
-    VM_HIP(hipEventSynchronize(c->ev1));
+    VM_HIP(hipEventRecord(c->ev1.get(), s));
+    VM_HIP(hipEventSynchronize(c->ev1.get()));
     float ms = 0;
-    VM_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    VM_HIP(hipEventElapsedTime(&ms, c->ev0.get(), c->ev1.get()));
     if (iters) *iters = total_it;
     if (rel_res) *rel_res = (float)rel;
     if (elapsed_ms) *elapsed_ms = ms;
@@ -468,13 +449,13 @@ extern "C" int vm_poisson_extend_frames(vm_frame *const *frames, int n, float to
     std::vector<int> sd(2 * n), its(2 * n, 0);
     std::vector<double> rel(2 * n, 0.0);
     for (int i = 0; i < n; ++i) { fr[2 * i] = fr[2 * i + 1] = frames[i]; sd[2 * i] = 1; sd[2 * i + 1] = 2; }
-    VM_HIP(hipEventRecord(c->ev0, s));
+    VM_HIP(hipEventRecord(c->ev0.get(), s));
     int rc = poisson_solve_batch(c, fr.data(), sd.data(), 2 * n, tol, max_it, its.data(), rel.data());
     if (rc != VM_OK) return rc;
-    VM_HIP(hipEventRecord(c->ev1, s));
-    VM_HIP(hipEventSynchronize(c->ev1));
+    VM_HIP(hipEventRecord(c->ev1.get(), s));
+    VM_HIP(hipEventSynchronize(c->ev1.get()));
     float ms = 0;
-    VM_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    VM_HIP(hipEventElapsedTime(&ms, c->ev0.get(), c->ev1.get()));
     if (elapsed_ms) *elapsed_ms = ms;
     double worst = 0;
     int at = 0;
@@ -504,17 +485,17 @@ extern "C" int vm_frame_quadratic_path(vm_frame *f, float tol, int max_it, int *
     hipStream_t s = c->stream;
     int it = 0;
     double rel = 0;
-    VM_HIP(hipEventRecord(c->ev0, s));
+    VM_HIP(hipEventRecord(c->ev0.get(), s));
     {
         // the batched solver on the whole grid: every pixel an unknown without a tie (type 2 everywhere), so the level-0
         // operator is the graph Laplacian of the pixel grid with Neumann ends (QuadraticPath.cpp:137-170); the
         // workspace is side 1's of the Poisson extension (the frame is no larger than its canvas, the two run in turn)
-        int rc = mgb_reserve(&f->pws2[0], &f->pws2_bytes[0], std::max(f->w, f->cw), std::max(f->h, f->ch), mgb_bytes(f->w, f->h, true));
+        int rc = f->pws2[0].reserve(std::max(mgb_bytes(std::max(f->w, f->cw), std::max(f->h, f->ch)), mgb_bytes(f->w, f->h, true)));
         if (rc != VM_OK) return rc;
         std::vector<MgbWork> W(1);
-        mgb_carve(W[0], f->w, f->h, (char *)f->pws2[0], true);
+        mgb_carve(W[0], f->w, f->h, f->pws2[0].get(), true);
         VM_HIP(hipMemsetAsync(W[0].type, 2, (size_t)f->w * f->h, s));
-        vm_qpath_launch_rhs3(f->v, f->rs, f->w, f->h, W[0].S.lv[0].b, W[0].S.X, s);
+        vm_qpath_launch_rhs3(f->v.get(), f->rs, f->w, f->h, W[0].S.lv[0].b, W[0].S.X, s);
         // project the right-hand side onto the range of the singular operator
         double *sums = &W[0].S.sc->bb[0][0];
         VM_HIP(hipMemsetAsync(W[0].S.sc, 0, sizeof(VmMgbScalars), s));
@@ -525,14 +506,14 @@ extern "C" int vm_frame_quadratic_path(vm_frame *f, float tol, int max_it, int *
         if (rc != VM_OK) return rc;
         VM_HIP(hipMemsetAsync(W[0].S.sc, 0, sizeof(VmMgbScalars), s));
         vm_qpath_launch_sum3(W[0].S.X, f->w, f->h, sums, s);
-        vm_qpath_launch_shift3(W[0].S.X, f->w, f->h, sums, f->u, f->rs, s);
+        vm_qpath_launch_shift3(W[0].S.X, f->w, f->h, sums, f->u.get(), f->rs, s);
     }
     f->u_zero = false;
     VM_HIP(hipGetLastError());
-    VM_HIP(hipEventRecord(c->ev1, s));
-    VM_HIP(hipEventSynchronize(c->ev1));
+    VM_HIP(hipEventRecord(c->ev1.get(), s));
+    VM_HIP(hipEventSynchronize(c->ev1.get()));
     float ms = 0;
-    VM_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    VM_HIP(hipEventElapsedTime(&ms, c->ev0.get(), c->ev1.get()));
     if (iters) *iters = it;
     if (rel_res) *rel_res = (float)rel;
     if (elapsed_ms) *elapsed_ms = ms;
@@ -548,7 +529,7 @@ extern "C" int vm_frame_download_qpath(vm_frame *f, float *u_xy)
     if (!vm_ctx_alive(f->ctx)) return vm_fail(VM_E_INVALID, "%s: the context was destroyed", __func__);
     VM_ON_DEVICE(f->ctx);
     hipStream_t s = f->ctx->stream;
-    VM_HIP(hipMemcpy2DAsync(u_xy, (size_t)f->w * 8, f->u, (size_t)f->rs * 8, (size_t)f->w * 8, f->h, hipMemcpyDeviceToHost, s));
+    VM_HIP(hipMemcpy2DAsync(u_xy, (size_t)f->w * 8, f->u.get(), (size_t)f->rs * 8, (size_t)f->w * 8, f->h, hipMemcpyDeviceToHost, s));
     VM_HIP(hipStreamSynchronize(s));
     return VM_OK;
 }
@@ -561,7 +542,7 @@ extern "C" int vm_frame_download_v(vm_frame *f, float *v_xy)
     if (!vm_ctx_alive(f->ctx)) return vm_fail(VM_E_INVALID, "%s: the context was destroyed", __func__);
     VM_ON_DEVICE(f->ctx);
     hipStream_t s = f->ctx->stream;
-    VM_HIP(hipMemcpy2DAsync(v_xy, (size_t)f->w * 8, f->v, (size_t)f->rs * 8, (size_t)f->w * 8, f->h, hipMemcpyDeviceToHost, s));
+    VM_HIP(hipMemcpy2DAsync(v_xy, (size_t)f->w * 8, f->v.get(), (size_t)f->rs * 8, (size_t)f->w * 8, f->h, hipMemcpyDeviceToHost, s));
     VM_HIP(hipStreamSynchronize(s));
     return VM_OK;
 }
@@ -657,15 +638,15 @@ extern "C" int vm_bcast_bytes(vm_ctx *const *ctxs, void *const *comms, int n, in
         if (!ctxs[i] || !dst_host[i] || (comms && !comms[i])) return vm_fail(VM_E_INVALID, "vm_bcast_bytes: context / buffer / communicator %d is NULL", i);
     Rccl &R = rccl();
     if (comms && (!R.bcast || !R.group_start || !R.group_end)) return vm_fail(VM_E_DEVICE, "vm_bcast_bytes: cannot load librccl");
-    std::vector<void *> buf(n, nullptr);
+    std::vector<VmDev<char>> buf(n);
     int rc = VM_OK;
     auto fail = [&](int code, const char *what) { rc = vm_fail(code, "vm_bcast_bytes: %s", what); };
     for (int i = 0; i < n && rc == VM_OK; ++i) {
         VmDeviceGuard g(ctxs[i]->device);
-        if (!g.ok || hipMalloc(&buf[i], (size_t)bytes) != hipSuccess) { fail(VM_E_DEVICE, "device buffer"); break; }
+        if (!g.ok || buf[i].reserve((size_t)bytes) != VM_OK) { fail(VM_E_DEVICE, "device buffer"); break; }
         // everybody but the root starts from zeros: what it ends up with is what travelled
-        hipError_t e = i == root ? hipMemcpyAsync(buf[i], src, (size_t)bytes, hipMemcpyHostToDevice, ctxs[i]->stream)
-                                 : hipMemsetAsync(buf[i], 0, (size_t)bytes, ctxs[i]->stream);
+        hipError_t e = i == root ? hipMemcpyAsync(buf[i].get(), src, (size_t)bytes, hipMemcpyHostToDevice, ctxs[i]->stream)
+                                 : hipMemsetAsync(buf[i].get(), 0, (size_t)bytes, ctxs[i]->stream);
         if (e == hipSuccess && i == root) e = hipStreamSynchronize(ctxs[i]->stream);      // src belongs to the caller
         if (e != hipSuccess) fail(VM_E_DEVICE, hipGetErrorString(e));
     }
@@ -673,7 +654,7 @@ extern "C" int vm_bcast_bytes(vm_ctx *const *ctxs, void *const *comms, int n, in
         if (R.group_start() != 0) fail(VM_E_DEVICE, "ncclGroupStart");
         for (int i = 0; i < n && rc == VM_OK; ++i) {
             VmDeviceGuard g(ctxs[i]->device);
-            if (!g.ok || R.bcast(buf[i], buf[i], (size_t)bytes, kNcclInt8, root, comms[i], ctxs[i]->stream) != 0)
+            if (!g.ok || R.bcast(buf[i].get(), buf[i].get(), (size_t)bytes, kNcclInt8, root, comms[i], ctxs[i]->stream) != 0)
                 fail(VM_E_DEVICE, "ncclBroadcast");
         }
         if (R.group_end() != 0 && rc == VM_OK) fail(VM_E_DEVICE, "ncclGroupEnd");
@@ -681,19 +662,19 @@ extern "C" int vm_bcast_bytes(vm_ctx *const *ctxs, void *const *comms, int n, in
         VmDeviceGuard g(ctxs[root]->device);
         if (hipStreamSynchronize(ctxs[root]->stream) != hipSuccess) fail(VM_E_DEVICE, "sync");
         for (int i = 0; i < n && rc == VM_OK; ++i)
-            if (i != root && hipMemcpyAsync(buf[i], buf[root], (size_t)bytes, hipMemcpyDeviceToDevice, ctxs[i]->stream) != hipSuccess)
+            if (i != root && hipMemcpyAsync(buf[i].get(), buf[root].get(), (size_t)bytes, hipMemcpyDeviceToDevice, ctxs[i]->stream) != hipSuccess)
                 fail(VM_E_DEVICE, "device-to-device copy");
     }
     for (int i = 0; i < n && rc == VM_OK; ++i) {
         VmDeviceGuard g(ctxs[i]->device);
-        if (hipMemcpyAsync(dst_host[i], buf[i], (size_t)bytes, hipMemcpyDeviceToHost, ctxs[i]->stream) != hipSuccess ||
+        if (hipMemcpyAsync(dst_host[i], buf[i].get(), (size_t)bytes, hipMemcpyDeviceToHost, ctxs[i]->stream) != hipSuccess ||
             hipStreamSynchronize(ctxs[i]->stream) != hipSuccess) { fail(VM_E_DEVICE, "read-back"); break; }
     }
-    for (int i = 0; i < n; ++i)
-        if (buf[i]) {
-            VmDeviceGuard g(ctxs[i]->device);
-            hipFree(buf[i]);
-        }
+    for (int i = 0; i < n; ++i) { // each buffer is freed on its own device
+        VmDeviceGuard g(ctxs[i]->device);
+        if (g.ok) buf[i].reset();
+        else buf[i].release();
+    }
     (void)hipGetLastError();
     return rc;
 }

@@ -48,26 +48,21 @@ std::vector<float> tri_factor(int n)
 
 struct Builder {
     vm_ctx *c;
-    std::map<int, float *> factors; // line length -> device factors
-    float *img = nullptr, *tmp = nullptr;
-    uint8_t *rgb = nullptr;
-    ~Builder()
-    {
-        for (auto &kv : factors) hipFree(kv.second);
-        hipFree(img); hipFree(tmp); hipFree(rgb);
-    }
+    std::map<int, VmDev<float>> factors; // line length -> device factors
+    VmDev<float> img, tmp;
+    VmDev<uint8_t> rgb;
     int factor(int n, float **out)
     {
         auto it = factors.find(n);
         if (it == factors.end()) {
             std::vector<float> A = tri_factor(n);
-            float *d = nullptr;
-            VM_HIP(hipMalloc((void **)&d, A.size() * 4));
-            VM_HIP(hipMemcpyAsync(d, A.data(), A.size() * 4, hipMemcpyHostToDevice, c->stream));
+            VmDev<float> d;
+            if (int rc = d.reserve(A.size())) return rc;
+            VM_HIP(hipMemcpyAsync(d.get(), A.data(), A.size() * 4, hipMemcpyHostToDevice, c->stream));
             VM_HIP(hipStreamSynchronize(c->stream));
-            it = factors.emplace(n, d).first;
+            it = factors.emplace(n, std::move(d)).first;
         }
-        *out = it->second;
+        *out = it->second.get();
         return VM_OK;
     }
     // one axis of scale(): src (w x h, 3 planes) -> dst; returns the new size in w, h
@@ -122,16 +117,16 @@ extern "C" int vm_pyramid_build_rgb(vm_pyr *p, const uint8_t *rgb0, const uint8_
     Builder B;
     B.c = c;
     const size_t n0 = (size_t)w0 * h0;
-    VM_HIP(hipMalloc((void **)&B.img, n0 * 12));
-    VM_HIP(hipMalloc((void **)&B.tmp, n0 * 12));
-    VM_HIP(hipMalloc((void **)&B.rgb, (size_t)pitch * h0));
+    if (int rc = B.img.reserve(n0 * 3)) return rc;
+    if (int rc = B.tmp.reserve(n0 * 3)) return rc;
+    if (int rc = B.rgb.reserve((size_t)pitch * h0)) return rc;
     hipStream_t s = c->stream;
     const uint8_t *src[2] = {rgb0, rgb1};
     for (int k = 0; k < 2; ++k) {
-        VM_HIP(hipMemcpyAsync(B.rgb, src[k], (size_t)pitch * h0, hipMemcpyHostToDevice, s));
-        float *a = B.img, *b = B.tmp;
+        VM_HIP(hipMemcpyAsync(B.rgb.get(), src[k], (size_t)pitch * h0, hipMemcpyHostToDevice, s));
+        float *a = B.img.get(), *b = B.tmp.get();
         int w = w0, h = h0;
-        vm_pyr_launch_load(B.rgb, pitch, a, w, h, s);
+        vm_pyr_launch_load(B.rgb.get(), pitch, a, w, h, s);
         for (int el = 0; el < L - 1; ++el) { // the coarsest level holds no images (pyramid.cu:329)
             const vm_level &lv = p->lv[el];
             int rc = B.scale(a, b, w, h, lv.w, lv.h); // el == 0: same size (pyramid.cu:270-273)
@@ -170,16 +165,16 @@ extern "C" int vm_video_build_rgb(vm_video *v, int frame, const uint8_t *rgb0, c
     Builder B;
     B.c = c;
     const size_t n0 = (size_t)w0 * h0;
-    VM_HIP(hipMalloc((void **)&B.img, n0 * 12));
-    VM_HIP(hipMalloc((void **)&B.tmp, n0 * 12));
-    VM_HIP(hipMalloc((void **)&B.rgb, (size_t)pitch * h0));
+    if (int rc = B.img.reserve(n0 * 3)) return rc;
+    if (int rc = B.tmp.reserve(n0 * 3)) return rc;
+    if (int rc = B.rgb.reserve((size_t)pitch * h0)) return rc;
     hipStream_t s = c->stream;
     const uint8_t *src[2] = {rgb0, rgb1};
     for (int k = 0; k < 2; ++k) {
-        VM_HIP(hipMemcpyAsync(B.rgb, src[k], (size_t)pitch * h0, hipMemcpyHostToDevice, s));
-        float *a = B.img, *b = B.tmp;
+        VM_HIP(hipMemcpyAsync(B.rgb.get(), src[k], (size_t)pitch * h0, hipMemcpyHostToDevice, s));
+        float *a = B.img.get(), *b = B.tmp.get();
         int w = w0, h = h0;
-        vm_pyr_launch_load(B.rgb, pitch, a, w, h, s);
+        vm_pyr_launch_load(B.rgb.get(), pitch, a, w, h, s);
         for (int el = 0; el < L - 1; ++el) {
             const vm_level &l0 = v->pages[el][0].lv;
             int rc = B.scale(a, b, w, h, l0.w, l0.h);
@@ -213,18 +208,19 @@ extern "C" int vm_video_build_flows(vm_video *v, const float *const *f0, const f
     const size_t n0 = (size_t)w0 * h0;
     Builder B;
     B.c = c;
-    VM_HIP(hipMalloc((void **)&B.img, n0 * 12));
-    VM_HIP(hipMalloc((void **)&B.tmp, n0 * 12));
+    if (int rc = B.img.reserve(n0 * 3)) return rc;
+    if (int rc = B.tmp.reserve(n0 * 3)) return rc;
     // working set: the current level's flows of every frame of the previous level, tight float2
-    struct Free { std::vector<void *> p; ~Free() { for (void *q : p) hipFree(q); } } guard;
-    std::vector<float2 *> cur[4];
+    std::vector<VmDev<float2>> flows(4 * (size_t)d0);
+    std::vector<float2 *> cur[4]; // views into flows
     const float *const *src[4] = {f0, f1, b0, b1};
     for (int k = 0; k < 4; ++k) {
         cur[k].resize(d0);
         for (int t = 0; t < d0; ++t) {
             if (!src[k][t]) return vm_fail(VM_E_INVALID, "vm_video_build_flows: flow %d of frame %d is NULL", k, t);
-            VM_HIP(hipMalloc((void **)&cur[k][t], n0 * 8));
-            guard.p.push_back(cur[k][t]);
+            VmDev<float2> &fl = flows[(size_t)k * d0 + t];
+            if (int rc = fl.reserve(n0)) return rc;
+            cur[k][t] = fl.get();
             VM_HIP(hipMemcpyAsync(cur[k][t], src[k][t], n0 * 8, hipMemcpyHostToDevice, s));
         }
     }
@@ -235,7 +231,7 @@ extern "C" int vm_video_build_flows(vm_video *v, const float *const *f0, const f
         const float ratiox = (float)w / (float)pw, ratioy = (float)h / (float)ph;
         for (int k = 0; k < 4; ++k)
             for (int t = 0; t < prev_d; ++t) {
-                float *a = B.img, *b = B.tmp;
+                float *a = B.img.get(), *b = B.tmp.get();
                 int cw = pw, ch = ph;
                 vm_flow_launch_load(cur[k][t], pw, a, pw, ph, s);
                 int rc = B.scale(a, b, cw, ch, w, h);

@@ -11,17 +11,17 @@
 
 struct vm_sync {
     vm_ctx *ctx = nullptr;
+    int device = 0;                           // of ctx: the buffers can be freed after the context is gone
     std::vector<int> w, h, d;                 // per level; [0] = full resolution (placeholder)
     std::vector<vm_sync_constraint> cons;
-    std::vector<std::array<float *, 3>> f;    // d_x[el], d_y[el], d_z[el]; null until the level is reached
-    void *ws = nullptr;                       // CG workspace of the level being solved (kept between levels)
-    size_t ws_bytes = 0;
+    std::vector<VmDev<float>> f;              // d_x[el], d_y[el], d_z[el] (field()); empty until the level is reached
+    VmDev<char> ws;                           // CG workspace of the level being solved (kept between levels)
     // stage-1 renderer: Pyramid::_video0/_video1/_forw0/_forw1 (Pyramid.h:46-47) and _vector[frame]
-    uchar4 *video[2] = {nullptr, nullptr};
-    float2 *forw[2] = {nullptr, nullptr};
-    float4 *vec = nullptr;
+    VmDev<uchar4> video[2];
+    VmDev<float2> forw[2];
+    VmDev<float4> vec;
     int vec_frame = -1;
-    uint8_t *out = nullptr;
+    VmDev<uint8_t> out;
 };
 
 #define CHECK_SYNC(s)                                                              \
@@ -75,40 +75,23 @@ extern "C" int vm_sync_create(vm_ctx *ctx, int nlevels, const int *w, const int 
     }
     vm_sync *s = new vm_sync();
     s->ctx = ctx;
+    s->device = ctx->device;
     s->w.assign(w, w + nlevels);
     s->h.assign(h, h + nlevels);
     s->d.assign(d, d + nlevels);
-    s->f.assign(nlevels, std::array<float *, 3>{nullptr, nullptr, nullptr});
+    s->f.resize(nlevels);
     *out = s;
     return VM_OK;
 }
 
 // the three components of a level live in ONE allocation (x at the base): large allocations get
 // large page fragments, which the plane-strided accesses of the CG kernels need
-static void free_field(vm_sync *s, int lvl)
+static float *field(vm_sync *s, int lvl, int c)
 {
-    if (s->f[lvl][0]) (void)hipFree(s->f[lvl][0]);
-    s->f[lvl] = {nullptr, nullptr, nullptr};
+    return s->f[lvl].get() + (size_t)c * s->w[lvl] * s->h[lvl] * s->d[lvl];
 }
 
-extern "C" void vm_sync_destroy(vm_sync *s)
-{
-    if (!s) return;
-    if (s->ctx && vm_ctx_alive(s->ctx)) {
-        std::lock_guard<std::recursive_mutex> lock(s->ctx->mu);
-        VM_ON_DEVICE_VOID(s->ctx);
-        (void)hipStreamSynchronize(s->ctx->stream);
-        for (size_t l = 0; l < s->f.size(); ++l) free_field(s, (int)l);
-        if (s->ws) (void)hipFree(s->ws);
-        for (int k = 0; k < 2; ++k) {
-            if (s->video[k]) (void)hipFree(s->video[k]);
-            if (s->forw[k]) (void)hipFree(s->forw[k]);
-        }
-        if (s->vec) (void)hipFree(s->vec);
-        if (s->out) (void)hipFree(s->out);
-    }
-    delete s;
-}
+extern "C" void vm_sync_destroy(vm_sync *s) { vm_destroy_object(s); }
 
 extern "C" int vm_sync_set_constraints(vm_sync *s, const vm_sync_constraint *c, int n)
 {
@@ -125,12 +108,10 @@ extern "C" int vm_sync_set_constraints(vm_sync *s, const vm_sync_constraint *c, 
 static int alloc_field(vm_sync *s, int lvl)
 {
     const size_t N = (size_t)s->w[lvl] * s->h[lvl] * s->d[lvl];
-    if (!s->f[lvl][0]) {
+    if (!s->f[lvl].get()) {
         const size_t bytes = (3 * N * sizeof(float) + ((size_t)2 << 20) - 1) & ~(((size_t)2 << 20) - 1);
-        float *base = nullptr;
-        VM_HIP(hipMalloc((void **)&base, bytes));
-        VM_HIP(hipMemsetAsync(base, 0, 3 * N * sizeof(float), s->ctx->stream));
-        s->f[lvl] = {base, base + N, base + 2 * N};
+        if (int rc = s->f[lvl].reserve(bytes / sizeof(float))) return rc;
+        VM_HIP(hipMemsetAsync(s->f[lvl].get(), 0, 3 * N * sizeof(float), s->ctx->stream));
     }
     return VM_OK;
 }
@@ -139,7 +120,7 @@ extern "C" int vm_sync_load_identity(vm_sync *s, int lvl)
 {
     CHECK_SYNC(s);
     CHECK_SLVL(s, lvl);
-    free_field(s, lvl);
+    s->f[lvl].reset();
     return alloc_field(s, lvl);
 }
 
@@ -150,16 +131,16 @@ extern "C" int vm_sync_upsample_level(vm_sync *s, int lvl)
     CHECK_SYNC(s);
     CHECK_SLVL(s, lvl);
     const int pel = lvl + 1;
-    if (pel >= (int)s->w.size() || !s->f[pel][0]) return vm_fail(VM_E_STATE, "vm_sync_upsample_level: level %d holds no field", pel);
-    free_field(s, lvl);
+    if (pel >= (int)s->w.size() || !s->f[pel].get()) return vm_fail(VM_E_STATE, "vm_sync_upsample_level: level %d holds no field", pel);
+    s->f[lvl].reset();
     if (int rc = alloc_field(s, lvl)) return rc;
     const float ratio[3] = {(float)s->w[lvl] / (float)s->w[pel], (float)s->h[lvl] / (float)s->h[pel], 1.0f};
     for (int c = 0; c < 3; ++c)
-        vm_sync_launch_upsample(s->f[lvl][c], s->w[lvl], s->h[lvl], s->f[pel][c], s->w[pel], s->h[pel], ratio[c], s->d[lvl],
+        vm_sync_launch_upsample(field(s, lvl, c), s->w[lvl], s->h[lvl], field(s, pel, c), s->w[pel], s->h[pel], ratio[c], s->d[lvl],
                                 s->ctx->stream);
     VM_HIP(hipGetLastError());
     VM_HIP(hipStreamSynchronize(s->ctx->stream));
-    free_field(s, pel);
+    s->f[pel].reset();
     return VM_OK;
 }
 
@@ -220,15 +201,13 @@ struct SyncWs {
     float *tab;
 };
 
-static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 extern "C" int vm_sync_optimize_level(vm_sync *s, int lvl, float max_iter, volatile const int *run_flag,
                                       vm_sync_progress *out)
 {
     CHECK_SYNC(s);
     CHECK_SLVL(s, lvl);
     vm_ctx *c = s->ctx;
-    if (!s->f[lvl][0]) return vm_fail(VM_E_STATE, "vm_sync_optimize_level: level %d holds no field (load_identity / upsample_level)", lvl);
+    if (!s->f[lvl].get()) return vm_fail(VM_E_STATE, "vm_sync_optimize_level: level %d holds no field (load_identity / upsample_level)", lvl);
     if (!std::isfinite(max_iter) || max_iter > 1048576.0f) return vm_fail(VM_E_INVALID, "vm_sync_optimize_level: max_iter %g", (double)max_iter);
     const int passes = max_iter < 0 ? 0 : (int)std::floor(max_iter) + 1; // k = 0; while (k <= max_iter) k++
     VmSyncGrid g;
@@ -266,24 +245,17 @@ extern "C" int vm_sync_optimize_level(vm_sync *s, int lvl, float max_iter, volat
     const int ne = (int)ui.size();
     // workspace
     size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += align256(bytes); return o; };
+    auto take = [&](size_t bytes) { size_t o = off; off += vm_align256(bytes); return o; };
     const size_t o_r = take(3 * N * sizeof(float)), o_p = take(6 * N * sizeof(float)), o_om = take(3 * N * sizeof(float));
     const size_t o_diag = take(N * sizeof(float)), o_tab = take(125 * 25 * sizeof(float));
     const size_t o_part = take((size_t)9 * g.nb * sizeof(double)), o_sc = take(VM_SYNC_SC_WORDS * sizeof(float));
     const size_t tk_bytes = (size_t)VM_SYNC_TICKET_WORDS(8 * g.per_xcd) * sizeof(unsigned), o_tk = take(tk_bytes);
     const size_t o_idx = take((size_t)std::max(ne, 1) * sizeof(int)), o_val = take((size_t)std::max(ne, 1) * 4 * sizeof(float));
-    if (off > s->ws_bytes) {
-        VM_HIP(hipStreamSynchronize(c->stream));
-        if (s->ws) (void)hipFree(s->ws);
-        s->ws = nullptr;
-        s->ws_bytes = 0;
-        VM_HIP(hipMalloc(&s->ws, off));
-        s->ws_bytes = off;
-    }
-    char *base = (char *)s->ws;
+    if (int rc = s->ws.reserve(off, c->stream)) return rc;
+    char *base = s->ws.get();
     VmSyncSys S;
     for (int k = 0; k < 3; ++k) {
-        S.x[k] = s->f[lvl][k];
+        S.x[k] = field(s, lvl, k);
         S.r[k] = (float *)(base + o_r) + (size_t)k * N;
         S.p[0][k] = (float *)(base + o_p) + (size_t)k * N;
         S.p[1][k] = (float *)(base + o_p) + (size_t)(3 + k) * N;
@@ -297,7 +269,7 @@ extern "C" int vm_sync_optimize_level(vm_sync *s, int lvl, float max_iter, volat
     int *d_idx = (int *)(base + o_idx);
     float *d_val = (float *)(base + o_val);
 
-    VM_HIP(hipEventRecord(c->ev0, c->stream));
+    VM_HIP(hipEventRecord(c->ev0.get(), c->stream));
     VM_HIP(hipMemsetAsync(base + o_r, 0, 3 * N * sizeof(float), c->stream));
     VM_HIP(hipMemsetAsync(S.diag, 0, N * sizeof(float), c->stream));
     VM_HIP(hipMemsetAsync(S.sc, 0, VM_SYNC_SC_WORDS * sizeof(float), c->stream));
@@ -345,7 +317,7 @@ extern "C" int vm_sync_optimize_level(vm_sync *s, int lvl, float max_iter, volat
     }
     vm_sync_launch_finish(g, S, k, c->stream);
     VM_HIP(hipGetLastError());
-    VM_HIP(hipEventRecord(c->ev1, c->stream));
+    VM_HIP(hipEventRecord(c->ev1.get(), c->stream));
     float sc[VM_SYNC_SC_WORDS];
     VM_HIP(hipMemcpyAsync(sc, S.sc, sizeof(sc), hipMemcpyDeviceToHost, c->stream));
     VM_HIP(hipStreamSynchronize(c->stream));
@@ -353,7 +325,7 @@ extern "C" int vm_sync_optimize_level(vm_sync *s, int lvl, float max_iter, volat
         out->iters = k;
         out->launches = launches;
         out->voxel_iters = (double)k * (double)N;
-        VM_HIP(hipEventElapsedTime(&out->elapsed_ms, c->ev0, c->ev1));
+        VM_HIP(hipEventElapsedTime(&out->elapsed_ms, c->ev0.get(), c->ev1.get()));
         for (int q = 0; q < 3; ++q) out->resid[q] = sc[3 + (k & 1) * 3 + q];
     }
     return VM_OK;
@@ -382,11 +354,11 @@ extern "C" int vm_sync_get_field(vm_sync *s, int lvl, float *x, float *y, float 
 {
     CHECK_SYNC(s);
     CHECK_SLVL(s, lvl);
-    if (!s->f[lvl][0]) return vm_fail(VM_E_STATE, "vm_sync_get_field: level %d holds no field", lvl);
+    if (!s->f[lvl].get()) return vm_fail(VM_E_STATE, "vm_sync_get_field: level %d holds no field", lvl);
     const size_t N = (size_t)s->w[lvl] * s->h[lvl] * s->d[lvl];
     float *dst[3] = {x, y, z};
     for (int c = 0; c < 3; ++c)
-        if (dst[c]) VM_HIP(hipMemcpyAsync(dst[c], s->f[lvl][c], N * sizeof(float), hipMemcpyDeviceToHost, s->ctx->stream));
+        if (dst[c]) VM_HIP(hipMemcpyAsync(dst[c], field(s, lvl, c), N * sizeof(float), hipMemcpyDeviceToHost, s->ctx->stream));
     VM_HIP(hipStreamSynchronize(s->ctx->stream));
     return VM_OK;
 }
@@ -399,7 +371,7 @@ extern "C" int vm_sync_set_field(vm_sync *s, int lvl, const float *x, const floa
     const size_t N = (size_t)s->w[lvl] * s->h[lvl] * s->d[lvl];
     const float *src[3] = {x, y, z};
     for (int c = 0; c < 3; ++c)
-        if (src[c]) VM_HIP(hipMemcpyAsync(s->f[lvl][c], src[c], N * sizeof(float), hipMemcpyHostToDevice, s->ctx->stream));
+        if (src[c]) VM_HIP(hipMemcpyAsync(field(s, lvl, c), src[c], N * sizeof(float), hipMemcpyHostToDevice, s->ctx->stream));
     VM_HIP(hipStreamSynchronize(s->ctx->stream));
     s->vec_frame = -1;
     return VM_OK;
@@ -407,16 +379,15 @@ extern "C" int vm_sync_set_field(vm_sync *s, int lvl, const float *x, const floa
 
 static int ensure_vec(vm_sync *s)
 {
-    if (!s->vec) VM_HIP(hipMalloc((void **)&s->vec, (size_t)s->w[0] * s->h[0] * sizeof(float4)));
-    return VM_OK;
+    return s->vec.reserve((size_t)s->w[0] * s->h[0]);
 }
 
 static int refresh_vec(vm_sync *s, int lvl, int frame)
 {
     if (int rc = ensure_vec(s)) return rc;
     const size_t page = (size_t)s->w[lvl] * s->h[lvl];
-    vm_sync_launch_result(s->f[lvl][0] + frame * page, s->f[lvl][1] + frame * page, s->f[lvl][2] + frame * page, s->w[lvl],
-                          s->h[lvl], s->w[0], s->h[0], s->vec, s->ctx->stream);
+    vm_sync_launch_result(field(s, lvl, 0) + frame * page, field(s, lvl, 1) + frame * page, field(s, lvl, 2) + frame * page, s->w[lvl],
+                          s->h[lvl], s->w[0], s->h[0], s->vec.get(), s->ctx->stream);
     VM_HIP(hipGetLastError());
     s->vec_frame = frame;
     return VM_OK;
@@ -427,9 +398,9 @@ extern "C" int vm_sync_result(vm_sync *s, int lvl, int frame, float *vec4)
     CHECK_SYNC(s);
     CHECK_SLVL(s, lvl);
     if (frame < 0 || frame >= s->d[lvl]) return vm_fail(VM_E_INVALID, "vm_sync_result: frame %d out of range", frame);
-    if (!s->f[lvl][0]) return vm_fail(VM_E_STATE, "vm_sync_result: level %d holds no field", lvl);
+    if (!s->f[lvl].get()) return vm_fail(VM_E_STATE, "vm_sync_result: level %d holds no field", lvl);
     if (int rc = refresh_vec(s, lvl, frame)) return rc;
-    if (vec4) VM_HIP(hipMemcpyAsync(vec4, s->vec, (size_t)s->w[0] * s->h[0] * sizeof(float4), hipMemcpyDeviceToHost, s->ctx->stream));
+    if (vec4) VM_HIP(hipMemcpyAsync(vec4, s->vec.get(), (size_t)s->w[0] * s->h[0] * sizeof(float4), hipMemcpyDeviceToHost, s->ctx->stream));
     VM_HIP(hipStreamSynchronize(s->ctx->stream));
     return VM_OK;
 }
@@ -441,11 +412,11 @@ extern "C" int vm_sync_upload_frame(vm_sync *s, int side, int frame, const uint8
     if (side < 0 || side > 1 || frame < 0 || frame >= d0 || !rgba || pitch_bytes < w0 * 4)
         return vm_fail(VM_E_INVALID, "vm_sync_upload_frame: bad arguments");
     const size_t page = (size_t)w0 * h0;
-    if (!s->video[side]) {
-        VM_HIP(hipMalloc((void **)&s->video[side], page * d0 * sizeof(uchar4)));
-        VM_HIP(hipMemsetAsync(s->video[side], 0, page * d0 * sizeof(uchar4), s->ctx->stream));
+    if (!s->video[side].get()) {
+        if (int rc = s->video[side].reserve(page * d0)) return rc;
+        VM_HIP(hipMemsetAsync(s->video[side].get(), 0, page * d0 * sizeof(uchar4), s->ctx->stream));
     }
-    VM_HIP(hipMemcpy2DAsync(s->video[side] + frame * page, (size_t)w0 * 4, rgba, (size_t)pitch_bytes, (size_t)w0 * 4, h0,
+    VM_HIP(hipMemcpy2DAsync(s->video[side].get() + frame * page, (size_t)w0 * 4, rgba, (size_t)pitch_bytes, (size_t)w0 * 4, h0,
                             hipMemcpyHostToDevice, s->ctx->stream));
     VM_HIP(hipStreamSynchronize(s->ctx->stream));
     return VM_OK;
@@ -458,11 +429,11 @@ extern "C" int vm_sync_upload_flow(vm_sync *s, int side, int frame, const float 
     if (side < 0 || side > 1 || frame < 0 || frame >= d0 || !flow_xy || pitch_floats < w0 * 2)
         return vm_fail(VM_E_INVALID, "vm_sync_upload_flow: bad arguments");
     const size_t page = (size_t)w0 * h0;
-    if (!s->forw[side]) {
-        VM_HIP(hipMalloc((void **)&s->forw[side], page * d0 * sizeof(float2)));
-        VM_HIP(hipMemsetAsync(s->forw[side], 0, page * d0 * sizeof(float2), s->ctx->stream));
+    if (!s->forw[side].get()) {
+        if (int rc = s->forw[side].reserve(page * d0)) return rc;
+        VM_HIP(hipMemsetAsync(s->forw[side].get(), 0, page * d0 * sizeof(float2), s->ctx->stream));
     }
-    VM_HIP(hipMemcpy2DAsync(s->forw[side] + frame * page, (size_t)w0 * 8, flow_xy, (size_t)pitch_floats * 4, (size_t)w0 * 8, h0,
+    VM_HIP(hipMemcpy2DAsync(s->forw[side].get() + frame * page, (size_t)w0 * 8, flow_xy, (size_t)pitch_floats * 4, (size_t)w0 * 8, h0,
                             hipMemcpyHostToDevice, s->ctx->stream));
     VM_HIP(hipStreamSynchronize(s->ctx->stream));
     return VM_OK;
@@ -474,19 +445,19 @@ static int render_common(vm_sync *s, float fa, int frame)
     if (frame < 0 || frame >= d0) return vm_fail(VM_E_INVALID, "vm_sync_render: frame %d out of range", frame);
     if (!std::isfinite(fa)) return vm_fail(VM_E_INVALID, "vm_sync_render: fa is not finite");
     for (int k = 0; k < 2; ++k)
-        if (!s->video[k] || !s->forw[k])
+        if (!s->video[k].get() || !s->forw[k].get())
             return vm_fail(VM_E_STATE, "vm_sync_render: video %d or its flow was never uploaded", k);
     if (s->vec_frame != frame) {
-        if (s->f[1][0]) {
+        if (s->f[1].get()) {
             if (int rc = refresh_vec(s, 1, frame)) return rc;
         } else { // Pyramid::build leaves _vector zero until the thread delivers (pyramid.cu:66-69)
             if (int rc = ensure_vec(s)) return rc;
-            VM_HIP(hipMemsetAsync(s->vec, 0, (size_t)w0 * h0 * sizeof(float4), s->ctx->stream));
+            VM_HIP(hipMemsetAsync(s->vec.get(), 0, (size_t)w0 * h0 * sizeof(float4), s->ctx->stream));
             s->vec_frame = frame;
         }
     }
-    if (!s->out) VM_HIP(hipMalloc((void **)&s->out, (size_t)w0 * h0 * 3));
-    vm_sync_launch_render(s->out, w0 * 3, w0, h0, d0, fa, frame, s->vec, s->video[0], s->video[1], s->forw[0], s->forw[1],
+    if (int rc = s->out.reserve((size_t)w0 * h0 * 3)) return rc;
+    vm_sync_launch_render(s->out.get(), w0 * 3, w0, h0, d0, fa, frame, s->vec.get(), s->video[0].get(), s->video[1].get(), s->forw[0].get(), s->forw[1].get(),
                           s->ctx->stream);
     VM_HIP(hipGetLastError());
     return VM_OK;
@@ -497,7 +468,7 @@ extern "C" int vm_sync_render(vm_sync *s, float fa, int frame, uint8_t *rgb_out,
     CHECK_SYNC(s);
     if (!rgb_out || pitch_bytes < s->w[0] * 3) return vm_fail(VM_E_INVALID, "vm_sync_render: bad output");
     if (int rc = render_common(s, fa, frame)) return rc;
-    VM_HIP(hipMemcpy2DAsync(rgb_out, (size_t)pitch_bytes, s->out, (size_t)s->w[0] * 3, (size_t)s->w[0] * 3, s->h[0],
+    VM_HIP(hipMemcpy2DAsync(rgb_out, (size_t)pitch_bytes, s->out.get(), (size_t)s->w[0] * 3, (size_t)s->w[0] * 3, s->h[0],
                             hipMemcpyDeviceToHost, s->ctx->stream));
     VM_HIP(hipStreamSynchronize(s->ctx->stream));
     return VM_OK;
@@ -506,10 +477,10 @@ extern "C" int vm_sync_render(vm_sync *s, float fa, int frame, uint8_t *rgb_out,
 extern "C" int vm_sync_render_dev(vm_sync *s, float fa, int frame, float *elapsed_ms)
 {
     CHECK_SYNC(s);
-    VM_HIP(hipEventRecord(s->ctx->ev0, s->ctx->stream));
+    VM_HIP(hipEventRecord(s->ctx->ev0.get(), s->ctx->stream));
     if (int rc = render_common(s, fa, frame)) return rc;
-    VM_HIP(hipEventRecord(s->ctx->ev1, s->ctx->stream));
+    VM_HIP(hipEventRecord(s->ctx->ev1.get(), s->ctx->stream));
     VM_HIP(hipStreamSynchronize(s->ctx->stream));
-    if (elapsed_ms) VM_HIP(hipEventElapsedTime(elapsed_ms, s->ctx->ev0, s->ctx->ev1));
+    if (elapsed_ms) VM_HIP(hipEventElapsedTime(elapsed_ms, s->ctx->ev0.get(), s->ctx->ev1.get()));
     return VM_OK;
 }

@@ -21,8 +21,6 @@
 #include <thread>
 #include <vector>
 
-static inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 #define CHECK_VID(v, lvl, page)                                                                        \
     if (!(v)) return vm_fail(VM_E_INVALID, "%s: video is NULL", __func__);                             \
     if ((lvl) < 0 || (lvl) >= (int)(v)->pages.size())                                                  \
@@ -85,14 +83,14 @@ extern "C" int vm_video_create(vm_ctx *c, int nlevels, const int *w, const int *
             l.view.factor_d = v->factor_d[i];
             if (with_images) {
                 const size_t n = (size_t)l.rs * l.h;
-                const size_t total = 5 * al256(n * 8) + al256(n * 4);
-                if (hipMalloc(&pg.tslab, total) != hipSuccess || hipMemsetAsync(pg.tslab, 0, total, c->stream) != hipSuccess) {
+                const size_t total = 5 * vm_align256(n * 8) + vm_align256(n * 4);
+                if (pg.tslab.reserve(total) != VM_OK || hipMemsetAsync(pg.tslab.get(), 0, total, c->stream) != hipSuccess) {
                     vm_video_destroy(v);
                     return vm_fail(VM_E_DEVICE, "vm_video_create: out of device memory");
                 }
-                char *b = (char *)pg.tslab;
-                for (int k = 0; k < 4; ++k) { pg.flow[k] = (float2 *)b; b += al256(n * 8); }
-                pg.temp_ref = (float2 *)b; b += al256(n * 8);
+                char *b = pg.tslab.get();
+                for (int k = 0; k < 4; ++k) { pg.flow[k] = (float2 *)b; b += vm_align256(n * 8); }
+                pg.temp_ref = (float2 *)b; b += vm_align256(n * 8);
                 pg.temp_mask = (float *)b;
                 l.temp_ref_store = pg.temp_ref;
                 l.temp_mask_store = pg.temp_mask;
@@ -102,10 +100,10 @@ extern "C" int vm_video_create(vm_ctx *c, int nlevels, const int *w, const int *
     {
         const vm_level &l0 = v->pages[0][0].lv;
         const size_t n = (size_t)l0.rs * l0.h;
-        hipError_t e = hipMalloc((void **)&v->acc, n * 3 * sizeof(long long));
-        if (e == hipSuccess) e = hipMalloc((void **)&v->vcur, n * 8);
-        if (e == hipSuccess) e = hipMalloc((void **)&v->weight, n * 4);
-        if (e != hipSuccess) { vm_video_destroy(v); return vm_fail(VM_E_DEVICE, "vm_video_create: %s", hipGetErrorString(e)); }
+        int rc = v->acc.reserve(n * 3);
+        if (rc == VM_OK) rc = v->vcur.reserve(n);
+        if (rc == VM_OK) rc = v->weight.reserve(n);
+        if (rc != VM_OK) { vm_video_destroy(v); return rc; }
     }
     *out = v;
     return VM_OK;
@@ -114,30 +112,8 @@ extern "C" int vm_video_create(vm_ctx *c, int nlevels, const int *w, const int *
 extern "C" void vm_video_destroy(vm_video *v)
 {
     if (!v) return;
-    for (vm_video_lane &ln : v->lanes) // the pipeline's lanes are contexts of their own
-        if (ln.c && vm_ctx_alive(ln.c)) {
-            {
-                VM_ON_DEVICE_VOID(ln.c);
-                hipStreamSynchronize(ln.c->stream);
-                hipFree(ln.acc);
-            }
-            vm_ctx_destroy(ln.c);
-        }
-    v->lanes.clear();
-    const bool alive = vm_ctx_alive(v->ctx); // destroyed after its context: freed without it (vm_api.cpp)
-    VmDeviceGuard g(v->device);
-    if (g.ok) {
-        if (alive) hipStreamSynchronize(v->ctx->stream);
-        else hipDeviceSynchronize();
-        for (auto &lv : v->pages)
-            for (auto &pg : lv) {
-                vm_level_free(pg.lv);
-                hipFree(pg.tslab);
-            }
-        hipFree(v->acc); hipFree(v->vcur); hipFree(v->weight); hipFree(v->result_tmp);
-        (void)hipGetLastError();
-    }
-    delete v;
+    for (vm_video_lane &ln : v->lanes) vm_ctx_destroy(ln.c); // the pipeline's lanes are contexts of their own
+    vm_destroy_object(v);
 }
 
 extern "C" int vm_video_levels(vm_video *v) { return v ? (int)v->pages.size() : 0; }
@@ -174,7 +150,7 @@ extern "C" int vm_video_upload_flows(vm_video *v, int lvl, int page, const float
     CHECK_VID(v, lvl, page);
     vm_video_page &pg = v->pages[lvl][page];
     vm_level &l = pg.lv;
-    if (!pg.tslab) return vm_fail(VM_E_STATE, "vm_video_upload_flows: the coarsest level holds no flows");
+    if (!pg.tslab.get()) return vm_fail(VM_E_STATE, "vm_video_upload_flows: the coarsest level holds no flows");
     if (pitch == 0) pitch = 2 * l.w;
     if (pitch < 2 * l.w) return vm_fail(VM_E_INVALID, "vm_video_upload_flows: pitch < 2*width");
     hipStream_t s = v->ctx->stream;
@@ -269,17 +245,16 @@ extern "C" int vm_video_result(vm_video *v, int lvl, int w0, int h0, float *out)
     std::lock_guard<std::recursive_mutex> lock(v->ctx->mu);
     hipStream_t s = v->ctx->stream;
     const size_t n = (size_t)w0 * h0;
-    float2 *buf = nullptr;
-    VM_HIP(hipMalloc((void **)&buf, 3 * n * 8));
+    VmDev<float2> buf;
+    if (int rc = buf.reserve(3 * n)) return rc;
     int rc = VM_OK;
     for (int f = 0; f < v->depth0 && rc == VM_OK; ++f) {
-        rc = video_result_frame(v, lvl, w0, h0, f, buf, w0, buf + n);
-        if (rc == VM_OK && hipMemcpyAsync(out + (size_t)f * n * 2, buf, n * 8, hipMemcpyDeviceToHost, s) != hipSuccess)
+        rc = video_result_frame(v, lvl, w0, h0, f, buf.get(), w0, buf.get() + n);
+        if (rc == VM_OK && hipMemcpyAsync(out + (size_t)f * n * 2, buf.get(), n * 8, hipMemcpyDeviceToHost, s) != hipSuccess)
             rc = vm_fail(VM_E_DEVICE, "vm_video_result: copy failed");
         if (rc == VM_OK && hipStreamSynchronize(s) != hipSuccess) rc = vm_fail(VM_E_DEVICE, "vm_video_result: sync failed");
     }
     hipStreamSynchronize(s);
-    hipFree(buf);
     return rc;
 }
 
@@ -290,15 +265,8 @@ extern "C" int vm_frame_set_v_from_video(vm_frame *f, vm_video *v, int lvl, int 
     if (frame < 0 || frame >= v->depth0) return vm_fail(VM_E_INVALID, "vm_frame_set_v_from_video: frame %d out of range (0..%d)", frame, v->depth0 - 1);
     std::lock_guard<std::recursive_mutex> lock(v->ctx->mu);
     const size_t n = (size_t)f->w * f->h;
-    if (!v->result_tmp || v->result_tmp_elems < 2 * n) {
-        VM_HIP(hipStreamSynchronize(v->ctx->stream));
-        hipFree(v->result_tmp);
-        v->result_tmp = nullptr;
-        v->result_tmp_elems = 0;
-        VM_HIP(hipMalloc((void **)&v->result_tmp, 2 * n * 8));
-        v->result_tmp_elems = 2 * n;
-    }
-    return video_result_frame(v, lvl, f->w, f->h, frame, f->v, f->rs, v->result_tmp);
+    if (int rc = v->result_tmp.reserve(2 * n, v->ctx->stream)) return rc;
+    return video_result_frame(v, lvl, f->w, f->h, frame, f->v.get(), f->rs, v->result_tmp.get());
 }
 
 extern "C" int vm_video_get_field(vm_video *v, int lvl, int page, int field, void *host)
@@ -307,7 +275,7 @@ extern "C" int vm_video_get_field(vm_video *v, int lvl, int page, int field, voi
     vm_video_page &pg = v->pages[lvl][page];
     if (field >= VM_F_FLOW_F0 && field <= VM_F_FLOW_B1) {
         if (!host) return vm_fail(VM_E_INVALID, "vm_video_get_field: NULL");
-        if (!pg.tslab) return vm_fail(VM_E_STATE, "vm_video_get_field: the coarsest level holds no flows");
+        if (!pg.tslab.get()) return vm_fail(VM_E_STATE, "vm_video_get_field: the coarsest level holds no flows");
         vm_level &l = pg.lv;
         hipStream_t s = v->ctx->stream;
         VM_HIP(hipMemcpy2DAsync(host, (size_t)l.w * 8, pg.flow[field - VM_F_FLOW_F0], (size_t)l.rs * 8, (size_t)l.w * 8, l.h, hipMemcpyDeviceToHost, s));
@@ -353,7 +321,7 @@ extern "C" int vm_video_coarse_solve(vm_video *v, const vm_video_constraint *con
 static int splat_page(vm_video *v, const vm_video_page &src, const float2 *fa, const float2 *fb, bool with_ssim)
 {
     const vm_level &l = src.lv;
-    vm_temp_launch_splat(l.w, l.h, l.rs, l.view.v, fa, fb, with_ssim ? l.view.value : nullptr, v->acc, v->ctx->stream);
+    vm_temp_launch_splat(l.w, l.h, l.rs, l.view.v, fa, fb, with_ssim ? l.view.value : nullptr, v->acc.get(), v->ctx->stream);
     VM_HIP(hipGetLastError());
     return VM_OK;
 }
@@ -380,13 +348,13 @@ extern "C" int vm_video_upsample(vm_video *v, int dst)
             vm_video_page &pg = v->pages[dst][i], &pp = v->pages[dst][i - 1], &pn = v->pages[dst][i + 1];
             vm_level &l = pg.lv;
             const size_t n = (size_t)l.rs * l.h;
-            VM_HIP(hipMemsetAsync(v->acc, 0, n * 3 * sizeof(long long), s));
+            VM_HIP(hipMemsetAsync(v->acc.get(), 0, n * 3 * sizeof(long long), s));
             if ((rc = splat_page(v, pp, pp.flow[0], pp.flow[1], false)) != VM_OK) return rc; // f0, f1 of page i-1
             if ((rc = splat_page(v, pn, pn.flow[2], pn.flow[3], false)) != VM_OK) return rc; // b0, b1 of page i+1
-            vm_temp_launch_finish(l.w, l.h, l.rs, v->acc, v->vcur, v->weight, 0, s);
+            vm_temp_launch_finish(l.w, l.h, l.rs, v->acc.get(), v->vcur.get(), v->weight.get(), 0, s);
             VM_HIP(hipMemsetAsync(l.view.v, 0, n * 8, s));
-            vm_temp_launch_smooth(l.w, l.h, l.rs, l.view.v, v->vcur, v->weight, s);
-            vm_temp_launch_fill_zeros_x(l.w, l.h, l.rs, l.view.v, v->weight, s);
+            vm_temp_launch_smooth(l.w, l.h, l.rs, l.view.v, v->vcur.get(), v->weight.get(), s);
+            vm_temp_launch_fill_zeros_x(l.w, l.h, l.rs, l.view.v, v->weight.get(), s);
             VM_HIP(hipGetLastError());
         }
     }
@@ -401,7 +369,7 @@ extern "C" int vm_video_init_level(vm_video *v, int lvl, const vm_video_constrai
     const int w0 = v->pages[0][0].lv.w, h0 = v->pages[0][0].lv.h;
     for (int z = 0; z < v->depth[lvl]; ++z) {
         vm_video_page &pg = v->pages[lvl][z];
-        if (!pg.tslab) return vm_fail(VM_E_STATE, "vm_video_init_level: the coarsest level is solved by vm_video_coarse_solve");
+        if (!pg.tslab.get()) return vm_fail(VM_E_STATE, "vm_video_init_level: the coarsest level is solved by vm_video_coarse_solve");
         std::vector<vm_constraint> pc = page_constraints(v, lvl, z, cons, n);
         int rc = vm_level_init(v->ctx, pg.lv, w0, h0, pc.data(), (int)pc.size());
         if (rc != VM_OK) return rc;
@@ -425,15 +393,15 @@ extern "C" int vm_video_initialize_temp(vm_video *v, int lvl, int page, int dir)
     const int j = page + dir;
     if (j < 0 || j >= v->depth[lvl]) return vm_fail(VM_E_INVALID, "vm_video_initialize_temp: page %d has no neighbour in direction %d", page, dir);
     vm_video_page &pg = v->pages[lvl][page], &src = v->pages[lvl][j];
-    if (!pg.tslab) return vm_fail(VM_E_STATE, "vm_video_initialize_temp: the coarsest level has no temporal state");
+    if (!pg.tslab.get()) return vm_fail(VM_E_STATE, "vm_video_initialize_temp: the coarsest level has no temporal state");
     if (!src.lv.has_state) return vm_fail(VM_E_STATE, "vm_video_initialize_temp: neighbour page not initialised");
     vm_level &l = pg.lv;
     hipStream_t s = v->ctx->stream;
-    VM_HIP(hipMemsetAsync(v->acc, 0, (size_t)l.rs * l.h * 3 * sizeof(long long), s));
+    VM_HIP(hipMemsetAsync(v->acc.get(), 0, (size_t)l.rs * l.h * 3 * sizeof(long long), s));
     // dir < 0: the neighbour's forward flows carry it here; dir > 0: its backward flows
     int rc = splat_page(v, src, dir < 0 ? src.flow[0] : src.flow[2], dir < 0 ? src.flow[1] : src.flow[3], true);
     if (rc != VM_OK) return rc;
-    vm_temp_launch_finish(l.w, l.h, l.rs, v->acc, pg.temp_ref, pg.temp_mask, 1, s);
+    vm_temp_launch_finish(l.w, l.h, l.rs, v->acc.get(), pg.temp_ref, pg.temp_mask, 1, s);
     VM_HIP(hipGetLastError());
     l.view.temp_ref = pg.temp_ref;   // flag == true for this page from now on
     l.view.temp_mask = pg.temp_mask;
@@ -524,7 +492,7 @@ static int ensure_lanes(vm_video *v, int n)
             for (vm_ctx *q : parked) vm_ctx_destroy(q);
             if (rc != VM_OK) return rc;
         }
-        if (hipMalloc((void **)&ln.acc, np * 3 * sizeof(long long)) != hipSuccess) {
+        if (ln.acc.reserve(np * 3) != VM_OK) {
             vm_ctx_destroy(ln.c);
             return vm_fail(VM_E_DEVICE, "vm_video_solve: out of device memory (pipeline lane)");
         }
@@ -547,7 +515,7 @@ static int ensure_lanes(vm_video *v, int n)
                 ln.c->stream = ps;
             }
         }
-        v->lanes.push_back(ln);
+        v->lanes.push_back(std::move(ln));
     }
     for (vm_video_lane &ln : v->lanes) { // the solver settings of the video's context, as they are now
         ln.c->kp = p->kp;
@@ -598,10 +566,10 @@ static int video_task(vm_video *v, vm_video_lane &ln, int el, int k, float max_i
         l.view.factor_d = v->factor_d[el];
         if (dir[i] != 0) { // initialize_temp(lvl, page, dir), upsample.cu:214-258
             const vm_video_page &src = v->pages[el][idx[i] + dir[i]];
-            VM_HIP(hipMemsetAsync(ln.acc, 0, np * 3 * sizeof(long long), s));
+            VM_HIP(hipMemsetAsync(ln.acc.get(), 0, np * 3 * sizeof(long long), s));
             vm_temp_launch_splat(src.lv.w, src.lv.h, src.lv.rs, src.lv.view.v, dir[i] < 0 ? src.flow[0] : src.flow[2],
-                                 dir[i] < 0 ? src.flow[1] : src.flow[3], src.lv.view.value, ln.acc, s);
-            vm_temp_launch_finish(l.w, l.h, l.rs, ln.acc, pg.temp_ref, pg.temp_mask, 1, s);
+                                 dir[i] < 0 ? src.flow[1] : src.flow[3], src.lv.view.value, ln.acc.get(), s);
+            vm_temp_launch_finish(l.w, l.h, l.rs, ln.acc.get(), pg.temp_ref, pg.temp_mask, 1, s);
             VM_HIP(hipGetLastError());
             l.view.temp_ref = pg.temp_ref;
             l.view.temp_mask = pg.temp_mask;
