@@ -2,7 +2,8 @@
 // (frames + optical flows), the temporally coupled Morph, the halfway field of every frame.
 //   solve_video W H D frames.u8 flows.f32 out_v.f32 [max_iter] [start_res] [exact|fast]
 // frames.u8: D x 2 RGB8 frames (video 0 frame t, video 1 frame t, ...), flows.f32: D x 4 fields
-// (f0, f1, b0, b1 of frame t), out: the full-resolution halfway field of every frame
+// (f0, f1, b0, b1 of frame t) -- or "-": the flows are computed on the device from the frames
+// (MdiEditor::OpticalFlow) --, out: the full-resolution halfway field of every frame
 // (Pyramid::_vector after CMatchingThread::update_result).
 #include <cstdio>
 #include <cstdlib>
@@ -32,7 +33,8 @@ int main(int argc, char **argv)
         params.max_iter_drop_factor = 1.0f;
         const size_t npx = (size_t)w * h;
         std::vector<unsigned char> frames = read_all<unsigned char>(argv[4], npx * 3 * 2 * d);
-        std::vector<float> flows = read_all<float>(argv[5], npx * 2 * 4 * d);
+        const bool computed = !strcmp(argv[5], "-");
+        std::vector<float> flows = computed ? std::vector<float>(npx * 2 * 4 * d) : read_all<float>(argv[5], npx * 2 * 4 * d);
         std::vector<const unsigned char *> v0, v1;
         std::vector<const float *> f0, f1, b0, b1;
         for (int t = 0; t < d; ++t) {
@@ -44,7 +46,10 @@ int main(int argc, char **argv)
             b1.push_back(flows.data() + npx * 2 * (4 * t + 3));
         }
         vmorph::VideoPyramid pyramid(ctx);
-        pyramid.build(v0, v1, f0, f1, b0, b1, w, h, params.start_res);
+        if (computed)
+            pyramid.build(v0, v1, w, h, params.start_res);
+        else
+            pyramid.build(v0, v1, f0, f1, b0, b1, w, h, params.start_res);
         // class CMatchingThread over the video pair: the solve on a worker thread, then update_result()
         vmorph::VideoMatchingThread thread(params, pyramid, w, h);
         thread.start();

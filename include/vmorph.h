@@ -481,6 +481,45 @@ int  vm_sync_render(vm_sync *s, float fa, int frame, uint8_t *rgb_out, int pitch
 /* the same, result left on the device (timing without the download) */
 int  vm_sync_render_dev(vm_sync *s, float fa, int frame, float *elapsed_ms);
 
+/* ---- dense optical flow ---------------------------------------------------- */
+/* MdiEditor::OpticalFlow, UI/MdiEditor.cpp:1584-1689: the reference converts each frame to grey and
+ * runs cuda::FarnebackOpticalFlow with its defaults.  Here: Farneback's two-frame polynomial-expansion
+ * method written from the published method, on the device (DESIGN.md 3.6 states the spec; it is not
+ * bit-compatible with OpenCV).  A flow d maps frame a to frame b: b(x + d(x)) ~ a(x).  Supported:
+ * num_levels >= 0, 0 < pyr_scale < 1, odd win_size in 3..31, num_iters >= 1, poly_n 5 or 7,
+ * poly_sigma > 0; fast_pyramids and flags must be 0; frames at least 32 x 32.  Everything else is
+ * VM_E_INVALID.  Results do not depend on how many flows share a call. */
+typedef struct {
+    int   num_levels;
+    float pyr_scale;
+    int   fast_pyramids;
+    int   win_size;
+    int   num_iters;
+    int   poly_n;
+    float poly_sigma;
+    int   flags;
+} vm_flow_params;
+/* the reference's values (cuda::FarnebackOpticalFlow defaults, UI/MdiEditor.cpp:1584-1689); no device needed */
+int  vm_flow_params_default(vm_flow_params *p);
+/* n independent flows a[i] -> b[i] of one size (UI/MdiEditor.cpp:1584-1689), all in the same launches;
+ * host frames in (RGB8 rows of pitch_bytes, or float luma rows of `pitch` floats; 0 = tight),
+ * flow_xy[i] = tight (h, w, 2) floats out; p == NULL: the defaults */
+int  vm_optical_flow_rgb(vm_ctx *ctx, int w, int h, int n, const uint8_t *const *a, const uint8_t *const *b,
+                         int pitch_bytes, const vm_flow_params *p, float *const *flow_xy);
+int  vm_optical_flow_luma(vm_ctx *ctx, int w, int h, int n, const float *const *a, const float *const *b,
+                          int pitch, const vm_flow_params *p, float *const *flow_xy);
+/* MdiEditor::OpticalFlow of both videos (UI/MdiEditor.cpp:1584-1689) followed by the flow half of
+ * Pyramid::build (as vm_video_build_flows): rgb0[t] / rgb1[t] = the depth0 frames of video 0 / 1;
+ * f[t] = frame t -> t + 1 (zero for the last frame), b[t] = t -> t - 1 (zero for frame 0).  The
+ * flows never leave the device; the pages get what vm_video_build_flows would give them for the
+ * flows vm_optical_flow_rgb returns. */
+int  vm_video_build_flows_rgb(vm_video *v, const uint8_t *const *rgb0, const uint8_t *const *rgb1,
+                              int pitch_bytes, const vm_flow_params *p);
+/* forward flows of both videos (UI/MdiEditor.cpp:1584-1689) from the frames vm_sync_upload_frame put
+ * there, into the layered flow arrays of pyramid.cu:93-141 (the last frame's flow is zero): what
+ * vm_sync_upload_flow of the same flows would leave */
+int  vm_sync_compute_flows(vm_sync *s, const vm_flow_params *p);
+
 /* ---- multi-GPU ----------------------------------------------------------- */
 /* The shared parameter block every rank needs (KernParameters + iteration
  * control + constraints), flattened so that any transport -- the RCCL

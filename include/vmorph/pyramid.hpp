@@ -30,6 +30,19 @@ private:
     vm_ctx *h_ = nullptr;
 };
 
+// MdiEditor::OpticalFlow (UI/MdiEditor.cpp:1584-1689) for n frame pairs of one size in one call: RGB8
+// frames (h*w*3 bytes), flows out as h*w*2 floats each, a[i] -> b[i]; params == nullptr: the defaults
+inline std::vector<std::vector<float>> optical_flow(Context &ctx, const std::vector<const unsigned char *> &a,
+                                                    const std::vector<const unsigned char *> &b, int w, int h,
+                                                    const vm_flow_params *params = nullptr)
+{
+    std::vector<std::vector<float>> out(a.size(), std::vector<float>((size_t)w * h * 2));
+    std::vector<float *> ptr;
+    for (auto &o : out) ptr.push_back(o.data());
+    check(vm_optical_flow_rgb(ctx.handle(), w, h, (int)a.size(), a.data(), b.data(), 0, params, ptr.data()));
+    return out;
+}
+
 class Pyramid;
 
 // struct PyramidLevel, Pyramid.h:52-98 (ctor: pyramid.cu:531-543)

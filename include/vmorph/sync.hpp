@@ -68,6 +68,10 @@ public:
         }
     }
 
+    // the forward flows of both uploaded videos (MdiEditor::OpticalFlow, UI/MdiEditor.cpp:1584-1689),
+    // computed on the device in place of the upload_flow half of build()
+    void compute_flows(const vm_flow_params *params = nullptr) { check(vm_sync_compute_flows(h_, params)); }
+
     size_t size() const { return levels.size(); }
     const SyncLevel &operator[](int el) const { return levels[el]; }
     vm_sync *handle() const { return h_; }

@@ -77,6 +77,18 @@ public:
         check(vm_video_build_flows(h_, f0.data(), f1.data(), b0.data(), b1.data()));
     }
 
+    // OpticalFlow(); pyramid.build(v1, v2, f1, f2, b1, b2, start_res) (UI/MdiEditor.cpp:499-512,
+    // 1584-1689): the same build with the flows computed on the device from the RGB8 frames
+    void build(const std::vector<const unsigned char *> &video0, const std::vector<const unsigned char *> &video1,
+               int w, int h, int start_res, const vm_flow_params *flow_params = nullptr)
+    {
+        const int d = (int)video0.size();
+        create(level_table(w, h, d, start_res), d);
+        for (int t = 0; t < d; ++t)
+            check(vm_video_build_rgb(h_, t, video0[t], video1[t], 0));
+        check(vm_video_build_flows_rgb(h_, video0.data(), video1.data(), 0, flow_params));
+    }
+
     std::vector<float> get_v(int lvl, int page) const
     {
         std::vector<float> v((size_t)levels[lvl].width * levels[lvl].height * 2);

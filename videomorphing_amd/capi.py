@@ -43,6 +43,7 @@ SYMBOLS = [
     "vm_sync_level_table", "vm_sync_create", "vm_sync_destroy", "vm_sync_set_constraints", "vm_sync_load_identity",
     "vm_sync_upsample_level", "vm_sync_optimize_level", "vm_sync_solve", "vm_sync_get_field", "vm_sync_set_field",
     "vm_sync_result", "vm_sync_upload_frame", "vm_sync_upload_flow", "vm_sync_render", "vm_sync_render_dev",
+    "vm_flow_params_default", "vm_optical_flow_rgb", "vm_optical_flow_luma", "vm_video_build_flows_rgb", "vm_sync_compute_flows",
 ]
 
 
@@ -84,6 +85,12 @@ class SyncProgress(C.Structure):
 class ParamBlock(C.Structure):
     _fields_ = [("kp", KernParams), ("max_iter", C.c_float), ("max_iter_drop_factor", C.c_float),
                 ("start_res", C.c_int), ("math_mode", C.c_int), ("n_constraints", C.c_int)]
+
+
+class FlowParams(C.Structure):
+    """vm_flow_params: cuda::FarnebackOpticalFlow's settings (UI/MdiEditor.cpp:1584-1689)"""
+    _fields_ = [("num_levels", C.c_int), ("pyr_scale", C.c_float), ("fast_pyramids", C.c_int), ("win_size", C.c_int),
+                ("num_iters", C.c_int), ("poly_n", C.c_int), ("poly_sigma", C.c_float), ("flags", C.c_int)]
 
 
 class VmError(RuntimeError):
@@ -191,6 +198,11 @@ def load():
         "vm_sync_upload_flow": [vp, i, i, vp, i],
         "vm_sync_render": [vp, f, i, vp, i],
         "vm_sync_render_dev": [vp, f, i, C.POINTER(f)],
+        "vm_flow_params_default": [C.POINTER(FlowParams)],
+        "vm_optical_flow_rgb": [vp, i, i, i, vp, vp, i, C.POINTER(FlowParams), vp],
+        "vm_optical_flow_luma": [vp, i, i, i, vp, vp, i, C.POINTER(FlowParams), vp],
+        "vm_video_build_flows_rgb": [vp, vp, vp, i, C.POINTER(FlowParams)],
+        "vm_sync_compute_flows": [vp, C.POINTER(FlowParams)],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

@@ -4,6 +4,7 @@
 #include "vm_host.h"
 #include "vm_pyramid.h"
 #include "vm_temporal.h"
+#include "vm_flow.h"
 
 #include <cmath>
 #include <map>
@@ -192,16 +193,13 @@ extern "C" int vm_video_build_rgb(vm_video *v, int frame, const uint8_t *rgb0, c
 }
 
 // The flow half of Pyramid::build (pyramid.cu:284-326, 375-456) on the device: the four flow
-// families of all depth0 frames (full resolution, tight (h0, w0, 2) floats) are scaled level by
-// level through load(-50, 50) -> scale() -> store, rescaled by the size ratio, concatenated in
-// time where the temporal pyramid halves the depth, and left in the pages' flow arrays.
-extern "C" int vm_video_build_flows(vm_video *v, const float *const *f0, const float *const *f1,
-                                    const float *const *b0, const float *const *b1)
+// families of all depth0 frames (full resolution, tight (h0, w0, 2) float2 device arrays,
+// flows[k * depth0 + t], k = f0, f1, b0, b1; consumed) are scaled level by level through
+// load(-50, 50) -> scale() -> store, rescaled by the size ratio, concatenated in time where the
+// temporal pyramid halves the depth, and left in the pages' flow arrays.
+static int build_flows_dev(vm_video *v, std::vector<VmDev<float2>> &flows)
 {
-    if (!v || !f0 || !f1 || !b0 || !b1) return vm_fail(VM_E_INVALID, "vm_video_build_flows: NULL argument");
     vm_ctx *c = v->ctx;
-    std::lock_guard<std::recursive_mutex> lock(c->mu);
-    VM_ON_DEVICE(c);
     hipStream_t s = c->stream;
     const int L = (int)v->pages.size(), d0 = v->depth[0];
     const int w0 = v->pages[0][0].lv.w, h0 = v->pages[0][0].lv.h;
@@ -211,20 +209,11 @@ extern "C" int vm_video_build_flows(vm_video *v, const float *const *f0, const f
     if (int rc = B.img.reserve(n0 * 3)) return rc;
     if (int rc = B.tmp.reserve(n0 * 3)) return rc;
     // working set: the current level's flows of every frame of the previous level, tight float2
-    std::vector<VmDev<float2>> flows(4 * (size_t)d0);
     std::vector<float2 *> cur[4]; // views into flows
-    const float *const *src[4] = {f0, f1, b0, b1};
     for (int k = 0; k < 4; ++k) {
         cur[k].resize(d0);
-        for (int t = 0; t < d0; ++t) {
-            if (!src[k][t]) return vm_fail(VM_E_INVALID, "vm_video_build_flows: flow %d of frame %d is NULL", k, t);
-            VmDev<float2> &fl = flows[(size_t)k * d0 + t];
-            if (int rc = fl.reserve(n0)) return rc;
-            cur[k][t] = fl.get();
-            VM_HIP(hipMemcpyAsync(cur[k][t], src[k][t], n0 * 8, hipMemcpyHostToDevice, s));
-        }
+        for (int t = 0; t < d0; ++t) cur[k][t] = flows[(size_t)k * d0 + t].get();
     }
-    VM_HIP(hipStreamSynchronize(s)); // the host arrays belong to the caller
     int pw = w0, ph = h0, prev_d = d0;
     for (int el = 0; el < L - 1; ++el) { // the coarsest level holds no flows (pyramid.cu:329)
         const int w = v->pages[el][0].lv.w, h = v->pages[el][0].lv.h, d = v->depth[el], ft = v->factor_t[el];
@@ -260,4 +249,75 @@ extern "C" int vm_video_build_flows(vm_video *v, const float *const *f0, const f
     }
     VM_HIP(hipStreamSynchronize(s));
     return VM_OK;
+}
+
+extern "C" int vm_video_build_flows(vm_video *v, const float *const *f0, const float *const *f1,
+                                    const float *const *b0, const float *const *b1)
+{
+    if (!v || !f0 || !f1 || !b0 || !b1) return vm_fail(VM_E_INVALID, "vm_video_build_flows: NULL argument");
+    vm_ctx *c = v->ctx;
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    VM_ON_DEVICE(c);
+    hipStream_t s = c->stream;
+    const int d0 = v->depth[0];
+    const size_t n0 = (size_t)v->pages[0][0].lv.w * v->pages[0][0].lv.h;
+    std::vector<VmDev<float2>> flows(4 * (size_t)d0);
+    const float *const *src[4] = {f0, f1, b0, b1};
+    for (int k = 0; k < 4; ++k)
+        for (int t = 0; t < d0; ++t) {
+            if (!src[k][t]) return vm_fail(VM_E_INVALID, "vm_video_build_flows: flow %d of frame %d is NULL", k, t);
+            VmDev<float2> &fl = flows[(size_t)k * d0 + t];
+            if (int rc = fl.reserve(n0)) return rc;
+            VM_HIP(hipMemcpyAsync(fl.get(), src[k][t], n0 * 8, hipMemcpyHostToDevice, s));
+        }
+    VM_HIP(hipStreamSynchronize(s)); // the host arrays belong to the caller
+    return build_flows_dev(v, flows);
+}
+
+// MdiEditor::OpticalFlow (UI/MdiEditor.cpp:1584-1689) of both videos on the device, then the same flow half.
+// Frames are walked in chunks [t0, t1] that share their end frame: f[t] is computed in the chunk with
+// t0 <= t < t1, b[t] in the one with t0 < t <= t1, each exactly once.
+extern "C" int vm_video_build_flows_rgb(vm_video *v, const uint8_t *const *rgb0, const uint8_t *const *rgb1,
+                                        int pitch_bytes, const vm_flow_params *pp)
+{
+    if (!v || !rgb0 || !rgb1) return vm_fail(VM_E_INVALID, "vm_video_build_flows_rgb: NULL argument");
+    const int d0 = v->depth[0], w0 = v->pages[0][0].lv.w, h0 = v->pages[0][0].lv.h;
+    vm_flow_params p;
+    if (int rc = vm_flow_resolve(pp, w0, h0, &p, "vm_video_build_flows_rgb")) return rc;
+    if (pitch_bytes == 0) pitch_bytes = 3 * w0;
+    if (pitch_bytes < 3 * w0) return vm_fail(VM_E_INVALID, "vm_video_build_flows_rgb: pitch < 3*width");
+    for (int t = 0; t < d0; ++t)
+        if (!rgb0[t] || !rgb1[t]) return vm_fail(VM_E_INVALID, "vm_video_build_flows_rgb: frame %d is NULL", t);
+    vm_ctx *c = v->ctx;
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    VM_ON_DEVICE(c);
+    hipStream_t s = c->stream;
+    const size_t n0 = (size_t)w0 * h0;
+    std::vector<VmDev<float2>> flows(4 * (size_t)d0); // f0, f1, b0, b1
+    for (auto &fl : flows) {
+        if (int rc = fl.reserve(n0)) return rc;
+        VM_HIP(hipMemsetAsync(fl.get(), 0, n0 * 8, s)); // f[d0 - 1] and b[0] stay zero
+    }
+    VmDev<uint8_t> stage;
+    if (int rc = stage.reserve(n0 * 3)) return rc;
+    const uint8_t *const *video[2] = {rgb0, rgb1};
+    const int F = vm_flow_video_chunk(w0, h0, p, 2);
+    for (int t0 = 0; t0 < d0 - 1; t0 += F - 1) {
+        const int t1 = std::min(d0 - 1, t0 + F - 1), nfr = t1 - t0 + 1;
+        std::vector<VmFlowPair> pairs;
+        for (int k = 0; k < 2; ++k)
+            for (int t = t0; t <= t1; ++t) { // frame slot of (video k, frame t): k * nfr + t - t0
+                const int slot = k * nfr + t - t0;
+                if (t < t1) pairs.push_back({slot, slot + 1, flows[(size_t)k * d0 + t].get()});
+                if (t > t0) pairs.push_back({slot, slot - 1, flows[(size_t)(2 + k) * d0 + t].get()});
+            }
+        auto src = [&](int f, float *dst) -> int {
+            const uint8_t *hs = video[f / nfr][t0 + f % nfr];
+            VM_HIP(hipMemcpy2DAsync(stage.get(), (size_t)w0 * 3, hs, (size_t)pitch_bytes, (size_t)w0 * 3, h0, hipMemcpyHostToDevice, s));
+            vm_flow_launch_grey_rgb(stage.get(), w0 * 3, w0, h0, dst, s);
+            return VM_OK;
+        };
+        if (int rc = vm_flow_run(c, w0, h0, p, 2 * nfr, src, pairs)) return rc;
+    }
+    return build_flows_dev(v, flows);
 }

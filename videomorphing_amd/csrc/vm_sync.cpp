@@ -3,6 +3,7 @@
 // UI/RenderWidget.cpp:205-227).  Kernels: vm_sync.hip.
 #include "vm_host.h"
 #include "vm_sync.h"
+#include "vm_flow.h"
 
 #include <array>
 #include <cmath>
@@ -436,6 +437,38 @@ extern "C" int vm_sync_upload_flow(vm_sync *s, int side, int frame, const float 
     VM_HIP(hipMemcpy2DAsync(s->forw[side].get() + frame * page, (size_t)w0 * 8, flow_xy, (size_t)pitch_floats * 4, (size_t)w0 * 8, h0,
                             hipMemcpyHostToDevice, s->ctx->stream));
     VM_HIP(hipStreamSynchronize(s->ctx->stream));
+    return VM_OK;
+}
+
+// MdiEditor::OpticalFlow's forward flows (UI/MdiEditor.cpp:1584-1689) of both videos, computed from the
+// uploaded frames straight into the layered flow arrays; the last frame's flow is zero
+extern "C" int vm_sync_compute_flows(vm_sync *s, const vm_flow_params *pp)
+{
+    CHECK_SYNC(s);
+    const int w0 = s->w[0], h0 = s->h[0], d0 = s->d[0];
+    vm_flow_params p;
+    if (int rc = vm_flow_resolve(pp, w0, h0, &p, "vm_sync_compute_flows")) return rc;
+    for (int k = 0; k < 2; ++k)
+        if (!s->video[k].get()) return vm_fail(VM_E_STATE, "vm_sync_compute_flows: no frame of video %d was uploaded", k);
+    hipStream_t st = s->ctx->stream;
+    const size_t page = (size_t)w0 * h0;
+    for (int k = 0; k < 2; ++k) {
+        if (int rc = s->forw[k].reserve(page * d0)) return rc;
+        VM_HIP(hipMemsetAsync(s->forw[k].get() + (d0 - 1) * page, 0, page * sizeof(float2), st));
+    }
+    const int F = vm_flow_video_chunk(w0, h0, p, 2);
+    for (int t0 = 0; t0 < d0 - 1; t0 += F - 1) {
+        const int t1 = std::min(d0 - 1, t0 + F - 1), nfr = t1 - t0 + 1;
+        std::vector<VmFlowPair> pairs;
+        for (int k = 0; k < 2; ++k)
+            for (int t = t0; t < t1; ++t) pairs.push_back({k * nfr + t - t0, k * nfr + t - t0 + 1, s->forw[k].get() + t * page});
+        auto src = [&](int f, float *dst) -> int {
+            vm_flow_launch_grey_rgba(s->video[f / nfr].get() + (t0 + f % nfr) * page, w0, h0, dst, st);
+            return VM_OK;
+        };
+        if (int rc = vm_flow_run(s->ctx, w0, h0, p, 2 * nfr, src, pairs)) return rc;
+    }
+    VM_HIP(hipStreamSynchronize(st));
     return VM_OK;
 }
 

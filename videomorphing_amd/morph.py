@@ -741,6 +741,25 @@ class VideoPyramid(object):
         rgb1 = np.ascontiguousarray(rgb1, dtype=np.uint8)
         capi.check(self._L.vm_video_build_rgb(self._h, int(frame), rgb0.ctypes.data, rgb1.ctypes.data, 0))
 
+    def build_flows_rgb(self, video0, video1, flow_params=None):
+        """MdiEditor::OpticalFlow (UI/MdiEditor.cpp:1584-1689) of both RGB8 videos on the device, then the
+        flow half of Pyramid::build; the flows never leave the device"""
+        v = [[np.ascontiguousarray(x, dtype=np.uint8) for x in vid] for vid in (video0, video1)]
+        n = len(v[0])
+        ptrs = [(C.c_void_p * n)(*[a.ctypes.data for a in vid]) for vid in v]
+        capi.check(self._L.vm_video_build_flows_rgb(self._h, ptrs[0], ptrs[1], 0, _flow_params(flow_params)))
+
+    def build_rgb(self, video0, video1, start_res, flow_params=None):
+        """OpticalFlow(); pyramid.build(v1, v2, f1, f2, b1, b2, start_res) (UI/MdiEditor.cpp:499-512) for RGB8
+        videos (d, h, w, 3): the level table of synth.video_levels, the device image chain per frame
+        (vm_video_build_rgb) and the flows computed on the device"""
+        d, h, w = len(video0), video0[0].shape[0], video0[0].shape[1]
+        levels, factor_t = synth.video_levels(w, h, d, start_res)
+        self.build_levels(levels, factor_t, d)
+        for t in range(d):
+            self.build_rgb_frame(t, video0[t], video1[t])
+        self.build_flows_rgb(video0, video1, flow_params)
+
     def build(self, video0, video1, f0, f1, b0, b1, start_res):
         """Pyramid::build(video0, video1, f0, f1, b0, b1, start_res), pyramid.cu:166-485, for float
         luma frames: geometry incl. the temporal pyramid (synth.video_levels), box-filtered lumas
@@ -909,6 +928,11 @@ class SyncPyramid(object):
         rgb = np.ascontiguousarray(rgb)
         capi.check(self._L.vm_sync_upload_frame(self._h, side, frame, rgb.ctypes.data, rgb.shape[1] * 4))
 
+    def compute_flows(self, params=None):
+        """the forward flows of both uploaded videos (MdiEditor::OpticalFlow, UI/MdiEditor.cpp:1584-1689),
+        computed on the device into the renderer's flow arrays"""
+        capi.check(self._L.vm_sync_compute_flows(self._h, _flow_params(params)))
+
     def upload_flow(self, side, frame, flow):
         flow = np.ascontiguousarray(flow, np.float32)
         capi.check(self._L.vm_sync_upload_flow(self._h, side, frame, flow.ctypes.data, flow.shape[1] * 2))
@@ -1035,3 +1059,60 @@ class SyncThread(object):
         for z in range(pyr.levels[el][2]):
             pyr._vector[z] = pyr.result(el, z)
         self.percentage = (self._current_iter / self._total_iter * 100.0) if self._total_iter else 100.0
+
+
+# ---- dense optical flow (MdiEditor::OpticalFlow, UI/MdiEditor.cpp:1584-1689) ---------------------------
+
+class FlowParams(capi.FlowParams):
+    """cuda::FarnebackOpticalFlow's settings; FlowParams() holds the reference's defaults, keywords override"""
+
+    def __init__(self, **kw):
+        capi.FlowParams.__init__(self)
+        capi.check(capi.load().vm_flow_params_default(C.byref(self)))
+        for k, v in kw.items():
+            if k not in dict(capi.FlowParams._fields_):
+                raise TypeError("FlowParams has no field %r" % k)
+            setattr(self, k, v)
+
+
+def _flow_params(params):
+    return None if params is None else C.byref(params)
+
+
+def optical_flow(ctx, frames_a, frames_b, params=None):
+    """n flows a[i] -> b[i] (b(x + d) ~ a(x)) in the same launches: frames (n, h, w, 3) uint8 or
+    (n, h, w) float luma (a single frame without the leading n is accepted); returns (n, h, w, 2) float32"""
+    a, b = np.asarray(frames_a), np.asarray(frames_b)
+    rgb = a.dtype == np.uint8
+    if a.ndim == (3 if rgb else 2):
+        a, b = a[None], b[None]
+    if a.shape != b.shape or a.ndim != (4 if rgb else 3) or (rgb and a.shape[-1] != 3):
+        raise ValueError("optical_flow: frames of shape %s and %s" % (a.shape, b.shape))
+    a = np.ascontiguousarray(a, np.uint8 if rgb else np.float32)
+    b = np.ascontiguousarray(b, np.uint8 if rgb else np.float32)
+    n, h, w = a.shape[:3]
+    out = np.zeros((n, h, w, 2), np.float32)
+    pa = (C.c_void_p * n)(*[a[i].ctypes.data for i in range(n)])
+    pb = (C.c_void_p * n)(*[b[i].ctypes.data for i in range(n)])
+    po = (C.c_void_p * n)(*[out[i].ctypes.data for i in range(n)])
+    fn = ctx._L.vm_optical_flow_rgb if rgb else ctx._L.vm_optical_flow_luma
+    capi.check(fn(ctx._h, w, h, n, pa, pb, 0, _flow_params(params), po))
+    return out
+
+
+def video_optical_flows(ctx, video0, video1, params=None):
+    """MdiEditor::OpticalFlow of two videos (d frames each, RGB8 or float luma): (f0, f1, b0, b1), each
+    (d, h, w, 2); f[t] = t -> t + 1 (zero for the last frame), b[t] = t -> t - 1 (zero for frame 0).  All
+    4 (d - 1) flows go through one vm_optical_flow_* call as independent pairs (a frame is expanded once per
+    pair it is in; VideoPyramid.build_rgb keeps the flows on the device and expands each frame once)."""
+    v0, v1 = np.asarray(video0), np.asarray(video1)
+    d = len(v0)
+    out = [np.zeros(v0.shape[:3] + (2,), np.float32) for _ in range(4)]
+    if d < 2:
+        return tuple(out)
+    a = np.concatenate([v0[:-1], v1[:-1], v0[1:], v1[1:]])
+    b = np.concatenate([v0[1:], v1[1:], v0[:-1], v1[:-1]])
+    fl = optical_flow(ctx, a, b, params)
+    m = d - 1
+    out[0][:-1], out[1][:-1], out[2][1:], out[3][1:] = fl[:m], fl[m:2 * m], fl[2 * m:3 * m], fl[3 * m:]
+    return tuple(out)
