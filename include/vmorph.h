@@ -520,6 +520,52 @@ int  vm_video_build_flows_rgb(vm_video *v, const uint8_t *const *rgb0, const uin
  * vm_sync_upload_flow of the same flows would leave */
 int  vm_sync_compute_flows(vm_sync *s, const vm_flow_params *p);
 
+/* ---- key-point tracks of stage 2 ------------------------------------------- */
+/* MdiEditor keeps the full-resolution frames and flows of both videos (resample1/2, f1/f2, b1/b2) and
+ * walks every user key-point through the other frames of its video along them: AddPoint
+ * (UI/MdiEditor.cpp:1230-1276), MovePoint (:1279-1393), each propagated point weighed by the histogram
+ * correlation of its patch against the key's (Histo, :1516-1582).  vm_track holds that data on the
+ * device; vm_track_propagate computes any number of track segments in one launch.  The arithmetic is
+ * stated in DESIGN.md 3.7 (tests/track_ref.py); side 0 = the left video, 1 = the right. */
+typedef struct vm_track vm_track;
+/* a track segment.  Chain (ofr < 0): from key (x, y, frame) in direction dir (+1 / -1) up to the last /
+ * first frame, AddPoint's loops and MovePoint's with no key on that side.  Blend (ofr >= 0): the frames
+ * strictly between the moved key (x, y, frame) and the neighbouring key (ox, oy, ofr), MovePoint's
+ * blend of the two chains (:1315-1339, :1368-1392); dir is 0 or the sign of ofr - frame. */
+typedef struct {
+    int side;
+    int x, y, frame;
+    int ox, oy, ofr;
+    int dir;
+} vm_track_segment;
+/* a propagated point (Conp with w = 0): position and weight */
+typedef struct {
+    int   x, y;
+    float weight;
+} vm_track_point;
+/* frames w x h (at least 32 x 32, as the flow), `depth` frames per video (1..16384) */
+int  vm_track_create(vm_ctx *ctx, int w, int h, int depth, vm_track **out);
+void vm_track_destroy(vm_track *t);
+/* one RGB8 frame of video `side` (pitch_bytes; 0 = tight) */
+int  vm_track_upload_frame(vm_track *t, int side, int frame, const uint8_t *rgb, int pitch_bytes);
+/* f[frame] (frame -> frame + 1) and b[frame] (frame -> frame - 1) of video `side`, tight rows of
+ * `pitch` floats (0 = 2 w); either may be NULL (left as it is).  Every value must be finite and within
+ * +-1e5 px (VM_E_INVALID otherwise): with keys within +-1e6 px every position stays an int. */
+int  vm_track_upload_flows(vm_track *t, int side, int frame, const float *f_xy, const float *b_xy, int pitch);
+/* MdiEditor::OpticalFlow (:1584-1689) of both uploaded videos, as vm_video_build_flows_rgb computes
+ * them; f[depth - 1] and b[0] are zero */
+int  vm_track_compute_flows(vm_track *t, const vm_flow_params *p);
+/* the flows of (side, frame) back to the host; either output may be NULL */
+int  vm_track_get_flows(vm_track *t, int side, int frame, float *f_xy, float *b_xy);
+/* n segments in one launch: segment i writes out[i * depth + s] for every frame s it covers and
+ * nothing else.  VM_E_INVALID for a bad side / frame / direction, equal key frames of a blend or a key
+ * beyond +-1e6 px,
+ * VM_E_STATE when a frame or flow the segment reads was never supplied. */
+int  vm_track_propagate(vm_track *t, const vm_track_segment *seg, int n, vm_track_point *out);
+/* the flow half of Pyramid::build (as vm_video_build_flows) from the tracker's flows: NextStage's one
+ * OpticalFlow (:1714-1791) serves the tracks and the stage-2 pyramid.  The sizes must match. */
+int  vm_video_build_flows_track(vm_video *v, const vm_track *t);
+
 /* ---- multi-GPU ----------------------------------------------------------- */
 /* The shared parameter block every rank needs (KernParameters + iteration
  * control + constraints), flattened so that any transport -- the RCCL

@@ -57,6 +57,8 @@ UNITS = [
     ("vm_sync.hip", "vm_sync_kernels.o", ["-ffp-contract=off"]),
     ("vm_flow.hip", "vm_flow_kernels.o", ["-ffp-contract=off"]),
     ("vm_flow.cpp", "vm_flow.o", ["-x", "hip"]),
+    ("vm_track.hip", "vm_track_kernels.o", ["-ffp-contract=off"]),
+    ("vm_track.cpp", "vm_track.o", ["-x", "hip"]),
     ("vm_sync.cpp", "vm_sync.o", ["-x", "hip"]),
     ("vm_video.cpp", "vm_video.o", ["-x", "hip"]),
     ("vm_pyramid_api.cpp", "vm_pyramid_api.o", ["-x", "hip"]),

@@ -44,6 +44,8 @@ SYMBOLS = [
     "vm_sync_upsample_level", "vm_sync_optimize_level", "vm_sync_solve", "vm_sync_get_field", "vm_sync_set_field",
     "vm_sync_result", "vm_sync_upload_frame", "vm_sync_upload_flow", "vm_sync_render", "vm_sync_render_dev",
     "vm_flow_params_default", "vm_optical_flow_rgb", "vm_optical_flow_luma", "vm_video_build_flows_rgb", "vm_sync_compute_flows",
+    "vm_track_create", "vm_track_destroy", "vm_track_upload_frame", "vm_track_upload_flows", "vm_track_compute_flows",
+    "vm_track_get_flows", "vm_track_propagate", "vm_video_build_flows_track",
 ]
 
 
@@ -91,6 +93,17 @@ class FlowParams(C.Structure):
     """vm_flow_params: cuda::FarnebackOpticalFlow's settings (UI/MdiEditor.cpp:1584-1689)"""
     _fields_ = [("num_levels", C.c_int), ("pyr_scale", C.c_float), ("fast_pyramids", C.c_int), ("win_size", C.c_int),
                 ("num_iters", C.c_int), ("poly_n", C.c_int), ("poly_sigma", C.c_float), ("flags", C.c_int)]
+
+
+class TrackSegment(C.Structure):
+    """vm_track_segment: key (x, y, frame) of video `side`; ofr < 0: a chain in direction dir, else the
+    blend towards the neighbouring key (ox, oy, ofr)"""
+    _fields_ = [("side", C.c_int), ("x", C.c_int), ("y", C.c_int), ("frame", C.c_int),
+                ("ox", C.c_int), ("oy", C.c_int), ("ofr", C.c_int), ("dir", C.c_int)]
+
+
+class TrackPoint(C.Structure):
+    _fields_ = [("x", C.c_int), ("y", C.c_int), ("weight", C.c_float)]
 
 
 class VmError(RuntimeError):
@@ -203,12 +216,19 @@ def load():
         "vm_optical_flow_luma": [vp, i, i, i, vp, vp, i, C.POINTER(FlowParams), vp],
         "vm_video_build_flows_rgb": [vp, vp, vp, i, C.POINTER(FlowParams)],
         "vm_sync_compute_flows": [vp, C.POINTER(FlowParams)],
+        "vm_track_create": [vp, i, i, i, C.POINTER(vp)],
+        "vm_track_upload_frame": [vp, i, i, vp, i],
+        "vm_track_upload_flows": [vp, i, i, vp, vp, i],
+        "vm_track_compute_flows": [vp, C.POINTER(FlowParams)],
+        "vm_track_get_flows": [vp, i, i, vp, vp],
+        "vm_track_propagate": [vp, vp, i, vp],
+        "vm_video_build_flows_track": [vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
         fn.argtypes = args
         fn.restype = i
-    for name in ("vm_ctx_destroy", "vm_pyramid_destroy", "vm_frame_destroy", "vm_video_destroy", "vm_sync_destroy", "vm_rccl_comm_destroy"):
+    for name in ("vm_ctx_destroy", "vm_pyramid_destroy", "vm_frame_destroy", "vm_video_destroy", "vm_sync_destroy", "vm_track_destroy", "vm_rccl_comm_destroy"):
         getattr(L, name).argtypes = [vp]
         getattr(L, name).restype = None
     _lib = L

@@ -5,6 +5,7 @@
 #include "vm_pyramid.h"
 #include "vm_temporal.h"
 #include "vm_flow.h"
+#include "vm_track.h"
 
 #include <cmath>
 #include <map>
@@ -271,6 +272,37 @@ extern "C" int vm_video_build_flows(vm_video *v, const float *const *f0, const f
             VM_HIP(hipMemcpyAsync(fl.get(), src[k][t], n0 * 8, hipMemcpyHostToDevice, s));
         }
     VM_HIP(hipStreamSynchronize(s)); // the host arrays belong to the caller
+    return build_flows_dev(v, flows);
+}
+
+// The same flow half from a tracker's flows (NextStage, UI/MdiEditor.cpp:1714-1791: one OpticalFlow serves the
+// tracks and the pyramid).  build_flows_dev consumes its input, so the flows are copied device to device.
+extern "C" int vm_video_build_flows_track(vm_video *v, const vm_track *t)
+{
+    if (!v || !t) return vm_fail(VM_E_INVALID, "vm_video_build_flows_track: NULL argument");
+    if (t->ctx != v->ctx) return vm_fail(VM_E_INVALID, "vm_video_build_flows_track: the tracker belongs to another context");
+    vm_ctx *c = v->ctx;
+    if (!vm_ctx_alive(c)) return vm_fail(VM_E_INVALID, "vm_video_build_flows_track: the context was destroyed");
+    const int d0 = v->depth[0], w0 = v->pages[0][0].lv.w, h0 = v->pages[0][0].lv.h;
+    if (t->w != w0 || t->h != h0 || t->depth != d0)
+        return vm_fail(VM_E_INVALID, "vm_video_build_flows_track: tracker of %d frames of %d x %d, video of %d frames of %d x %d",
+                       t->depth, t->w, t->h, d0, w0, h0);
+    for (int k = 0; k < 2; ++k)
+        for (int i = 0; i < d0; ++i)
+            if (!t->has_f[k][i] || !t->has_b[k][i])
+                return vm_fail(VM_E_STATE, "vm_video_build_flows_track: the flows of frame %d of video %d were never supplied", i, k);
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    VM_ON_DEVICE(c);
+    hipStream_t s = c->stream;
+    const size_t n0 = (size_t)w0 * h0;
+    std::vector<VmDev<float2>> flows(4 * (size_t)d0); // f0, f1, b0, b1
+    const VmDev<float2> *src[4] = {&t->f[0], &t->f[1], &t->b[0], &t->b[1]};
+    for (int k = 0; k < 4; ++k)
+        for (int i = 0; i < d0; ++i) {
+            VmDev<float2> &fl = flows[(size_t)k * d0 + i];
+            if (int rc = fl.reserve(n0)) return rc;
+            VM_HIP(hipMemcpyAsync(fl.get(), src[k]->get() + (size_t)i * n0, n0 * 8, hipMemcpyDeviceToDevice, s));
+        }
     return build_flows_dev(v, flows);
 }
 

@@ -1116,3 +1116,194 @@ def video_optical_flows(ctx, video0, video1, params=None):
     m = d - 1
     out[0][:-1], out[1][:-1], out[2][1:], out[3][1:] = fl[:m], fl[m:2 * m], fl[2 * m:3 * m], fl[3 * m:]
     return tuple(out)
+
+
+# ---- key-point tracks of stage 2 (MdiEditor::AddPoint / MovePoint / NextStage, UI/MdiEditor.cpp) -------
+
+TRACK_POINT = np.dtype([("x", "<i4"), ("y", "<i4"), ("weight", "<f4")])
+
+
+class PointTracker(object):
+    """MdiEditor's resample1/2, f1/f2, b1/b2 on the device (vm_track): the full-resolution RGB8 frames
+    of both videos (d, h, w, 3) and their flows.  flows = (f0, f1, b0, b1), each (d, h, w, 2) as
+    video_optical_flows returns them; None: computed on the device (vm_track_compute_flows)."""
+
+    def __init__(self, ctx, video0, video1, flows=None, flow_params=None):
+        self._ctx, self._L = ctx, capi.load()
+        self._h = None
+        v = [np.asarray(x) for x in (video0, video1)]
+        if v[0].shape != v[1].shape or v[0].ndim != 4 or v[0].shape[-1] != 3 or v[0].dtype != np.uint8:
+            raise ValueError("PointTracker: two RGB8 videos (d, h, w, 3) of one shape wanted")
+        self.depth, self.height, self.width = v[0].shape[:3]
+        h = C.c_void_p()
+        capi.check(self._L.vm_track_create(ctx._h, self.width, self.height, self.depth, C.byref(h)))
+        self._h = h
+        for side in range(2):
+            for t in range(self.depth):
+                fr = np.ascontiguousarray(v[side][t])
+                capi.check(self._L.vm_track_upload_frame(self._h, side, t, fr.ctypes.data, 0))
+        if flows is None:
+            capi.check(self._L.vm_track_compute_flows(self._h, _flow_params(flow_params)))
+        else:
+            fam = [np.ascontiguousarray(x, dtype=np.float32) for x in flows]
+            for side in range(2):
+                for t in range(self.depth):
+                    capi.check(self._L.vm_track_upload_flows(self._h, side, t, fam[side][t].ctypes.data,
+                                                             fam[2 + side][t].ctypes.data, 0))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.vm_track_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def get_flows(self, side, frame):
+        """(f[frame], b[frame]) of video `side`, each (h, w, 2) float32"""
+        f = np.zeros((self.height, self.width, 2), np.float32)
+        b = np.zeros_like(f)
+        capi.check(self._L.vm_track_get_flows(self._h, int(side), int(frame), f.ctypes.data, b.ctypes.data))
+        return f, b
+
+    def propagate(self, segments):
+        """vm_track_propagate: segments [(side, x, y, frame, ox, oy, ofr, dir)] -> (n, depth) TRACK_POINT array;
+        only the frames a segment covers are written (the rest stay zero)"""
+        n = len(segments)
+        segs = (capi.TrackSegment * max(n, 1))()
+        for i, s in enumerate(segments):
+            segs[i] = capi.TrackSegment(*[int(v) for v in s])
+        out = np.zeros((n, self.depth), TRACK_POINT)
+        capi.check(self._L.vm_track_propagate(self._h, segs, n, out.ctypes.data))
+        return out
+
+
+def _segment_tuple(side, seg):
+    """("chain", key, dir) / ("blend", m, o) with keys (x, y, z) -> the vm_track_segment fields"""
+    if seg[0] == "chain":
+        k = seg[1]
+        return (side, k[0], k[1], k[2], 0, 0, -1, seg[2])
+    m, o = seg[1], seg[2]
+    return (side, m[0], m[1], m[2], o[0], o[1], o[2], 0)
+
+
+def _covered(seg, d):
+    if seg[0] == "chain":
+        z = seg[1][2]
+        return range(z + 1, d) if seg[2] > 0 else range(0, z)
+    a, b = sorted((seg[1][2], seg[2][2]))
+    return range(a + 1, b)
+
+
+def _apply(track, seg, row, d):
+    for s in _covered(seg, d):
+        track[s] = Conp(int(row[s]["x"]), int(row[s]["y"]), s, 0, float(row[s]["weight"]))
+
+
+def _track_points(P, side):
+    return P.lp if side == 0 else P.rp
+
+
+def _add_point(self, side, x, y, frame, tracker):
+    """MdiEditor::AddPoint (UI/MdiEditor.cpp:1230-1276) on the device: a new track of `side` (0 = lp, 1 = rp)
+    from the key (x, y) at `frame`, walked through every other frame; returns the track's index"""
+    d = tracker.depth
+    key = (int(x), int(y), int(frame))
+    segs = [("chain", key, -1), ("chain", key, 1)]
+    out = tracker.propagate([_segment_tuple(side, s) for s in segs])
+    track = [None] * d
+    track[key[2]] = Conp(key[0], key[1], key[2], 1, 1.0)
+    for s, row in zip(segs, out):
+        _apply(track, s, row, d)
+    pts = _track_points(self, side)
+    pts.append(track)
+    return len(pts) - 1
+
+
+def _move_point(self, side, track, frame, x, y, tracker):
+    """MdiEditor::MovePoint (UI/MdiEditor.cpp:1279-1393) on the device: the key of `track` at `frame` becomes
+    (x, y); the frames up to the neighbouring keys (or the ends) are propagated again, blended with the
+    neighbours' chains"""
+    pts = _track_points(self, side)[track]
+    d = len(pts)
+    frame = int(frame)
+    pts[frame] = Conp(int(x), int(y), frame, 1, 1.0)
+    m = (int(x), int(y), frame)
+    beg = next((j for j in range(frame - 1, -1, -1) if pts[j].p[3]), None)
+    end = next((j for j in range(frame + 1, d) if pts[j].p[3]), None)
+    segs = [("chain", m, -1) if beg is None else ("blend", m, pts[beg].p[:3]),
+            ("chain", m, 1) if end is None else ("blend", m, pts[end].p[:3])]
+    out = tracker.propagate([_segment_tuple(side, s) for s in segs])
+    for s, row in zip(segs, out):
+        _apply(pts, s, row, d)
+
+
+def _connect_point(self, l_track, r_track):
+    """the stage-2 branch of MdiEditor::ConnectPoint (UI/MdiEditor.cpp:1395-1475, thread_flag >= 2): a per-frame
+    list (l_track, t) - (r_track, t) is added when neither track is connected, removed when exactly this pair
+    is; nothing happens when only one of them is connected elsewhere"""
+    for k, row in enumerate(self.cnt):
+        for c in row:
+            if c.li[0] == l_track or c.ri[0] == r_track:
+                if c.li[0] == l_track and c.ri[0] == r_track:
+                    del self.cnt[k]
+                return
+    d = len(self.lp[l_track])
+    self.cnt.append([Connect((l_track, t), (r_track, t)) for t in range(d)])
+
+
+Parameters.add_point = _add_point
+Parameters.move_point = _move_point
+Parameters.connect_point = _connect_point
+
+
+def stage_two_parameters(P_sync, tracker):
+    """NextStage's points section (UI/MdiEditor.cpp:1714-1791): stage-1 connection j of list i becomes a key at
+    ((x, y), (lz + rz) / 2) on track i of either side -- AddPoint for j = 0, MovePoint for a later j -- and list
+    i becomes the d connects (i, t) - (i, t).  All segments of both sides go through ONE vm_track_propagate
+    call, in the segment form.  Returns a new Parameters with P_sync's settings.  An empty
+    stage-1 list (which the editor never leaves) is a ValueError."""
+    import copy
+    P = copy.copy(P_sync)
+    P.lp, P.rp, P.cnt = [], [], []
+    d = tracker.depth
+    keys = [[], []]  # per side, per list: {z: ((x, y, z), time of the last edit)}
+    for i, row in enumerate(P_sync.cnt):
+        if not row:
+            raise ValueError("stage_two_parameters: stage-1 connection list %d is empty" % i)
+        kk = [{}, {}]
+        for j, c in enumerate(row):
+            l, r = P_sync.lp[c.li[0]][c.li[1]].p, P_sync.rp[c.ri[0]][c.ri[1]].p
+            z = int((l[2] + r[2]) // 2 + 0.5)
+            kk[0][z] = ((l[0], l[1], z), j)
+            kk[1][z] = ((r[0], r[1], z), j)
+        keys[0].append(kk[0])
+        keys[1].append(kk[1])
+    jobs = []  # (side, list, segment)
+    for side in range(2):
+        for i, kk in enumerate(keys[side]):
+            zs = sorted(kk)
+            jobs.append((side, i, ("chain", kk[zs[0]][0], -1)))
+            jobs.append((side, i, ("chain", kk[zs[-1]][0], 1)))
+            for a, b in zip(zs, zs[1:]):
+                (ka, ta), (kb, tb) = kk[a], kk[b]
+                jobs.append((side, i, ("blend", ka, kb) if ta > tb else ("blend", kb, ka)))
+    out = tracker.propagate([_segment_tuple(side, s) for side, _, s in jobs])
+    tracks = [[[None] * d for _ in keys[0]], [[None] * d for _ in keys[1]]]
+    for side in range(2):
+        for i, kk in enumerate(keys[side]):
+            for z, (k, _) in kk.items():
+                tracks[side][i][z] = Conp(k[0], k[1], z, 1, 1.0)
+    for (side, i, s), row in zip(jobs, out):
+        _apply(tracks[side][i], s, row, d)
+    P.lp, P.rp = tracks
+    P.cnt = [[Connect((i, t), (i, t)) for t in range(d)] for i in range(len(keys[0]))]
+    return P
+
+
+def _video_build_flows_track(self, tracker):
+    """the flow half of Pyramid::build from the tracker's flows (device to device): NextStage's one
+    OpticalFlow serves the tracks and the stage-2 pyramid"""
+    capi.check(self._L.vm_video_build_flows_track(self._h, tracker._h))
+
+
+VideoPyramid.build_flows_track = _video_build_flows_track
