@@ -1065,7 +1065,7 @@ def test_dense_sweeps_do_not_depend_on_the_workgroup_size(gpu_ctx, w, h):
     256- and with 512-thread workgroups: the same bits in every state array and the same counters -- the lane
     fan-out per candidate, which orders the FAST sums, is a constant of the kernel; a 256-thread workgroup takes
     a full phase in two rounds.  (The library picks 256 for such levels when enough of their workgroups are in
-    flight on the device to pair up on the CUs: vm_api.cpp, SmallDensePresence.)"""
+    flight on the device to pair up on the CUs: vm_sweep_sched.cpp, SmallDensePresence.)"""
     gpu_ctx.set_math_mode(capi.MATH_FAST)
     gpu_ctx.set_params(morph.KernParameters(morph.Parameters()))
     i0, i1 = synth.make_pair(w, h)

@@ -63,6 +63,7 @@ UNITS = [
     ("vm_video.cpp", "vm_video.o", ["-x", "hip"]),
     ("vm_pyramid_api.cpp", "vm_pyramid_api.o", ["-x", "hip"]),
     ("vm_api.cpp", "vm_api.o", ["-x", "hip"]),
+    ("vm_sweep_sched.cpp", "vm_sweep_sched.o", ["-x", "hip"]),
     ("vm_host.cpp", "vm_host.o", ["-x", "hip"]),
     ("vm_frame.cpp", "vm_frame.o", ["-x", "hip"]),
     ("vm_poisson_api.cpp", "vm_poisson_api.o", ["-x", "hip"]),

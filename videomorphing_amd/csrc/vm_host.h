@@ -94,7 +94,7 @@ struct vm_ctx {
     int sweep_parts = 0;             // workgroups per tile in the SPLIT schedule, 0 = automatic
     VmDev<VmLevelView> views;        // device copies of the level views of the current batch
     VmDev<vm_constraint> cons_dev;
-    // hipGraph replay of launch-bound TILE sweeps (vm_api.cpp): 8 iterations per graph
+    // hipGraph replay of launch-bound TILE sweeps (vm_sweep_sched.cpp): 8 iterations per graph
     VmDev<int> iter_dev;             // device iteration counter read by the replayed kernels
     struct SweepGraph {
         int math_mode;
@@ -122,7 +122,7 @@ struct vm_ctx {
 struct vm_level {
     int w = 0, h = 0, rs = 0, imp_rs = 0, imp_rows = 0;
     VmDev<char> slab;
-    VmDev<char> ws;                  // SPLIT / STEP workspace, allocated on first use (vm_api.cpp)
+    VmDev<char> ws;                  // SPLIT / STEP workspace, allocated on first use (vm_sweep_sched.cpp)
     VmDev<char> sp_ws;               // SPARSE workspace (word lists, stamps), allocated on first use
     bool has_state = false;
     VmLevelView view{};
@@ -220,6 +220,7 @@ int vm_level_alloc(vm_ctx *c, vm_level &l, bool with_images);
 int vm_level_upsample(vm_ctx *c, vm_level &dst, const vm_level &src);
 int vm_level_init(vm_ctx *c, vm_level &l, int w0, int h0, const vm_constraint *cons, int n);
 int vm_level_read_field(vm_ctx *c, vm_level &l, int field, void *host);
+// the sweep of one level (vm_sweep_sched.cpp)
 int vm_iteration_cap(float max_iter, int *cap);
 int vm_optimize_levels(vm_ctx *c, vm_level **lv, int n, float max_iter, volatile const int *run_flag,
                        int fixed_work, vm_progress *out);
