@@ -1,10 +1,17 @@
-"""CPU statement (numpy, float64) of the dense optical flow the library computes on the GPU
+"""CPU statement (numpy, float64 by default) of the dense optical flow the library computes on the GPU
 (DESIGN.md 3.6): Farneback's two-frame polynomial-expansion method with the parameters of the
 reference's cuda::FarnebackOpticalFlow defaults (UI/MdiEditor.cpp:1584-1689).  Written from the
 published method; it is the spec the HIP kernels (videomorphing_amd/csrc/vm_flow.hip) are checked
 against, not a copy of any library's code.
 
-Sign convention: frame_b(x + d(x)) ~= frame_a(x).  Arrays are (h, w) images and (h, w, 2) flows."""
+Sign convention: frame_b(x + d(x)) ~= frame_a(x).  Arrays are (h, w) images and (h, w, 2) flows.
+
+Working precision: blur, resize, poly_exp, iterate and flow take `dtype`.  With np.float32 every array and
+every intermediate is float32; the constants (taps, inverse Gram entries, 1 / pyr_scale) are computed in
+float64 and rounded once, as the host code does.  dist(flow(.., dtype=float32), flow(..)) is the yardstick
+of the GPU checks: what float32 arithmetic in another order may differ by (tests/test_gpu_flow_stages.py).
+
+pyr_scale and poly_sigma cross the C ABI as float32: pass f32(v) to state what the library is given."""
 import numpy as np
 
 DEFAULTS = dict(num_levels=5, pyr_scale=0.5, fast_pyramids=0, win_size=13, num_iters=10,
@@ -12,10 +19,18 @@ DEFAULTS = dict(num_levels=5, pyr_scale=0.5, fast_pyramids=0, win_size=13, num_i
 EDGE_W = (0.14, 0.14, 0.4472, 0.4472, 0.4472)
 
 
+MAX_BLUR_R = 96  # the library's VM_FLOW_MAX_BLUR_R
+
+
 def params(**kw):
     p = dict(DEFAULTS)
     p.update(kw)
     return p
+
+
+def f32(v):
+    """the double a float32 field of vm_flow_params holds when it is set to v"""
+    return float(np.float32(v))
 
 
 def grey(rgb):
@@ -52,8 +67,9 @@ def _reflect101(i, n):
     return np.where(i >= n, 2 * n - 2 - i, i)
 
 
-def blur(img, taps):
+def blur(img, taps, dtype=np.float64):
     """separable Gaussian, rows then columns, reflect-101 border"""
+    img, taps = img.astype(dtype), np.asarray(taps).astype(dtype)
     h, w = img.shape
     r = len(taps) // 2
     xs = _reflect101(np.arange(-r, w + r), w)
@@ -62,29 +78,30 @@ def blur(img, taps):
     return sum(taps[j] * tmp[ys[j:j + h], :] for j in range(2 * r + 1))
 
 
-def _axis(n_dst, n_src):
-    s = np.clip((np.arange(n_dst) + 0.5) * n_src / n_dst - 0.5, 0, n_src - 1)
-    i0 = np.floor(s).astype(np.int64)
+def _axis(n_dst, n_src, dtype=np.float64):
+    s = np.clip((np.arange(n_dst, dtype=dtype) + 0.5) * n_src / n_dst - 0.5, 0, n_src - 1)
+    i0 = np.minimum(np.floor(s).astype(np.int64), n_src - 1)
     i1 = np.minimum(i0 + 1, n_src - 1)
-    return i0, i1, s - i0
+    return i0, i1, s - i0.astype(dtype)
 
 
-def resize(img, w, h):
+def resize(img, w, h, dtype=np.float64):
     """bilinear, source coordinate (x + 0.5) * W / w - 0.5 clamped to the image; (h, w) or (h, w, c)"""
+    img = img.astype(dtype)
     H, W = img.shape[:2]
-    x0, x1, fx = _axis(w, W)
-    y0, y1, fy = _axis(h, H)
+    x0, x1, fx = _axis(w, W, dtype)
+    y0, y1, fy = _axis(h, H, dtype)
     if img.ndim == 3:
         fx, fy = fx[:, None], fy[:, None]
     rows = img[y0] * (1 - fy[:, None]) + img[y1] * fy[:, None]
     return rows[:, x0] * (1 - fx) + rows[:, x1] * fx
 
 
-def scale_images(frame, p):
+def scale_images(frame, p, dtype=np.float64):
     h, w = frame.shape
     out = []
     for k, (s, wk, hk) in enumerate(scales(w, h, p["num_levels"], p["pyr_scale"])):
-        out.append(frame.astype(np.float64) if k == 0 else resize(blur(frame.astype(np.float64), blur_taps(s)), wk, hk))
+        out.append(frame.astype(dtype) if k == 0 else resize(blur(frame, blur_taps(s), dtype), wk, hk, dtype))
     return out
 
 
@@ -97,13 +114,20 @@ def poly_inverse(n, sigma):
     return g, t, np.linalg.inv(G), 1.0 / (m0 * m2), 1.0 / (m2 * m2)
 
 
-def poly_exp(img, poly_n=5, poly_sigma=1.1):
+def poly_consts(n, sigma, dtype=np.float64):
+    """poly_inverse's pieces, computed in float64 and rounded once to the working precision"""
+    g, t, Gi, ib, ixy = poly_inverse(n, sigma)
+    return g.astype(dtype), t.astype(dtype), Gi.astype(dtype), dtype(ib), dtype(ixy)
+
+
+def poly_exp(img, poly_n=5, poly_sigma=1.1, dtype=np.float64):
     """per pixel f ~ c + b.x + x'Ax by weighted least squares over a poly_n^2 window
     (weights g(u) g(v), replicate border), separably; returns (h, w, 5) = b_x, b_y, A_xx, A_yy, A_xy
     (A_xy the full coefficient of x*y)"""
+    img = img.astype(dtype)
     h, w = img.shape
     n = poly_n // 2
-    g, t, Gi, ib, ixy = poly_inverse(n, poly_sigma)
+    g, t, Gi, ib, ixy = poly_consts(n, poly_sigma, dtype)
     ys = np.clip(np.arange(-n, h + n), 0, h - 1)
     xs = np.clip(np.arange(-n, w + n), 0, w - 1)
     rows = [img[ys[j:j + h], :] for j in range(2 * n + 1)]
@@ -133,9 +157,9 @@ def poly_exp_direct(img, poly_n=5, poly_sigma=1.1):
     return out
 
 
-def _edge_weight(i, n):
+def _edge_weight(i, n, dtype=np.float64):
     d = np.minimum(i, n - 1 - i)
-    wts = np.ones(n)
+    wts = np.ones(n, dtype)
     for k, e in enumerate(EDGE_W):
         wts[d == k] = e
     return wts
@@ -151,16 +175,21 @@ def _box(a, win):
     return sum(c[:, xs[j:j + w]] for j in range(win)) / float(win * win)
 
 
-def iterate(Pa, Pb, d, win):
-    """one update of d at one scale"""
+def iterate(Pa, Pb, d, win, dtype=np.float64, dist=False):
+    """one update of d at one scale.  dist=True: also the per-pixel distance (px) of the sample position
+    x + d to the nearest threshold of `inside` (x + d_x = 0 or w - 1, y + d_y = 0 or h - 1).  An axis on
+    which d is exactly 0 has no distance (inf): its position is the integer pixel coordinate in any
+    precision and cannot change sides."""
+    Pa, Pb, d = Pa.astype(dtype), Pb.astype(dtype), d.astype(dtype)
     h, w = Pa.shape[:2]
-    y, x = np.mgrid[0:h, 0:w].astype(np.float64)
+    y, x = np.mgrid[0:h, 0:w].astype(dtype)
     fx, fy = x + d[..., 0], y + d[..., 1]
     x0, y0 = np.floor(fx), np.floor(fy)
     inside = (x0 >= 0) & (y0 >= 0) & (x0 < w - 1) & (y0 < h - 1)
     xi = np.where(inside, x0, 0).astype(np.int64)
     yi = np.where(inside, y0, 0).astype(np.int64)
-    ax, ay = (fx - xi)[..., None], (fy - yi)[..., None]
+    ax = np.where(inside, fx - x0, 0)[..., None]
+    ay = np.where(inside, fy - y0, 0)[..., None]
     Pb_s = ((1 - ay) * ((1 - ax) * Pb[yi, xi] + ax * Pb[yi, xi + 1]) +
             ay * ((1 - ax) * Pb[yi + 1, xi] + ax * Pb[yi + 1, xi + 1]))
     a11, a22, a12 = Pa[..., 2], Pa[..., 3], Pa[..., 4] * 0.5
@@ -169,9 +198,10 @@ def iterate(Pa, Pb, d, win):
     A22 = np.where(i, (a22 + Pb_s[..., 3]) * 0.5, a22)
     A12 = np.where(i, (a12 + Pb_s[..., 4] * 0.5) * 0.5, a12)
     dx, dy = d[..., 0], d[..., 1]
-    db1 = np.where(i, -(Pb_s[..., 0] - Pa[..., 0]) * 0.5, 0.0) + A11 * dx + A12 * dy
-    db2 = np.where(i, -(Pb_s[..., 1] - Pa[..., 1]) * 0.5, 0.0) + A12 * dx + A22 * dy
-    s = np.outer(_edge_weight(np.arange(h), h), _edge_weight(np.arange(w), w))
+    zero = np.zeros((), dtype)
+    db1 = np.where(i, -(Pb_s[..., 0] - Pa[..., 0]) * 0.5, zero) + A11 * dx + A12 * dy
+    db2 = np.where(i, -(Pb_s[..., 1] - Pa[..., 1]) * 0.5, zero) + A12 * dx + A22 * dy
+    s = np.outer(_edge_weight(np.arange(h), h, dtype), _edge_weight(np.arange(w), w, dtype))
     A11, A22, A12, db1, db2 = A11 * s, A22 * s, A12 * s, db1 * s, db2 * s
     g11 = _box(A11 * A11 + A12 * A12, win)
     g12 = _box(A12 * (A11 + A22), win)
@@ -179,7 +209,13 @@ def iterate(Pa, Pb, d, win):
     h1 = _box(A11 * db1 + A12 * db2, win)
     h2 = _box(A12 * db1 + A22 * db2, win)
     idet = 1.0 / (g11 * g22 - g12 * g12 + 1e-3)
-    return np.stack([(g22 * h1 - g12 * h2) * idet, (g11 * h2 - g12 * h1) * idet], -1)
+    out = np.stack([(g22 * h1 - g12 * h2) * idet, (g11 * h2 - g12 * h1) * idet], -1)
+    if not dist:
+        return out
+    inf = np.full((), np.inf, dtype)
+    tx = np.where(dx != 0, np.minimum(np.abs(fx), np.abs(fx - (w - 1))), inf)
+    ty = np.where(dy != 0, np.minimum(np.abs(fy), np.abs(fy - (h - 1))), inf)
+    return out, np.minimum(tx, ty)
 
 
 def check_params(p, w, h):
@@ -188,24 +224,72 @@ def check_params(p, w, h):
           and p["fast_pyramids"] == 0 and p["flags"] == 0 and w >= 32 and h >= 32)
     if not ok:
         raise ValueError("unsupported flow parameters %r at %dx%d" % (p, w, h))
+    for s, _, _ in scales(w, h, p["num_levels"], p["pyr_scale"])[1:]:
+        if len(blur_taps(s)) // 2 > MAX_BLUR_R:
+            raise ValueError("the scale %g needs a blur radius above %d px" % (s, MAX_BLUR_R))
 
 
-def flow(a, b, p=None):
-    """dense flow a -> b of two float luma frames (h, w), or RGB8 (h, w, 3) frames"""
+# ---- pixels excused from a float32-against-float64 comparison ---------------------------------------
+# `inside` is a discontinuity: a sample position within rounding distance of a threshold can fall on
+# either side in float32 and in float64, and the two results then differ by far more than rounding.
+# A flip candidate is a pixel whose distance (iterate(dist=True)) is below FLIP_ULPS float32 ulps of the
+# largest coordinate of its scale.  Its value enters the win x win box of its neighbours, the next
+# iteration spreads those by another win / 2, and the resize to the next finer scale by its 2 x 2
+# footprint: flow(excuse=True) carries that mask along the chain.
+FLIP_ULPS = 64
+
+
+def flip_eps(w, h):
+    return FLIP_ULPS * float(np.spacing(np.float32(max(w, h) - 1)))
+
+
+def _dilate(m, r):
+    """m grown by r pixels in the maximum norm"""
+    h, w = m.shape
+    ys = np.clip(np.arange(-r, h + r), 0, h - 1)
+    xs = np.clip(np.arange(-r, w + r), 0, w - 1)
+    c = np.zeros_like(m)
+    for j in range(2 * r + 1):
+        c |= m[ys[j:j + h], :]
+    out = np.zeros_like(m)
+    for j in range(2 * r + 1):
+        out |= c[:, xs[j:j + w]]
+    return out
+
+
+def _resize_mask(m, w, h):
+    """the pixels of a w x h resize whose bilinear footprint touches m"""
+    H, W = m.shape
+    x0, x1, _ = _axis(w, W)
+    y0, y1, _ = _axis(h, H)
+    return m[y0][:, x0] | m[y0][:, x1] | m[y1][:, x0] | m[y1][:, x1]
+
+
+def flow(a, b, p=None, dtype=np.float64, excuse=False):
+    """dense flow a -> b of two float luma frames (h, w), or RGB8 (h, w, 3) frames.
+    excuse=True: (flow, mask), the mask of the pixels a flip candidate of this run can reach"""
     p = params() if p is None else p
-    a = grey(a) if a.ndim == 3 else a.astype(np.float64)
-    b = grey(b) if b.ndim == 3 else b.astype(np.float64)
+    a = grey(a) if a.ndim == 3 else a
+    b = grey(b) if b.ndim == 3 else b
     h, w = a.shape
     check_params(p, w, h)
-    ia, ib = scale_images(a, p), scale_images(b, p)
-    d = None
+    ia, ib = scale_images(a, p, dtype), scale_images(b, p, dtype)
+    up = dtype(1) / dtype(p["pyr_scale"])  # the library's 1.f / pyr_scale when dtype is float32
+    d = mask = None
     for k in range(len(ia) - 1, -1, -1):
         hk, wk = ia[k].shape
-        d = np.zeros((hk, wk, 2)) if d is None else resize(d, wk, hk) / p["pyr_scale"]
-        Pa, Pb = poly_exp(ia[k], p["poly_n"], p["poly_sigma"]), poly_exp(ib[k], p["poly_n"], p["poly_sigma"])
+        d = np.zeros((hk, wk, 2), dtype) if d is None else resize(d, wk, hk, dtype) * up
+        if excuse:
+            mask = np.zeros((hk, wk), bool) if mask is None else _resize_mask(mask, wk, hk)
+        Pa = poly_exp(ia[k], p["poly_n"], p["poly_sigma"], dtype)
+        Pb = poly_exp(ib[k], p["poly_n"], p["poly_sigma"], dtype)
         for _ in range(p["num_iters"]):
-            d = iterate(Pa, Pb, d, p["win_size"])
-    return d
+            if excuse:
+                d, dist = iterate(Pa, Pb, d, p["win_size"], dtype, dist=True)
+                mask = _dilate(mask | (dist < flip_eps(wk, hk)), p["win_size"] // 2)
+            else:
+                d = iterate(Pa, Pb, d, p["win_size"], dtype)
+    return (d, mask) if excuse else d
 
 
 def endpoint_error(d, truth, border=16):
