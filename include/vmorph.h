@@ -204,6 +204,10 @@ int  vm_dbg_pass_placement(vm_ctx *ctx, uint8_t *xcc_of_block, int n);
  * kernel on each stream overlaps the other's, 0 if they serialise.  A host that needs the overlap creates another context
  * when the answer is 0 (keeping the rejected one alive meanwhile, so that the next stream gets another queue). */
 int  vm_dbg_streams_overlap(vm_ctx *a, vm_ctx *b, int *overlap);
+/* Diagnostic of the device pyramid builder: scale() of include/resample as vm_pyramid_build_rgb and the flow pyramid
+ * drive it (scale.cpp:225-272), on its own.  planes: 3 tight planar float planes of w x h (host), out: 3 planes of
+ * wout x hout (host); any side from 1 to 16384.  The public entries reach scale() only between load and store. */
+int  vm_dbg_pyramid_scale(vm_ctx *ctx, const float *planes, int w, int h, int wout, int hout, float *out);
 /* device facts for reports: name (<=255 chars), CU count, HBM bytes */
 int  vm_device_info(vm_ctx *ctx, char *name256, int *cus, uint64_t *hbm_bytes);
 

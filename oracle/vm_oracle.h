@@ -159,6 +159,8 @@ int  vmo_poisson_prepare(uint8_t *rgba_ext, int w, int h, int ex,
  * include/resample): rgb h*w*3 bytes -> lumas of levels 1..nlevels concatenated.
  * Pinned by tests/golden/pyramid_ref.npz (outputs of the reference's own library). */
 void vmo_luma_pyramid(const uint8_t *rgb, int w, int h, int nlevels, float *out);
+/* scale() of that chain on its own: 3 planar float planes of w x h -> 3 planes of wout x hout */
+void vmo_scale_planes(const float *planes, int w, int h, int wout, int hout, float *out);
 
 /* test hooks: prevent_foldover (morph.cu:872-883) and energy_change (:730-761)
  * evaluated at one pixel of an initialised level */

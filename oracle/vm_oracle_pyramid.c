@@ -186,6 +186,18 @@ static float *scale_image(float *img, int *w, int *h, int wout, int hout)
     return img;
 }
 
+/* scale() alone, for the tests of the device builder's stages: planes = 3 planar float planes of
+ * w x h (linear light, any values), out = 3 planes of wout x hout */
+void vmo_scale_planes(const float *planes, int w, int h, int wout, int hout, float *out)
+{
+    const size_t n = (size_t)3 * w * h;
+    float *img = (float *)malloc(sizeof(float) * n);
+    memcpy(img, planes, sizeof(float) * n);
+    img = scale_image(img, &w, &h, wout, hout);
+    memcpy(out, img, sizeof(float) * 3 * (size_t)w * h);
+    free(img);
+}
+
 static void store_gray(float *out, const float *img, int w, int h) /* image.cpp:87-103 */
 {
     const size_t n = (size_t)w * h;

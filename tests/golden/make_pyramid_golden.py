@@ -1,9 +1,10 @@
-"""Generates tests/golden/pyramid_ref.npz: luma pyramids computed by the REFERENCE's own
+"""Generates tests/golden/pyramid_ref.npz and pyramid_edges_ref.npz: luma pyramids computed by the REFERENCE's own
 resampling library (oracle/_ref/libresample_ref.so, built by `make -C oracle ref` from
 /root/reference/include/resample where it lies) for small synthetic RGB frames.
 Run in the build container (the reference is not available on the GPU box):
     python tests/golden/make_pyramid_golden.py
-The fixture holds data only: input frames (uint8) and the expected level lumas."""
+The fixtures hold data only: input frames (uint8) and the expected level lumas; the edge cases (thin, tiny
+and odd frames, tests/pyramid_cases.py) are generated from seeds, so their file holds the lumas alone."""
 import ctypes as C
 import os
 import subprocess
@@ -14,6 +15,8 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import pyramid_cases  # noqa: E402
 from videomorphing_amd import synth  # noqa: E402
 
 subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "ref"])
@@ -45,3 +48,7 @@ for name, (w, h, nl, frame) in {"a": (75, 52, 3, 0), "b": (64, 48, 3, 1), "c": (
         cases["%s%s_luma" % (name, k)] = run(rgb, nl)
 np.savez_compressed(os.path.join(HERE, "pyramid_ref.npz"), **cases)
 print("wrote", os.path.join(HERE, "pyramid_ref.npz"), {k: v.shape for k, v in cases.items() if k.endswith("luma")})
+
+edges = {name: run(pyramid_cases.edge_rgb(name), nl) for name, (_, _, nl, _) in pyramid_cases.LUMA_EDGES.items()}
+np.savez_compressed(os.path.join(HERE, "pyramid_edges_ref.npz"), **edges)
+print("wrote", os.path.join(HERE, "pyramid_edges_ref.npz"), {k: v.shape for k, v in edges.items()})

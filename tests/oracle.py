@@ -120,6 +120,8 @@ def lib():
     L.vmo_quadratic_path.restype = C.c_int
     L.vmo_luma_pyramid.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
     L.vmo_luma_pyramid.restype = None
+    L.vmo_scale_planes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    L.vmo_scale_planes.restype = None
     L.vmo_level_set_temporal.argtypes = [C.c_void_p, C.c_int, C.c_float]
     L.vmo_level_set_temporal.restype = None
     L.vmo_temp_splat.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -367,6 +369,15 @@ def luma_pyramid(rgb, nlevels):
         res.append(out[off:off + a * b].reshape(b, a))
         off += a * b
     return res
+
+
+def scale_planes(planes, wout, hout):
+    """scale() of the pyramid chain alone: (3, h, w) float32 planes -> (3, hout, wout)"""
+    planes = np.ascontiguousarray(planes, dtype=np.float32)
+    _, h, w = planes.shape
+    out = np.zeros((3, hout, wout), dtype=np.float32)
+    lib().vmo_scale_planes(planes.ctypes.data, w, h, wout, hout, out.ctypes.data)
+    return out
 
 
 # ---------------------------------------------------------------------------------------------

@@ -5,6 +5,8 @@ import os
 import numpy as np
 import pytest
 
+import oracle as O
+import pyramid_ref as R
 from videomorphing_amd import capi, morph, synth
 
 pytestmark = pytest.mark.gpu
@@ -14,6 +16,14 @@ GOLD = np.load(os.path.join(HERE, "golden", "pyramid_ref.npz"))
 # float tolerance on the [0, 255] luma scale: the device's powf differs from glibc's by
 # a few ulp, amplified by the x255 of store_gray
 TOL = 2e-3
+
+
+def _bound(rgb, nl):
+    """the derived bound of tests/test_gpu_pyramid_stages.py where it is the smaller one: with D = max |oracle -
+    float64 statement| for this frame, the device stays within 4 D of float64, hence within 5 D of the oracle (and of
+    the reference library's output, which the oracle equals up to an ulp of powf)"""
+    orc, f64 = O.luma_pyramid(rgb, nl), R.luma_pyramid(rgb, nl)
+    return min(TOL, 5 * max(np.abs(a - b).max() for a, b in zip(orc, f64)))
 
 
 def _device_lumas(gpu_ctx, rgb0, rgb1, nlevels):
@@ -31,7 +41,7 @@ def test_device_pyramid_matches_reference_library(gpu_ctx, case):
         got = np.concatenate([l[k].ravel() for l in lum])
         want = GOLD[key]
         assert got.shape == want.shape
-        assert np.abs(got - want).max() <= TOL, np.abs(got - want).max()
+        assert np.abs(got - want).max() <= _bound((rgb0, rgb1)[k], nl), np.abs(got - want).max()
 
 
 def test_device_pyramid_matches_oracle_and_feeds_the_solver(gpu_ctx, oracle):
@@ -40,8 +50,9 @@ def test_device_pyramid_matches_oracle_and_feeds_the_solver(gpu_ctx, oracle):
     pyr, lum = _device_lumas(gpu_ctx, rgb0, rgb1, nl)
     for k, rgb in enumerate((rgb0, rgb1)):
         ref = oracle.luma_pyramid(rgb, nl)
+        bound = _bound(rgb, nl)
         for el in range(nl):
-            assert np.abs(lum[el][k] - ref[el]).max() <= TOL
+            assert np.abs(lum[el][k] - ref[el]).max() <= bound
     gpu_ctx.set_math_mode(capi.MATH_FAST)
     prm = morph.Parameters()
     prm.max_iter, prm.max_iter_drop_factor = 40, 1.0

@@ -303,7 +303,12 @@ def test_device_flow_pyramid_matches_the_oracle(gpu_ctx, oracle):
         for t in range(levels[l][2]):
             for k in ("f0", "f1", "b0", "b1"):
                 worst = max(worst, np.abs(dev.pages[l][t].field(k) - want[l][k][t]).max())
-    assert worst < 5e-3, worst                              # px; powf on the device vs libm
+    # px.  The derived bound of tests/test_gpu_pyramid_stages.py where it is the smaller one: with D = max |oracle -
+    # float64 statement| the device stays within 4 D of float64, hence within 5 D of the oracle
+    import pyramid_ref as R
+    f64 = R.flow_pyramids(fam[0], fam[1], fam[2], fam[3], levels, ft)
+    D = max(np.abs(np.stack(want[l][k]) - np.stack(f64[l][k])).max() for l in range(len(levels) - 1) for k in ("f0", "f1", "b0", "b1"))
+    assert worst <= min(5e-3, 5 * D), (worst, D)
     # the flows of the halved level span two frames: about twice a plain rescale of one frame's flow
     one = oracle.flow_scale(want[1]["f0"][0], levels[2][0], levels[2][1])
     assert np.abs(want[2]["f0"][0]).mean() > 1.5 * np.abs(one).mean()
@@ -322,10 +327,12 @@ def test_device_video_luma_pyramid_pages(gpu_ctx, oracle):
         dev.build_rgb_frame(t, *rgbs[t])
     for l, t in ((0, 3), (1, 31), (2, 4), (2, 16)):
         f = frames[l][t]
-        want0 = oracle.luma_pyramid(rgbs[f][0], l + 1)[l]
-        want1 = oracle.luma_pyramid(rgbs[f][1], l + 1)[l]
-        assert np.abs(dev.pages[l][t].field("img0") - want0).max() < 2e-2
-        assert np.abs(dev.pages[l][t].field("img1") - want1).max() < 2e-2
+        # the derived bound of tests/test_gpu_pyramid_stages.py where it is the smaller one: 5 D, D = max |oracle - float64|
+        import pyramid_ref as R
+        for k, name in enumerate(("img0", "img1")):
+            want, f64 = oracle.luma_pyramid(rgbs[f][k], l + 1), R.luma_pyramid(rgbs[f][k], l + 1)
+            D = max(np.abs(a - b).max() for a, b in zip(want, f64))
+            assert np.abs(dev.pages[l][t].field(name) - want[l]).max() <= min(2e-2, 5 * D), (l, t, name, D)
 
 
 def test_temporal_video_at_1080p(gpu_ctx):

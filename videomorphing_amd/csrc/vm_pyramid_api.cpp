@@ -7,8 +7,10 @@
 #include "vm_flow.h"
 #include "vm_track.h"
 
+#include <algorithm>
 #include <cmath>
 #include <map>
+#include <utility>
 #include <vector>
 
 namespace {
@@ -105,6 +107,29 @@ struct Builder {
     }
 };
 
+// Samples per plane the builder's buffers must hold for a chain of scale() calls through these sizes.  Either axis
+// order of a step passes through (w or wout) x (h or hout), so the largest width times the largest height covers
+// every step -- also where a level is larger than the one before it (vm_pyramid_create / vm_video_create admit that).
+template <class Sizes> size_t chain_capacity(int w0, int h0, int nscaled, Sizes size_of)
+{
+    int mw = w0, mh = h0;
+    for (int el = 0; el < nscaled; ++el) {
+        const std::pair<int, int> wh = size_of(el);
+        mw = std::max(mw, wh.first);
+        mh = std::max(mh, wh.second);
+    }
+    return (size_t)mw * mh;
+}
+size_t chain_capacity(const vm_pyr *p)
+{
+    return chain_capacity(p->lv[0].w, p->lv[0].h, (int)p->lv.size() - 1, [&](int el) { return std::make_pair(p->lv[el].w, p->lv[el].h); });
+}
+size_t chain_capacity(const vm_video *v)
+{
+    return chain_capacity(v->pages[0][0].lv.w, v->pages[0][0].lv.h, (int)v->pages.size() - 1,
+                          [&](int el) { return std::make_pair(v->pages[el][0].lv.w, v->pages[el][0].lv.h); });
+}
+
 } // namespace
 
 extern "C" int vm_pyramid_build_rgb(vm_pyr *p, const uint8_t *rgb0, const uint8_t *rgb1, int pitch)
@@ -118,9 +143,9 @@ extern "C" int vm_pyramid_build_rgb(vm_pyr *p, const uint8_t *rgb0, const uint8_
     if (pitch < 3 * w0) return vm_fail(VM_E_INVALID, "vm_pyramid_build_rgb: pitch < 3*width");
     Builder B;
     B.c = c;
-    const size_t n0 = (size_t)w0 * h0;
-    if (int rc = B.img.reserve(n0 * 3)) return rc;
-    if (int rc = B.tmp.reserve(n0 * 3)) return rc;
+    const size_t cap = chain_capacity(p);
+    if (int rc = B.img.reserve(cap * 3)) return rc;
+    if (int rc = B.tmp.reserve(cap * 3)) return rc;
     if (int rc = B.rgb.reserve((size_t)pitch * h0)) return rc;
     hipStream_t s = c->stream;
     const uint8_t *src[2] = {rgb0, rgb1};
@@ -141,6 +166,33 @@ extern "C" int vm_pyramid_build_rgb(vm_pyr *p, const uint8_t *rgb0, const uint8_
     return VM_OK;
 }
 
+
+// Diagnostic: Builder::scale on its own (the public entries wrap it in load / store, i.e. in two powf), for the
+// tests of the stages.  planes: 3 tight planar float planes of w x h on the host, out: 3 planes of wout x hout.
+extern "C" int vm_dbg_pyramid_scale(vm_ctx *c, const float *planes, int w, int h, int wout, int hout, float *out)
+{
+    if (!c || !planes || !out) return vm_fail(VM_E_INVALID, "vm_dbg_pyramid_scale: NULL argument");
+    const int lim = 1 << 14;
+    if (w < 1 || h < 1 || wout < 1 || hout < 1 || w > lim || h > lim || wout > lim || hout > lim)
+        return vm_fail(VM_E_INVALID, "vm_dbg_pyramid_scale: %d x %d -> %d x %d (sides of 1 to %d)", w, h, wout, hout, lim);
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    VM_ON_DEVICE(c);
+    Builder B;
+    B.c = c;
+    // either axis order passes through (w or wout) x (h or hout)
+    const size_t cap = (size_t)3 * std::max(w, wout) * std::max(h, hout);
+    if (int rc = B.img.reserve(cap)) return rc;
+    if (int rc = B.tmp.reserve(cap)) return rc;
+    hipStream_t s = c->stream;
+    float *a = B.img.get(), *b = B.tmp.get();
+    VM_HIP(hipMemcpyAsync(a, planes, (size_t)3 * w * h * 4, hipMemcpyHostToDevice, s));
+    int cw = w, ch = h;
+    if (int rc = B.scale(a, b, cw, ch, wout, hout)) return rc;
+    VM_HIP(hipGetLastError());
+    VM_HIP(hipMemcpyAsync(out, a, (size_t)3 * wout * hout * 4, hipMemcpyDeviceToHost, s));
+    VM_HIP(hipStreamSynchronize(s));
+    return VM_OK;
+}
 
 // frame of the video a page shows: page t of level l is scaled from page
 // min(t * factor_t, prev_d - 1) of level l-1 (pyramid.cu:363-364)
@@ -166,9 +218,9 @@ extern "C" int vm_video_build_rgb(vm_video *v, int frame, const uint8_t *rgb0, c
     if (pitch < 3 * w0) return vm_fail(VM_E_INVALID, "vm_video_build_rgb: pitch < 3*width");
     Builder B;
     B.c = c;
-    const size_t n0 = (size_t)w0 * h0;
-    if (int rc = B.img.reserve(n0 * 3)) return rc;
-    if (int rc = B.tmp.reserve(n0 * 3)) return rc;
+    const size_t cap = chain_capacity(v);
+    if (int rc = B.img.reserve(cap * 3)) return rc;
+    if (int rc = B.tmp.reserve(cap * 3)) return rc;
     if (int rc = B.rgb.reserve((size_t)pitch * h0)) return rc;
     hipStream_t s = c->stream;
     const uint8_t *src[2] = {rgb0, rgb1};
@@ -204,11 +256,11 @@ static int build_flows_dev(vm_video *v, std::vector<VmDev<float2>> &flows)
     hipStream_t s = c->stream;
     const int L = (int)v->pages.size(), d0 = v->depth[0];
     const int w0 = v->pages[0][0].lv.w, h0 = v->pages[0][0].lv.h;
-    const size_t n0 = (size_t)w0 * h0;
+    const size_t cap = chain_capacity(v); // the callers sized every flow array to it: a level is stored over its source
     Builder B;
     B.c = c;
-    if (int rc = B.img.reserve(n0 * 3)) return rc;
-    if (int rc = B.tmp.reserve(n0 * 3)) return rc;
+    if (int rc = B.img.reserve(cap * 3)) return rc;
+    if (int rc = B.tmp.reserve(cap * 3)) return rc;
     // working set: the current level's flows of every frame of the previous level, tight float2
     std::vector<float2 *> cur[4]; // views into flows
     for (int k = 0; k < 4; ++k) {
@@ -268,7 +320,7 @@ extern "C" int vm_video_build_flows(vm_video *v, const float *const *f0, const f
         for (int t = 0; t < d0; ++t) {
             if (!src[k][t]) return vm_fail(VM_E_INVALID, "vm_video_build_flows: flow %d of frame %d is NULL", k, t);
             VmDev<float2> &fl = flows[(size_t)k * d0 + t];
-            if (int rc = fl.reserve(n0)) return rc;
+            if (int rc = fl.reserve(chain_capacity(v))) return rc;
             VM_HIP(hipMemcpyAsync(fl.get(), src[k][t], n0 * 8, hipMemcpyHostToDevice, s));
         }
     VM_HIP(hipStreamSynchronize(s)); // the host arrays belong to the caller
@@ -300,7 +352,7 @@ extern "C" int vm_video_build_flows_track(vm_video *v, const vm_track *t)
     for (int k = 0; k < 4; ++k)
         for (int i = 0; i < d0; ++i) {
             VmDev<float2> &fl = flows[(size_t)k * d0 + i];
-            if (int rc = fl.reserve(n0)) return rc;
+            if (int rc = fl.reserve(chain_capacity(v))) return rc;
             VM_HIP(hipMemcpyAsync(fl.get(), src[k]->get() + (size_t)i * n0, n0 * 8, hipMemcpyDeviceToDevice, s));
         }
     return build_flows_dev(v, flows);
@@ -327,7 +379,7 @@ extern "C" int vm_video_build_flows_rgb(vm_video *v, const uint8_t *const *rgb0,
     const size_t n0 = (size_t)w0 * h0;
     std::vector<VmDev<float2>> flows(4 * (size_t)d0); // f0, f1, b0, b1
     for (auto &fl : flows) {
-        if (int rc = fl.reserve(n0)) return rc;
+        if (int rc = fl.reserve(chain_capacity(v))) return rc;
         VM_HIP(hipMemsetAsync(fl.get(), 0, n0 * 8, s)); // f[d0 - 1] and b[0] stay zero
     }
     VmDev<uint8_t> stage;
