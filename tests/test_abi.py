@@ -83,6 +83,56 @@ def test_null_handles_are_rejected_not_dereferenced(vmlib):
     assert b"vmorph" in vmlib.vm_version()
 
 
+# Entry points of capi.SYMBOLS that do not answer a NULL handle with a status: what they answer instead ...
+NULL_ANSWERS = {"vm_pyramid_levels": 0, "vm_video_levels": 0, "vm_dbg_pass_fallbacks": -1,   # counts
+                "vm_ctx_destroy": None, "vm_pyramid_destroy": None, "vm_frame_destroy": None, "vm_video_destroy": None,
+                "vm_sync_destroy": None, "vm_track_destroy": None}                                # void: a no-op
+# ... and those that take no handle at all
+NO_HANDLE = {"vm_last_error", "vm_version", "vm_host_register", "vm_host_unregister", "vm_rccl_comm_init_all",
+             "vm_rccl_comm_destroy", "vm_sync_level_table", "vm_flow_params_default"}
+# Where the handles sit in the argument list when not just in front: a second handle, an array of handles (the
+# call gets an array of one NULL), the handle vm_ctx_create hands out
+HANDLE_ARGS = {"vm_frame_set_v_from_level": (0, 1), "vm_frame_set_v_from_video": (0, 1), "vm_dbg_streams_overlap": (0, 1),
+               "vm_video_build_flows_track": (0, 1), "vm_ctx_create": (1,)}
+HANDLE_ARRAYS = {"vm_optimize_level_batch", "vm_solve_batch", "vm_solve_batch_cons", "vm_poisson_extend_frames",
+                 "vm_bcast_params", "vm_bcast_bytes"}
+
+
+def test_every_entry_point_refuses_a_null_handle(vmlib):
+    """every status-returning entry point that takes a handle answers NULL with VM_E_INVALID and a message of its
+    own, before it touches anything (no device is needed: a NULL handle never reaches one); the other arguments are
+    usable buffers and small numbers.  The table is total: SYMBOLS minus the two lists of exceptions."""
+    table = [n for n in capi.SYMBOLS if n not in NULL_ANSWERS and n not in NO_HANDLE]
+    assert set(HANDLE_ARGS) | HANDLE_ARRAYS <= set(table) and len(table) == len(capi.SYMBOLS) - 17
+    assert not (set(NULL_ANSWERS) | NO_HANDLE) - set(capi.SYMBOLS)
+    buf = C.create_string_buffer(1 << 16)
+    null_array = (C.c_void_p * 1)(None)
+
+    def arg(t):
+        if t is C.c_int:
+            return 1
+        if t is C.c_float:
+            return 1.0
+        if t is C.c_uint64:
+            return 8
+        return C.cast(buf, t)          # c_void_p, c_char_p and every typed pointer
+
+    for name in table:
+        fn = getattr(vmlib, name)
+        args = [arg(t) for t in fn.argtypes]
+        if name in HANDLE_ARRAYS:
+            args[0] = C.cast(null_array, fn.argtypes[0])
+        else:
+            for k in HANDLE_ARGS.get(name, (0,)):
+                args[k] = None
+        assert vmlib.vm_host_unregister(None) == capi.VM_E_INVALID    # a message that is not this call's
+        stale = vmlib.vm_last_error()
+        assert fn(*args) == capi.VM_E_INVALID, name
+        assert vmlib.vm_last_error() and vmlib.vm_last_error() != stale, name
+    for name, answer in NULL_ANSWERS.items():
+        assert getattr(vmlib, name)(None) == answer, name
+
+
 def test_product_never_touches_the_oracle():
     """the oracle is test infrastructure: nothing under videomorphing_amd/ or include/
     may import, link or name it"""

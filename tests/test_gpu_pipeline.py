@@ -476,3 +476,81 @@ def test_objects_destroyed_after_their_context_free_their_memory(vmlib, gpu_ctx,
         destroy()
     free1 = _device_free_bytes(vmlib)
     assert free1 > free0 - (1 << 30), (kind, (free0 - free1) / 2 ** 30)
+
+
+# the non-destroy entry points of each kind of object; where the handle is not the first argument: its position
+# ("array": the first argument is an array of handles, here of this one)
+_ENTRY_POINTS = {
+    "pyramid": ["vm_level_dims", "vm_level_upload_luma", "vm_pyramid_build_rgb", "vm_level_set_v", "vm_level_get_v",
+                "vm_level_get_field", "vm_level_clear", "vm_dbg_level_set_mask", "vm_coarse_solve", "vm_upsample_v",
+                "vm_init_level", "vm_optimize_level", "vm_solve", "vm_upscale_result", "vm_optimize_level_batch",
+                "vm_solve_batch", "vm_solve_batch_cons"],
+    "video": ["vm_video_level_dims", "vm_video_upload_luma", "vm_video_upload_flows", "vm_video_build_rgb",
+              "vm_video_build_flows", "vm_video_build_flows_rgb", "vm_video_build_flows_track", "vm_video_set_v",
+              "vm_video_get_v", "vm_video_get_field", "vm_video_coarse_solve", "vm_video_upsample", "vm_video_init_level",
+              "vm_video_initialize_temp", "vm_video_optimize_level", "vm_video_solve", "vm_video_result",
+              "vm_frame_set_v_from_video"],
+    "frame": ["vm_frame_upload", "vm_frame_upload_rgb", "vm_frame_download_ext", "vm_render_halfway", "vm_render_halfway_dev",
+              "vm_poisson_extend", "vm_poisson_extend_frames", "vm_frame_quadratic_path", "vm_frame_download_qpath",
+              "vm_frame_download_v"],
+    "sync": ["vm_sync_set_constraints", "vm_sync_load_identity", "vm_sync_upsample_level", "vm_sync_optimize_level",
+             "vm_sync_solve", "vm_sync_get_field", "vm_sync_set_field", "vm_sync_result", "vm_sync_upload_frame",
+             "vm_sync_upload_flow", "vm_sync_compute_flows", "vm_sync_render", "vm_sync_render_dev"],
+    "track": ["vm_track_upload_frame", "vm_track_upload_flows", "vm_track_compute_flows", "vm_track_get_flows",
+              "vm_track_propagate"],
+}
+_HANDLE_AT = {"vm_frame_set_v_from_video": 1, "vm_optimize_level_batch": "array", "vm_solve_batch": "array",
+              "vm_solve_batch_cons": "array", "vm_poisson_extend_frames": "array"}
+
+
+def _plain(kind, ctx):
+    """an object of the given kind on ctx, nothing done with it; returns its handle and its destroy function"""
+    import ctypes as C
+    if kind == "pyramid":
+        pyr = morph.Pyramid(ctx)
+        pyr.build(*synth.make_pair(192, 120), 32)
+        return pyr._h, pyr.clear
+    if kind == "video":
+        vid = morph.VideoPyramid(ctx)
+        vid.build_levels([(96, 64, 3), (48, 32, 3), (24, 16, 3)])
+        return vid._h, vid.clear
+    if kind == "frame":
+        fr = morph.Frame(ctx, 320, 200, 24)
+        return fr._h, fr.close
+    if kind == "sync":
+        syn = morph.SyncPyramid(ctx)
+        syn.build_levels(morph.sync_level_table(96, 64, 4, 8))
+        return syn._h, syn.clear
+    L, h = capi.load(), C.c_void_p()
+    capi.check(L.vm_track_create(ctx._h, 64, 64, 3, C.byref(h)))
+    return h, lambda: L.vm_track_destroy(h)
+
+
+@pytest.mark.parametrize("kind", ["pyramid", "video", "frame", "sync", "track"])
+def test_objects_refuse_every_call_after_their_context(vmlib, kind):
+    """context gone, object still held: every non-destroy entry point of the object answers VM_E_INVALID ("the context
+    was destroyed") before it reads anything of the context or calls the device; the object can then be destroyed.
+    The other arguments are valid ones (usable buffers, small numbers, pitch 0), so it is the guard that answers."""
+    import ctypes as C
+    ctx = morph.Context(0, capi.MATH_FAST)
+    handle, destroy = _plain(kind, ctx)
+    ctx.close()
+    buf = C.create_string_buffer(1 << 16)
+    array = (C.c_void_p * 1)(handle.value)
+
+    def arg(t):
+        return 1 if t is C.c_int else 1.0 if t is C.c_float else 8 if t is C.c_uint64 else C.cast(buf, t)
+
+    for name in _ENTRY_POINTS[kind]:
+        fn = getattr(vmlib, name)
+        args = [arg(t) for t in fn.argtypes]
+        at = _HANDLE_AT.get(name, 0)
+        if at == "array":
+            args[0] = C.cast(array, fn.argtypes[0])
+        else:
+            args[at] = handle
+        if name == "vm_upscale_result":
+            args[-1] = 0                   # pitch: tight
+        assert fn(*args) == capi.VM_E_INVALID, name
+        assert b"the context was destroyed" in vmlib.vm_last_error(), (name, vmlib.vm_last_error())
+    destroy()

@@ -67,6 +67,7 @@ UNITS = [
     ("vm_host.cpp", "vm_host.o", ["-x", "hip"]),
     ("vm_frame.cpp", "vm_frame.o", ["-x", "hip"]),
     ("vm_poisson_api.cpp", "vm_poisson_api.o", ["-x", "hip"]),
+    ("vm_rccl.cpp", "vm_rccl.o", ["-x", "hip"]),
 ]
 
 

@@ -172,8 +172,7 @@ extern "C" void vm_ctx_destroy(vm_ctx *c)
 
 extern "C" int vm_ctx_sync(vm_ctx *c)
 {
-    if (!c) return vm_fail(VM_E_INVALID, "ctx is NULL");
-    VM_ON_DEVICE(c);
+    VM_ENTER(c);
     VM_HIP(hipStreamSynchronize(c->stream));
     return VM_OK;
 }
@@ -245,9 +244,8 @@ extern "C" int vm_dbg_pass_fallbacks(vm_ctx *c)
 
 extern "C" int vm_dbg_pass_placement(vm_ctx *c, uint8_t *xcc_of_block, int n)
 {
-    if (!c || !xcc_of_block || n < 1 || n > 2048) return vm_fail(VM_E_INVALID, "vm_dbg_pass_placement: bad argument");
-    std::lock_guard<std::recursive_mutex> lock(c->mu);
-    VM_ON_DEVICE(c);
+    if (!xcc_of_block || n < 1 || n > 2048) return vm_fail(VM_E_INVALID, "vm_dbg_pass_placement: bad argument");
+    VM_ENTER_LOCKED(c);
     if (!c->pass_dbg.get()) { // arm: the next PASS launches record where their workgroups run
         if (int rc = c->pass_dbg.reserve(2048)) return rc;
         VM_HIP(hipMemsetAsync(c->pass_dbg.get(), 0xFF, 2048 * sizeof(uint32_t), c->stream));
@@ -275,7 +273,7 @@ extern "C" int vm_set_tuning(vm_ctx *c, int sweep_mode, int threads, int parts)
 
 extern "C" int vm_device_info(vm_ctx *c, char *name256, int *cus, uint64_t *hbm)
 {
-    if (!c) return vm_fail(VM_E_INVALID, "ctx is NULL");
+    VM_ENTER(c);
     hipDeviceProp_t pr;
     VM_HIP(hipGetDeviceProperties(&pr, c->device));
     if (name256) snprintf(name256, 256, "%s (%s)", pr.name, pr.gcnArchName);
@@ -369,66 +367,86 @@ extern "C" void vm_pyramid_destroy(vm_pyr *p) { vm_destroy_object(p); }
 
 extern "C" int vm_pyramid_levels(vm_pyr *p) { return p ? (int)p->lv.size() : 0; }
 
-#define CHECK_LVL(p, lvl)                                                        \
-    if (!(p)) return vm_fail(VM_E_INVALID, "%s: pyramid is NULL", __func__);     \
-    if ((lvl) < 0 || (lvl) >= (int)(p)->lv.size())                               \
-        return vm_fail(VM_E_INVALID, "%s: level %d out of range", __func__, (lvl)); \
-    if (!vm_ctx_alive((p)->ctx)) return vm_fail(VM_E_INVALID, "%s: the context was destroyed", __func__); \
-    VM_ON_DEVICE((p)->ctx);
+static int check_level(const vm_pyr *p, int lvl, const char *fn)
+{
+    if (lvl < 0 || lvl >= (int)p->lv.size()) return vm_fail(VM_E_INVALID, "%s: level %d out of range", fn, lvl);
+    return VM_OK;
+}
+
+int vm_pitch_resolve(const char *fn, int *pitch, size_t unit, size_t row_bytes)
+{
+    if (*pitch == 0) *pitch = (int)((row_bytes + unit - 1) / unit);
+    if (*pitch < 0 || (size_t)*pitch * unit < row_bytes)
+        return vm_fail(VM_E_INVALID, "%s: pitch %d below the row of %zu", fn, *pitch, (row_bytes + unit - 1) / unit);
+    return VM_OK;
+}
+
+int vm_copy_pitched(const char *fn, hipMemcpyKind kind, void *dev, size_t dev_pitch_bytes, const void *host, int pitch,
+                    size_t unit, size_t row_bytes, int h, hipStream_t s)
+{
+    if (int rc = vm_pitch_resolve(fn, &pitch, unit, row_bytes)) return rc;
+    const size_t hp = (size_t)pitch * unit;
+    if (kind == hipMemcpyHostToDevice)
+        VM_HIP(hipMemcpy2DAsync(dev, dev_pitch_bytes, host, hp, row_bytes, h, kind, s));
+    else
+        VM_HIP(hipMemcpy2DAsync((void *)host, hp, dev, dev_pitch_bytes, row_bytes, h, kind, s));
+    return VM_OK;
+}
 
 extern "C" int vm_level_dims(vm_pyr *p, int lvl, int *w, int *h, int *rs)
 {
-    CHECK_LVL(p, lvl);
+    VM_ENTER(p);
+    if (int rc = check_level(p, lvl, __func__)) return rc;
     if (w) *w = p->lv[lvl].w;
     if (h) *h = p->lv[lvl].h;
     if (rs) *rs = p->lv[lvl].rs;
     return VM_OK;
 }
 
+int vm_level_write_luma(vm_ctx *c, vm_level &l, const float *img0, const float *img1, int pitch, const char *fn)
+{
+    if (!l.view.img0) return vm_fail(VM_E_STATE, "%s: the coarsest level holds no images", fn);
+    if (!img0 || !img1) return vm_fail(VM_E_INVALID, "%s: NULL image", fn);
+    const float *src[2] = {img0, img1}, *dst[2] = {l.view.img0, l.view.img1};
+    for (int k = 0; k < 2; ++k)
+        if (int rc = vm_copy_pitched(fn, hipMemcpyHostToDevice, (void *)dst[k], l.rs * 4, src[k], pitch, 4, (size_t)l.w * 4, l.h, c->stream)) return rc;
+    VM_HIP(hipStreamSynchronize(c->stream));
+    return VM_OK;
+}
+
+int vm_level_copy_v(vm_ctx *c, vm_level &l, hipMemcpyKind kind, const float *v, int pitch, const char *fn)
+{
+    if (!v) return vm_fail(VM_E_INVALID, "%s: NULL", fn);
+    if (int rc = vm_copy_pitched(fn, kind, l.view.v, l.rs * 8, v, pitch, 4, (size_t)l.w * 8, l.h, c->stream)) return rc;
+    VM_HIP(hipStreamSynchronize(c->stream));
+    return VM_OK;
+}
+
 extern "C" int vm_level_upload_luma(vm_pyr *p, int lvl, const float *img0, const float *img1, int pitch)
 {
-    CHECK_LVL(p, lvl);
-    vm_level &l = p->lv[lvl];
-    if (!l.view.img0) return vm_fail(VM_E_STATE, "vm_level_upload_luma: coarsest level holds no images");
-    if (!img0 || !img1) return vm_fail(VM_E_INVALID, "vm_level_upload_luma: NULL image");
-    if (pitch == 0) pitch = l.w;
-    if (pitch < l.w) return vm_fail(VM_E_INVALID, "vm_level_upload_luma: pitch < width");
-    hipStream_t s = p->ctx->stream;
-    VM_HIP(hipMemcpy2DAsync((void *)l.view.img0, l.rs * 4, img0, (size_t)pitch * 4, (size_t)l.w * 4, l.h, hipMemcpyHostToDevice, s));
-    VM_HIP(hipMemcpy2DAsync((void *)l.view.img1, l.rs * 4, img1, (size_t)pitch * 4, (size_t)l.w * 4, l.h, hipMemcpyHostToDevice, s));
-    VM_HIP(hipStreamSynchronize(s));
-    return VM_OK;
+    VM_ENTER(p);
+    if (int rc = check_level(p, lvl, __func__)) return rc;
+    return vm_level_write_luma(p->ctx, p->lv[lvl], img0, img1, pitch, __func__);
 }
 
 extern "C" int vm_level_set_v(vm_pyr *p, int lvl, const float *v, int pitch)
 {
-    CHECK_LVL(p, lvl);
-    vm_level &l = p->lv[lvl];
-    if (!v) return vm_fail(VM_E_INVALID, "vm_level_set_v: NULL");
-    if (pitch == 0) pitch = 2 * l.w;
-    if (pitch < 2 * l.w) return vm_fail(VM_E_INVALID, "vm_level_set_v: pitch < 2*width");
-    hipStream_t s = p->ctx->stream;
-    VM_HIP(hipMemcpy2DAsync(l.view.v, l.rs * 8, v, (size_t)pitch * 4, (size_t)l.w * 8, l.h, hipMemcpyHostToDevice, s));
-    VM_HIP(hipStreamSynchronize(s));
-    return VM_OK;
+    VM_ENTER(p);
+    if (int rc = check_level(p, lvl, __func__)) return rc;
+    return vm_level_copy_v(p->ctx, p->lv[lvl], hipMemcpyHostToDevice, v, pitch, __func__);
 }
 
 extern "C" int vm_level_get_v(vm_pyr *p, int lvl, float *v, int pitch)
 {
-    CHECK_LVL(p, lvl);
-    vm_level &l = p->lv[lvl];
-    if (!v) return vm_fail(VM_E_INVALID, "vm_level_get_v: NULL");
-    if (pitch == 0) pitch = 2 * l.w;
-    if (pitch < 2 * l.w) return vm_fail(VM_E_INVALID, "vm_level_get_v: pitch < 2*width");
-    hipStream_t s = p->ctx->stream;
-    VM_HIP(hipMemcpy2DAsync(v, (size_t)pitch * 4, l.view.v, l.rs * 8, (size_t)l.w * 8, l.h, hipMemcpyDeviceToHost, s));
-    VM_HIP(hipStreamSynchronize(s));
-    return VM_OK;
+    VM_ENTER(p);
+    if (int rc = check_level(p, lvl, __func__)) return rc;
+    return vm_level_copy_v(p->ctx, p->lv[lvl], hipMemcpyDeviceToHost, v, pitch, __func__);
 }
 
 extern "C" int vm_level_get_field(vm_pyr *p, int lvl, int field, void *host)
 {
-    CHECK_LVL(p, lvl);
+    VM_ENTER(p);
+    if (int rc = check_level(p, lvl, __func__)) return rc;
     return vm_level_read_field(p->ctx, p->lv[lvl], field, host);
 }
 
@@ -485,14 +503,15 @@ int vm_level_read_field(vm_ctx *c, vm_level &l, int field, void *host)
         return vm_fail(VM_E_INVALID, "vm_level_get_field: unknown field %d", field);
     }
     if (!src) return vm_fail(VM_E_STATE, "vm_level_get_field: the level has no such array");
-    VM_HIP(hipMemcpy2DAsync(host, (size_t)l.w * elem, src, (size_t)l.rs * elem, (size_t)l.w * elem, l.h, hipMemcpyDeviceToHost, s));
+    if (int rc = vm_copy_pitched("vm_level_get_field", hipMemcpyDeviceToHost, (void *)src, (size_t)l.rs * elem, host, 0, elem, (size_t)l.w * elem, l.h, s)) return rc;
     VM_HIP(hipStreamSynchronize(s));
     return VM_OK;
 }
 
 extern "C" int vm_dbg_level_set_mask(vm_pyr *p, int lvl, const uint32_t *words)
 {
-    CHECK_LVL(p, lvl);
+    VM_ENTER(p);
+    if (int rc = check_level(p, lvl, __func__)) return rc;
     vm_level &l = p->lv[lvl];
     if (!words) return vm_fail(VM_E_INVALID, "vm_dbg_level_set_mask: NULL");
     if (!l.has_state || !l.view.impmask) return vm_fail(VM_E_STATE, "vm_dbg_level_set_mask: level not initialised");
@@ -504,7 +523,8 @@ extern "C" int vm_dbg_level_set_mask(vm_pyr *p, int lvl, const uint32_t *words)
 
 extern "C" int vm_level_clear(vm_pyr *p, int lvl)
 {
-    CHECK_LVL(p, lvl);
+    VM_ENTER(p);
+    if (int rc = check_level(p, lvl, __func__)) return rc;
     // Morph::clear_level frees the per-level state; the slab stays allocated
     // (288 GB of HBM: reuse beats hipFree/hipMalloc churn), it is only marked stale
     p->lv[lvl].has_state = false;
@@ -523,7 +543,8 @@ static int upload_constraints(vm_ctx *c, const vm_constraint *cons, int n)
 
 extern "C" int vm_coarse_solve(vm_pyr *p, int lvl, int w0, int h0, const vm_constraint *cons, int n)
 {
-    CHECK_LVL(p, lvl);
+    VM_ENTER(p);
+    if (int rc = check_level(p, lvl, __func__)) return rc;
     if (n < 0 || (n > 0 && !cons)) return vm_fail(VM_E_INVALID, "vm_coarse_solve: constraints");
     vm_level &l = p->lv[lvl];
     std::vector<float> v((size_t)2 * l.w * l.h, 0.0f);
@@ -549,14 +570,16 @@ int vm_level_upsample(vm_ctx *c, vm_level &d, const vm_level &s)
 
 extern "C" int vm_upsample_v(vm_pyr *p, int dst, int src)
 {
-    CHECK_LVL(p, dst);
-    CHECK_LVL(p, src);
+    VM_ENTER(p);
+    if (int rc = check_level(p, dst, __func__)) return rc;
+    if (int rc = check_level(p, src, __func__)) return rc;
     return vm_level_upsample(p->ctx, p->lv[dst], p->lv[src]);
 }
 
 extern "C" int vm_init_level(vm_pyr *p, int lvl, int w0, int h0, const vm_constraint *cons, int n)
 {
-    CHECK_LVL(p, lvl);
+    VM_ENTER(p);
+    if (int rc = check_level(p, lvl, __func__)) return rc;
     return vm_level_init(p->ctx, p->lv[lvl], w0, h0, cons, n);
 }
 
@@ -607,7 +630,8 @@ static int optimize_level_batch(vm_pyr **ps, int n, int lvl, float max_iter, vol
 extern "C" int vm_optimize_level(vm_pyr *p, int lvl, float max_iter, volatile const int *run_flag,
                                  int fixed_work, vm_progress *out)
 {
-    CHECK_LVL(p, lvl);
+    VM_ENTER(p);
+    if (int rc = check_level(p, lvl, __func__)) return rc;
     return optimize_level_batch(&p, 1, lvl, max_iter, run_flag, fixed_work, out);
 }
 
@@ -615,6 +639,7 @@ extern "C" int vm_optimize_level_batch(vm_pyr **pyrs, int n, int lvl, float max_
                                        volatile const int *run_flag, int fixed_work, vm_progress *out)
 {
     if (!pyrs || n < 1 || !pyrs[0]) return vm_fail(VM_E_INVALID, "vm_optimize_level_batch: empty batch");
+    VM_ENTER(pyrs[0]);
     return optimize_level_batch(pyrs, n, lvl, max_iter, run_flag, fixed_work, out);
 }
 
@@ -626,7 +651,7 @@ extern "C" int vm_solve_batch_cons(vm_pyr **pyrs, int n, float max_iter, float d
     if (!pyrs || n < 1 || !pyrs[0]) return vm_fail(VM_E_INVALID, "vm_solve_batch: empty batch");
     if (!(drop > 0)) return vm_fail(VM_E_INVALID, "vm_solve_batch: max_iter_drop_factor must be > 0");
     if (cons && !ncons) return vm_fail(VM_E_INVALID, "vm_solve_batch_cons: constraints without their counts");
-    std::lock_guard<std::recursive_mutex> lock(pyrs[0]->ctx->mu);
+    VM_ENTER_LOCKED(pyrs[0]);
     const int L = (int)pyrs[0]->lv.size();
     const int w0 = pyrs[0]->lv[0].w, h0 = pyrs[0]->lv[0].h;
     int rc;
@@ -660,8 +685,7 @@ extern "C" int vm_solve_batch(vm_pyr **pyrs, int n, float max_iter, float drop, 
 extern "C" int vm_solve(vm_pyr *p, float max_iter, float drop, const vm_constraint *cons, int n,
                         volatile const int *run_flag, int fixed_work, vm_progress *per_level)
 {
-    if (!p) return vm_fail(VM_E_INVALID, "vm_solve: pyramid is NULL");
-    std::lock_guard<std::recursive_mutex> lock(p->ctx->mu);
+    VM_ENTER_LOCKED(p);
     if (!(drop > 0)) return vm_fail(VM_E_INVALID, "vm_solve: max_iter_drop_factor must be > 0");
     const int L = (int)p->lv.size();
     const int w0 = p->lv[0].w, h0 = p->lv[0].h;

@@ -1,7 +1,7 @@
 // vm_flow.cpp -- host side of the dense optical flow (MdiEditor::OpticalFlow, UI/MdiEditor.cpp:1584-1689):
 // parameter checks, the scale table, the per-call working set and the launch sequence of vm_flow.hip;
 // the C-ABI entry points for independent frame pairs.  The video and sync entry points live beside
-// their objects (vm_pyramid_api.cpp, vm_sync.cpp) and call vm_flow_run.
+// their objects (vm_pyramid_api.cpp, vm_sync.cpp, vm_track.cpp) and call vm_flow_run_videos.
 #include "vm_host.h"
 #include "vm_flow.h"
 
@@ -99,7 +99,8 @@ size_t vm_flow_frame_bytes(int w, int h, const vm_flow_params &p)
 
 size_t vm_flow_flow_bytes(int w, int h) { return (size_t)w * h * 24; }
 
-int vm_flow_video_chunk(int w, int h, const vm_flow_params &p, int videos)
+// the frames per chunk of a video walk (F frames of each of `videos` videos, 2 (F - 1) flows each)
+static int vm_flow_video_chunk(int w, int h, const vm_flow_params &p, int videos)
 {
     // F frames of each video: videos * (F frame_bytes + 2 (F - 1) flow_bytes) <= budget
     const double per = (double)videos * ((double)vm_flow_frame_bytes(w, h, p) + 2.0 * vm_flow_flow_bytes(w, h));
@@ -189,6 +190,25 @@ int vm_flow_run(vm_ctx *c, int w, int h, const vm_flow_params &p, int nframes, c
     return VM_OK;
 }
 
+int vm_flow_run_videos(vm_ctx *c, int w, int h, int d, const vm_flow_params &p, const VmFlowVideoSource &src,
+                       const VmFlowVideoOut &fwd, const VmFlowVideoOut &bwd)
+{
+    const int F = vm_flow_video_chunk(w, h, p, 2);
+    for (int t0 = 0; t0 < d - 1; t0 += F - 1) {
+        const int t1 = std::min(d - 1, t0 + F - 1), nfr = t1 - t0 + 1;
+        std::vector<VmFlowPair> pairs;
+        for (int k = 0; k < 2; ++k)
+            for (int t = t0; t <= t1; ++t) { // frame slot of (video k, frame t): k * nfr + t - t0
+                const int slot = k * nfr + t - t0;
+                if (t < t1) pairs.push_back({slot, slot + 1, fwd(k, t)});
+                if (bwd && t > t0) pairs.push_back({slot, slot - 1, bwd(k, t)});
+            }
+        auto chunk = [&](int f, float *dst) -> int { return src(f / nfr, t0 + f % nfr, dst); };
+        if (int rc = vm_flow_run(c, w, h, p, 2 * nfr, chunk, pairs)) return rc;
+    }
+    return VM_OK;
+}
+
 extern "C" int vm_flow_params_default(vm_flow_params *p)
 {
     if (!p) return vm_fail(VM_E_INVALID, "vm_flow_params_default: NULL argument");
@@ -211,9 +231,8 @@ static int optical_flow_pairs(vm_ctx *ctx, int w, int h, int n, const void *cons
     if (n < 0 || (n > 0 && (!a || !b || !flow_xy))) return vm_fail(VM_E_INVALID, "%s: bad arguments", fn);
     vm_flow_params p;
     if (int rc = vm_flow_resolve(pp, w, h, &p, fn)) return rc;
-    const int row = rgb ? 3 * w : w; // bytes of an RGB row, floats of a luma row
-    if (pitch == 0) pitch = row;
-    if (pitch < row) return vm_fail(VM_E_INVALID, "%s: pitch below the row length", fn);
+    const size_t unit = rgb ? 1 : 4, row = rgb ? (size_t)3 * w : (size_t)4 * w; // pitch in bytes (RGB) or floats (luma)
+    if (int rc = vm_pitch_resolve(fn, &pitch, unit, row)) return rc;
     for (int i = 0; i < n; ++i)
         if (!a[i] || !b[i] || !flow_xy[i]) return vm_fail(VM_E_INVALID, "%s: pair %d has a NULL array", fn, i);
     if (!vm_ctx_alive(ctx)) return vm_fail(VM_E_INVALID, "%s: the context was destroyed", fn);
@@ -233,12 +252,8 @@ static int optical_flow_pairs(vm_ctx *ctx, int w, int h, int n, const void *cons
         for (int j = 0; j < m; ++j) pairs[j] = {2 * j, 2 * j + 1, out.get() + (size_t)j * n0};
         auto src = [&](int f, float *dst) -> int {
             const void *hs = (f & 1 ? b : a)[i0 + f / 2];
-            if (rgb) {
-                VM_HIP(hipMemcpy2DAsync(stage.get(), (size_t)w * 3, hs, (size_t)pitch, (size_t)w * 3, h, hipMemcpyHostToDevice, s));
-                vm_flow_launch_grey_rgb(stage.get(), w * 3, w, h, dst, s);
-            } else {
-                VM_HIP(hipMemcpy2DAsync(dst, (size_t)w * 4, hs, (size_t)pitch * 4, (size_t)w * 4, h, hipMemcpyHostToDevice, s));
-            }
+            if (int rc = vm_copy_pitched(fn, hipMemcpyHostToDevice, rgb ? (void *)stage.get() : (void *)dst, row, hs, pitch, unit, row, h, s)) return rc;
+            if (rgb) vm_flow_launch_grey_rgb(stage.get(), w * 3, w, h, dst, s);
             return VM_OK;
         };
         if (int rc = vm_flow_run(ctx, w, h, p, 2 * m, src, pairs)) return rc;

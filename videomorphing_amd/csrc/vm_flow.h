@@ -60,6 +60,13 @@ struct VmFlowPair {
 using VmFlowSource = std::function<int(int frame, float *dst)>;
 int vm_flow_run(vm_ctx *c, int w, int h, const vm_flow_params &p, int nframes, const VmFlowSource &src,
                 const std::vector<VmFlowPair> &pairs);
-// the frames per chunk of a video walk (F frames of each of `videos` videos, 2 (F - 1) flows each)
-int vm_flow_video_chunk(int w, int h, const vm_flow_params &p, int videos);
+// The flows along two videos of d frames each (MdiEditor::OpticalFlow, UI/MdiEditor.cpp:1584-1689), walked in chunks
+// [t0, t1] that share their end frame and fit VM_FLOW_BUDGET with both families: the forward flow of (video k, frame
+// t) is computed in the chunk with t0 <= t < t1 and lands in fwd(k, t), the backward flow in the chunk with
+// t0 < t <= t1 and lands in bwd(k, t) (bwd empty: forward flows only), each exactly once; fwd(k, d - 1) and bwd(k, 0)
+// are never asked for.  src(k, t, dst) writes the frame's grey plane as for vm_flow_run.
+using VmFlowVideoSource = std::function<int(int video, int frame, float *dst)>;
+using VmFlowVideoOut = std::function<float2 *(int video, int frame)>;
+int vm_flow_run_videos(vm_ctx *c, int w, int h, int d, const vm_flow_params &p, const VmFlowVideoSource &src,
+                       const VmFlowVideoOut &fwd, const VmFlowVideoOut &bwd);
 #endif

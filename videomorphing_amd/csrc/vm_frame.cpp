@@ -46,9 +46,7 @@ extern "C" void vm_frame_destroy(vm_frame *f) { vm_destroy_object(f); }
 extern "C" int vm_frame_upload(vm_frame *f, const uint8_t *e0, const uint8_t *e1, const float *v,
                                const float *q)
 {
-    if (!f) return vm_fail(VM_E_INVALID, "vm_frame_upload: frame is NULL");
-    if (!vm_ctx_alive(f->ctx)) return vm_fail(VM_E_INVALID, "%s: the context was destroyed", __func__);
-    VM_ON_DEVICE(f->ctx);
+    VM_ENTER(f);
     hipStream_t s = f->ctx->stream;
     size_t nc = (size_t)f->cw * f->ch * 4;
     const uint8_t *e[2] = {e0, e1};
@@ -58,9 +56,12 @@ extern "C" int vm_frame_upload(vm_frame *f, const uint8_t *e0, const uint8_t *e1
             // the originals both sides' fills sample from (cloned before any solve)
             vm_poisson_launch_crop(f->crop[k].get(), f->ext[k].get(), f->w, f->h, f->ex, s);
         }
-    if (v) VM_HIP(hipMemcpy2DAsync(f->v.get(), (size_t)f->rs * 8, v, (size_t)f->w * 8, (size_t)f->w * 8, f->h, hipMemcpyHostToDevice, s));
-    if (q) VM_HIP(hipMemcpy2DAsync(f->u.get(), (size_t)f->rs * 8, q, (size_t)f->w * 8, (size_t)f->w * 8, f->h, hipMemcpyHostToDevice, s));
-    else if (!f->u_zero) VM_HIP(hipMemsetAsync(f->u.get(), 0, (size_t)f->rs * f->h * 8, s));
+    const float *src[2] = {v, q};
+    float2 *dst[2] = {f->v.get(), f->u.get()};
+    for (int k = 0; k < 2; ++k) // tight (h, w, 2) floats
+        if (src[k])
+            if (int rc = vm_copy_pitched(__func__, hipMemcpyHostToDevice, dst[k], (size_t)f->rs * 8, src[k], 0, 8, (size_t)f->w * 8, f->h, s)) return rc;
+    if (!q && !f->u_zero) VM_HIP(hipMemsetAsync(f->u.get(), 0, (size_t)f->rs * f->h * 8, s));
     f->u_zero = q == nullptr;
     VM_HIP(hipStreamSynchronize(s));
     return VM_OK;
@@ -71,17 +72,15 @@ extern "C" int vm_frame_upload(vm_frame *f, const uint8_t *e0, const uint8_t *e1
 // v and the quadratic path stay what they are.
 extern "C" int vm_frame_upload_rgb(vm_frame *f, const uint8_t *rgb0, const uint8_t *rgb1, int pitch_bytes)
 {
-    if (!f || !rgb0 || !rgb1) return vm_fail(VM_E_INVALID, "vm_frame_upload_rgb: NULL argument");
-    if (!vm_ctx_alive(f->ctx)) return vm_fail(VM_E_INVALID, "%s: the context was destroyed", __func__);
-    if (pitch_bytes == 0) pitch_bytes = 3 * f->w;
-    if (pitch_bytes < 3 * f->w) return vm_fail(VM_E_INVALID, "vm_frame_upload_rgb: pitch < 3 * w");
-    VM_ON_DEVICE(f->ctx);
+    if (!rgb0 || !rgb1) return vm_fail(VM_E_INVALID, "vm_frame_upload_rgb: NULL argument");
+    VM_ENTER(f);
+    if (int rc = vm_pitch_resolve(__func__, &pitch_bytes, 1, (size_t)3 * f->w)) return rc;
     hipStream_t s = f->ctx->stream;
     const size_t one = (size_t)f->w * f->h * 3;
     if (int rc = f->rgb_stage.reserve(2 * one)) return rc;
     const uint8_t *src[2] = {rgb0, rgb1};
     for (int k = 0; k < 2; ++k) {
-        VM_HIP(hipMemcpy2DAsync(f->rgb_stage.get() + k * one, (size_t)3 * f->w, src[k], (size_t)pitch_bytes, (size_t)3 * f->w, f->h, hipMemcpyHostToDevice, s));
+        if (int rc = vm_copy_pitched(__func__, hipMemcpyHostToDevice, f->rgb_stage.get() + k * one, (size_t)3 * f->w, src[k], pitch_bytes, 1, (size_t)3 * f->w, f->h, s)) return rc;
         vm_poisson_launch_canvas(f->ext[k].get(), f->crop[k].get(), f->rgb_stage.get() + k * one, f->w, f->h, f->ex, s);
     }
     VM_HIP(hipGetLastError());
@@ -170,10 +169,9 @@ extern "C" int vm_host_unregister(void *ptr)
 
 extern "C" int vm_frame_download_ext(vm_frame *f, int side, uint8_t *ext)
 {
-    if (!f || !ext || (side != 1 && side != 2))
+    if (!ext || (side != 1 && side != 2))
         return vm_fail(VM_E_INVALID, "vm_frame_download_ext: bad argument");
-    if (!vm_ctx_alive(f->ctx)) return vm_fail(VM_E_INVALID, "%s: the context was destroyed", __func__);
-    VM_ON_DEVICE(f->ctx);
+    VM_ENTER(f);
     hipStream_t s = f->ctx->stream;
     VM_HIP(hipMemcpyAsync(ext, f->ext[side - 1].get(), (size_t)f->cw * f->ch * 4, hipMemcpyDeviceToHost, s));
     VM_HIP(hipStreamSynchronize(s));
@@ -214,30 +212,25 @@ extern "C" int vm_frame_set_v_from_level(vm_frame *f, vm_pyr *p, int lvl)
 
 extern "C" int vm_upscale_result(vm_pyr *p, int lvl, int w0, int h0, float *out, int pitch)
 {
-    if (!p || lvl < 0 || lvl >= (int)p->lv.size() || !out || w0 < 1 || h0 < 1)
-        return vm_fail(VM_E_INVALID, "vm_upscale_result: bad argument");
-    if (pitch == 0) pitch = 2 * w0;
-    if (pitch < 2 * w0) return vm_fail(VM_E_INVALID, "vm_upscale_result: pitch < 2*w0");
-    VM_ON_DEVICE(p->ctx);
+    if (!out || w0 < 1 || h0 < 1) return vm_fail(VM_E_INVALID, "vm_upscale_result: bad argument");
+    if (int rc = vm_pitch_resolve(__func__, &pitch, 4, (size_t)w0 * 8)) return rc;
+    VM_ENTER(p);
+    if (lvl < 0 || lvl >= (int)p->lv.size()) return vm_fail(VM_E_INVALID, "vm_upscale_result: bad argument");
     vm_level &l = p->lv[lvl];
     hipStream_t s = p->ctx->stream;
     VmDev<float2> tmp;
     if (int rc = tmp.reserve((size_t)w0 * h0)) return rc;
     vm_launch_upscale(tmp.get(), w0, h0, w0, l.view.v, l.w, l.h, l.rs, s);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess)
-        e = hipMemcpy2DAsync(out, (size_t)pitch * 4, tmp.get(), (size_t)w0 * 8, (size_t)w0 * 8, h0, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return vm_fail(VM_E_DEVICE, "vm_upscale_result: %s", hipGetErrorString(e));
+    VM_HIP(hipGetLastError());
+    if (int rc = vm_copy_pitched(__func__, hipMemcpyDeviceToHost, tmp.get(), (size_t)w0 * 8, out, pitch, 4, (size_t)w0 * 8, h0, s)) return rc;
+    VM_HIP(hipStreamSynchronize(s));
     return VM_OK;
 }
 
 static int render_dev(vm_frame *f, float color_fa, float geo_fa, int color_from, float *ms)
 {
-    if (!f) return vm_fail(VM_E_INVALID, "vm_render_halfway: frame is NULL");
     if (color_from < 0 || color_from > 2) return vm_fail(VM_E_INVALID, "vm_render_halfway: color_from %d", color_from);
     vm_ctx *c = f->ctx;
-    VM_ON_DEVICE(c);
     if (ms) VM_HIP(hipEventRecord(c->ev0.get(), c->stream));
     vm_launch_render(f->out.get(), f->w * 3, f->w, f->h, f->rs, f->ex, color_fa, geo_fa, color_from,
                      f->ext[0].get(), f->ext[1].get(), f->v.get(), f->u_zero ? nullptr : f->u.get(), c->stream);
@@ -252,6 +245,7 @@ static int render_dev(vm_frame *f, float color_fa, float geo_fa, int color_from,
 
 extern "C" int vm_render_halfway_dev(vm_frame *f, float color_fa, float geo_fa, int color_from, float *ms)
 {
+    VM_ENTER(f);
     return render_dev(f, color_fa, geo_fa, color_from, ms);
 }
 
@@ -259,14 +253,11 @@ extern "C" int vm_render_halfway(vm_frame *f, float color_fa, float geo_fa, int 
                                  uint8_t *rgb, int pitch)
 {
     if (!rgb) return vm_fail(VM_E_INVALID, "vm_render_halfway: output is NULL");
-    int rc = render_dev(f, color_fa, geo_fa, color_from, nullptr);
-    if (rc != VM_OK) return rc;
-    if (pitch == 0) pitch = f->w * 3;
-    if (pitch < f->w * 3) return vm_fail(VM_E_INVALID, "vm_render_halfway: pitch < 3*w");
-    if (!vm_ctx_alive(f->ctx)) return vm_fail(VM_E_INVALID, "%s: the context was destroyed", __func__);
-    VM_ON_DEVICE(f->ctx);
+    VM_ENTER(f);
+    if (int rc = vm_pitch_resolve(__func__, &pitch, 1, (size_t)f->w * 3)) return rc;
+    if (int rc = render_dev(f, color_fa, geo_fa, color_from, nullptr)) return rc;
     hipStream_t s = f->ctx->stream;
-    VM_HIP(hipMemcpy2DAsync(rgb, pitch, f->out.get(), (size_t)f->w * 3, (size_t)f->w * 3, f->h, hipMemcpyDeviceToHost, s));
+    if (int rc = vm_copy_pitched(__func__, hipMemcpyDeviceToHost, f->out.get(), (size_t)f->w * 3, rgb, pitch, 1, (size_t)f->w * 3, f->h, s)) return rc;
     VM_HIP(hipStreamSynchronize(s));
     return VM_OK;
 }

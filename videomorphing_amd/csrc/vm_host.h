@@ -56,6 +56,22 @@ struct VmDeviceGuard {
 // ... and in destructors / void functions (best effort)
 #define VM_ON_DEVICE_VOID(ctx) VmDeviceGuard VM_CAT(vm_device_guard_, __LINE__)((ctx)->device)
 
+// The guard of the C-ABI's entry points, for a handle with a `ctx` member or a bare vm_ctx *: not NULL -> its context
+// alive (nothing of a destroyed one is read) -> VM_ENTER_LOCKED only: ctx->mu held to the end of the function -> the
+// device current.  Which form an entry point uses belongs to the locking contract (vm_frame_set_v_from_level).
+inline vm_ctx *vm_ctx_of(vm_ctx *c) { return c; }
+template <class T> vm_ctx *vm_ctx_of(T *o) { return o->ctx; }
+#define VM_GUARD(obj, locked)                                                                                         \
+    if (!(obj)) return vm_fail(VM_E_INVALID, "%s: NULL handle", __func__);                                            \
+    vm_ctx *const VM_CAT(vm_guard_ctx_, __LINE__) = vm_ctx_of(obj);                                                   \
+    if (!vm_ctx_alive(VM_CAT(vm_guard_ctx_, __LINE__)))                                                               \
+        return vm_fail(VM_E_INVALID, "%s: the context was destroyed", __func__);                                      \
+    std::unique_lock<std::recursive_mutex> VM_CAT(vm_guard_lock_, __LINE__)(VM_CAT(vm_guard_ctx_, __LINE__)->mu, std::defer_lock); \
+    if (locked) VM_CAT(vm_guard_lock_, __LINE__).lock();                                                              \
+    VM_ON_DEVICE(VM_CAT(vm_guard_ctx_, __LINE__))
+#define VM_ENTER(obj) VM_GUARD(obj, false)
+#define VM_ENTER_LOCKED(obj) VM_GUARD(obj, true)
+
 struct VmMgbSys; // vm_mgb.h
 
 struct vm_ctx {
@@ -220,6 +236,16 @@ int vm_level_alloc(vm_ctx *c, vm_level &l, bool with_images);
 int vm_level_upsample(vm_ctx *c, vm_level &dst, const vm_level &src);
 int vm_level_init(vm_ctx *c, vm_level &l, int w0, int h0, const vm_constraint *cons, int n);
 int vm_level_read_field(vm_ctx *c, vm_level &l, int field, void *host);
+// ... and its copies from / to the host (drained on return): pitch in floats, 0 = tight; fn names the entry point;
+// `kind` = hipMemcpyHostToDevice writes v, hipMemcpyDeviceToHost reads it into v
+int vm_level_write_luma(vm_ctx *c, vm_level &l, const float *img0, const float *img1, int pitch, const char *fn);
+int vm_level_copy_v(vm_ctx *c, vm_level &l, hipMemcpyKind kind, const float *v, int pitch, const char *fn);
+// A caller's host image of h rows: `pitch` counts units of `unit` bytes (what include/vmorph.h documents for the entry
+// point fn: floats 4, bytes 1), 0 = tight.  vm_pitch_resolve turns 0 into the row and refuses a pitch below it;
+// vm_copy_pitched does that and copies the rows to or from a device image of dev_pitch_bytes (by `kind`) on s.
+int vm_pitch_resolve(const char *fn, int *pitch, size_t unit, size_t row_bytes);
+int vm_copy_pitched(const char *fn, hipMemcpyKind kind, void *dev, size_t dev_pitch_bytes, const void *host, int pitch,
+                    size_t unit, size_t row_bytes, int h, hipStream_t s);
 // the sweep of one level (vm_sweep_sched.cpp)
 int vm_iteration_cap(float max_iter, int *cap);
 int vm_optimize_levels(vm_ctx *c, vm_level **lv, int n, float max_iter, volatile const int *run_flag,

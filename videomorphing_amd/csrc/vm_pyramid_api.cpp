@@ -134,13 +134,11 @@ size_t chain_capacity(const vm_video *v)
 
 extern "C" int vm_pyramid_build_rgb(vm_pyr *p, const uint8_t *rgb0, const uint8_t *rgb1, int pitch)
 {
-    if (!p || !rgb0 || !rgb1) return vm_fail(VM_E_INVALID, "vm_pyramid_build_rgb: NULL argument");
-    std::lock_guard<std::recursive_mutex> lock(p->ctx->mu);
+    if (!rgb0 || !rgb1) return vm_fail(VM_E_INVALID, "vm_pyramid_build_rgb: NULL argument");
+    VM_ENTER_LOCKED(p);
     vm_ctx *c = p->ctx;
-    VM_ON_DEVICE(c);
     const int w0 = p->lv[0].w, h0 = p->lv[0].h, L = (int)p->lv.size();
-    if (pitch == 0) pitch = 3 * w0;
-    if (pitch < 3 * w0) return vm_fail(VM_E_INVALID, "vm_pyramid_build_rgb: pitch < 3*width");
+    if (int rc = vm_pitch_resolve(__func__, &pitch, 1, (size_t)3 * w0)) return rc;
     Builder B;
     B.c = c;
     const size_t cap = chain_capacity(p);
@@ -171,12 +169,11 @@ extern "C" int vm_pyramid_build_rgb(vm_pyr *p, const uint8_t *rgb0, const uint8_
 // tests of the stages.  planes: 3 tight planar float planes of w x h on the host, out: 3 planes of wout x hout.
 extern "C" int vm_dbg_pyramid_scale(vm_ctx *c, const float *planes, int w, int h, int wout, int hout, float *out)
 {
-    if (!c || !planes || !out) return vm_fail(VM_E_INVALID, "vm_dbg_pyramid_scale: NULL argument");
+    if (!planes || !out) return vm_fail(VM_E_INVALID, "vm_dbg_pyramid_scale: NULL argument");
     const int lim = 1 << 14;
     if (w < 1 || h < 1 || wout < 1 || hout < 1 || w > lim || h > lim || wout > lim || hout > lim)
         return vm_fail(VM_E_INVALID, "vm_dbg_pyramid_scale: %d x %d -> %d x %d (sides of 1 to %d)", w, h, wout, hout, lim);
-    std::lock_guard<std::recursive_mutex> lock(c->mu);
-    VM_ON_DEVICE(c);
+    VM_ENTER_LOCKED(c);
     Builder B;
     B.c = c;
     // either axis order passes through (w or wout) x (h or hout)
@@ -208,14 +205,12 @@ static int page_frame(const vm_video *v, int lvl, int t)
 // pyramid stands for the frame min(t * factor_t, prev_d - 1) of the level above).
 extern "C" int vm_video_build_rgb(vm_video *v, int frame, const uint8_t *rgb0, const uint8_t *rgb1, int pitch)
 {
-    if (!v || !rgb0 || !rgb1) return vm_fail(VM_E_INVALID, "vm_video_build_rgb: NULL argument");
+    if (!rgb0 || !rgb1) return vm_fail(VM_E_INVALID, "vm_video_build_rgb: NULL argument");
+    VM_ENTER_LOCKED(v);
     if (frame < 0 || frame >= v->depth[0]) return vm_fail(VM_E_INVALID, "vm_video_build_rgb: frame %d out of range", frame);
     vm_ctx *c = v->ctx;
-    std::lock_guard<std::recursive_mutex> lock(c->mu);
-    VM_ON_DEVICE(c);
     const int w0 = v->pages[0][0].lv.w, h0 = v->pages[0][0].lv.h, L = (int)v->pages.size();
-    if (pitch == 0) pitch = 3 * w0;
-    if (pitch < 3 * w0) return vm_fail(VM_E_INVALID, "vm_video_build_rgb: pitch < 3*width");
+    if (int rc = vm_pitch_resolve(__func__, &pitch, 1, (size_t)3 * w0)) return rc;
     Builder B;
     B.c = c;
     const size_t cap = chain_capacity(v);
@@ -307,10 +302,9 @@ static int build_flows_dev(vm_video *v, std::vector<VmDev<float2>> &flows)
 extern "C" int vm_video_build_flows(vm_video *v, const float *const *f0, const float *const *f1,
                                     const float *const *b0, const float *const *b1)
 {
-    if (!v || !f0 || !f1 || !b0 || !b1) return vm_fail(VM_E_INVALID, "vm_video_build_flows: NULL argument");
+    if (!f0 || !f1 || !b0 || !b1) return vm_fail(VM_E_INVALID, "vm_video_build_flows: NULL argument");
+    VM_ENTER_LOCKED(v);
     vm_ctx *c = v->ctx;
-    std::lock_guard<std::recursive_mutex> lock(c->mu);
-    VM_ON_DEVICE(c);
     hipStream_t s = c->stream;
     const int d0 = v->depth[0];
     const size_t n0 = (size_t)v->pages[0][0].lv.w * v->pages[0][0].lv.h;
@@ -331,10 +325,10 @@ extern "C" int vm_video_build_flows(vm_video *v, const float *const *f0, const f
 // tracks and the pyramid).  build_flows_dev consumes its input, so the flows are copied device to device.
 extern "C" int vm_video_build_flows_track(vm_video *v, const vm_track *t)
 {
-    if (!v || !t) return vm_fail(VM_E_INVALID, "vm_video_build_flows_track: NULL argument");
+    if (!t) return vm_fail(VM_E_INVALID, "vm_video_build_flows_track: NULL argument");
+    VM_ENTER_LOCKED(v);
     if (t->ctx != v->ctx) return vm_fail(VM_E_INVALID, "vm_video_build_flows_track: the tracker belongs to another context");
     vm_ctx *c = v->ctx;
-    if (!vm_ctx_alive(c)) return vm_fail(VM_E_INVALID, "vm_video_build_flows_track: the context was destroyed");
     const int d0 = v->depth[0], w0 = v->pages[0][0].lv.w, h0 = v->pages[0][0].lv.h;
     if (t->w != w0 || t->h != h0 || t->depth != d0)
         return vm_fail(VM_E_INVALID, "vm_video_build_flows_track: tracker of %d frames of %d x %d, video of %d frames of %d x %d",
@@ -343,8 +337,6 @@ extern "C" int vm_video_build_flows_track(vm_video *v, const vm_track *t)
         for (int i = 0; i < d0; ++i)
             if (!t->has_f[k][i] || !t->has_b[k][i])
                 return vm_fail(VM_E_STATE, "vm_video_build_flows_track: the flows of frame %d of video %d were never supplied", i, k);
-    std::lock_guard<std::recursive_mutex> lock(c->mu);
-    VM_ON_DEVICE(c);
     hipStream_t s = c->stream;
     const size_t n0 = (size_t)w0 * h0;
     std::vector<VmDev<float2>> flows(4 * (size_t)d0); // f0, f1, b0, b1
@@ -358,23 +350,20 @@ extern "C" int vm_video_build_flows_track(vm_video *v, const vm_track *t)
     return build_flows_dev(v, flows);
 }
 
-// MdiEditor::OpticalFlow (UI/MdiEditor.cpp:1584-1689) of both videos on the device, then the same flow half.
-// Frames are walked in chunks [t0, t1] that share their end frame: f[t] is computed in the chunk with
-// t0 <= t < t1, b[t] in the one with t0 < t <= t1, each exactly once.
+// MdiEditor::OpticalFlow (UI/MdiEditor.cpp:1584-1689) of both videos on the device (vm_flow_run_videos), then the
+// same flow half.
 extern "C" int vm_video_build_flows_rgb(vm_video *v, const uint8_t *const *rgb0, const uint8_t *const *rgb1,
                                         int pitch_bytes, const vm_flow_params *pp)
 {
-    if (!v || !rgb0 || !rgb1) return vm_fail(VM_E_INVALID, "vm_video_build_flows_rgb: NULL argument");
+    if (!rgb0 || !rgb1) return vm_fail(VM_E_INVALID, "vm_video_build_flows_rgb: NULL argument");
+    VM_ENTER_LOCKED(v);
     const int d0 = v->depth[0], w0 = v->pages[0][0].lv.w, h0 = v->pages[0][0].lv.h;
     vm_flow_params p;
     if (int rc = vm_flow_resolve(pp, w0, h0, &p, "vm_video_build_flows_rgb")) return rc;
-    if (pitch_bytes == 0) pitch_bytes = 3 * w0;
-    if (pitch_bytes < 3 * w0) return vm_fail(VM_E_INVALID, "vm_video_build_flows_rgb: pitch < 3*width");
+    if (int rc = vm_pitch_resolve(__func__, &pitch_bytes, 1, (size_t)3 * w0)) return rc;
     for (int t = 0; t < d0; ++t)
         if (!rgb0[t] || !rgb1[t]) return vm_fail(VM_E_INVALID, "vm_video_build_flows_rgb: frame %d is NULL", t);
     vm_ctx *c = v->ctx;
-    std::lock_guard<std::recursive_mutex> lock(c->mu);
-    VM_ON_DEVICE(c);
     hipStream_t s = c->stream;
     const size_t n0 = (size_t)w0 * h0;
     std::vector<VmDev<float2>> flows(4 * (size_t)d0); // f0, f1, b0, b1
@@ -385,23 +374,13 @@ extern "C" int vm_video_build_flows_rgb(vm_video *v, const uint8_t *const *rgb0,
     VmDev<uint8_t> stage;
     if (int rc = stage.reserve(n0 * 3)) return rc;
     const uint8_t *const *video[2] = {rgb0, rgb1};
-    const int F = vm_flow_video_chunk(w0, h0, p, 2);
-    for (int t0 = 0; t0 < d0 - 1; t0 += F - 1) {
-        const int t1 = std::min(d0 - 1, t0 + F - 1), nfr = t1 - t0 + 1;
-        std::vector<VmFlowPair> pairs;
-        for (int k = 0; k < 2; ++k)
-            for (int t = t0; t <= t1; ++t) { // frame slot of (video k, frame t): k * nfr + t - t0
-                const int slot = k * nfr + t - t0;
-                if (t < t1) pairs.push_back({slot, slot + 1, flows[(size_t)k * d0 + t].get()});
-                if (t > t0) pairs.push_back({slot, slot - 1, flows[(size_t)(2 + k) * d0 + t].get()});
-            }
-        auto src = [&](int f, float *dst) -> int {
-            const uint8_t *hs = video[f / nfr][t0 + f % nfr];
-            VM_HIP(hipMemcpy2DAsync(stage.get(), (size_t)w0 * 3, hs, (size_t)pitch_bytes, (size_t)w0 * 3, h0, hipMemcpyHostToDevice, s));
-            vm_flow_launch_grey_rgb(stage.get(), w0 * 3, w0, h0, dst, s);
-            return VM_OK;
-        };
-        if (int rc = vm_flow_run(c, w0, h0, p, 2 * nfr, src, pairs)) return rc;
-    }
+    auto src = [&](int k, int t, float *dst) -> int {
+        if (int rc = vm_copy_pitched("vm_video_build_flows_rgb", hipMemcpyHostToDevice, stage.get(), (size_t)w0 * 3, video[k][t], pitch_bytes, 1, (size_t)w0 * 3, h0, s)) return rc;
+        vm_flow_launch_grey_rgb(stage.get(), w0 * 3, w0, h0, dst, s);
+        return VM_OK;
+    };
+    if (int rc = vm_flow_run_videos(c, w0, h0, d0, p, src, [&](int k, int t) { return flows[(size_t)k * d0 + t].get(); },
+                                    [&](int k, int t) { return flows[(size_t)(2 + k) * d0 + t].get(); }))
+        return rc;
     return build_flows_dev(v, flows);
 }

@@ -25,12 +25,6 @@ struct vm_sync {
     VmDev<uint8_t> out;
 };
 
-#define CHECK_SYNC(s)                                                              \
-    if (!(s) || !(s)->ctx) return vm_fail(VM_E_INVALID, "%s: null handle", __func__);  \
-    if (!vm_ctx_alive((s)->ctx)) return vm_fail(VM_E_INVALID, "%s: the context was destroyed", __func__); \
-    std::lock_guard<std::recursive_mutex> lock_((s)->ctx->mu);                     \
-    VM_ON_DEVICE((s)->ctx)
-
 // Pyramid::build(video0, video1, f0, f1, start_res), pyramid.cu:143-163 -- evaluated in float as
 // there (`w /= decres_fa` on an int, the log2 template of pyramid.cu:50-55, ceil(w / 2.0f))
 extern "C" int vm_sync_level_table(int w, int h, int d, int start_res, int *lw, int *lh, int *ld, int cap, int *n_out)
@@ -96,15 +90,17 @@ extern "C" void vm_sync_destroy(vm_sync *s) { vm_destroy_object(s); }
 
 extern "C" int vm_sync_set_constraints(vm_sync *s, const vm_sync_constraint *c, int n)
 {
-    CHECK_SYNC(s);
+    VM_ENTER_LOCKED(s);
     if (n < 0 || (n > 0 && !c)) return vm_fail(VM_E_INVALID, "vm_sync_set_constraints: bad arguments");
     s->cons.assign(c, c + n);
     return VM_OK;
 }
 
-#define CHECK_SLVL(s, lvl)                                                                          \
-    if ((lvl) < 1 || (lvl) >= (int)(s)->w.size())                                                   \
-        return vm_fail(VM_E_INVALID, "%s: level %d out of range (1..%d)", __func__, (lvl), (int)(s)->w.size() - 1)
+static int check_level(const vm_sync *s, int lvl, const char *fn)
+{
+    if (lvl < 1 || lvl >= (int)s->w.size()) return vm_fail(VM_E_INVALID, "%s: level %d out of range (1..%d)", fn, lvl, (int)s->w.size() - 1);
+    return VM_OK;
+}
 
 static int alloc_field(vm_sync *s, int lvl)
 {
@@ -119,8 +115,8 @@ static int alloc_field(vm_sync *s, int lvl)
 
 extern "C" int vm_sync_load_identity(vm_sync *s, int lvl)
 {
-    CHECK_SYNC(s);
-    CHECK_SLVL(s, lvl);
+    VM_ENTER_LOCKED(s);
+    if (int rc = check_level(s, lvl, __func__)) return rc;
     s->f[lvl].reset();
     return alloc_field(s, lvl);
 }
@@ -129,8 +125,8 @@ extern "C" int vm_sync_load_identity(vm_sync *s, int lvl)
 // ratio, the frame displacement does not; the coarser field is released
 extern "C" int vm_sync_upsample_level(vm_sync *s, int lvl)
 {
-    CHECK_SYNC(s);
-    CHECK_SLVL(s, lvl);
+    VM_ENTER_LOCKED(s);
+    if (int rc = check_level(s, lvl, __func__)) return rc;
     const int pel = lvl + 1;
     if (pel >= (int)s->w.size() || !s->f[pel].get()) return vm_fail(VM_E_STATE, "vm_sync_upsample_level: level %d holds no field", pel);
     s->f[lvl].reset();
@@ -205,8 +201,8 @@ struct SyncWs {
 extern "C" int vm_sync_optimize_level(vm_sync *s, int lvl, float max_iter, volatile const int *run_flag,
                                       vm_sync_progress *out)
 {
-    CHECK_SYNC(s);
-    CHECK_SLVL(s, lvl);
+    VM_ENTER_LOCKED(s);
+    if (int rc = check_level(s, lvl, __func__)) return rc;
     vm_ctx *c = s->ctx;
     if (!s->f[lvl].get()) return vm_fail(VM_E_STATE, "vm_sync_optimize_level: level %d holds no field (load_identity / upsample_level)", lvl);
     if (!std::isfinite(max_iter) || max_iter > 1048576.0f) return vm_fail(VM_E_INVALID, "vm_sync_optimize_level: max_iter %g", (double)max_iter);
@@ -335,7 +331,7 @@ extern "C" int vm_sync_optimize_level(vm_sync *s, int lvl, float max_iter, volat
 // CSyncThread::run, SyncThread.cpp:58-84
 extern "C" int vm_sync_solve(vm_sync *s, float max_iter, volatile const int *run_flag, vm_sync_progress *out)
 {
-    CHECK_SYNC(s);
+    VM_ENTER_LOCKED(s);
     const int total = (int)s->w.size() - 1;
     float mi = max_iter * 10;
     for (int el = total; el > 0; --el) {
@@ -353,8 +349,8 @@ extern "C" int vm_sync_solve(vm_sync *s, float max_iter, volatile const int *run
 
 extern "C" int vm_sync_get_field(vm_sync *s, int lvl, float *x, float *y, float *z)
 {
-    CHECK_SYNC(s);
-    CHECK_SLVL(s, lvl);
+    VM_ENTER_LOCKED(s);
+    if (int rc = check_level(s, lvl, __func__)) return rc;
     if (!s->f[lvl].get()) return vm_fail(VM_E_STATE, "vm_sync_get_field: level %d holds no field", lvl);
     const size_t N = (size_t)s->w[lvl] * s->h[lvl] * s->d[lvl];
     float *dst[3] = {x, y, z};
@@ -366,8 +362,8 @@ extern "C" int vm_sync_get_field(vm_sync *s, int lvl, float *x, float *y, float 
 
 extern "C" int vm_sync_set_field(vm_sync *s, int lvl, const float *x, const float *y, const float *z)
 {
-    CHECK_SYNC(s);
-    CHECK_SLVL(s, lvl);
+    VM_ENTER_LOCKED(s);
+    if (int rc = check_level(s, lvl, __func__)) return rc;
     if (int rc = alloc_field(s, lvl)) return rc;
     const size_t N = (size_t)s->w[lvl] * s->h[lvl] * s->d[lvl];
     const float *src[3] = {x, y, z};
@@ -396,8 +392,8 @@ static int refresh_vec(vm_sync *s, int lvl, int frame)
 
 extern "C" int vm_sync_result(vm_sync *s, int lvl, int frame, float *vec4)
 {
-    CHECK_SYNC(s);
-    CHECK_SLVL(s, lvl);
+    VM_ENTER_LOCKED(s);
+    if (int rc = check_level(s, lvl, __func__)) return rc;
     if (frame < 0 || frame >= s->d[lvl]) return vm_fail(VM_E_INVALID, "vm_sync_result: frame %d out of range", frame);
     if (!s->f[lvl].get()) return vm_fail(VM_E_STATE, "vm_sync_result: level %d holds no field", lvl);
     if (int rc = refresh_vec(s, lvl, frame)) return rc;
@@ -408,7 +404,7 @@ extern "C" int vm_sync_result(vm_sync *s, int lvl, int frame, float *vec4)
 
 extern "C" int vm_sync_upload_frame(vm_sync *s, int side, int frame, const uint8_t *rgba, int pitch_bytes)
 {
-    CHECK_SYNC(s);
+    VM_ENTER_LOCKED(s);
     const int w0 = s->w[0], h0 = s->h[0], d0 = s->d[0];
     if (side < 0 || side > 1 || frame < 0 || frame >= d0 || !rgba || pitch_bytes < w0 * 4)
         return vm_fail(VM_E_INVALID, "vm_sync_upload_frame: bad arguments");
@@ -417,15 +413,14 @@ extern "C" int vm_sync_upload_frame(vm_sync *s, int side, int frame, const uint8
         if (int rc = s->video[side].reserve(page * d0)) return rc;
         VM_HIP(hipMemsetAsync(s->video[side].get(), 0, page * d0 * sizeof(uchar4), s->ctx->stream));
     }
-    VM_HIP(hipMemcpy2DAsync(s->video[side].get() + frame * page, (size_t)w0 * 4, rgba, (size_t)pitch_bytes, (size_t)w0 * 4, h0,
-                            hipMemcpyHostToDevice, s->ctx->stream));
+    if (int rc = vm_copy_pitched(__func__, hipMemcpyHostToDevice, s->video[side].get() + frame * page, (size_t)w0 * 4, rgba, pitch_bytes, 1, (size_t)w0 * 4, h0, s->ctx->stream)) return rc;
     VM_HIP(hipStreamSynchronize(s->ctx->stream));
     return VM_OK;
 }
 
 extern "C" int vm_sync_upload_flow(vm_sync *s, int side, int frame, const float *flow_xy, int pitch_floats)
 {
-    CHECK_SYNC(s);
+    VM_ENTER_LOCKED(s);
     const int w0 = s->w[0], h0 = s->h[0], d0 = s->d[0];
     if (side < 0 || side > 1 || frame < 0 || frame >= d0 || !flow_xy || pitch_floats < w0 * 2)
         return vm_fail(VM_E_INVALID, "vm_sync_upload_flow: bad arguments");
@@ -434,8 +429,7 @@ extern "C" int vm_sync_upload_flow(vm_sync *s, int side, int frame, const float 
         if (int rc = s->forw[side].reserve(page * d0)) return rc;
         VM_HIP(hipMemsetAsync(s->forw[side].get(), 0, page * d0 * sizeof(float2), s->ctx->stream));
     }
-    VM_HIP(hipMemcpy2DAsync(s->forw[side].get() + frame * page, (size_t)w0 * 8, flow_xy, (size_t)pitch_floats * 4, (size_t)w0 * 8, h0,
-                            hipMemcpyHostToDevice, s->ctx->stream));
+    if (int rc = vm_copy_pitched(__func__, hipMemcpyHostToDevice, s->forw[side].get() + frame * page, (size_t)w0 * 8, flow_xy, pitch_floats, 4, (size_t)w0 * 8, h0, s->ctx->stream)) return rc;
     VM_HIP(hipStreamSynchronize(s->ctx->stream));
     return VM_OK;
 }
@@ -444,7 +438,7 @@ extern "C" int vm_sync_upload_flow(vm_sync *s, int side, int frame, const float 
 // uploaded frames straight into the layered flow arrays; the last frame's flow is zero
 extern "C" int vm_sync_compute_flows(vm_sync *s, const vm_flow_params *pp)
 {
-    CHECK_SYNC(s);
+    VM_ENTER_LOCKED(s);
     const int w0 = s->w[0], h0 = s->h[0], d0 = s->d[0];
     vm_flow_params p;
     if (int rc = vm_flow_resolve(pp, w0, h0, &p, "vm_sync_compute_flows")) return rc;
@@ -456,18 +450,11 @@ extern "C" int vm_sync_compute_flows(vm_sync *s, const vm_flow_params *pp)
         if (int rc = s->forw[k].reserve(page * d0)) return rc;
         VM_HIP(hipMemsetAsync(s->forw[k].get() + (d0 - 1) * page, 0, page * sizeof(float2), st));
     }
-    const int F = vm_flow_video_chunk(w0, h0, p, 2);
-    for (int t0 = 0; t0 < d0 - 1; t0 += F - 1) {
-        const int t1 = std::min(d0 - 1, t0 + F - 1), nfr = t1 - t0 + 1;
-        std::vector<VmFlowPair> pairs;
-        for (int k = 0; k < 2; ++k)
-            for (int t = t0; t < t1; ++t) pairs.push_back({k * nfr + t - t0, k * nfr + t - t0 + 1, s->forw[k].get() + t * page});
-        auto src = [&](int f, float *dst) -> int {
-            vm_flow_launch_grey_rgba(s->video[f / nfr].get() + (t0 + f % nfr) * page, w0, h0, dst, st);
-            return VM_OK;
-        };
-        if (int rc = vm_flow_run(s->ctx, w0, h0, p, 2 * nfr, src, pairs)) return rc;
-    }
+    auto src = [&](int k, int t, float *dst) -> int {
+        vm_flow_launch_grey_rgba(s->video[k].get() + t * page, w0, h0, dst, st);
+        return VM_OK;
+    };
+    if (int rc = vm_flow_run_videos(s->ctx, w0, h0, d0, p, src, [&](int k, int t) { return s->forw[k].get() + t * page; }, nullptr)) return rc;
     VM_HIP(hipStreamSynchronize(st));
     return VM_OK;
 }
@@ -498,18 +485,17 @@ static int render_common(vm_sync *s, float fa, int frame)
 
 extern "C" int vm_sync_render(vm_sync *s, float fa, int frame, uint8_t *rgb_out, int pitch_bytes)
 {
-    CHECK_SYNC(s);
+    VM_ENTER_LOCKED(s);
     if (!rgb_out || pitch_bytes < s->w[0] * 3) return vm_fail(VM_E_INVALID, "vm_sync_render: bad output");
     if (int rc = render_common(s, fa, frame)) return rc;
-    VM_HIP(hipMemcpy2DAsync(rgb_out, (size_t)pitch_bytes, s->out.get(), (size_t)s->w[0] * 3, (size_t)s->w[0] * 3, s->h[0],
-                            hipMemcpyDeviceToHost, s->ctx->stream));
+    if (int rc = vm_copy_pitched(__func__, hipMemcpyDeviceToHost, s->out.get(), (size_t)s->w[0] * 3, rgb_out, pitch_bytes, 1, (size_t)s->w[0] * 3, s->h[0], s->ctx->stream)) return rc;
     VM_HIP(hipStreamSynchronize(s->ctx->stream));
     return VM_OK;
 }
 
 extern "C" int vm_sync_render_dev(vm_sync *s, float fa, int frame, float *elapsed_ms)
 {
-    CHECK_SYNC(s);
+    VM_ENTER_LOCKED(s);
     VM_HIP(hipEventRecord(s->ctx->ev0.get(), s->ctx->stream));
     if (int rc = render_common(s, fa, frame)) return rc;
     VM_HIP(hipEventRecord(s->ctx->ev1.get(), s->ctx->stream));

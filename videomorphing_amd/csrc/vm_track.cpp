@@ -10,12 +10,6 @@
 #include <cmath>
 #include <cstdlib>
 
-#define CHECK_TRACK(t)                                                                                       \
-    if (!(t) || !(t)->ctx) return vm_fail(VM_E_INVALID, "%s: null handle", __func__);                       \
-    if (!vm_ctx_alive((t)->ctx)) return vm_fail(VM_E_INVALID, "%s: the context was destroyed", __func__);   \
-    std::lock_guard<std::recursive_mutex> lock_((t)->ctx->mu);                                               \
-    VM_ON_DEVICE((t)->ctx)
-
 extern "C" int vm_track_create(vm_ctx *ctx, int w, int h, int depth, vm_track **out)
 {
     if (!ctx || !out) return vm_fail(VM_E_INVALID, "vm_track_create: NULL argument");
@@ -59,15 +53,14 @@ static int check_side_frame(const vm_track *t, int side, int frame, const char *
 
 extern "C" int vm_track_upload_frame(vm_track *t, int side, int frame, const uint8_t *rgb, int pitch_bytes)
 {
-    CHECK_TRACK(t);
+    VM_ENTER_LOCKED(t);
     if (int rc = check_side_frame(t, side, frame, __func__)) return rc;
     if (!rgb) return vm_fail(VM_E_INVALID, "vm_track_upload_frame: NULL frame");
-    if (pitch_bytes == 0) pitch_bytes = 3 * t->w;
-    if (pitch_bytes < 3 * t->w) return vm_fail(VM_E_INVALID, "vm_track_upload_frame: pitch < 3*width");
+    if (int rc = vm_pitch_resolve(__func__, &pitch_bytes, 1, (size_t)3 * t->w)) return rc;
     hipStream_t s = t->ctx->stream;
     VmDev<uint8_t> stage;
     if (int rc = stage.reserve((size_t)3 * t->w * t->h)) return rc;
-    VM_HIP(hipMemcpy2DAsync(stage.get(), (size_t)3 * t->w, rgb, (size_t)pitch_bytes, (size_t)3 * t->w, t->h, hipMemcpyHostToDevice, s));
+    if (int rc = vm_copy_pitched(__func__, hipMemcpyHostToDevice, stage.get(), (size_t)3 * t->w, rgb, pitch_bytes, 1, (size_t)3 * t->w, t->h, s)) return rc;
     vm_track_launch_rgba(stage.get(), 3 * t->w, t->w, t->h, t->frames[side].get() + (size_t)frame * t->w * t->h, s);
     VM_HIP(hipGetLastError());
     VM_HIP(hipStreamSynchronize(s)); // the stage is freed on return
@@ -77,10 +70,9 @@ extern "C" int vm_track_upload_frame(vm_track *t, int side, int frame, const uin
 
 extern "C" int vm_track_upload_flows(vm_track *t, int side, int frame, const float *f_xy, const float *b_xy, int pitch)
 {
-    CHECK_TRACK(t);
+    VM_ENTER_LOCKED(t);
     if (int rc = check_side_frame(t, side, frame, __func__)) return rc;
-    if (pitch == 0) pitch = 2 * t->w;
-    if (pitch < 2 * t->w) return vm_fail(VM_E_INVALID, "vm_track_upload_flows: pitch < 2*width");
+    if (int rc = vm_pitch_resolve(__func__, &pitch, 4, (size_t)t->w * 8)) return rc;
     for (const float *src : {f_xy, b_xy}) // every position a step can reach stays an int
         if (src)
             for (int y = 0; y < t->h; ++y)
@@ -96,19 +88,16 @@ extern "C" int vm_track_upload_flows(vm_track *t, int side, int frame, const flo
     VmDev<float2> *dst[2] = {&t->f[side], &t->b[side]};
     for (int k = 0; k < 2; ++k)
         if (src[k])
-            VM_HIP(hipMemcpy2DAsync(dst[k]->get() + frame * page, (size_t)t->w * 8, src[k], (size_t)pitch * 4, (size_t)t->w * 8, t->h,
-                                    hipMemcpyHostToDevice, s));
+            if (int rc = vm_copy_pitched(__func__, hipMemcpyHostToDevice, dst[k]->get() + frame * page, (size_t)t->w * 8, src[k], pitch, 4, (size_t)t->w * 8, t->h, s)) return rc;
     VM_HIP(hipStreamSynchronize(s));
     if (f_xy) t->has_f[side][frame] = 1;
     if (b_xy) t->has_b[side][frame] = 1;
     return VM_OK;
 }
 
-// Frames are walked in chunks [t0, t1] that share their end frame, as vm_video_build_flows_rgb does: f[t] is
-// computed in the chunk with t0 <= t < t1, b[t] in the one with t0 < t <= t1
 extern "C" int vm_track_compute_flows(vm_track *t, const vm_flow_params *pp)
 {
-    CHECK_TRACK(t);
+    VM_ENTER_LOCKED(t);
     const int w = t->w, h = t->h, d = t->depth;
     vm_flow_params p;
     if (int rc = vm_flow_resolve(pp, w, h, &p, "vm_track_compute_flows")) return rc;
@@ -125,22 +114,13 @@ extern "C" int vm_track_compute_flows(vm_track *t, const vm_flow_params *pp)
         VM_HIP(hipMemsetAsync(t->f[k].get() + (size_t)(d - 1) * page, 0, page * sizeof(float2), s));
         VM_HIP(hipMemsetAsync(t->b[k].get(), 0, page * sizeof(float2), s));
     }
-    const int F = vm_flow_video_chunk(w, h, p, 2);
-    for (int t0 = 0; t0 < d - 1; t0 += F - 1) {
-        const int t1 = std::min(d - 1, t0 + F - 1), nfr = t1 - t0 + 1;
-        std::vector<VmFlowPair> pairs;
-        for (int k = 0; k < 2; ++k)
-            for (int i = t0; i <= t1; ++i) { // frame slot of (video k, frame i): k * nfr + i - t0
-                const int slot = k * nfr + i - t0;
-                if (i < t1) pairs.push_back({slot, slot + 1, t->f[k].get() + (size_t)i * page});
-                if (i > t0) pairs.push_back({slot, slot - 1, t->b[k].get() + (size_t)i * page});
-            }
-        auto src = [&](int f, float *dst) -> int {
-            vm_flow_launch_grey_rgba(t->frames[f / nfr].get() + (size_t)(t0 + f % nfr) * page, w, h, dst, s);
-            return VM_OK;
-        };
-        if (int rc = vm_flow_run(t->ctx, w, h, p, 2 * nfr, src, pairs)) return rc;
-    }
+    auto src = [&](int k, int i, float *dst) -> int {
+        vm_flow_launch_grey_rgba(t->frames[k].get() + (size_t)i * page, w, h, dst, s);
+        return VM_OK;
+    };
+    if (int rc = vm_flow_run_videos(t->ctx, w, h, d, p, src, [&](int k, int i) { return t->f[k].get() + (size_t)i * page; },
+                                    [&](int k, int i) { return t->b[k].get() + (size_t)i * page; }))
+        return rc;
     VM_HIP(hipStreamSynchronize(s));
     for (int k = 0; k < 2; ++k) {
         t->has_f[k].assign(d, 1);
@@ -151,7 +131,7 @@ extern "C" int vm_track_compute_flows(vm_track *t, const vm_flow_params *pp)
 
 extern "C" int vm_track_get_flows(vm_track *t, int side, int frame, float *f_xy, float *b_xy)
 {
-    CHECK_TRACK(t);
+    VM_ENTER_LOCKED(t);
     if (int rc = check_side_frame(t, side, frame, __func__)) return rc;
     if ((f_xy && !t->has_f[side][frame]) || (b_xy && !t->has_b[side][frame]))
         return vm_fail(VM_E_STATE, "vm_track_get_flows: a flow of frame %d of video %d was never supplied", frame, side);
@@ -200,7 +180,7 @@ static int check_segment(const vm_track *t, const vm_track_segment &g, int i)
 
 extern "C" int vm_track_propagate(vm_track *t, const vm_track_segment *seg, int n, vm_track_point *out)
 {
-    CHECK_TRACK(t);
+    VM_ENTER_LOCKED(t);
     if (n < 0 || (n > 0 && (!seg || !out))) return vm_fail(VM_E_INVALID, "vm_track_propagate: bad arguments");
     for (int i = 0; i < n; ++i)
         if (int rc = check_segment(t, seg[i], i)) return rc;

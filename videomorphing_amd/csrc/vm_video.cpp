@@ -21,14 +21,13 @@
 #include <thread>
 #include <vector>
 
-#define CHECK_VID(v, lvl, page)                                                                        \
-    if (!(v)) return vm_fail(VM_E_INVALID, "%s: video is NULL", __func__);                             \
-    if ((lvl) < 0 || (lvl) >= (int)(v)->pages.size())                                                  \
-        return vm_fail(VM_E_INVALID, "%s: level %d out of range", __func__, (lvl));                    \
-    if ((page) < 0 || (page) >= (v)->depth[(lvl)])                                                     \
-        return vm_fail(VM_E_INVALID, "%s: page %d out of range (level %d has %d)", __func__, (page), (lvl), (v)->depth[(lvl)]); \
-    if (!vm_ctx_alive((v)->ctx)) return vm_fail(VM_E_INVALID, "%s: the context was destroyed", __func__); \
-    VM_ON_DEVICE((v)->ctx);
+static int check_page(const vm_video *v, int lvl, int page, const char *fn)
+{
+    if (lvl < 0 || lvl >= (int)v->pages.size()) return vm_fail(VM_E_INVALID, "%s: level %d out of range", fn, lvl);
+    if (page < 0 || page >= v->depth[lvl])
+        return vm_fail(VM_E_INVALID, "%s: page %d out of range (level %d has %d)", fn, page, lvl, v->depth[lvl]);
+    return VM_OK;
+}
 
 extern "C" int vm_video_create(vm_ctx *c, int nlevels, const int *w, const int *h, const int *d,
                                const int *factor_t, int depth0, vm_video **out)
@@ -120,7 +119,8 @@ extern "C" int vm_video_levels(vm_video *v) { return v ? (int)v->pages.size() : 
 
 extern "C" int vm_video_level_dims(vm_video *v, int lvl, int *w, int *h, int *depth, float *factor_d)
 {
-    CHECK_VID(v, lvl, 0);
+    VM_ENTER(v);
+    if (int rc = check_page(v, lvl, 0, __func__)) return rc;
     if (w) *w = v->pages[lvl][0].lv.w;
     if (h) *h = v->pages[lvl][0].lv.h;
     if (depth) *depth = v->depth[lvl];
@@ -130,62 +130,42 @@ extern "C" int vm_video_level_dims(vm_video *v, int lvl, int *w, int *h, int *de
 
 extern "C" int vm_video_upload_luma(vm_video *v, int lvl, int page, const float *img0, const float *img1, int pitch)
 {
-    CHECK_VID(v, lvl, page);
-    vm_level &l = v->pages[lvl][page].lv;
-    if (!l.view.img0) return vm_fail(VM_E_STATE, "vm_video_upload_luma: the coarsest level holds no images");
-    if (!img0 || !img1) return vm_fail(VM_E_INVALID, "vm_video_upload_luma: NULL image");
-    if (pitch == 0) pitch = l.w;
-    if (pitch < l.w) return vm_fail(VM_E_INVALID, "vm_video_upload_luma: pitch < width");
-    hipStream_t s = v->ctx->stream;
-    VM_HIP(hipMemcpy2DAsync((void *)l.view.img0, l.rs * 4, img0, (size_t)pitch * 4, (size_t)l.w * 4, l.h, hipMemcpyHostToDevice, s));
-    VM_HIP(hipMemcpy2DAsync((void *)l.view.img1, l.rs * 4, img1, (size_t)pitch * 4, (size_t)l.w * 4, l.h, hipMemcpyHostToDevice, s));
-    VM_HIP(hipStreamSynchronize(s));
-    return VM_OK;
+    VM_ENTER(v);
+    if (int rc = check_page(v, lvl, page, __func__)) return rc;
+    return vm_level_write_luma(v->ctx, v->pages[lvl][page].lv, img0, img1, pitch, __func__);
 }
 
 // the cudaMemcpy2DToArray uploads of lvl.f0/f1/b0/b1, pyramid.cu:323-326, 452-455
 extern "C" int vm_video_upload_flows(vm_video *v, int lvl, int page, const float *f0, const float *f1,
                                      const float *b0, const float *b1, int pitch)
 {
-    CHECK_VID(v, lvl, page);
+    VM_ENTER(v);
+    if (int rc = check_page(v, lvl, page, __func__)) return rc;
     vm_video_page &pg = v->pages[lvl][page];
     vm_level &l = pg.lv;
     if (!pg.tslab.get()) return vm_fail(VM_E_STATE, "vm_video_upload_flows: the coarsest level holds no flows");
-    if (pitch == 0) pitch = 2 * l.w;
-    if (pitch < 2 * l.w) return vm_fail(VM_E_INVALID, "vm_video_upload_flows: pitch < 2*width");
+    if (int rc = vm_pitch_resolve(__func__, &pitch, 4, (size_t)l.w * 8)) return rc;
     hipStream_t s = v->ctx->stream;
     const float *src[4] = {f0, f1, b0, b1};
     for (int k = 0; k < 4; ++k)
         if (src[k])
-            VM_HIP(hipMemcpy2DAsync(pg.flow[k], l.rs * 8, src[k], (size_t)pitch * 4, (size_t)l.w * 8, l.h, hipMemcpyHostToDevice, s));
+            if (int rc = vm_copy_pitched(__func__, hipMemcpyHostToDevice, pg.flow[k], l.rs * 8, src[k], pitch, 4, (size_t)l.w * 8, l.h, s)) return rc;
     VM_HIP(hipStreamSynchronize(s));
     return VM_OK;
 }
 
 extern "C" int vm_video_set_v(vm_video *v, int lvl, int page, const float *vxy, int pitch)
 {
-    CHECK_VID(v, lvl, page);
-    vm_level &l = v->pages[lvl][page].lv;
-    if (!vxy) return vm_fail(VM_E_INVALID, "vm_video_set_v: NULL");
-    if (pitch == 0) pitch = 2 * l.w;
-    if (pitch < 2 * l.w) return vm_fail(VM_E_INVALID, "vm_video_set_v: pitch < 2*width");
-    hipStream_t s = v->ctx->stream;
-    VM_HIP(hipMemcpy2DAsync(l.view.v, l.rs * 8, vxy, (size_t)pitch * 4, (size_t)l.w * 8, l.h, hipMemcpyHostToDevice, s));
-    VM_HIP(hipStreamSynchronize(s));
-    return VM_OK;
+    VM_ENTER(v);
+    if (int rc = check_page(v, lvl, page, __func__)) return rc;
+    return vm_level_copy_v(v->ctx, v->pages[lvl][page].lv, hipMemcpyHostToDevice, vxy, pitch, __func__);
 }
 
 extern "C" int vm_video_get_v(vm_video *v, int lvl, int page, float *vxy, int pitch)
 {
-    CHECK_VID(v, lvl, page);
-    vm_level &l = v->pages[lvl][page].lv;
-    if (!vxy) return vm_fail(VM_E_INVALID, "vm_video_get_v: NULL");
-    if (pitch == 0) pitch = 2 * l.w;
-    if (pitch < 2 * l.w) return vm_fail(VM_E_INVALID, "vm_video_get_v: pitch < 2*width");
-    hipStream_t s = v->ctx->stream;
-    VM_HIP(hipMemcpy2DAsync(vxy, (size_t)pitch * 4, l.view.v, l.rs * 8, (size_t)l.w * 8, l.h, hipMemcpyDeviceToHost, s));
-    VM_HIP(hipStreamSynchronize(s));
-    return VM_OK;
+    VM_ENTER(v);
+    if (int rc = check_page(v, lvl, page, __func__)) return rc;
+    return vm_level_copy_v(v->ctx, v->pages[lvl][page].lv, hipMemcpyDeviceToHost, vxy, pitch, __func__);
 }
 
 // CMatchingThread::update_result for one frame of the full-resolution result
@@ -240,9 +220,9 @@ static int video_result_frame(vm_video *v, int lvl, int w0, int h0, int f, float
 
 extern "C" int vm_video_result(vm_video *v, int lvl, int w0, int h0, float *out)
 {
-    CHECK_VID(v, lvl, 0);
+    VM_ENTER_LOCKED(v);
+    if (int rc = check_page(v, lvl, 0, __func__)) return rc;
     if (!out || w0 < 1 || h0 < 1) return vm_fail(VM_E_INVALID, "vm_video_result: bad argument");
-    std::lock_guard<std::recursive_mutex> lock(v->ctx->mu);
     hipStream_t s = v->ctx->stream;
     const size_t n = (size_t)w0 * h0;
     VmDev<float2> buf;
@@ -260,10 +240,10 @@ extern "C" int vm_video_result(vm_video *v, int lvl, int w0, int h0, float *out)
 
 extern "C" int vm_frame_set_v_from_video(vm_frame *f, vm_video *v, int lvl, int frame)
 {
-    CHECK_VID(v, lvl, 0);
+    VM_ENTER_LOCKED(v);
+    if (int rc = check_page(v, lvl, 0, __func__)) return rc;
     if (!f || f->ctx != v->ctx) return vm_fail(VM_E_INVALID, "vm_frame_set_v_from_video: the frame and the video must share a context");
     if (frame < 0 || frame >= v->depth0) return vm_fail(VM_E_INVALID, "vm_frame_set_v_from_video: frame %d out of range (0..%d)", frame, v->depth0 - 1);
-    std::lock_guard<std::recursive_mutex> lock(v->ctx->mu);
     const size_t n = (size_t)f->w * f->h;
     if (int rc = v->result_tmp.reserve(2 * n, v->ctx->stream)) return rc;
     return video_result_frame(v, lvl, f->w, f->h, frame, f->v.get(), f->rs, v->result_tmp.get());
@@ -271,14 +251,15 @@ extern "C" int vm_frame_set_v_from_video(vm_frame *f, vm_video *v, int lvl, int 
 
 extern "C" int vm_video_get_field(vm_video *v, int lvl, int page, int field, void *host)
 {
-    CHECK_VID(v, lvl, page);
+    VM_ENTER(v);
+    if (int rc = check_page(v, lvl, page, __func__)) return rc;
     vm_video_page &pg = v->pages[lvl][page];
     if (field >= VM_F_FLOW_F0 && field <= VM_F_FLOW_B1) {
         if (!host) return vm_fail(VM_E_INVALID, "vm_video_get_field: NULL");
         if (!pg.tslab.get()) return vm_fail(VM_E_STATE, "vm_video_get_field: the coarsest level holds no flows");
         vm_level &l = pg.lv;
         hipStream_t s = v->ctx->stream;
-        VM_HIP(hipMemcpy2DAsync(host, (size_t)l.w * 8, pg.flow[field - VM_F_FLOW_F0], (size_t)l.rs * 8, (size_t)l.w * 8, l.h, hipMemcpyDeviceToHost, s));
+        if (int rc = vm_copy_pitched(__func__, hipMemcpyDeviceToHost, pg.flow[field - VM_F_FLOW_F0], (size_t)l.rs * 8, host, 0, 8, (size_t)l.w * 8, l.h, s)) return rc;
         VM_HIP(hipStreamSynchronize(s));
         return VM_OK;
     }
@@ -301,9 +282,8 @@ static std::vector<vm_constraint> page_constraints(const vm_video *v, int lvl, i
 // Morph::cpu_optimize_level for every page of the coarsest level, morph.cu:419-590
 extern "C" int vm_video_coarse_solve(vm_video *v, const vm_video_constraint *cons, int n)
 {
-    if (!v) return vm_fail(VM_E_INVALID, "vm_video_coarse_solve: video is NULL");
     if (n < 0 || (n > 0 && !cons)) return vm_fail(VM_E_INVALID, "vm_video_coarse_solve: constraints");
-    VM_ON_DEVICE(v->ctx);
+    VM_ENTER(v);
     const int L = (int)v->pages.size() - 1;
     const int w0 = v->pages[0][0].lv.w, h0 = v->pages[0][0].lv.h;
     for (int z = 0; z < v->depth[L]; ++z) {
@@ -329,7 +309,8 @@ static int splat_page(vm_video *v, const vm_video_page &src, const float2 *fa, c
 // upsample(pyr[dst], pyr[dst+1]), upsample.cu:260-340
 extern "C" int vm_video_upsample(vm_video *v, int dst)
 {
-    CHECK_VID(v, dst, 0);
+    VM_ENTER(v);
+    if (int rc = check_page(v, dst, 0, __func__)) return rc;
     if (dst + 1 >= (int)v->pages.size()) return vm_fail(VM_E_INVALID, "vm_video_upsample: level %d has no coarser level", dst);
     vm_ctx *c = v->ctx;
     hipStream_t s = c->stream;
@@ -364,7 +345,8 @@ extern "C" int vm_video_upsample(vm_video *v, int dst)
 // Morph::initialize_level for every page, morph.cu:264-390
 extern "C" int vm_video_init_level(vm_video *v, int lvl, const vm_video_constraint *cons, int n)
 {
-    CHECK_VID(v, lvl, 0);
+    VM_ENTER(v);
+    if (int rc = check_page(v, lvl, 0, __func__)) return rc;
     if (n < 0 || (n > 0 && !cons)) return vm_fail(VM_E_INVALID, "vm_video_init_level: constraints");
     const int w0 = v->pages[0][0].lv.w, h0 = v->pages[0][0].lv.h;
     for (int z = 0; z < v->depth[lvl]; ++z) {
@@ -388,7 +370,8 @@ extern "C" int vm_video_init_level(vm_video *v, int lvl, const vm_video_constrai
 // initialize_temp(lvl, i, dir), upsample.cu:214-258
 extern "C" int vm_video_initialize_temp(vm_video *v, int lvl, int page, int dir)
 {
-    CHECK_VID(v, lvl, page);
+    VM_ENTER(v);
+    if (int rc = check_page(v, lvl, page, __func__)) return rc;
     if (dir != 1 && dir != -1) return vm_fail(VM_E_INVALID, "vm_video_initialize_temp: dir must be +1 or -1");
     const int j = page + dir;
     if (j < 0 || j >= v->depth[lvl]) return vm_fail(VM_E_INVALID, "vm_video_initialize_temp: page %d has no neighbour in direction %d", page, dir);
@@ -412,9 +395,9 @@ extern "C" int vm_video_initialize_temp(vm_video *v, int lvl, int page, int dir)
 extern "C" int vm_video_optimize_level(vm_video *v, int lvl, float max_iter, volatile const int *run_flag,
                                        int fixed_work, vm_progress *out)
 {
-    CHECK_VID(v, lvl, 0);
+    VM_ENTER_LOCKED(v);
+    if (int rc = check_page(v, lvl, 0, __func__)) return rc;
     vm_ctx *c = v->ctx;
-    std::lock_guard<std::recursive_mutex> lock(c->mu);
     const int d = v->depth[lvl], mid = d / 2;
     int rc;
     {
@@ -596,10 +579,8 @@ static int video_task(vm_video *v, vm_video_lane &ln, int el, int k, float max_i
 extern "C" int vm_video_solve(vm_video *v, float max_iter, float drop, const vm_video_constraint *cons, int n,
                               volatile const int *run_flag, int fixed_work, vm_progress *per_page)
 {
-    if (!v) return vm_fail(VM_E_INVALID, "vm_video_solve: video is NULL");
     if (!(drop > 0)) return vm_fail(VM_E_INVALID, "vm_video_solve: max_iter_drop_factor must be > 0");
-    std::lock_guard<std::recursive_mutex> lock(v->ctx->mu);
-    VM_ON_DEVICE(v->ctx);
+    VM_ENTER_LOCKED(v);
     const int L = (int)v->pages.size();
     int rc = vm_video_coarse_solve(v, cons, n);
     if (rc != VM_OK) return rc;
