@@ -1,16 +1,14 @@
 // vmorph/morph.hpp -- C++ host mirror of Algorithm/morph.h (class Morph) and
-// Algorithm/MatchingThread.h (class CMatchingThread, QThread -> std::thread),
+// Algorithm/MatchingThread.h (class CMatchingThread, QThread -> detail::Worker),
 // reference repository.  Same constructor arguments, same public progress
 // members, same cancellation through a caller-owned flag.
 #ifndef VMORPH_MORPH_HPP
 #define VMORPH_MORPH_HPP
 
-#include <atomic>
-#include <chrono>
 #include <map>
-#include <thread>
 
 #include "pyramid.hpp"
+#include "worker.hpp"
 
 namespace vmorph {
 
@@ -75,35 +73,15 @@ private:
 };
 
 // class CMatchingThread, MatchingThread.h:7-37
-class MatchingThread {
+class MatchingThread : public detail::Worker {
 public:
     MatchingThread(Parameters &parameters, Pyramid &pyramids)
-        : runflag(1), _pyramids(pyramids), _parameters(parameters), gpu_morph(parameters, pyramids, runflag) {}
-    // joins the worker; an exception it stored is dropped here (a destructor must not throw:
-    // call wait() first to see it)
-    ~MatchingThread()
-    {
-        if (thread_.joinable()) thread_.join();
-    }
-
-    // MatchingThread.cpp:138-150
-    void run()
-    {
-        auto t0 = std::chrono::steady_clock::now();
-        gpu_morph.calculate_halfway_parametrization();
-        run_time = std::chrono::duration<float>(std::chrono::steady_clock::now() - t0).count();
-        update_result();
-    }
-    void start() { thread_ = std::thread([this] { try { run(); } catch (...) { error_ = std::current_exception(); } }); }
-    void wait()
-    {
-        if (thread_.joinable()) thread_.join();
-        if (error_) { auto e = error_; error_ = nullptr; std::rethrow_exception(e); }
-    }
+        : _pyramids(pyramids), _parameters(parameters), gpu_morph(parameters, pyramids, runflag) {}
+    ~MatchingThread() { join(); } // before gpu_morph goes
 
     // MatchingThread.cpp:22-84: v of the current level scaled and resized to full
     // resolution into pyramid._vector[0]
-    void update_result()
+    void update_result() override
     {
         int el = std::max(gpu_morph._current_l, 1);
         int w0 = _pyramids[0].width, h0 = _pyramids[0].height;
@@ -114,17 +92,13 @@ public:
     }
 
     float percentage = 0.0f;
-    float run_time = 0.0f;
-    volatile int runflag; // the reference's `bool runflag`, written by the UI thread
 
 private:
+    void solve() override { gpu_morph.calculate_halfway_parametrization(); } // MatchingThread.cpp:138-150
     Pyramid &_pyramids;
     Parameters &_parameters;
 public:
     Morph gpu_morph;
-private:
-    std::thread thread_;
-    std::exception_ptr error_;
 };
 
 } // namespace vmorph

@@ -1,19 +1,18 @@
 // vmorph/sync.hpp -- C++ host mirror of the reference's synchronisation stage: what class Pyramid
 // holds after build(video0, video1, f0, f1, start_res) (Algorithm/pyramid.cu:57-165: the level
 // table, the layered video / forward-flow arrays, _vector) and class CSyncThread
-// (Algorithm/SyncThread.h:7-39; QThread -> std::thread): runflag, percentage, run_time, run(),
+// (Algorithm/SyncThread.h:7-39; QThread -> detail::Worker): runflag, percentage, run_time, run(),
 // load_identity / upsample_level / optimize_level, update_result().  The CG solves, the level
 // transfer and the stage-1 renderer (render_resample_image, render.cu:99-246) live behind the
 // C-ABI (vm_sync_*).
 #ifndef VMORPH_SYNC_HPP
 #define VMORPH_SYNC_HPP
 
-#include <chrono>
 #include <map>
-#include <thread>
 #include <vector>
 
 #include "pyramid.hpp"
+#include "worker.hpp"
 
 namespace vmorph {
 
@@ -94,10 +93,10 @@ private:
 };
 
 // class CSyncThread, SyncThread.h:7-39
-class SyncThread {
+class SyncThread : public detail::Worker {
 public:
     // SyncThread.cpp:6-38
-    SyncThread(Parameters &parameters, SyncPyramid &pyramids) : runflag(1), _pyramids(pyramids), _parameters(parameters)
+    SyncThread(Parameters &parameters, SyncPyramid &pyramids) : _pyramids(pyramids), _parameters(parameters)
     {
         _total_l = (int)pyramids.size() - 1;
         _current_l = _total_l;
@@ -110,11 +109,7 @@ public:
                 iter_num = (int)(iter_num / parameters.max_iter_drop_factor);
             }
     }
-    // joins the worker; a stored exception is dropped (a destructor must not throw: wait() shows it)
-    ~SyncThread()
-    {
-        if (thread_.joinable()) thread_.join();
-    }
+    ~SyncThread() { join(); } // before progress goes
 
     void load_identity(int el) { check(vm_sync_load_identity(_pyramids.handle(), el)); }
     void upsample_level(int el, int /*pel*/) { check(vm_sync_upsample_level(_pyramids.handle(), el)); }
@@ -137,10 +132,23 @@ public:
         _current_iter += (float)pr.voxel_iters;
     }
 
-    // SyncThread.cpp:58-84
-    void run()
+    // SyncThread.cpp:482-521
+    void update_result() override
     {
-        auto t0 = std::chrono::steady_clock::now();
+        const int el = std::max(_current_l, 1);
+        for (int z = 0; z < _pyramids[el].depth; ++z) check(vm_sync_result(_pyramids.handle(), el, z, _pyramids._vector[z].data()));
+        percentage = _total_iter > 0 ? _current_iter / _total_iter * 100.0f : 100.0f;
+    }
+
+    float percentage = 0.0f;
+    std::map<int, vm_sync_progress> progress;
+    int _total_l, _current_l;
+    float _total_iter, _current_iter, _max_iter;
+
+private:
+    // SyncThread.cpp:58-84
+    void solve() override
+    {
         for (_current_l = _total_l; _current_l > 0; _current_l--) {
             const int el = _current_l;
             if (el == _total_l) load_identity(el);
@@ -149,36 +157,9 @@ public:
             _max_iter /= 2;
             if (!runflag) break;
         }
-        run_time = std::chrono::duration<float>(std::chrono::steady_clock::now() - t0).count();
-        update_result();
     }
-    void start() { thread_ = std::thread([this] { try { run(); } catch (...) { error_ = std::current_exception(); } }); }
-    void wait()
-    {
-        if (thread_.joinable()) thread_.join();
-        if (error_) { auto e = error_; error_ = nullptr; std::rethrow_exception(e); }
-    }
-
-    // SyncThread.cpp:482-521
-    void update_result()
-    {
-        const int el = std::max(_current_l, 1);
-        for (int z = 0; z < _pyramids[el].depth; ++z) check(vm_sync_result(_pyramids.handle(), el, z, _pyramids._vector[z].data()));
-        percentage = _total_iter > 0 ? _current_iter / _total_iter * 100.0f : 100.0f;
-    }
-
-    volatile int runflag; // the reference's `bool runflag`, written by the UI thread
-    float percentage = 0.0f;
-    float run_time = 0.0f;
-    std::map<int, vm_sync_progress> progress;
-    int _total_l, _current_l;
-    float _total_iter, _current_iter, _max_iter;
-
-private:
     SyncPyramid &_pyramids;
     Parameters &_parameters;
-    std::thread thread_;
-    std::exception_ptr error_;
 };
 
 } // namespace vmorph

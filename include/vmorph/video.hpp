@@ -5,13 +5,11 @@
 #ifndef VMORPH_VIDEO_HPP
 #define VMORPH_VIDEO_HPP
 
-#include <chrono>
 #include <cmath>
-#include <exception>
-#include <thread>
 #include <vector>
 
 #include "pyramid.hpp"
+#include "worker.hpp"
 
 namespace vmorph {
 
@@ -148,35 +146,19 @@ private:
 };
 
 // class CMatchingThread (MatchingThread.h:7-37) over a video pair: the coupled solve on a worker
-// thread (QThread -> std::thread), then update_result(): pyramid._vector[frame] for EVERY frame of the
+// thread (QThread -> detail::Worker), then update_result(): pyramid._vector[frame] for EVERY frame of the
 // video at w0 x h0 -- pages scaled and resized, the frames the temporal pyramid skipped blended from
 // their neighbours (MatchingThread.cpp:22-84)
-class VideoMatchingThread {
+class VideoMatchingThread : public detail::Worker {
 public:
     VideoMatchingThread(Parameters &parameters, VideoPyramid &pyramids, int w0 = 0, int h0 = 0)
-        : runflag(1), _pyramids(pyramids), _parameters(parameters), gpu_morph(parameters, pyramids, runflag),
+        : _pyramids(pyramids), _parameters(parameters), gpu_morph(parameters, pyramids, runflag),
           w0_(w0 ? w0 : pyramids.levels.at(0).width), h0_(h0 ? h0 : pyramids.levels.at(0).height) {}
-    ~VideoMatchingThread()
-    {
-        if (thread_.joinable()) thread_.join(); // a stored exception is dropped: wait() shows it
-    }
-
-    void run() // MatchingThread.cpp:138-150
-    {
-        auto t0 = std::chrono::steady_clock::now();
-        gpu_morph.calculate_halfway_parametrization();
-        run_time = std::chrono::duration<float>(std::chrono::steady_clock::now() - t0).count();
-        update_result();
-    }
-    void start() { thread_ = std::thread([this] { try { run(); } catch (...) { error_ = std::current_exception(); } }); }
-    void wait()
-    {
-        if (thread_.joinable()) thread_.join();
-        if (error_) { auto e = error_; error_ = nullptr; std::rethrow_exception(e); }
-    }
+    ~VideoMatchingThread() { join(); } // before gpu_morph goes
 
     // MatchingThread.cpp:22-84 from level `lvl` (after run(): the finest)
-    void update_result(int lvl = 0)
+    void update_result() override { update_result(0); }
+    void update_result(int lvl)
     {
         const size_t n = (size_t)w0_ * h0_ * 2;
         std::vector<float> all(n * _pyramids.depth0());
@@ -188,18 +170,15 @@ public:
     }
 
     float percentage = 0.0f;
-    float run_time = 0.0f;
-    volatile int runflag; // the reference's `bool runflag`, written by the UI thread
 
 private:
+    void solve() override { gpu_morph.calculate_halfway_parametrization(); } // MatchingThread.cpp:138-150
     VideoPyramid &_pyramids;
     Parameters &_parameters;
 public:
     VideoMorph gpu_morph;
 private:
     int w0_, h0_;
-    std::thread thread_;
-    std::exception_ptr error_;
 };
 
 } // namespace vmorph

@@ -553,17 +553,32 @@ extern "C" int vm_coarse_solve(vm_pyr *p, int lvl, int w0, int h0, const vm_cons
     return vm_level_set_v(p, lvl, v.data(), 0);
 }
 
+// The level kernels of one arithmetic mode, picked the way sweep_launchers() picks the sweep's.  The TEX8 modes have
+// their own init_level / upsample (the reference upsamples through a linear-filtered texture too) and EXACT's splat;
+// EXACT_FMA and REF_FASTMATH have no level kernels of their own and take EXACT's.
+struct LevelLaunchers {
+    decltype(&vm_launch_init_level_exact) init_level;
+    decltype(&vm_launch_upsample_exact) upsample;
+    decltype(&vm_launch_splat_exact) splat;
+};
+static const LevelLaunchers &level_launchers(int math_mode)
+{
+    static const LevelLaunchers exact = {vm_launch_init_level_exact, vm_launch_upsample_exact, vm_launch_splat_exact};
+    static const LevelLaunchers fast = {vm_launch_init_level_fast, vm_launch_upsample_fast, vm_launch_splat_fast};
+    static const LevelLaunchers tex8 = {vm_launch_init_level_tex8, vm_launch_upsample_tex8, vm_launch_splat_exact};
+    static const LevelLaunchers tex8t = {vm_launch_init_level_tex8t, vm_launch_upsample_tex8t, vm_launch_splat_exact};
+    switch (math_mode) {
+    case VM_MATH_FAST: return fast;
+    case VM_MATH_REF_TEX8: return tex8;
+    case VM_MATH_REF_TEX8_TRUNC: return tex8t;
+    default: return exact;
+    }
+}
+
 // upsample(PyramidLevel&dest, PyramidLevel&orig) for one page, upsample.cu:260-286
 int vm_level_upsample(vm_ctx *c, vm_level &d, const vm_level &s)
 {
-    if (c->math_mode == VM_MATH_REF_TEX8)          // the reference upsamples through a linear-filtered texture too
-        vm_launch_upsample_tex8(d.view.v, d.w, d.h, d.rs, s.view.v, s.w, s.h, s.rs, c->stream);
-    else if (c->math_mode == VM_MATH_REF_TEX8_TRUNC)
-        vm_launch_upsample_tex8t(d.view.v, d.w, d.h, d.rs, s.view.v, s.w, s.h, s.rs, c->stream);
-    else if (c->math_mode != VM_MATH_FAST)
-        vm_launch_upsample_exact(d.view.v, d.w, d.h, d.rs, s.view.v, s.w, s.h, s.rs, c->stream);
-    else
-        vm_launch_upsample_fast(d.view.v, d.w, d.h, d.rs, s.view.v, s.w, s.h, s.rs, c->stream);
+    level_launchers(c->math_mode).upsample(d.view.v, d.w, d.h, d.rs, s.view.v, s.w, s.h, s.rs, c->stream);
     VM_HIP(hipGetLastError());
     return VM_OK;
 }
@@ -590,19 +605,9 @@ int vm_level_init(vm_ctx *c, vm_level &l, int w0, int h0, const vm_constraint *c
     if (n < 0 || (n > 0 && !cons)) return vm_fail(VM_E_INVALID, "vm_init_level: constraints");
     int rc = upload_constraints(c, cons, n);
     if (rc != VM_OK) return rc;
-    if (c->math_mode == VM_MATH_REF_TEX8) {
-        vm_launch_init_level_tex8(l.view, c->kp.ssim_clamp, c->tables.get(), c->stream);
-        if (n > 0) vm_launch_splat_exact(l.view, w0, h0, c->cons_dev.get(), n, c->stream);
-    } else if (c->math_mode == VM_MATH_REF_TEX8_TRUNC) {
-        vm_launch_init_level_tex8t(l.view, c->kp.ssim_clamp, c->tables.get(), c->stream);
-        if (n > 0) vm_launch_splat_exact(l.view, w0, h0, c->cons_dev.get(), n, c->stream);
-    } else if (c->math_mode != VM_MATH_FAST) {
-        vm_launch_init_level_exact(l.view, c->kp.ssim_clamp, c->tables.get(), c->stream);
-        if (n > 0) vm_launch_splat_exact(l.view, w0, h0, c->cons_dev.get(), n, c->stream);
-    } else {
-        vm_launch_init_level_fast(l.view, c->kp.ssim_clamp, c->tables.get(), c->stream);
-        if (n > 0) vm_launch_splat_fast(l.view, w0, h0, c->cons_dev.get(), n, c->stream);
-    }
+    const LevelLaunchers &LL = level_launchers(c->math_mode);
+    LL.init_level(l.view, c->kp.ssim_clamp, c->tables.get(), c->stream);
+    if (n > 0) LL.splat(l.view, w0, h0, c->cons_dev.get(), n, c->stream);
     VM_HIP(hipGetLastError());
     l.has_state = true;
     return VM_OK;

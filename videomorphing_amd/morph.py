@@ -407,15 +407,14 @@ def solve_batch(pyramids, max_iter, max_iter_drop_factor=1.0, fixed_work=False, 
     return out
 
 
-class MatchingThread(object):
-    """class CMatchingThread, MatchingThread.h:7-37, on threading.Thread."""
+class _SolverThread(object):
+    """What the reference's QThread subclasses (CMatchingThread, CSyncThread) share: the cancel flag the solver polls,
+    percentage / run_time, a worker thread, and wait() re-raising what the worker met."""
 
-    def __init__(self, parameters, pyramids, fixed_work=False):
-        self._parameters, self._pyramids = parameters, pyramids
+    def __init__(self):
         self._flag = C.c_int(1)
         self.percentage = 0.0
         self.run_time = 0.0
-        self.gpu_morph = Morph(parameters, pyramids, self._flag, fixed_work)
         self._thread = None
         self.error = None
 
@@ -427,11 +426,15 @@ class MatchingThread(object):
     def runflag(self, v):
         self._flag.value = 1 if v else 0
 
+    def _flag_ptr(self):
+        """the flag as the C-ABI's `volatile const int *run_flag`"""
+        return C.cast(C.pointer(self._flag), C.c_void_p)
+
     def run(self):
-        """MatchingThread.cpp:138-150"""
+        """CMatchingThread::run / CSyncThread::run: _solve(), then update_result(); run_time is the solve's"""
         t0 = time.time()
         try:   # the whole body: an error of the delivery must reach wait() like one of the solve
-            self.gpu_morph.calculate_halfway_parametrization()
+            self._solve()
             self.run_time = time.time() - t0
             self.update_result()
         except Exception as e:  # surfaced to the caller of wait()
@@ -447,6 +450,19 @@ class MatchingThread(object):
             self._thread.join()
         if self.error is not None:
             raise self.error
+
+
+class MatchingThread(_SolverThread):
+    """class CMatchingThread, MatchingThread.h:7-37, on threading.Thread."""
+
+    def __init__(self, parameters, pyramids, fixed_work=False):
+        _SolverThread.__init__(self)
+        self._parameters, self._pyramids = parameters, pyramids
+        self.gpu_morph = Morph(parameters, pyramids, self._flag, fixed_work)
+
+    def _solve(self):
+        """MatchingThread.cpp:138-150"""
+        self.gpu_morph.calculate_halfway_parametrization()
 
     def update_result(self):
         """MatchingThread.cpp:22-84: fetch v of the current level, scale to full
@@ -806,50 +822,21 @@ class VideoMorph(object):
         return True
 
 
-class VideoMatchingThread(object):
+class VideoMatchingThread(_SolverThread):
     """class CMatchingThread (MatchingThread.h:7-37) over a video pair: the temporally coupled solve on
     a worker thread, then update_result() -- pyramid._vector[frame] for every frame of the video,
     at w0 x h0 (the size of the reference's placeholder level pyramid[0]; default: the finest level's)."""
 
     def __init__(self, parameters, pyramids, w0=None, h0=None, fixed_work=False):
+        _SolverThread.__init__(self)
         self._parameters, self._pyramids = parameters, pyramids
-        self._flag = C.c_int(1)
         self.w0 = int(w0 if w0 is not None else pyramids.levels[0][0])
         self.h0 = int(h0 if h0 is not None else pyramids.levels[0][1])
-        self.percentage = 0.0
-        self.run_time = 0.0
         self.gpu_morph = VideoMorph(parameters, pyramids, self._flag, fixed_work)
-        self._thread = None
-        self.error = None
 
-    @property
-    def runflag(self):
-        return bool(self._flag.value)
-
-    @runflag.setter
-    def runflag(self, v):
-        self._flag.value = 1 if v else 0
-
-    def run(self):
+    def _solve(self):
         """MatchingThread.cpp:138-150"""
-        t0 = time.time()
-        try:   # the whole body: an error of the delivery (vm_video_result) must reach wait() like one of the solve
-            self.gpu_morph.calculate_halfway_parametrization()
-            self.run_time = time.time() - t0
-            self.update_result()
-        except Exception as e:  # surfaced to the caller of wait()
-            self.error = e
-            self.run_time = time.time() - t0
-
-    def start(self):
-        self._thread = threading.Thread(target=self.run)
-        self._thread.start()
-
-    def wait(self):
-        if self._thread is not None:
-            self._thread.join()
-        if self.error is not None:
-            raise self.error
+        self.gpu_morph.calculate_halfway_parametrization()
 
     def update_result(self, lvl=0):
         """MatchingThread.cpp:22-84 (the level the solver has reached; after run(): the finest)"""
@@ -967,15 +954,13 @@ class SyncPyramid(object):
         return ms.value
 
 
-class SyncThread(object):
+class SyncThread(_SolverThread):
     """class CSyncThread (SyncThread.h:7-39) on threading.Thread: runflag, percentage, run_time,
     run(), update_result()."""
 
     def __init__(self, parameters, pyramids):
+        _SolverThread.__init__(self)
         self._parameters, self._pyramids = parameters, pyramids
-        self._flag = C.c_int(1)
-        self.percentage = 0.0
-        self.run_time = 0.0
         self._total_l = pyramids.size() - 1
         self._current_l = self._total_l
         self._max_iter = float(parameters.max_iter * 10)
@@ -987,16 +972,6 @@ class SyncThread(object):
             self._total_iter += float(it) * w * h * d
             it = int(it / parameters.max_iter_drop_factor)
         self.progress = {}
-        self._thread = None
-        self.error = None
-
-    @property
-    def runflag(self):
-        return bool(self._flag.value)
-
-    @runflag.setter
-    def runflag(self, v):
-        self._flag.value = 1 if v else 0
 
     def load_identity(self, el):
         capi.check(self._pyramids._L.vm_sync_load_identity(self._pyramids._h, el))
@@ -1013,44 +988,26 @@ class SyncThread(object):
             arr[i] = capi.SyncConstraint(*c)
         capi.check(pyr._L.vm_sync_set_constraints(pyr._h, arr, len(cons)))
         pr = capi.SyncProgress()
-        flag = C.cast(C.pointer(self._flag), C.c_void_p)
-        capi.check(pyr._L.vm_sync_optimize_level(pyr._h, el, self._max_iter, flag, C.byref(pr)))
+        capi.check(pyr._L.vm_sync_optimize_level(pyr._h, el, self._max_iter, self._flag_ptr(), C.byref(pr)))
         self.progress[el] = dict(iters=pr.iters, launches=pr.launches, voxel_iters=pr.voxel_iters,
                                  elapsed_ms=pr.elapsed_ms, resid=tuple(pr.resid))
         self._current_iter += pr.voxel_iters
         return pr
 
-    def run(self):
+    def _solve(self):
         """SyncThread.cpp:58-84"""
-        t0 = time.time()
-        try:
-            self._current_l = self._total_l
-            while self._current_l > 0:
-                el = self._current_l
-                if el == self._total_l:
-                    self.load_identity(el)
-                else:
-                    self.upsample_level(el, el + 1)
-                self.optimize_level(el)
-                self._max_iter = float(np.float32(self._max_iter) / np.float32(2))
-                if not self.runflag:
-                    break
-                self._current_l -= 1
-        except Exception as e:
-            self.error = e
-        self.run_time = time.time() - t0
-        if self.error is None:
-            self.update_result()
-
-    def start(self):
-        self._thread = threading.Thread(target=self.run)
-        self._thread.start()
-
-    def wait(self):
-        if self._thread is not None:
-            self._thread.join()
-        if self.error is not None:
-            raise self.error
+        self._current_l = self._total_l
+        while self._current_l > 0:
+            el = self._current_l
+            if el == self._total_l:
+                self.load_identity(el)
+            else:
+                self.upsample_level(el, el + 1)
+            self.optimize_level(el)
+            self._max_iter = float(np.float32(self._max_iter) / np.float32(2))
+            if not self.runflag:
+                break
+            self._current_l -= 1
 
     def update_result(self):
         """SyncThread.cpp:482-521: _vector[z] = (X ratio_x, Y ratio_y, Z, 0) resized to full size"""
