@@ -46,12 +46,13 @@ template <class T> static bool read_all(const char *path, std::vector<T> &v)
 int main(int argc, char **argv)
 {
     if (argc < 11) {
-        fprintf(stderr, "usage: %s G W H N EX frames.f32 rgb.u8 cons.f32 out_v.f32 out_rgb.u8 [max_iter] [start_res] [exact|fast] [--one-device]\n", argv[0]);
+        fprintf(stderr, "usage: %s G W H N EX frames.f32 rgb.u8 cons.f32 out_v.f32 out_rgb.u8 [max_iter] [start_res] [exact|fast] [--one-device] [--ordered]\n", argv[0]);
         return 2;
     }
     const int G = atoi(argv[1]), w = atoi(argv[2]), h = atoi(argv[3]), N = atoi(argv[4]), ex = atoi(argv[5]);
-    bool one_device = false;
+    bool one_device = false, ordered = false;
     for (int a = 11; a < argc; ++a) one_device = one_device || !strcmp(argv[a], "--one-device");
+    for (int a = 11; a < argc; ++a) ordered = ordered || !strcmp(argv[a], "--ordered");     // the same bytes whatever G is
     const size_t npx = (size_t)w * h;
     std::vector<float> frames, cons_in;
     std::vector<unsigned char> rgb;
@@ -87,6 +88,7 @@ int main(int argc, char **argv)
         for (int r = 0; r < G; ++r) {
             devices.push_back(one_device ? 0 : r);
             ctxs.emplace_back(new vmorph::Context(devices.back(), VM_MATH_EXACT));
+            if (ordered) ctxs.back()->set_reduction(VM_REDUCE_ORDERED);
             handles.push_back(ctxs.back()->handle());
         }
         std::vector<void *> comms(G, nullptr);

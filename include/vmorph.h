@@ -173,6 +173,23 @@ int  vm_set_tuning(vm_ctx *ctx, int sweep_mode, int threads, int parts);
  * (the per-frame chaos floor FAST is judged against, tests/test_gpu_fullsize.py).  Other
  * values: VM_E_INVALID. */
 int  vm_set_commit_order(vm_ctx *ctx, int order);
+/* How the compositor's linear solver -- the batched multigrid PCG behind vm_poisson_extend, vm_poisson_extend_frames and
+ * vm_frame_quadratic_path -- and the quadratic path's mean shift add up their dot products.  The reference extends by a
+ * direct sparse solve (MKL DSS, PoissonExt.cpp:321-329): one answer per input.
+ *   VM_REDUCE_ATOMIC  (default) one double atomic per workgroup and channel: the sum order is arrival order, so two
+ *                     runs -- or one frame alone and in a batch -- may stop an iteration apart and differ by a level
+ *                     on some bytes;
+ *   VM_REDUCE_ORDERED every sum is a fold in ONE fixed order that depends on the system alone (its own block and tile
+ *                     lists): the same bytes, iteration counts and residual bits from run to run, process to
+ *                     process, alone or in any batch, on any context.  (The development switch VM_MGB_FUSE_MIN_SYS
+ *                     moves the PCG update between two kernels that partition level 0 differently -- by tiles, by
+ *                     blocks: the ordered bits of the two settings may differ.)
+ * Contexts the library creates on behalf of this one (the lanes of vm_video_solve) inherit the mode.  The environment
+ * variable VM_REDUCTION=ordered|atomic sets the mode a context starts with (any other value: vm_ctx_create fails
+ * with VM_E_INVALID).  A NULL context or another mode: VM_E_INVALID. */
+#define VM_REDUCE_ATOMIC 0
+#define VM_REDUCE_ORDERED 1
+int  vm_set_reduction(vm_ctx *ctx, int mode);
 /* Test hooks of the PASS schedule's safety net.  k_pass spins at tile-local barriers with a bounded
  * wait; under VM_SWEEP_AUTO a timeout (compute units masked away or held by someone else) restores the
  * level to where the batch of iterations started, reruns the batch with the STEP schedule and keeps the

@@ -25,6 +25,8 @@ public:
     Context &operator=(const Context &) = delete;
     vm_ctx *handle() const { return h_; }
     void set_math_mode(int m) { check(vm_set_math_mode(h_, m)); }
+    // VM_REDUCE_ATOMIC (default) / VM_REDUCE_ORDERED: reproducible bytes out of the compositor's linear solver (vm_set_reduction)
+    void set_reduction(int mode) { check(vm_set_reduction(h_, mode)); }
     void sync() { check(vm_ctx_sync(h_)); }
 private:
     vm_ctx *h_ = nullptr;

@@ -15,6 +15,7 @@ VM_OK = 0
 VM_E_INVALID, VM_E_DEVICE, VM_E_STATE, VM_E_NUMERIC, VM_E_CANCELLED = -1, -2, -3, -4, -5
 BCOND_NONE, BCOND_CORNER, BCOND_BORDER = 0, 1, 2
 MATH_EXACT, MATH_FAST, MATH_EXACT_FMA, MATH_REF_FASTMATH, MATH_REF_TEX8, MATH_REF_TEX8_TRUNC = 0, 1, 2, 3, 4, 5
+REDUCE_ATOMIC, REDUCE_ORDERED = 0, 1          # vm_set_reduction
 SWEEP_AUTO, SWEEP_TILE, SWEEP_SPLIT, SWEEP_STEP, SWEEP_SPARSE, SWEEP_PASS = 0, 1, 2, 3, 4, 5
 
 FIELDS = {  # name -> (id, channels)
@@ -27,7 +28,7 @@ FIELDS = {  # name -> (id, channels)
 # every symbol include/vmorph.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
     "vm_last_error", "vm_version", "vm_ctx_create", "vm_ctx_destroy", "vm_ctx_sync",
-    "vm_set_params", "vm_get_params", "vm_set_math_mode", "vm_set_tuning", "vm_set_commit_order", "vm_dbg_pass_placement", "vm_dbg_pass_force_timeout",
+    "vm_set_params", "vm_get_params", "vm_set_math_mode", "vm_set_tuning", "vm_set_commit_order", "vm_set_reduction", "vm_dbg_pass_placement", "vm_dbg_pass_force_timeout",
     "vm_dbg_pass_fallbacks", "vm_dbg_level_set_mask", "vm_dbg_sparse_resident", "vm_dbg_sparse_resident_visits", "vm_dbg_streams_overlap", "vm_dbg_pyramid_scale", "vm_device_info",
     "vm_pyramid_create", "vm_pyramid_destroy", "vm_pyramid_levels", "vm_level_dims",
     "vm_level_upload_luma", "vm_pyramid_build_rgb", "vm_level_set_v", "vm_level_get_v", "vm_level_get_field",
@@ -134,6 +135,7 @@ def load():
         "vm_set_math_mode": [vp, i],
         "vm_set_tuning": [vp, i, i, i],
         "vm_set_commit_order": [vp, i],
+        "vm_set_reduction": [vp, i],
         "vm_dbg_pass_placement": [vp, vp, i],
         "vm_dbg_pass_force_timeout": [vp, i],
         "vm_dbg_pass_fallbacks": [vp],

@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -109,6 +110,12 @@ extern "C" int vm_ctx_create(int device, vm_ctx **out)
 {
     if (!out) return vm_fail(VM_E_INVALID, "vm_ctx_create: out is NULL");
     *out = nullptr;
+    // VM_REDUCTION=ordered|atomic: the reduction mode the context starts with (vm_set_reduction), for drivers that do not call it
+    int reduction = VM_REDUCE_ATOMIC;
+    if (const char *e = getenv("VM_REDUCTION")) {
+        if (!strcmp(e, "ordered")) reduction = VM_REDUCE_ORDERED;
+        else if (strcmp(e, "atomic")) return vm_fail(VM_E_INVALID, "vm_ctx_create: VM_REDUCTION=%s (ordered or atomic)", e);
+    }
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev <= 0)
@@ -118,6 +125,7 @@ extern "C" int vm_ctx_create(int device, vm_ctx **out)
         return vm_fail(VM_E_INVALID, "vm_ctx_create: device %d out of range (0..%d)", device, ndev - 1);
     vm_ctx *c = new vm_ctx();
     c->device = device;
+    c->reduction = reduction;
     VM_ON_DEVICE(c);
     c->math_mode = VM_MATH_EXACT;
     c->kp = {10.0f, 1e5f, 0.05f, 100.0f, 0.0f, 0.01f, VM_BCOND_NONE}; // UI/MdiEditor.cpp:131-140
@@ -207,6 +215,15 @@ extern "C" int vm_set_commit_order(vm_ctx *c, int order)
     if (!c) return vm_fail(VM_E_INVALID, "vm_set_commit_order: ctx is NULL");
     if (order < 0 || order > 3) return vm_fail(VM_E_INVALID, "vm_set_commit_order: order %d (0 row-major, 1 reversed, 2 column-major, 3 column-major reversed)", order);
     c->commit_order = order;
+    return VM_OK;
+}
+
+extern "C" int vm_set_reduction(vm_ctx *c, int mode)
+{
+    if (!c) return vm_fail(VM_E_INVALID, "vm_set_reduction: ctx is NULL");
+    if (mode != VM_REDUCE_ATOMIC && mode != VM_REDUCE_ORDERED)
+        return vm_fail(VM_E_INVALID, "vm_set_reduction: mode %d (0 atomic, 1 ordered)", mode);
+    c->reduction = mode;
     return VM_OK;
 }
 

@@ -130,6 +130,10 @@ struct vm_ctx {
     // vm_dbg_poisson_profile: HIP-event time of the launch that carries the PCG update (k_mgb_update, or the level-0
     // restriction with the update fused in), summed over the launches of the solves since the probe was switched on,
     // and what those launches processed
+    // vm_set_reduction: VM_REDUCE_ATOMIC (0) or VM_REDUCE_ORDERED (1), how the batched PCG and the quadratic path's mean
+    // shift reduce (vm_mgb.h); mgb_ord: the ordered mode's partials, tickets and group sums of the current batch
+    int reduction = 0;
+    VmDev<char> mgb_ord;
     bool mgb_prof = false;
     double mgb_prof_us = 0, mgb_prof_unknown_launches = 0;
     int mgb_prof_launches = 0, mgb_prof_fused = 0;

@@ -70,6 +70,34 @@ struct VmMgbScalars {
     double pq[2][VM_MGB_SLOTS][16];
 };
 
+// ---------------------------------------------------------------------------
+// ORDERED reduction (vm_set_reduction(ctx, VM_REDUCE_ORDERED); the default, VM_REDUCE_ATOMIC, is the slots above).
+// Every dot product of the PCG becomes a fold in ONE fixed order that is a function of the system alone:
+//   * a producing workgroup is entry i of the system's OWN list of the launch -- i < n, n = ceil(nblocks / MGB_G) in the
+//     streaming kernels (init, dirspmv, update, dot_rz), n = ntiles of level 0 in the tile kernels (the fused update in
+//     the restriction, the prolongation) -- and leaves the three channel sums of its cells (the same shuffle tree and
+//     wave order as the default) in part[acc][i].  Workgroups the launch holds beyond n (the grid is the batch's
+//     maximum) publish nothing and take no ticket;
+//   * workgroups i with the same i / VM_MGB_ORD_GROUP share an arrival ticket; the one that arrives LAST adds the
+//     group's partials in ascending i from zero into gpart[acc][i / VM_MGB_ORD_GROUP] and resets the ticket.  Nobody
+//     waits for anybody;
+//   * the consumers -- the NEXT launch, where the default sums its slots, and the host's stop test -- fold the
+//     ng = ceil(n / VM_MGB_ORD_GROUP) group partials: on the device lane j of 32 adds entries j, j + 32, ... in ascending
+//     order from zero and the 32 lanes are joined by a butterfly (xor 16, 8, 4, 2, 1); the host adds entries 0 .. ng - 1
+//     in ascending order (bb and rr, which only the host reads).
+// gridDim, the batch-mates, the system's index, the stream and the context do not enter.  The fused and the separate
+// update partition level 0 by tiles and by blocks: their ordered bits may differ (VM_MGB_FUSE_MIN_SYS is a dev switch).
+#define VM_MGB_ORD_GROUP 32
+#define VM_MGB_ORD_TSTRIDE 32   // words between tickets: one 128-byte line each
+enum { VM_MGB_ACC_BB = 0, VM_MGB_ACC_RR = 1, VM_MGB_ACC_RZ = 3, VM_MGB_ACC_PQ = 5, VM_MGB_NACC = 7 };   // + the iteration's parity
+struct VmMgbOrd {               // one system's storage (device), constant during a solve
+    int cap, gcap;              // producing workgroups / groups there is room for
+    double *part;               // [VM_MGB_NACC][cap][4]: a workgroup's channel sums (written through, read by its group's last arriver)
+    double *gpart;              // [VM_MGB_NACC][gcap][4]: the groups' sums
+    unsigned *ticket;           // [VM_MGB_NACC][gcap] x VM_MGB_ORD_TSTRIDE words, zero between launches
+    int *ng;                    // [VM_MGB_NACC]: groups of the launch that last produced the accumulator
+};
+
 struct VmMgbSys {
     int nlev;
     VmMgbLevel lv[VM_MGB_MAXLEV];
@@ -78,7 +106,10 @@ struct VmMgbSys {
     // the level-0 restriction (vm_mgb.hip: k_mgb_restrict<true, true>), else R[0] again (k_mgb_update works in place)
     VmV3 *R[2];
     const uint8_t *type;     // level 0's type map (PoissonExt.cpp:59-101)
-    VmMgbScalars *sc;
+    union {
+        VmMgbScalars *sc;    // VM_REDUCE_ATOMIC
+        const VmMgbOrd *ord; // VM_REDUCE_ORDERED (the kernels' ORD = true instantiations)
+    };
 };
 
 #define VM_MGB_COARSEST 64      // the hierarchy ends at a grid of at most this many cells ...
@@ -110,18 +141,20 @@ struct VmMgbSys {
 void vm_mgb_launch_level0(const VmMgbSys *sys, int nsys, int gx, int gy, hipStream_t s);
 void vm_mgb_launch_coarsen(const VmMgbSys *sys, int nsys, int l, int gx, int gy, hipStream_t s);   // level l from l - 1
 void vm_mgb_launch_compact(const VmMgbSys *sys, int nsys, int nlev_max, hipStream_t s);
+// The launchers below that end in a dot product or read one take `ord`: false = the slot atomics, true = the ordered fold
+// (kernels of their own: the default's are the code they were)
 // r = b - A x (in place, level 0's b), bb, rr[1]
-void vm_mgb_launch_init(const VmMgbSys *sys, int nsys, int nb0, uint64_t active, hipStream_t s);
+void vm_mgb_launch_init(const VmMgbSys *sys, int nsys, int nb0, uint64_t active, bool ord, hipStream_t s);
 // V-cycle pieces
 // (nu: the level's sweeps each way, VmMgbLevel::nu of every system of the batch)
 // lv[l+1].b from lv[l], over lv[l]'s tiles; k: the PCG iteration (level 0 reads R[k & 1]); upd (l == 0, nu == 1, k >= 1): the
 // update of iteration k - 1 first (x += alpha p, R[k & 1] = R[(k - 1) & 1] - alpha q, rr[(k - 1) & 1]) -- instead of vm_mgb_launch_update
-void vm_mgb_launch_restrict(const VmMgbSys *sys, int nsys, int l, int nu, int nt_fine, int k, bool upd, uint64_t active, hipStream_t s);
-void vm_mgb_launch_prolong(const VmMgbSys *sys, int nsys, int l, int nu, int nt_fine, int k, uint64_t active, hipStream_t s);   // lv[l].x; l == 0: rz[k & 1] += r.z
+void vm_mgb_launch_restrict(const VmMgbSys *sys, int nsys, int l, int nu, int nt_fine, int k, bool upd, uint64_t active, bool ord, hipStream_t s);
+void vm_mgb_launch_prolong(const VmMgbSys *sys, int nsys, int l, int nu, int nt_fine, int k, uint64_t active, bool ord, hipStream_t s);   // lv[l].x; l == 0: rz[k & 1] += r.z
 void vm_mgb_launch_tail(const VmMgbSys *sys, int nsys, int l, uint64_t active, hipStream_t s);             // levels l .. nlev - 1 in one workgroup
-void vm_mgb_launch_dot_rz(const VmMgbSys *sys, int nsys, int nb0, int k, uint64_t active, hipStream_t s);                           // hierarchies that are all tail only
+void vm_mgb_launch_dot_rz(const VmMgbSys *sys, int nsys, int nb0, int k, uint64_t active, bool ord, hipStream_t s);                           // hierarchies that are all tail only
 // PCG on level 0
-void vm_mgb_launch_dirspmv(const VmMgbSys *sys, int nsys, int nb0, int k, uint64_t active, hipStream_t s);   // p = z + beta p, q = A p, pq[k & 1]
-void vm_mgb_launch_update(const VmMgbSys *sys, int nsys, int nb0, int k, uint64_t active, hipStream_t s);    // x += alpha p, r -= alpha q, rr[k & 1]
+void vm_mgb_launch_dirspmv(const VmMgbSys *sys, int nsys, int nb0, int k, uint64_t active, bool ord, hipStream_t s);   // p = z + beta p, q = A p, pq[k & 1]
+void vm_mgb_launch_update(const VmMgbSys *sys, int nsys, int nb0, int k, uint64_t active, bool ord, hipStream_t s);    // x += alpha p, r -= alpha q, rr[k & 1]
 
 #endif

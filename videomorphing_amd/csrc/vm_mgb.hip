@@ -215,6 +215,108 @@ __device__ __forceinline__ void slot_clear(double (*a)[16])
 }
 
 // ---------------------------------------------------------------------------
+// The ORDERED reduction (vm_mgb.h: VmMgbOrd).  Workgroup `idx` of the system's own n producers of accumulator `acc`.
+
+// The channel sums of the workgroup (block_sum3's tree) go to part[acc][idx], written through; its ticket-taking lane
+// drains them and arrives at the group's ticket; the workgroup whose arrival completes the group folds the group's
+// partials in index order.  Nobody polls: a workgroup that is not last just leaves.  idx >= n: nothing at all.
+__device__ __forceinline__ void ord_sum3(double a, double b, double c, const VmMgbOrd *ord, int acc, int idx, int n)
+{
+    __shared__ double sh[3][4];
+    __shared__ int s_last;
+    for (int o = 32; o > 0; o >>= 1) {
+        a += __shfl_down(a, o);
+        b += __shfl_down(b, o);
+        c += __shfl_down(c, o);
+    }
+    const int tid = threadIdx.y * blockDim.x + threadIdx.x;
+    const int wave = tid >> 6, lane = tid & 63;
+    if (lane == 0) { sh[0][wave] = a; sh[1][wave] = b; sh[2][wave] = c; }
+    __syncthreads();
+    const int cap = ord->cap, gcap = ord->gcap;
+    if (idx < n && n <= cap) {                               // (workgroup-uniform)
+        const int grp = idx / VM_MGB_ORD_GROUP, ng = (n + VM_MGB_ORD_GROUP - 1) / VM_MGB_ORD_GROUP;
+        const int gsize = min(VM_MGB_ORD_GROUP, n - grp * VM_MGB_ORD_GROUP);
+        VM_G double *part = G(ord->part) + ((size_t)acc * cap + (size_t)grp * VM_MGB_ORD_GROUP) * 4;
+        if (tid == 0) {
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {
+                const double s = sh[ch][0] + sh[ch][1] + sh[ch][2] + sh[ch][3];
+                __hip_atomic_store((VM_G unsigned long long *)(part + (size_t)(idx - grp * VM_MGB_ORD_GROUP) * 4 + ch),
+                                   (unsigned long long)__double_as_longlong(s), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            VM_G unsigned *tk = G(ord->ticket) + ((size_t)acc * gcap + grp) * VM_MGB_ORD_TSTRIDE;
+            int last = 0;
+            if (__hip_atomic_fetch_add(tk, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)gsize - 1u) {
+                __hip_atomic_store(tk, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                last = 1;
+            }
+            s_last = last;
+        }
+        __syncthreads();
+        if (s_last && tid < 3) {
+            double s = 0;
+            for (int i = 0; i < gsize; ++i) {
+                const unsigned long long u =
+                    __hip_atomic_load((const VM_G unsigned long long *)(part + (size_t)i * 4 + tid), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                s += __longlong_as_double((long long)u);
+            }
+            G(ord->gpart)[((size_t)acc * gcap + grp) * 4 + tid] = s;     // read by the NEXT launch (and the host): a plain store
+            if (grp == 0 && tid == 0)
+                G(ord->ng)[acc] = ng;
+        }
+    }
+    __syncthreads();
+}
+
+// the three channel sums of two accumulators for the whole workgroup (slot_sums2's job): 6 x 32 lanes, lane j of a sum
+// takes group partials j, j + 32, ... in sequence, a butterfly joins the 32 -- the same bits in every workgroup
+__device__ __forceinline__ void ord_sums2(const VmMgbOrd *ord, int acca, int accb, double *sa, double *sb)
+{
+    __shared__ double sh[6];
+    const int tid = threadIdx.y * blockDim.x + threadIdx.x;
+    if (tid < 192) {
+        const int q = tid >> 5, j = tid & 31, acc = q < 3 ? acca : accb, gcap = ord->gcap;
+        const int ng = min(G(ord->ng)[acc], gcap);
+        const VM_G double *gp = G(ord->gpart) + (size_t)acc * gcap * 4 + q % 3;
+        double s = 0;
+        for (int i = j; i < ng; i += 32)
+            s += gp[(size_t)i * 4];
+#pragma unroll
+        for (int o = 16; o > 0; o >>= 1)
+            s = s + __shfl_xor(s, o);
+        if (j == 0)
+            sh[q] = s;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        sa[c] = sh[c];
+        sb[c] = sh[3 + c];
+    }
+}
+
+// the two reductions by mode: the default's call is the call it was
+template <bool ORD>
+__device__ __forceinline__ void sum3(double a, double b, double c, double (*dst)[16], const VmMgbSys &S, int acc, int n)
+{
+    if constexpr (ORD)
+        ord_sum3(a, b, c, S.ord, acc, (int)blockIdx.x, n);
+    else
+        block_sum3(a, b, c, dst);
+}
+template <bool ORD>
+__device__ __forceinline__ void sums2(const double (*a)[16], const double (*b)[16], const VmMgbSys &S, int acca, int accb, double *sa, double *sb)
+{
+    if constexpr (ORD)
+        ord_sums2(S.ord, acca, accb, sa, sb);
+    else
+        slot_sums2(a, b, sa, sb);
+}
+__device__ __forceinline__ int list_groups(int nb) { return (nb + MGB_G - 1) / MGB_G; }
+
+// ---------------------------------------------------------------------------
 // set-up
 
 // level 0 from the type map (PoissonExt.cpp:214-312: unknown <=> type > 0, ring pixels tied to their colour)
@@ -340,6 +442,7 @@ __global__ __launch_bounds__(1024) void k_mgb_compact(const VmMgbSys *__restrict
 // PCG, level 0
 
 // r = b - A x in place of b;  bb = b.b, rr[1] = r.r (the iteration "before the first")
+template <bool ORD>
 __global__ __launch_bounds__(256) void k_mgb_init(const VmMgbSys *__restrict__ sys, uint64_t active)
 {
     if (!sys_active(active))
@@ -366,14 +469,14 @@ __global__ __launch_bounds__(256) void k_mgb_init(const VmMgbSys *__restrict__ s
             st3(L.b, ii, r);
         }
     }
-    block_sum3(bb[0], bb[1], bb[2], S.sc->bb);
-    block_sum3(rr[0], rr[1], rr[2], S.sc->rr[1]);
+    sum3<ORD>(bb[0], bb[1], bb[2], S.sc->bb, S, VM_MGB_ACC_BB, list_groups(nb));
+    sum3<ORD>(rr[0], rr[1], rr[2], S.sc->rr[1], S, VM_MGB_ACC_RR + 1, list_groups(nb));
 }
 
 // beta = rz_k / rz_{k-1} (0 in the first iteration);  p = z + beta p_old at the cell and its neighbours, q = A p;
 // pq[k & 1] += p.q.  Clears rr[k & 1], which k_mgb_update accumulates next.  p and q are written for every cell of
 // an active block (zeros off the ring), so that nothing downstream of the loads hangs on the info byte.
-template <bool FIRST>
+template <bool FIRST, bool ORD>
 __global__ __launch_bounds__(256) void k_mgb_dirspmv(const VmMgbSys *__restrict__ sys, int k, uint64_t active)
 {
     if (!sys_active(active))
@@ -382,12 +485,12 @@ __global__ __launch_bounds__(256) void k_mgb_dirspmv(const VmMgbSys *__restrict_
     const VmMgbLevel &L = S.lv[0];
     const Op<true> A(L);
     const int nb = G(L.nblocks)[0], par = k & 1;
-    if (blockIdx.x == 0)
+    if (!ORD && blockIdx.x == 0)        // (the ordered fold overwrites, it does not accumulate: nothing to clear)
         slot_clear(S.sc->rr[par]);
     float be[3] = {0, 0, 0};
     if (!FIRST) {
         double cur[3], prev[3];
-        slot_sums2(S.sc->rz[par], S.sc->rz[par ^ 1], cur, prev);
+        sums2<ORD>(S.sc->rz[par], S.sc->rz[par ^ 1], S, VM_MGB_ACC_RZ + par, VM_MGB_ACC_RZ + (par ^ 1), cur, prev);
 #pragma unroll
         for (int c = 0; c < 3; ++c)
             be[c] = prev[c] > 0 ? (float)(cur[c] / prev[c]) : 0.0f;
@@ -418,12 +521,13 @@ __global__ __launch_bounds__(256) void k_mgb_dirspmv(const VmMgbSys *__restrict_
         st3(Q, ii, q);
         pq[0] += (double)p.x * q.x; pq[1] += (double)p.y * q.y; pq[2] += (double)p.z * q.z;
     }
-    block_sum3(pq[0], pq[1], pq[2], S.sc->pq[par]);
+    sum3<ORD>(pq[0], pq[1], pq[2], S.sc->pq[par], S, VM_MGB_ACC_PQ + par, list_groups(nb));
 }
 
 // alpha = rz_k / pq_k;  x += alpha p;  r -= alpha q;  rr[k & 1] += r.r.  Clears rz and pq of the other parity:
 // their last readers (k_mgb_dirspmv of this iteration, k_mgb_update of the previous one) are done, their next
 // writers (the coming cycle's level-0 prolongation, the coming k_mgb_dirspmv) have not started.
+template <bool ORD>
 __global__ __launch_bounds__(256) void k_mgb_update(const VmMgbSys *__restrict__ sys, int k, uint64_t active)
 {
     if (!sys_active(active))
@@ -431,14 +535,14 @@ __global__ __launch_bounds__(256) void k_mgb_update(const VmMgbSys *__restrict__
     const VmMgbSys &S = sys[blockIdx.z];
     const VmMgbLevel &L = S.lv[0];
     const int nb = G(L.nblocks)[0], par = k & 1;
-    if (blockIdx.x == 0) {
+    if (!ORD && blockIdx.x == 0) {
         slot_clear(S.sc->rz[par ^ 1]);
         slot_clear(S.sc->pq[par ^ 1]);
     }
     float al[3];
     {
         double rz[3], pq[3];
-        slot_sums2(S.sc->rz[par], S.sc->pq[par], rz, pq);
+        sums2<ORD>(S.sc->rz[par], S.sc->pq[par], S, VM_MGB_ACC_RZ + par, VM_MGB_ACC_PQ + par, rz, pq);
 #pragma unroll
         for (int c = 0; c < 3; ++c)
             al[c] = pq[c] > 0 ? (float)(rz[c] / pq[c]) : 0.0f;
@@ -463,10 +567,11 @@ __global__ __launch_bounds__(256) void k_mgb_update(const VmMgbSys *__restrict__
             rr[0] += (double)r.x * r.x; rr[1] += (double)r.y * r.y; rr[2] += (double)r.z * r.z;
         }
     }
-    block_sum3(rr[0], rr[1], rr[2], S.sc->rr[par]);
+    sum3<ORD>(rr[0], rr[1], rr[2], S.sc->rr[par], S, VM_MGB_ACC_RR + par, list_groups(nb));
 }
 
 // rz[k & 1] += r.z for hierarchies whose level 0 is solved inside the one-workgroup tail
+template <bool ORD>
 __global__ __launch_bounds__(256) void k_mgb_dot_rz(const VmMgbSys *__restrict__ sys, int k, uint64_t active)
 {
     if (!sys_active(active))
@@ -485,7 +590,7 @@ __global__ __launch_bounds__(256) void k_mgb_dot_rz(const VmMgbSys *__restrict__
             rz[0] += (double)r.x * z.x; rz[1] += (double)r.y * z.y; rz[2] += (double)r.z * z.z;
         }
     }
-    block_sum3(rz[0], rz[1], rz[2], S.sc->rz[k & 1]);
+    sum3<ORD>(rz[0], rz[1], rz[2], S.sc->rz[k & 1], S, VM_MGB_ACC_RZ + (k & 1), list_groups(nb));
 }
 
 // ---------------------------------------------------------------------------
@@ -610,10 +715,11 @@ __device__ __forceinline__ float4 black_update(const TileOp<L0> &op, float4 *val
 // r_k recomputed on the apron.  r ping-pongs (S.R[(k - 1) & 1] -> S.R[k & 1]): a tile's apron is another tile's interior,
 // which may or may not have been rewritten yet.  The separate update kernel streamed 73 B per unknown at the HBM ceiling;
 // here its loads travel with a kernel that waits for latency, not for bytes, and r is not read twice.
-template <bool L0, bool UPD>
+template <bool L0, bool UPD, bool ORD>
 __global__ __launch_bounds__(256) void k_mgb_restrict(const VmMgbSys *__restrict__ sys, int l, int k, uint64_t active)
 {
     static_assert(L0 || !UPD, "the PCG update rides on level 0 only");
+    static_assert(UPD || !ORD, "only the update's r.r is reduced here");
     if (!sys_active(active))
         return;
     const VmMgbSys &S = sys[blockIdx.z];
@@ -664,12 +770,12 @@ __global__ __launch_bounds__(256) void k_mgb_restrict(const VmMgbSys *__restrict
     float al[3] = {0, 0, 0};
     if constexpr (UPD) {        // (what k_mgb_update(k - 1) does first: its scalars, its clears)
         const int par = (k - 1) & 1;
-        if (blockIdx.x == 0) {
+        if (!ORD && blockIdx.x == 0) {
             slot_clear(S.sc->rz[par ^ 1]);
             slot_clear(S.sc->pq[par ^ 1]);
         }
         double rz[3], pq[3];
-        slot_sums2(S.sc->rz[par], S.sc->pq[par], rz, pq);
+        sums2<ORD>(S.sc->rz[par], S.sc->pq[par], S, VM_MGB_ACC_RZ + par, VM_MGB_ACC_PQ + par, rz, pq);
 #pragma unroll
         for (int c = 0; c < 3; ++c)
             al[c] = pq[c] > 0 ? (float)(rz[c] / pq[c]) : 0.0f;
@@ -756,14 +862,15 @@ __global__ __launch_bounds__(256) void k_mgb_restrict(const VmMgbSys *__restrict
         }
     }
     if constexpr (UPD)
-        block_sum3(rr[0], rr[1], rr[2], S.sc->rr[(k - 1) & 1]);
+        sum3<ORD>(rr[0], rr[1], rr[2], S.sc->rr[(k - 1) & 1], S, VM_MGB_ACC_RR + ((k - 1) & 1), G(FL.ntiles)[0]);
 }
 
 // F.x = black, red post-smoothing of x + P C.x (x = the red-black pre-smoothing of F.b from zero), over F's tile list;
 // level 0 (L0): rz[k & 1] += F.b . F.x  = r.z
-template <bool L0>
+template <bool L0, bool ORD>
 __global__ __launch_bounds__(256) void k_mgb_prolong(const VmMgbSys *__restrict__ sys, int l, int k, uint64_t active)
 {
+    static_assert(L0 || !ORD, "only level 0's r.z is reduced here");
     if (!sys_active(active))
         return;
     const VmMgbSys &S = sys[blockIdx.z];
@@ -833,7 +940,7 @@ __global__ __launch_bounds__(256) void k_mgb_prolong(const VmMgbSys *__restrict_
         }
     }
     if (L0)
-        block_sum3(rz[0], rz[1], rz[2], S.sc->rz[k & 1]);
+        sum3<ORD>(rz[0], rz[1], rz[2], S.sc->rz[k & 1], S, VM_MGB_ACC_RZ + (k & 1), G(FL.ntiles)[0]);
 }
 
 // ---------------------------------------------------------------------------
@@ -997,9 +1104,10 @@ __global__ __launch_bounds__(256) void k_mgb_restrict2(const VmMgbSys *__restric
     }
 }
 
-template <bool L0>
+template <bool L0, bool ORD>
 __global__ __launch_bounds__(256) void k_mgb_prolong2(const VmMgbSys *__restrict__ sys, int l, int k, uint64_t active)
 {
+    static_assert(L0 || !ORD, "only level 0's r.z is reduced here");
     if (!sys_active(active))
         return;
     const VmMgbSys &S = sys[blockIdx.z];
@@ -1095,7 +1203,7 @@ __global__ __launch_bounds__(256) void k_mgb_prolong2(const VmMgbSys *__restrict
         }
     }
     if (L0)
-        block_sum3(rz[0], rz[1], rz[2], S.sc->rz[k & 1]);
+        sum3<ORD>(rz[0], rz[1], rz[2], S.sc->rz[k & 1], S, VM_MGB_ACC_RZ + (k & 1), G(FL.ntiles)[0]);
 }
 
 // ---------------------------------------------------------------------------
@@ -1354,6 +1462,8 @@ __global__ __launch_bounds__(TAILT) void k_mgb_tail(const VmMgbSys *__restrict__
 
 const dim3 blk2(64, 4);
 inline int groups(int nb) { return (nb + MGB_G - 1) / MGB_G; }
+// a kernel picked at run time (the reduction mode)
+template <class... A> inline void launch(void (*k)(A...), dim3 grid, hipStream_t s, A... a) { hipLaunchKernelGGL(k, grid, blk2, 0, s, a...); }
 
 } // namespace
 
@@ -1375,12 +1485,12 @@ void vm_mgb_launch_compact(const VmMgbSys *sys, int nsys, int nlev_max, hipStrea
     hipLaunchKernelGGL(k_mgb_compact, dim3(nlev_max, 1, nsys), dim3(1024), 0, s, sys);
 }
 
-void vm_mgb_launch_init(const VmMgbSys *sys, int nsys, int nb0, uint64_t active, hipStream_t s)
+void vm_mgb_launch_init(const VmMgbSys *sys, int nsys, int nb0, uint64_t active, bool ord, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_mgb_init, dim3(groups(nb0), 1, nsys), blk2, 0, s, sys, active);
+    launch(ord ? k_mgb_init<true> : k_mgb_init<false>, dim3(groups(nb0), 1, nsys), s, sys, active);
 }
 
-void vm_mgb_launch_restrict(const VmMgbSys *sys, int nsys, int l, int nu, int nt_fine, int k, bool upd, uint64_t active, hipStream_t s)
+void vm_mgb_launch_restrict(const VmMgbSys *sys, int nsys, int l, int nu, int nt_fine, int k, bool upd, uint64_t active, bool ord, hipStream_t s)
 {
     const dim3 grid(nt_fine, 1, nsys);
     if (nu == 2) {
@@ -1389,26 +1499,26 @@ void vm_mgb_launch_restrict(const VmMgbSys *sys, int nsys, int l, int nu, int nt
         else
             hipLaunchKernelGGL(k_mgb_restrict2<false>, grid, blk2, 0, s, sys, l, active);
     } else if (l == 0 && upd) {
-        hipLaunchKernelGGL((k_mgb_restrict<true, true>), grid, blk2, 0, s, sys, l, k, active);
+        launch(ord ? k_mgb_restrict<true, true, true> : k_mgb_restrict<true, true, false>, grid, s, sys, l, k, active);
     } else if (l == 0) {
-        hipLaunchKernelGGL((k_mgb_restrict<true, false>), grid, blk2, 0, s, sys, l, k, active);
+        hipLaunchKernelGGL((k_mgb_restrict<true, false, false>), grid, blk2, 0, s, sys, l, k, active);
     } else {
-        hipLaunchKernelGGL((k_mgb_restrict<false, false>), grid, blk2, 0, s, sys, l, k, active);
+        hipLaunchKernelGGL((k_mgb_restrict<false, false, false>), grid, blk2, 0, s, sys, l, k, active);
     }
 }
 
-void vm_mgb_launch_prolong(const VmMgbSys *sys, int nsys, int l, int nu, int nt_fine, int k, uint64_t active, hipStream_t s)
+void vm_mgb_launch_prolong(const VmMgbSys *sys, int nsys, int l, int nu, int nt_fine, int k, uint64_t active, bool ord, hipStream_t s)
 {
     const dim3 grid(nt_fine, 1, nsys);
     if (nu == 2) {
         if (l == 0)
-            hipLaunchKernelGGL(k_mgb_prolong2<true>, grid, blk2, 0, s, sys, l, k, active);
+            launch(ord ? k_mgb_prolong2<true, true> : k_mgb_prolong2<true, false>, grid, s, sys, l, k, active);
         else
-            hipLaunchKernelGGL(k_mgb_prolong2<false>, grid, blk2, 0, s, sys, l, k, active);
+            hipLaunchKernelGGL((k_mgb_prolong2<false, false>), grid, blk2, 0, s, sys, l, k, active);
     } else if (l == 0) {
-        hipLaunchKernelGGL(k_mgb_prolong<true>, grid, blk2, 0, s, sys, l, k, active);
+        launch(ord ? k_mgb_prolong<true, true> : k_mgb_prolong<true, false>, grid, s, sys, l, k, active);
     } else {
-        hipLaunchKernelGGL(k_mgb_prolong<false>, grid, blk2, 0, s, sys, l, k, active);
+        hipLaunchKernelGGL((k_mgb_prolong<false, false>), grid, blk2, 0, s, sys, l, k, active);
     }
 }
 
@@ -1420,20 +1530,20 @@ void vm_mgb_launch_tail(const VmMgbSys *sys, int nsys, int l, uint64_t active, h
         hipLaunchKernelGGL(k_mgb_tail<false>, dim3(1, 1, nsys), dim3(TAILT), 0, s, sys, l, active);
 }
 
-void vm_mgb_launch_dot_rz(const VmMgbSys *sys, int nsys, int nb0, int k, uint64_t active, hipStream_t s)
+void vm_mgb_launch_dot_rz(const VmMgbSys *sys, int nsys, int nb0, int k, uint64_t active, bool ord, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_mgb_dot_rz, dim3(groups(nb0), 1, nsys), blk2, 0, s, sys, k, active);
+    launch(ord ? k_mgb_dot_rz<true> : k_mgb_dot_rz<false>, dim3(groups(nb0), 1, nsys), s, sys, k, active);
 }
 
-void vm_mgb_launch_dirspmv(const VmMgbSys *sys, int nsys, int nb0, int k, uint64_t active, hipStream_t s)
+void vm_mgb_launch_dirspmv(const VmMgbSys *sys, int nsys, int nb0, int k, uint64_t active, bool ord, hipStream_t s)
 {
     if (k == 0)
-        hipLaunchKernelGGL(k_mgb_dirspmv<true>, dim3(groups(nb0), 1, nsys), blk2, 0, s, sys, k, active);
+        launch(ord ? k_mgb_dirspmv<true, true> : k_mgb_dirspmv<true, false>, dim3(groups(nb0), 1, nsys), s, sys, k, active);
     else
-        hipLaunchKernelGGL(k_mgb_dirspmv<false>, dim3(groups(nb0), 1, nsys), blk2, 0, s, sys, k, active);
+        launch(ord ? k_mgb_dirspmv<false, true> : k_mgb_dirspmv<false, false>, dim3(groups(nb0), 1, nsys), s, sys, k, active);
 }
 
-void vm_mgb_launch_update(const VmMgbSys *sys, int nsys, int nb0, int k, uint64_t active, hipStream_t s)
+void vm_mgb_launch_update(const VmMgbSys *sys, int nsys, int nb0, int k, uint64_t active, bool ord, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_mgb_update, dim3(groups(nb0), 1, nsys), blk2, 0, s, sys, k, active);
+    launch(ord ? k_mgb_update<true> : k_mgb_update<false>, dim3(groups(nb0), 1, nsys), s, sys, k, active);
 }

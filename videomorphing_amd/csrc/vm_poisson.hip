@@ -289,10 +289,9 @@ __global__ __launch_bounds__(256) void k_qp_rhs(const float2 *__restrict__ v, in
 // workgroups, the atomics spread over `nslots` lines (one workgroup per 64x4 cells adding to ONE address took 99 us
 // on a 1080p field: 8100 same-address double atomics in a row)
 template <class V>
-__global__ __launch_bounds__(256) void k_qp_sum(const V *__restrict__ X, int w, int h, double *dst, int nslots)
+__device__ __forceinline__ void qp_colsums(const V *__restrict__ X, int w, int h, double &a, double &b)
 {
     const int gx = (w + 63) / 64, gy = (h + 3) / 4, nb = gx * gy;
-    double a = 0, b = 0;
     for (int blk = blockIdx.x; blk < nb; blk += gridDim.x) {
         const int x = (blk % gx) * 64 + threadIdx.x, y = (blk / gx) * 4 + threadIdx.y;
         if (x < w && y < h) {
@@ -301,7 +300,47 @@ __global__ __launch_bounds__(256) void k_qp_sum(const V *__restrict__ X, int w, 
             b += v.y;
         }
     }
+}
+template <class V>
+__global__ __launch_bounds__(256) void k_qp_sum(const V *__restrict__ X, int w, int h, double *dst, int nslots)
+{
+    double a = 0, b = 0;
+    qp_colsums(X, w, h, a, b);
     block_sum3(a, b, 0.0, dst + (size_t)(blockIdx.x % nslots) * 16);
+}
+
+// The same sums in ONE fixed order (vm_set_reduction(ctx, VM_REDUCE_ORDERED)): workgroup i of the launch -- whose size is a
+// function of the field's size alone (sum_grid) -- leaves its two sums (block_sum3's tree) in part[i]; k_qp_fold, the next
+// launch, adds them up: lane j of 32 takes entries j, j + 32, ... in sequence, a butterfly joins the lanes.
+template <class V>
+__global__ __launch_bounds__(256) void k_qp_sum_ord(const V *__restrict__ X, int w, int h, double *part)
+{
+    __shared__ double sh[2][4];
+    double a = 0, b = 0;
+    qp_colsums(X, w, h, a, b);
+    for (int o = 32; o > 0; o >>= 1) {
+        a += __shfl_down(a, o);
+        b += __shfl_down(b, o);
+    }
+    const int tid = threadIdx.y * blockDim.x + threadIdx.x;
+    const int wave = tid >> 6, lane = tid & 63;
+    if (lane == 0) { sh[0][wave] = a; sh[1][wave] = b; }
+    __syncthreads();
+    if (tid < 2)
+        part[(size_t)blockIdx.x * 2 + tid] = sh[tid][0] + sh[tid][1] + sh[tid][2] + sh[tid][3];
+}
+// dst[0], dst[1] = the totals (slot 0 of the lines k_qp_shift adds up; the caller has zeroed the others)
+__global__ __launch_bounds__(64) void k_qp_fold(const double *__restrict__ part, int n, double *dst)
+{
+    const int q = threadIdx.x >> 5, j = threadIdx.x & 31;
+    double s = 0;
+    for (int i = j; i < n; i += 32)
+        s += part[(size_t)i * 2 + q];
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1)
+        s = s + __shfl_xor(s, o);
+    if (j == 0)
+        dst[q] = s;
 }
 
 // B -= mean(B) (the float sums leave the right-hand side a hair off the range of the singular
@@ -367,12 +406,19 @@ void vm_qpath_launch_rhs3(const float2 *v, int rs, int w, int h, VmV3 *B, VmV3 *
 // sums[0..1] += column sums of X (sums must be zeroed by the caller)
 static inline dim3 sum_grid(int w, int h)
 {
-    return dim3(std::min(((w + 63) / 64) * ((h + 3) / 4), 1024));
+    return dim3(std::min(((w + 63) / 64) * ((h + 3) / 4), VM_QP_ORD_PARTS));
 }
 
 // the atomics spread over VM_QP_SLOTS lines of 16 doubles (the solver's scalar block has room for 8)
-void vm_qpath_launch_sum3(const VmV3 *X, int w, int h, double *sums, hipStream_t s)
+// ord_part != nullptr: the ordered fold, through sum_grid(w, h).x x 2 doubles of scratch (VM_QP_ORD_PARTS at most)
+void vm_qpath_launch_sum3(const VmV3 *X, int w, int h, double *sums, double *ord_part, hipStream_t s)
 {
+    if (ord_part) {
+        const dim3 g = sum_grid(w, h);
+        hipLaunchKernelGGL(k_qp_sum_ord<VmV3>, g, dim3(64, 4), 0, s, X, w, h, ord_part);
+        hipLaunchKernelGGL(k_qp_fold, dim3(1), dim3(64), 0, s, ord_part, (int)g.x, sums);
+        return;
+    }
     hipLaunchKernelGGL(k_qp_sum<VmV3>, sum_grid(w, h), dim3(64, 4), 0, s, X, w, h, sums, VM_QP_SLOTS);
 }
 

@@ -156,26 +156,26 @@ void mgb_carve(MgbWork &W, int w, int h, char *b, bool qpath = false)
 //                     k_mgb_update by itself -- after which x, r and r.r of k completed iterations stand in memory;
 //   mgb_iter_rest(k): the rest of cycle k and p = z + beta p, q = A p.
 void mgb_iter_head(const VmMgbSys *dev, int nsys, bool fused, const std::vector<int> &nb, const std::vector<int> &nt, int k, uint64_t active,
-                   hipStream_t s)
+                   bool ord, hipStream_t s)
 {
     if (fused)
-        vm_mgb_launch_restrict(dev, nsys, 0, 1, nt[0], k, k > 0, active, s);
+        vm_mgb_launch_restrict(dev, nsys, 0, 1, nt[0], k, k > 0, active, ord, s);
     else if (k > 0)
-        vm_mgb_launch_update(dev, nsys, nb[0], k - 1, active, s);
+        vm_mgb_launch_update(dev, nsys, nb[0], k - 1, active, ord, s);
 }
 
 void mgb_iter_rest(const VmMgbSys *dev, int nsys, const MgbWork &W0, bool fused, const std::vector<int> &nb, const std::vector<int> &nt, int k,
-                   uint64_t active, hipStream_t s)
+                   uint64_t active, bool ord, hipStream_t s)
 {
     const int tail = W0.tail;       // levels tail .. nlev - 1 run in one workgroup
     for (int l = fused ? 1 : 0; l < tail; ++l)
-        vm_mgb_launch_restrict(dev, nsys, l, W0.S.lv[l].nu, nt[l], k, false, active, s);
+        vm_mgb_launch_restrict(dev, nsys, l, W0.S.lv[l].nu, nt[l], k, false, active, false, s);
     vm_mgb_launch_tail(dev, nsys, tail, active, s);
     if (tail == 0)
-        vm_mgb_launch_dot_rz(dev, nsys, nb[0], k, active, s);
+        vm_mgb_launch_dot_rz(dev, nsys, nb[0], k, active, ord, s);
     for (int l = tail - 1; l >= 0; --l)
-        vm_mgb_launch_prolong(dev, nsys, l, W0.S.lv[l].nu, nt[l], k, active, s);
-    vm_mgb_launch_dirspmv(dev, nsys, nb[0], k, active, s);
+        vm_mgb_launch_prolong(dev, nsys, l, W0.S.lv[l].nu, nt[l], k, active, ord && l == 0, s);
+    vm_mgb_launch_dirspmv(dev, nsys, nb[0], k, active, ord, s);
 }
 
 double mgb_rel(const VmMgbScalars &h, int par)
@@ -184,6 +184,45 @@ double mgb_rel(const VmMgbScalars &h, int par)
     for (int c = 0; c < 3; ++c) {
         double bb = 0, rr = 0;
         for (int k = 0; k < VM_MGB_SLOTS; ++k) { bb += h.bb[k][c]; rr += h.rr[par][k][c]; }
+        if (!(bb == bb) || !(rr == rr) || std::isinf(bb) || std::isinf(rr)) return -1;
+        if (bb > 0) worst = std::max(worst, std::sqrt(rr / bb));
+    }
+    return worst;
+}
+
+// The ordered mode's storage of one system, as the host sees it (vm_mgb.h: VmMgbOrd).  The head -- the descriptor, the
+// group counts and the group sums of the accumulators the HOST reads (bb, rr[0], rr[1]: the first three) -- is what a
+// residual check reads back.
+struct MgbOrdLayout {
+    int cap, gcap;
+    size_t o_ng, o_gpart, head, o_ticket, o_part, bytes;    // offsets from the system's base; head = bytes of a read-back
+    MgbOrdLayout(int gx, int gy)
+    {
+        // producing workgroups of a launch at most: groups of MGB_G = 4 blocks (streaming kernels), tiles of four block rows
+        cap = std::max((gx * gy + 3) / 4, gx * ((gy + 3) / 4));
+        gcap = (cap + VM_MGB_ORD_GROUP - 1) / VM_MGB_ORD_GROUP;
+        o_ng = vm_align256(sizeof(VmMgbOrd));
+        o_gpart = o_ng + vm_align256(VM_MGB_NACC * sizeof(int));
+        head = o_gpart + (size_t)(VM_MGB_ACC_RR + 2) * gcap * 4 * sizeof(double);
+        o_ticket = o_gpart + vm_align256((size_t)VM_MGB_NACC * gcap * 4 * sizeof(double));
+        o_part = o_ticket + vm_align256((size_t)VM_MGB_NACC * gcap * VM_MGB_ORD_TSTRIDE * sizeof(unsigned));
+        bytes = o_part + vm_align256((size_t)VM_MGB_NACC * cap * 4 * sizeof(double));
+    }
+};
+
+// ... and the stop test's two totals from a read-back head: group sums 0 .. ng - 1 in ascending order from zero
+double mgb_rel_ordered(const char *head, const MgbOrdLayout &Y, int par)
+{
+    const int *ng = (const int *)(head + Y.o_ng);
+    const double *gp = (const double *)(head + Y.o_gpart);
+    auto total = [&](int acc, int c) {
+        double t = 0;
+        for (int g = 0; g < std::min(ng[acc], Y.gcap); ++g) t += gp[((size_t)acc * Y.gcap + g) * 4 + c];
+        return t;
+    };
+    double worst = 0;
+    for (int c = 0; c < 3; ++c) {
+        const double bb = total(VM_MGB_ACC_BB, c), rr = total(VM_MGB_ACC_RR + par, c);
         if (!(bb == bb) || !(rr == rr) || std::isinf(bb) || std::isinf(rr)) return -1;
         if (bb > 0) worst = std::max(worst, std::sqrt(rr / bb));
     }
@@ -211,6 +250,15 @@ static int mgb_solve(vm_ctx *c, std::vector<MgbWork> &W, int nsys, float tol, in
     VmMgbSys *dev = c->mgb_sys.get();
     std::vector<VmMgbSys> hs(nsys);
     const int nlev = W[0].S.nlev;
+    // VM_REDUCE_ORDERED: every system's partials, tickets and group sums, from the context like the scalars; the descriptors,
+    // group counts and tickets are cleared once per solve (a launch leaves its tickets at zero again)
+    const bool ord = c->reduction == VM_REDUCE_ORDERED;
+    const MgbOrdLayout Y(W[0].S.lv[0].gx, W[0].S.lv[0].gy);
+    char *ord_dev = nullptr;
+    if (ord) {
+        if (int rc = c->mgb_ord.reserve((size_t)nsys * Y.bytes)) return rc;
+        ord_dev = c->mgb_ord.get();
+    }
     // The PCG update rides in the level-0 restriction wherever the hierarchy allows it.  Measured on the 2304 x 1464 canvas
     // (tools/exp/fuse_ab.sh, ms per frame at 1e-5, fused against the separate k_mgb_update): 8 systems per batch 1.61 / 1.70,
     // 4 systems 1.95 / 1.99, 2 systems 2.49 / 2.51, one system 1.78 / 1.81 per side (with the fused kernel's loads issued cell
@@ -222,6 +270,7 @@ static int mgb_solve(vm_ctx *c, std::vector<MgbWork> &W, int nsys, float tol, in
         W[i].S.R[1] = fused ? W[i].r1 : W[i].S.R[0];
         hs[i] = W[i].S;
         hs[i].sc = sc_dev + i;
+        if (ord) hs[i].ord = (const VmMgbOrd *)(ord_dev + (size_t)i * Y.bytes);
         for (int l = 0; l < nlev; ++l) {
             hs[i].lv[l].nblocks = cnt_dev + (size_t)i * 2 * VM_MGB_MAXLEV + l;
             hs[i].lv[l].ntiles = cnt_dev + (size_t)i * 2 * VM_MGB_MAXLEV + VM_MGB_MAXLEV + l;
@@ -229,6 +278,17 @@ static int mgb_solve(vm_ctx *c, std::vector<MgbWork> &W, int nsys, float tol, in
     }
     VM_HIP(hipMemcpyAsync(dev, hs.data(), nsys * sizeof(VmMgbSys), hipMemcpyHostToDevice, s));
     VM_HIP(hipMemsetAsync(sc_dev, 0, nsys * sizeof(VmMgbScalars), s));
+    std::vector<char> ord_head;        // the systems' descriptors going up, then their read-back heads
+    if (ord) {
+        ord_head.assign((size_t)nsys * Y.head, 0);
+        for (int i = 0; i < nsys; ++i) {
+            char *base = ord_dev + (size_t)i * Y.bytes;
+            VM_HIP(hipMemsetAsync(base, 0, Y.o_part, s));
+            const VmMgbOrd d{Y.cap, Y.gcap, (double *)(base + Y.o_part), (double *)(base + Y.o_gpart), (unsigned *)(base + Y.o_ticket), (int *)(base + Y.o_ng)};
+            memcpy(&ord_head[(size_t)i * Y.head], &d, sizeof(d));
+            VM_HIP(hipMemcpyAsync(base, &ord_head[(size_t)i * Y.head], sizeof(d), hipMemcpyHostToDevice, s));
+        }
+    }
     for (int i = 0; i < nsys; ++i)
         if (W[i].xcoarse_bytes) VM_HIP(hipMemsetAsync(W[i].xcoarse, 0, W[i].xcoarse_bytes, s));
     // the hierarchy and its block lists (batched)
@@ -250,7 +310,7 @@ static int mgb_solve(vm_ctx *c, std::vector<MgbWork> &W, int nsys, float tol, in
         return VM_OK;
     }
     uint64_t active = nsys == 64 ? ~0ull : ((1ull << nsys) - 1);
-    vm_mgb_launch_init(dev, nsys, nb[0], active, s);
+    vm_mgb_launch_init(dev, nsys, nb[0], active, ord, s);
     std::vector<VmMgbScalars> h(nsys);
     std::vector<double> best(nsys, 1e300);
     std::vector<int> best_it(nsys, 0), next_check(nsys, 0), saved(nsys, 0);
@@ -267,11 +327,16 @@ static int mgb_solve(vm_ctx *c, std::vector<MgbWork> &W, int nsys, float tol, in
         for (int i = 0; i < nsys; ++i)
             if (((active >> i) & 1) && next_check[i] == it) { lo = std::min(lo, i); hi = i; }
         if (hi < lo) return VM_OK;
-        VM_HIP(hipMemcpyAsync(&h[lo], sc_dev + lo, (size_t)(hi - lo + 1) * sizeof(VmMgbScalars), hipMemcpyDeviceToHost, s));
+        if (ord)
+            VM_HIP(hipMemcpy2DAsync(&ord_head[(size_t)lo * Y.head], Y.head, ord_dev + (size_t)lo * Y.bytes, Y.bytes, Y.head, (size_t)(hi - lo + 1),
+                                    hipMemcpyDeviceToHost, s));
+        else
+            VM_HIP(hipMemcpyAsync(&h[lo], sc_dev + lo, (size_t)(hi - lo + 1) * sizeof(VmMgbScalars), hipMemcpyDeviceToHost, s));
         VM_HIP(hipStreamSynchronize(s));
         for (int i = 0; i < nsys; ++i) {
             if (!((active >> i) & 1) || next_check[i] != it) continue;
-            const double worst = mgb_rel(h[i], (it - 1) & 1);   // it == 0: parity 1, where k_mgb_init left r.r
+            // it == 0: parity 1, where k_mgb_init left r.r
+            const double worst = ord ? mgb_rel_ordered(&ord_head[(size_t)i * Y.head], Y, (it - 1) & 1) : mgb_rel(h[i], (it - 1) & 1);
             if (worst < 0)
                 return vm_fail(VM_E_NUMERIC, it == 0 ? "multigrid PCG: the right-hand side is not finite" : "multigrid PCG broke down (NaN)");
             if (worst < best[i]) {
@@ -313,18 +378,18 @@ static int mgb_solve(vm_ctx *c, std::vector<MgbWork> &W, int nsys, float tol, in
             if (int rc = e0.create()) return rc;
             if (int rc = e1.create()) return rc;
             VM_HIP(hipEventRecord(e0.get(), s));
-            mgb_iter_head(dev, nsys, fused, nb, nt, it, active, s);
+            mgb_iter_head(dev, nsys, fused, nb, nt, it, active, ord, s);
             VM_HIP(hipEventRecord(e1.get(), s));
             prof_sys.push_back(__builtin_popcountll(active));
         } else {
-            mgb_iter_head(dev, nsys, fused, nb, nt, it, active, s);
+            mgb_iter_head(dev, nsys, fused, nb, nt, it, active, ord, s);
         }
         if (it > 0) {
             const int rc = check(it);
             if (rc != VM_OK) return rc;
             if (!active) break;
         }
-        mgb_iter_rest(dev, nsys, W[0], fused, nb, nt, it, active, s);
+        mgb_iter_rest(dev, nsys, W[0], fused, nb, nt, it, active, ord, s);
         ++it;
         VM_HIP(hipGetLastError());
     }
@@ -493,14 +558,17 @@ extern "C" int vm_frame_quadratic_path(vm_frame *f, float tol, int max_it, int *
         vm_qpath_launch_rhs3(f->v.get(), f->rs, f->w, f->h, W[0].S.lv[0].b, W[0].S.X, s);
         // project the right-hand side onto the range of the singular operator
         double *sums = &W[0].S.sc->bb[0][0];
+        // VM_REDUCE_ORDERED: the sums' workgroup partials go through scratch of the workspace -- Q, which the solve writes
+        // before it reads and nobody reads after it (16 bytes per 64 x 4-cell block at most, of 12 per cell of a field >= 2 x 2)
+        double *const ord_part = c->reduction == VM_REDUCE_ORDERED ? (double *)W[0].S.Q : nullptr;
         VM_HIP(hipMemsetAsync(W[0].S.sc, 0, sizeof(VmMgbScalars), s));
-        vm_qpath_launch_sum3(W[0].S.lv[0].b, f->w, f->h, sums, s);
+        vm_qpath_launch_sum3(W[0].S.lv[0].b, f->w, f->h, sums, ord_part, s);
         vm_qpath_launch_shift3(W[0].S.lv[0].b, f->w, f->h, sums, nullptr, 0, s);
         VM_HIP(hipGetLastError());
         rc = mgb_solve(c, W, 1, tol, max_it, &it, &rel);
         if (rc != VM_OK) return rc;
         VM_HIP(hipMemsetAsync(W[0].S.sc, 0, sizeof(VmMgbScalars), s));
-        vm_qpath_launch_sum3(W[0].S.X, f->w, f->h, sums, s);
+        vm_qpath_launch_sum3(W[0].S.X, f->w, f->h, sums, ord_part, s);
         vm_qpath_launch_shift3(W[0].S.X, f->w, f->h, sums, f->u.get(), f->rs, s);
     }
     f->u_zero = false;

@@ -19,7 +19,7 @@ import weakref
 import numpy as np
 
 from . import capi
-from .capi import BCOND_NONE, BCOND_CORNER, BCOND_BORDER, MATH_EXACT, MATH_FAST  # noqa: F401
+from .capi import BCOND_NONE, BCOND_CORNER, BCOND_BORDER, MATH_EXACT, MATH_FAST, REDUCE_ATOMIC, REDUCE_ORDERED  # noqa: F401
 from . import synth
 
 
@@ -92,6 +92,8 @@ class Context(object):
         capi.check(self._L.vm_ctx_create(int(device), C.byref(h)))
         self._h = h
         self.device = int(device)
+        # (what vm_ctx_create read from the environment; any other value made it fail)
+        self.reduction = REDUCE_ORDERED if os.environ.get("VM_REDUCTION") == "ordered" else REDUCE_ATOMIC
         self.set_math_mode(math_mode)
 
     def close(self):
@@ -130,6 +132,13 @@ class Context(object):
         """diagnostic (EXACT): the order a phase's commits are folded in -- 0 row-major (the oracle's),
         1 reversed, 2 column-major, 3 column-major reversed (vm_set_commit_order)"""
         capi.check(self._L.vm_set_commit_order(self._h, int(order)))
+
+    def set_reduction(self, mode=REDUCE_ORDERED):
+        """how the compositor's linear solver adds up its dot products (vm_set_reduction): REDUCE_ATOMIC (0, the default:
+        arrival order, run-dependent in the last bit) or REDUCE_ORDERED (1: one fixed order per system -- the same bytes from
+        run to run, alone or in any batch, on any context)"""
+        capi.check(self._L.vm_set_reduction(self._h, int(mode)))
+        self.reduction = int(mode)
 
     def set_sparse_resident(self, mode=0):
         """test hook of the SPARSE schedule's resident visits (FAST): 0 automatic, 1 never, 2 re-centre the LDS copy
@@ -591,11 +600,14 @@ def context_beside(device, math_mode, others, tries=8):
     runtime deals new streams to its GPU_MAX_HW_QUEUES hardware queues as it likes, and two streams on one queue run their
     kernels one after the other.  Candidates that share a queue with one of `others` are kept alive while the search goes on
     (so that the next stream gets another queue) and closed at the end; after `tries` candidates the last one is returned
-    whatever it shares.  Returns (context, number of rejected candidates)."""
+    whatever it shares.  The new context takes the reduction mode of others[0].  Returns (context, number of rejected
+    candidates)."""
     rejected = []
     probe = not os.environ.get("VM_NO_STREAM_PROBE")          # development switch: take the first stream, as rounds 1-5 did
     while True:
         c = Context(device, math_mode)
+        if others and others[0].reduction != c.reduction:
+            c.set_reduction(others[0].reduction)
         if not probe or len(rejected) >= tries - 1 or all(c.runs_beside(o) for o in others):
             for r in rejected:
                 r.close()
