@@ -424,6 +424,25 @@ int  vm_poisson_extend_frames(vm_frame *const *frames, int n, float tol, int max
  * event time (microseconds), the number of launches, the number of active systems summed over them and how many of the launches
  * were of the fused form.  Any of the four may be NULL.  bench.py's `poisson_extend_1080p_ex192.roofline.dominant_kernel`. */
 int  vm_dbg_poisson_profile(vm_ctx *ctx, int on, double *update_us, int *update_launches, double *active_systems, int *fused_launches);
+/* Read-only views of that solver's preconditioner, for tests that pin it stage by stage (the reference has no counterpart: MKL DSS
+ * factorises the matrix CPoissonExt::poissonExtend assembles, Algorithm/PoissonExt.cpp:214-329; CQuadraticPath::optimize runs plain
+ * CG, Algorithm/QuadraticPath.cpp:173-215).  `which`: side 1 or 2 of the frame's Poisson extension, or VM_DBG_MGB_QPATH, the
+ * quadratic path's whole-grid system.  They run the solver's own set-up and cycle on the solver's own workspace, from the canvas
+ * as it stands (classified, not filled: the canvases, v and u are not touched), one system, in the context's reduction mode.
+ * vm_dbg_mgb_setup builds the hierarchy and reports its number of levels, the first level of the one-workgroup tail, and per level
+ * (arrays of 14 entries at most) the grid's size, the smoothing sweeps each way and the numbers of 64x4-cell blocks and 64x16-cell
+ * tiles that hold an unknown.  Any output may be NULL. */
+#define VM_DBG_MGB_QPATH 3
+int  vm_dbg_mgb_setup(vm_frame *f, int which, int *nlev, int *tail, int *w, int *h, int *nu, int *nblocks, int *ntiles);
+/* Level l of the hierarchy the last vm_dbg_mgb_setup / _cycle of this system left in the frame (VM_E_STATE if there is none; launches
+ * nothing): the diagonal and the weights of the edges to the east / south neighbour, h x w floats each (level 0: decoded from its
+ * one byte per cell), and the level's right-hand side b and result x of the last cycle, h x w x 3 floats, where they stand in
+ * memory: down to the first level of the tail.  *have: bit 0 = b, bit 1 = x were delivered.  Cells without an unknown (dg == 0)
+ * of b and x hold whatever the memory held.  Any output may be NULL. */
+int  vm_dbg_mgb_level(vm_frame *f, int which, int l, float *dg, float *we, float *ws, float *b, float *x, int *have);
+/* One cycle z = M^-1 r of that hierarchy (rebuilt) as iteration 0 of the PCG runs it: r_in (h x w x 3 floats, zero off the
+ * unknowns) is the residual; z_out = z, q_out = A z, zero off the unknowns.  z_out / q_out may be NULL. */
+int  vm_dbg_mgb_cycle(vm_frame *f, int which, const float *r_in, float *z_out, float *q_out);
 /* CQuadraticPath::optimize for one frame, Algorithm/QuadraticPath.cpp:24-223
  * (QuadraticPath.h:14-24): from the frame's halfway field v the per-pixel optimal
  * Jacobian blend and the Neumann Poisson solve for the quadratic motion path u,

@@ -1,5 +1,5 @@
-"""numpy model of the device's multigrid-preconditioned CG (vm_mgb.hip) on the Poisson extension's system of one side of a
-fixture frame: iteration counts of smoother / cycle variants BEFORE any kernel is written (build container, CPU only).
+"""The numpy model of the device's multigrid-preconditioned CG (tests/mgb_ref.py, which the tests compare vm_mgb.hip with) on
+the Poisson extension's system of one side of a fixture frame: iteration counts of smoother / cycle variants BEFORE any kernel is written (build container, CPU only).
 
 The hierarchy is the device's: 2x2 aggregation, piecewise-constant transfer, Galerkin operator with the edge weights
 halved, down to a grid of <= 64 cells that gets 2 symmetric sweeps each way; the smoother is red-black Gauss-Seidel,
@@ -22,6 +22,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import oracle  # noqa: E402
 import fullsize_fixture as FX  # noqa: E402
 from videomorphing_amd import synth  # noqa: E402
+import mgb_ref  # noqa: E402  (the model itself: the tests compare the device with it)
 
 
 def arg(name, default):
@@ -66,118 +67,11 @@ def system(w, h, ex, frame, side):
     return unk, E.astype(np.float64), S.astype(np.float64), tie, B
 
 
-class Level:
-    def __init__(self, we, ws, sc):
-        # we[y, x]: weight of the edge to the east (shape h x (w - 1)), ws: to the south ((h - 1) x w), sc: screening
-        self.h, self.w = sc.shape
-        self.we, self.ws = we, ws
-        dg = np.maximum(sc, 0).copy()
-        dg[:, :-1] += we
-        dg[:, 1:] += we
-        dg[:-1] += ws
-        dg[1:] += ws
-        self.dg = dg
-        self.sc = sc
-        self.unk = dg > 0
-        self.inv = np.where(self.unk, 1.0 / np.where(self.unk, dg, 1), 0.0)
-        yy, xx = np.mgrid[0:self.h, 0:self.w]
-        self.red = ((xx + yy) & 1) == 0
-
-    def nbsum(self, x):
-        s = np.zeros_like(x)
-        s[:, :-1] += self.we[..., None] * x[:, 1:]
-        s[:, 1:] += self.we[..., None] * x[:, :-1]
-        s[:-1] += self.ws[..., None] * x[1:]
-        s[1:] += self.ws[..., None] * x[:-1]
-        return s
-
-    def apply(self, x):
-        return self.dg[..., None] * x - self.nbsum(x)
-
-    def half(self, x, b, red):
-        m = (self.red == red) & self.unk
-        s = self.nbsum(x)
-        x[m] = (self.inv[..., None] * (b + s))[m]
-
-    def coarsen(self):
-        h2, w2 = (self.h + 1) // 2, (self.w + 1) // 2
-
-        def pad(a, hh, ww):
-            out = np.zeros((hh, ww))
-            out[:a.shape[0], :a.shape[1]] = a
-            return out
-        # edges leaving an aggregate to the east: fine edges at odd x; to the south: odd y; x 1/2
-        wef = pad(self.we, 2 * h2, 2 * w2)
-        wsf = pad(self.ws, 2 * h2, 2 * w2)
-        we = 0.5 * (wef[0::2, 1::2] + wef[1::2, 1::2])[:, :w2 - 1]
-        ws = 0.5 * (wsf[1::2, 0::2] + wsf[1::2, 1::2])[:h2 - 1]
-        scf = pad(self.sc, 2 * h2, 2 * w2)
-        sc = scf[0::2, 0::2] + scf[0::2, 1::2] + scf[1::2, 0::2] + scf[1::2, 1::2]
-        return Level(we, ws, sc)
-
-
-def restrict(r):
-    h, w = r.shape[:2]
-    h2, w2 = (h + 1) // 2, (w + 1) // 2
-    p = np.zeros((2 * h2, 2 * w2, r.shape[2]))
-    p[:h, :w] = r
-    return p[0::2, 0::2] + p[0::2, 1::2] + p[1::2, 0::2] + p[1::2, 1::2]
-
-
-def prolong(xc, h, w):
-    return np.repeat(np.repeat(xc, 2, axis=0), 2, axis=1)[:h, :w]
-
-
-def vcycle(levels, l, b, nu, coarsest_sweeps=2):
-    L = levels[l]
-    x = np.zeros_like(b)
-    if l == len(levels) - 1:
-        for _ in range(coarsest_sweeps):
-            L.half(x, b, True)
-            L.half(x, b, False)
-        for _ in range(coarsest_sweeps):
-            L.half(x, b, False)
-            L.half(x, b, True)
-        return x
-    n = nu[min(l, len(nu) - 1)]
-    for _ in range(n):
-        L.half(x, b, True)
-        L.half(x, b, False)
-    r = b - L.apply(x)
-    r[~L.unk] = 0
-    xc = vcycle(levels, l + 1, restrict(r), nu, coarsest_sweeps)
-    x += prolong(xc, L.h, L.w)
-    x[~L.unk] = 0
-    for _ in range(n):
-        L.half(x, b, False)
-        L.half(x, b, True)
-    return x
-
-
 def pcg(levels, B, nu, tols, max_it=60):
-    L = levels[0]
-    x = np.zeros_like(B)
-    r = B.copy()
-    bb = (B * B).sum(axis=(0, 1))
-    out = {}
-    p = None
-    rz_old = None
-    for it in range(max_it + 1):
-        rel = float(np.sqrt(((r * r).sum(axis=(0, 1)) / bb).max()))
-        for t in tols:
-            if t not in out and rel <= t:
-                out[t] = it
-        if len(out) == len(tols):
-            break
-        z = vcycle(levels, 0, r, nu)
-        rz = (r * z).sum(axis=(0, 1))
-        p = z if p is None else z + (rz / rz_old) * p
-        rz_old = rz
-        q = L.apply(p)
-        al = rz / (p * q).sum(axis=(0, 1))
-        x += al * p
-        r -= al * q
-    return [out.get(t, -1) for t in tols]
+    """iterations to each tolerance, from zero (the statement of the iteration: tests/mgb_ref.py)"""
+    nul = [nu[min(l, len(nu) - 1)] for l in range(len(levels))]
+    hist = mgb_ref.pcg(levels, B, np.zeros_like(B), nul, min(tols), max_it)[1]
+    return [next((it for it, rel in enumerate(hist) if rel <= t), -1) for t in tols]
 
 
 def main():
@@ -187,9 +81,7 @@ def main():
     variants = [[int(t) for t in v.split(",")] for v in arg("--nu", "1;2").split(";")]
     t0 = time.time()
     unk, E, S, tie, B = system(w, h, ex, frame, side)
-    levels = [Level(E, S, tie)]
-    while levels[-1].w * levels[-1].h > 64:
-        levels.append(levels[-1].coarsen())
+    levels = mgb_ref.hierarchy(mgb_ref.Level(E, S, tie))
     print("canvas %dx%d, %d unknowns, %d levels (coarsest %dx%d), set-up %.0f s" % (
         w + 2 * ex, h + 2 * ex, int(unk.sum()), len(levels), levels[-1].w, levels[-1].h, time.time() - t0), flush=True)
     tols = (1e-4, 1e-5, 1e-6)

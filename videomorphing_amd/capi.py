@@ -16,6 +16,7 @@ VM_E_INVALID, VM_E_DEVICE, VM_E_STATE, VM_E_NUMERIC, VM_E_CANCELLED = -1, -2, -3
 BCOND_NONE, BCOND_CORNER, BCOND_BORDER = 0, 1, 2
 MATH_EXACT, MATH_FAST, MATH_EXACT_FMA, MATH_REF_FASTMATH, MATH_REF_TEX8, MATH_REF_TEX8_TRUNC = 0, 1, 2, 3, 4, 5
 REDUCE_ATOMIC, REDUCE_ORDERED = 0, 1          # vm_set_reduction
+DBG_MGB_QPATH = 3                             # vm_dbg_mgb_*: the quadratic path's system (1, 2: the sides of the extension)
 SWEEP_AUTO, SWEEP_TILE, SWEEP_SPLIT, SWEEP_STEP, SWEEP_SPARSE, SWEEP_PASS = 0, 1, 2, 3, 4, 5
 
 FIELDS = {  # name -> (id, channels)
@@ -37,6 +38,7 @@ SYMBOLS = [
     "vm_frame_download_ext", "vm_host_register", "vm_host_unregister", "vm_frame_set_v_from_level", "vm_render_halfway",
     "vm_render_halfway_dev", "vm_poisson_extend", "vm_poisson_extend_frames", "vm_frame_quadratic_path", "vm_frame_download_qpath", "vm_frame_download_v",
     "vm_rccl_bcast", "vm_rccl_comm_init_all", "vm_rccl_comm_destroy", "vm_bcast_params", "vm_bcast_bytes", "vm_dbg_poisson_profile",
+    "vm_dbg_mgb_setup", "vm_dbg_mgb_level", "vm_dbg_mgb_cycle",
     "vm_video_create", "vm_video_destroy", "vm_video_levels", "vm_video_level_dims", "vm_video_upload_luma",
     "vm_video_upload_flows", "vm_video_build_rgb", "vm_video_build_flows", "vm_video_set_v", "vm_video_get_v",
     "vm_video_get_field", "vm_video_coarse_solve", "vm_video_upsample", "vm_video_init_level",
@@ -182,6 +184,9 @@ def load():
         "vm_bcast_params": [C.POINTER(vp), C.POINTER(vp), i, i, C.POINTER(ParamBlock), C.POINTER(ParamBlock)],
         "vm_bcast_bytes": [C.POINTER(vp), C.POINTER(vp), i, i, vp, C.c_uint64, C.POINTER(vp)],
         "vm_dbg_poisson_profile": [vp, i, C.POINTER(C.c_double), C.POINTER(i), C.POINTER(C.c_double), C.POINTER(i)],
+        "vm_dbg_mgb_setup": [vp, i, C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i)],
+        "vm_dbg_mgb_level": [vp, i, i, vp, vp, vp, vp, vp, C.POINTER(i)],
+        "vm_dbg_mgb_cycle": [vp, i, vp, vp, vp],
         "vm_video_create": [vp, i, C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i), i, C.POINTER(vp)],
         "vm_video_levels": [vp],
         "vm_video_level_dims": [vp, i, C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(f)],

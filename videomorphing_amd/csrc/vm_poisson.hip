@@ -380,11 +380,16 @@ void vm_poisson_launch_canvas(uchar4 *ext, uchar4 *crop, const uint8_t *rgb, int
     hipLaunchKernelGGL(k_canvas, grid2(w + 2 * ex, h + 2 * ex), B2, 0, s, ext, crop, rgb, w, h, ex);
 }
 
+void vm_poisson_launch_classify(const uchar4 *ext, uint8_t *type, int cw, int ch, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_classify, grid2(cw, ch), B2, 0, s, ext, type, cw, ch);
+}
+
 void vm_poisson_launch_prepare(uchar4 *ext, uint8_t *type, const uchar4 *other, const float2 *v,
                                int w, int h, int rs, int ex, int sign, hipStream_t s)
 {
     const int cw = w + 2 * ex, ch = h + 2 * ex;
-    hipLaunchKernelGGL(k_classify, grid2(cw, ch), B2, 0, s, ext, type, cw, ch);
+    vm_poisson_launch_classify(ext, type, cw, ch, s);
     hipLaunchKernelGGL(k_fill, grid2(cw, ch), B2, 0, s, ext, type, other, v, w, h, rs, ex, sign);
 }
 

@@ -231,33 +231,44 @@ double mgb_rel_ordered(const char *head, const MgbOrdLayout &Y, int par)
 
 } // namespace
 
-// The batched PCG proper: nsys systems of one size whose workspaces are carved, whose type maps, right-hand sides
-// (lv[0].b) and initial guesses (X) are enqueued on the context's stream.  Leaves every system's solution in its X
-// (the iterate it stopped at; the best one seen near the tolerance if the workspace was carved with room for it), its
-// iteration count and relative residual in iters / rels.
-static int mgb_solve(vm_ctx *c, std::vector<MgbWork> &W, int nsys, float tol, int max_it, int *iters, double *rels)
+// What mgb_setup leaves for the iterations of one batch: where the context keeps the batch's descriptors, scalars and
+// ordered-mode storage, and the block / tile counts per level (the largest among the systems)
+struct MgbBatch {
+    VmMgbSys *dev = nullptr;
+    VmMgbScalars *sc_dev = nullptr;
+    char *ord_dev = nullptr;
+    bool ord = false, fused = false;
+    int nlev = 0;
+    MgbOrdLayout Y{1, 1};
+    std::vector<char> ord_head;        // the systems' descriptors going up, then their read-back heads
+    std::vector<int> cnt, nb, nt;      // cnt: every system's counts as mgb_carve lays them out (nblocks, then ntiles per level)
+};
+
+// The set-up of a batch: nsys systems of one size whose workspaces are carved and whose type maps are enqueued on the
+// context's stream.  Descriptors up, scalars and ordered-mode storage cleared, the hierarchy (level 0, coarsening) and its
+// block / tile lists built, their counts read back.
+static int mgb_setup(vm_ctx *c, std::vector<MgbWork> &W, int nsys, MgbBatch &B)
 {
     hipStream_t s = c->stream;
-    const size_t N0 = (size_t)W[0].S.lv[0].w * W[0].S.lv[0].h;
     if (int rc = c->mgb_sys.reserve(VM_MGB_MAXSYS)) return rc;
     // the systems' PCG scalars and block / tile counts live side by side in one buffer of the context (the descriptors
     // handed to the kernels point there): one clear per solve, one read-back per residual check for the whole batch
     // instead of one per system
     const size_t cnt_bytes = (size_t)VM_MGB_MAXSYS * 2 * VM_MGB_MAXLEV * sizeof(int);
     if (int rc = c->mgb_shared.reserve(VM_MGB_MAXSYS * sizeof(VmMgbScalars) + cnt_bytes)) return rc;
-    VmMgbScalars *sc_dev = (VmMgbScalars *)c->mgb_shared.get();
+    VmMgbScalars *sc_dev = B.sc_dev = (VmMgbScalars *)c->mgb_shared.get();
     int *cnt_dev = (int *)(c->mgb_shared.get() + VM_MGB_MAXSYS * sizeof(VmMgbScalars));
-    VmMgbSys *dev = c->mgb_sys.get();
+    VmMgbSys *dev = B.dev = c->mgb_sys.get();
     std::vector<VmMgbSys> hs(nsys);
-    const int nlev = W[0].S.nlev;
+    const int nlev = B.nlev = W[0].S.nlev;
     // VM_REDUCE_ORDERED: every system's partials, tickets and group sums, from the context like the scalars; the descriptors,
     // group counts and tickets are cleared once per solve (a launch leaves its tickets at zero again)
-    const bool ord = c->reduction == VM_REDUCE_ORDERED;
-    const MgbOrdLayout Y(W[0].S.lv[0].gx, W[0].S.lv[0].gy);
+    const bool ord = B.ord = c->reduction == VM_REDUCE_ORDERED;
+    const MgbOrdLayout Y = B.Y = MgbOrdLayout(W[0].S.lv[0].gx, W[0].S.lv[0].gy);
     char *ord_dev = nullptr;
     if (ord) {
         if (int rc = c->mgb_ord.reserve((size_t)nsys * Y.bytes)) return rc;
-        ord_dev = c->mgb_ord.get();
+        ord_dev = B.ord_dev = c->mgb_ord.get();
     }
     // The PCG update rides in the level-0 restriction wherever the hierarchy allows it.  Measured on the 2304 x 1464 canvas
     // (tools/exp/fuse_ab.sh, ms per frame at 1e-5, fused against the separate k_mgb_update): 8 systems per batch 1.61 / 1.70,
@@ -265,7 +276,7 @@ static int mgb_solve(vm_ctx *c, std::vector<MgbWork> &W, int nsys, float tol, in
     // by cell it lost on one and two systems, 2.56 / 2.49: vm_mgb.hip).  Same arithmetic either way.
     // VM_MGB_FUSE_MIN_SYS (dev switch): the smallest batch that fuses (0: never).
     static const int fuse_min = [] { const char *e = getenv("VM_MGB_FUSE_MIN_SYS"); return e ? atoi(e) : 1; }();
-    const bool fused = W[0].fused && fuse_min > 0 && nsys >= fuse_min;
+    const bool fused = B.fused = W[0].fused && fuse_min > 0 && nsys >= fuse_min;
     for (int i = 0; i < nsys; ++i) {
         W[i].S.R[1] = fused ? W[i].r1 : W[i].S.R[0];
         hs[i] = W[i].S;
@@ -278,7 +289,7 @@ static int mgb_solve(vm_ctx *c, std::vector<MgbWork> &W, int nsys, float tol, in
     }
     VM_HIP(hipMemcpyAsync(dev, hs.data(), nsys * sizeof(VmMgbSys), hipMemcpyHostToDevice, s));
     VM_HIP(hipMemsetAsync(sc_dev, 0, nsys * sizeof(VmMgbScalars), s));
-    std::vector<char> ord_head;        // the systems' descriptors going up, then their read-back heads
+    std::vector<char> &ord_head = B.ord_head;
     if (ord) {
         ord_head.assign((size_t)nsys * Y.head, 0);
         for (int i = 0; i < nsys; ++i) {
@@ -297,7 +308,10 @@ static int mgb_solve(vm_ctx *c, std::vector<MgbWork> &W, int nsys, float tol, in
         vm_mgb_launch_coarsen(dev, nsys, l, W[0].S.lv[l].gx, W[0].S.lv[l].gy, s);
     vm_mgb_launch_compact(dev, nsys, nlev, s);
     VM_HIP(hipGetLastError());
-    std::vector<int> cnt((size_t)nsys * 2 * VM_MGB_MAXLEV), nb(nlev, 0), nt(nlev, 0);
+    std::vector<int> &cnt = B.cnt, &nb = B.nb, &nt = B.nt;
+    cnt.assign((size_t)nsys * 2 * VM_MGB_MAXLEV, 0);
+    nb.assign(nlev, 0);
+    nt.assign(nlev, 0);
     VM_HIP(hipMemcpyAsync(cnt.data(), cnt_dev, (size_t)nsys * 2 * VM_MGB_MAXLEV * sizeof(int), hipMemcpyDeviceToHost, s));
     VM_HIP(hipStreamSynchronize(s));
     for (int i = 0; i < nsys; ++i)
@@ -305,6 +319,26 @@ static int mgb_solve(vm_ctx *c, std::vector<MgbWork> &W, int nsys, float tol, in
             nb[l] = std::max(nb[l], cnt[(size_t)i * 2 * VM_MGB_MAXLEV + l]);
             nt[l] = std::max(nt[l], cnt[(size_t)i * 2 * VM_MGB_MAXLEV + VM_MGB_MAXLEV + l]);
         }
+    return VM_OK;
+}
+
+// The batched PCG proper: nsys systems of one size whose workspaces are carved, whose type maps, right-hand sides
+// (lv[0].b) and initial guesses (X) are enqueued on the context's stream.  Leaves every system's solution in its X
+// (the iterate it stopped at; the best one seen near the tolerance if the workspace was carved with room for it), its
+// iteration count and relative residual in iters / rels.
+static int mgb_solve(vm_ctx *c, std::vector<MgbWork> &W, int nsys, float tol, int max_it, int *iters, double *rels)
+{
+    hipStream_t s = c->stream;
+    const size_t N0 = (size_t)W[0].S.lv[0].w * W[0].S.lv[0].h;
+    MgbBatch B;
+    if (int rc = mgb_setup(c, W, nsys, B)) return rc;
+    VmMgbSys *const dev = B.dev;
+    VmMgbScalars *const sc_dev = B.sc_dev;
+    char *const ord_dev = B.ord_dev;
+    const bool ord = B.ord, fused = B.fused;
+    const MgbOrdLayout &Y = B.Y;
+    std::vector<char> &ord_head = B.ord_head;
+    const std::vector<int> &nb = B.nb, &nt = B.nt;
     if (nb[0] == 0) {                       // no unknown anywhere: nothing to extend
         for (int i = 0; i < nsys; ++i) { iters[i] = 0; rels[i] = 0; }
         return VM_OK;
@@ -435,6 +469,34 @@ extern "C" int vm_dbg_poisson_profile(vm_ctx *c, int on, double *update_us, int 
     return VM_OK;
 }
 
+// One system's workspace and type map, enqueued: `which` = side 1 or 2 of the frame's Poisson extension (the canvas classified;
+// fill: and its outside pixels filled from the other image, vm_poisson_launch_prepare -- what a solve needs for its right-hand
+// side) or VM_DBG_MGB_QPATH, the quadratic path's whole-grid system (every pixel an unknown without a tie: type 2 everywhere,
+// so the level-0 operator is the graph Laplacian of the pixel grid with Neumann ends, QuadraticPath.cpp:137-170; the workspace
+// is side 1's of the Poisson extension: the frame is no larger than its canvas, the two run in turn)
+static int mgb_system(vm_frame *f, int which, MgbWork &W, bool fill)
+{
+    hipStream_t s = f->ctx->stream;
+    if (which == VM_DBG_MGB_QPATH) {
+        int rc = f->pws2[0].reserve(std::max(mgb_bytes(std::max(f->w, f->cw), std::max(f->h, f->ch)), mgb_bytes(f->w, f->h, true)));
+        if (rc != VM_OK) return rc;
+        mgb_carve(W, f->w, f->h, f->pws2[0].get(), true);
+        VM_HIP(hipMemsetAsync(W.type, 2, (size_t)f->w * f->h, s));
+        return VM_OK;
+    }
+    const int side = which;
+    if (int rc = f->pws2[side - 1].reserve(mgb_bytes(f->cw, f->ch))) return rc;
+    mgb_carve(W, f->cw, f->ch, f->pws2[side - 1].get());
+    uchar4 *ext = f->ext[side - 1].get();
+    if (fill) {
+        const uchar4 *other = f->crop[side == 1 ? 1 : 0].get(); // PoissonExt.cpp:54-57
+        vm_poisson_launch_prepare(ext, W.type, other, f->v.get(), f->w, f->h, f->rs, f->ex, side == 1 ? 1 : -1, s);
+    } else {
+        vm_poisson_launch_classify(ext, W.type, f->cw, f->ch, s);
+    }
+    return VM_OK;
+}
+
 // Poisson extension of nsys systems (frames[i], sides[i]) of one context and one canvas size as ONE batch
 static int poisson_solve_batch(vm_ctx *c, vm_frame *const *frames, const int *sides, int nsys, float tol, int max_it,
                                int *iters, double *rels)
@@ -446,12 +508,8 @@ static int poisson_solve_batch(vm_ctx *c, vm_frame *const *frames, const int *si
     for (int i = 0; i < nsys; ++i) {
         vm_frame *f = frames[i];
         const int side = sides[i];
-        if (int rc = f->pws2[side - 1].reserve(mgb_bytes(cw, ch))) return rc;
-        mgb_carve(W[i], cw, ch, f->pws2[side - 1].get());
-        uchar4 *ext = f->ext[side - 1].get();
-        const uchar4 *other = f->crop[side == 1 ? 1 : 0].get(); // PoissonExt.cpp:54-57
-        vm_poisson_launch_prepare(ext, W[i].type, other, f->v.get(), f->w, f->h, f->rs, f->ex, side == 1 ? 1 : -1, s);
-        vm_poisson_launch_setup3(ext, W[i].type, W[i].S.lv[0].b, W[i].S.X, cw, ch, s);
+        if (int rc = mgb_system(f, side, W[i], true)) return rc;
+        vm_poisson_launch_setup3(f->ext[side - 1].get(), W[i].type, W[i].S.lv[0].b, W[i].S.X, cw, ch, s);
     }
     int rc = mgb_solve(c, W, nsys, tol, max_it, iters, rels);
     if (rc != VM_OK) return rc;
@@ -531,6 +589,129 @@ extern "C" int vm_poisson_extend_frames(vm_frame *const *frames, int n, float to
     return VM_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Read-only views of the preconditioner for the tests (include/vmorph.h: vm_dbg_mgb_*): the production set-up (mgb_system,
+// mgb_setup) and the production cycle (mgb_iter_head / mgb_iter_rest) on the production workspace, and downloads.
+
+namespace {
+
+// the hierarchy of system `which` of the frame, built as a solve of ONE system would build it -- but from the canvas as it
+// stands: classified, not filled
+int mgb_dbg_build(vm_frame *f, int which, const char *fn, std::vector<MgbWork> &W, MgbBatch &B)
+{
+    if (which != 1 && which != 2 && which != VM_DBG_MGB_QPATH)
+        return vm_fail(VM_E_INVALID, "%s: which must be 1, 2 or VM_DBG_MGB_QPATH", fn);
+    if (which == VM_DBG_MGB_QPATH && (f->w < 2 || f->h < 2))
+        return vm_fail(VM_E_INVALID, "%s: the quadratic path needs a frame of at least 2x2 pixels", fn);
+    W.resize(1);
+    if (int rc = mgb_system(f, which, W[0], false)) return rc;
+    return mgb_setup(f->ctx, W, 1, B);
+}
+
+int mgb_dbg_download(void *host, const void *dev, size_t bytes, hipStream_t s)
+{
+    if (host) VM_HIP(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, s));
+    return VM_OK;
+}
+
+} // namespace
+
+extern "C" int vm_dbg_mgb_setup(vm_frame *f, int which, int *nlev, int *tail, int *w, int *h, int *nu, int *nblocks, int *ntiles)
+{
+    VM_ENTER_LOCKED(f);
+    std::vector<MgbWork> W;
+    MgbBatch B;
+    if (int rc = mgb_dbg_build(f, which, __func__, W, B)) return rc;
+    if (nlev) *nlev = B.nlev;
+    if (tail) *tail = W[0].tail;
+    for (int l = 0; l < B.nlev; ++l) {
+        if (w) w[l] = W[0].S.lv[l].w;
+        if (h) h[l] = W[0].S.lv[l].h;
+        if (nu) nu[l] = W[0].S.lv[l].nu;
+        if (nblocks) nblocks[l] = B.cnt[l];
+        if (ntiles) ntiles[l] = B.cnt[VM_MGB_MAXLEV + l];
+    }
+    return VM_OK;
+}
+
+extern "C" int vm_dbg_mgb_level(vm_frame *f, int which, int l, float *dg, float *we, float *ws, float *b, float *x, int *have)
+{
+    VM_ENTER_LOCKED(f);
+    if (which != 1 && which != 2 && which != VM_DBG_MGB_QPATH)
+        return vm_fail(VM_E_INVALID, "vm_dbg_mgb_level: which must be 1, 2 or VM_DBG_MGB_QPATH");
+    const bool qpath = which == VM_DBG_MGB_QPATH;
+    const int gw = qpath ? f->w : f->cw, gh = qpath ? f->h : f->ch;
+    VmDev<char> &ws_buf = f->pws2[qpath ? 0 : which - 1];
+    if (!ws_buf.get() || ws_buf.capacity() < mgb_bytes(gw, gh, qpath))
+        return vm_fail(VM_E_STATE, "vm_dbg_mgb_level: no hierarchy in the frame (vm_dbg_mgb_setup or vm_dbg_mgb_cycle first)");
+    MgbWork W;
+    mgb_carve(W, gw, gh, ws_buf.get(), qpath);       // where the set-up put things: pointers only, nothing is launched
+    if (l < 0 || l >= W.S.nlev)
+        return vm_fail(VM_E_INVALID, "vm_dbg_mgb_level: level %d of %d", l, W.S.nlev);
+    hipStream_t s = f->ctx->stream;
+    const VmMgbLevel &L = W.S.lv[l];
+    const size_t N = (size_t)L.w * L.h;
+    std::vector<uint8_t> info;
+    if (l == 0) {
+        info.resize(N);
+        if (int rc = mgb_dbg_download(info.data(), L.info, N, s)) return rc;
+    } else {
+        if (int rc = mgb_dbg_download(dg, L.dg, N * 4, s)) return rc;
+        if (int rc = mgb_dbg_download(we, L.we, N * 4, s)) return rc;
+        if (int rc = mgb_dbg_download(ws, L.ws, N * 4, s)) return rc;
+    }
+    // a level's right-hand side and result stand in memory down to the first level of the tail (the tail keeps the rest in LDS)
+    const bool in_memory = l <= W.tail;
+    if (in_memory) {
+        if (int rc = mgb_dbg_download(b, L.b, N * sizeof(VmV3), s)) return rc;
+        if (int rc = mgb_dbg_download(x, L.x, N * sizeof(VmV3), s)) return rc;
+    }
+    VM_HIP(hipStreamSynchronize(s));
+    if (l == 0)                                      // the info byte, decoded (vm_mgb.h)
+        for (size_t i = 0; i < N; ++i) {
+            if (dg) dg[i] = (float)(info[i] >> 4);
+            if (we) we[i] = (float)(info[i] & 1u);
+            if (ws) ws[i] = (float)((info[i] >> 2) & 1u);
+        }
+    if (have) *have = in_memory ? 3 : 0;
+    return VM_OK;
+}
+
+extern "C" int vm_dbg_mgb_cycle(vm_frame *f, int which, const float *r_in, float *z_out, float *q_out)
+{
+    if (!r_in) return vm_fail(VM_E_INVALID, "vm_dbg_mgb_cycle: r_in is NULL");
+    VM_ENTER_LOCKED(f);
+    vm_ctx *c = f->ctx;
+    hipStream_t s = c->stream;
+    std::vector<MgbWork> W;
+    MgbBatch B;
+    if (int rc = mgb_dbg_build(f, which, __func__, W, B)) return rc;
+    const VmMgbLevel &L = W[0].S.lv[0];
+    const size_t N0 = (size_t)L.w * L.h;
+    if (B.nb[0] == 0) {                              // no unknown: M^-1 of nothing
+        if (z_out) memset(z_out, 0, N0 * sizeof(VmV3));
+        if (q_out) memset(q_out, 0, N0 * sizeof(VmV3));
+        return VM_OK;
+    }
+    VM_HIP(hipMemcpyAsync(L.b, r_in, N0 * sizeof(VmV3), hipMemcpyHostToDevice, s));      // the residual of iteration 0: R[0]
+    mgb_iter_head(B.dev, 1, B.fused, B.nb, B.nt, 0, 1ull, B.ord, s);
+    mgb_iter_rest(B.dev, 1, W[0], B.fused, B.nb, B.nt, 0, 1ull, B.ord, s);
+    VM_HIP(hipGetLastError());
+    std::vector<uint8_t> info(N0);
+    if (int rc = mgb_dbg_download(info.data(), L.info, N0, s)) return rc;
+    if (int rc = mgb_dbg_download(z_out, L.x, N0 * sizeof(VmV3), s)) return rc;
+    if (int rc = mgb_dbg_download(q_out, W[0].S.Q, N0 * sizeof(VmV3), s)) return rc;
+    VM_HIP(hipStreamSynchronize(s));
+    // cells without an unknown outside every swept tile / block are memory nobody wrote: zeros in what is handed out
+    for (size_t i = 0; i < N0; ++i)
+        if ((info[i] >> 4) == 0)
+            for (int ch = 0; ch < 3; ++ch) {
+                if (z_out) z_out[3 * i + ch] = 0;
+                if (q_out) q_out[3 * i + ch] = 0;
+            }
+    return VM_OK;
+}
+
 // CQuadraticPath::optimize for the frame's halfway field (QuadraticPath.cpp:24-223): u goes
 // to the frame's quadratic-path buffer, where vm_render_halfway reads it
 extern "C" int vm_frame_quadratic_path(vm_frame *f, float tol, int max_it, int *iters, float *rel_res,
@@ -547,14 +728,10 @@ extern "C" int vm_frame_quadratic_path(vm_frame *f, float tol, int max_it, int *
     double rel = 0;
     VM_HIP(hipEventRecord(c->ev0.get(), s));
     {
-        // the batched solver on the whole grid: every pixel an unknown without a tie (type 2 everywhere), so the level-0
-        // operator is the graph Laplacian of the pixel grid with Neumann ends (QuadraticPath.cpp:137-170); the
-        // workspace is side 1's of the Poisson extension (the frame is no larger than its canvas, the two run in turn)
-        int rc = f->pws2[0].reserve(std::max(mgb_bytes(std::max(f->w, f->cw), std::max(f->h, f->ch)), mgb_bytes(f->w, f->h, true)));
-        if (rc != VM_OK) return rc;
+        // the batched solver on the whole grid (mgb_system)
         std::vector<MgbWork> W(1);
-        mgb_carve(W[0], f->w, f->h, f->pws2[0].get(), true);
-        VM_HIP(hipMemsetAsync(W[0].type, 2, (size_t)f->w * f->h, s));
+        int rc = mgb_system(f, VM_DBG_MGB_QPATH, W[0], false);
+        if (rc != VM_OK) return rc;
         vm_qpath_launch_rhs3(f->v.get(), f->rs, f->w, f->h, W[0].S.lv[0].b, W[0].S.X, s);
         // project the right-hand side onto the range of the singular operator
         double *sums = &W[0].S.sc->bb[0][0];
