@@ -369,6 +369,40 @@ int  vm_video_solve(vm_video *v, float max_iter, float max_iter_drop_factor,
                     const vm_video_constraint *c, int n, volatile const int *run_flag,
                     int fixed_work, vm_progress *per_page);
 
+/* ---- error view: where the match is poor, and how good the solve is -------- */
+/* The reference's UI has an "Error Image" entry next to "Halfway Image" whose slot only sets a flag
+ * (UI/MdiEditor.cpp:1928-1933): the image is never computed.  Here it is.  Per pixel of a level (or of one page of a
+ * video level) the terms of the energy the sweep minimises, morph.cu:730-761 -- float32 planes, DESIGN.md 3.8:
+ *   e_ssim = (w_ssim * (1 - value)) * inv_wh
+ *   e_tps  =  w_tps * (0.5 * (v.x * tps_b.x + v.y * tps_b.y))
+ *   e_ui   =  ui_axy > 0 ? (w_ui * ((ui_b.x^2 + ui_b.y^2) / (4 * ui_axy))) * inv_wh : 0
+ *   e_temp =  flag ? (((w_temp * (|v.x - ref.x| + |v.y - ref.y|)) * temp_mask) * factor_d) * inv_wh : 0
+ *   e_all  = ((e_ssim + e_tps) + e_ui) + e_temp
+ * from the arrays vm_level_get_field returns at that moment and the context's vm_kern_params; flag is what the sweep
+ * of that page runs with (false for a vm_pyr and for the page a video level solves first).  The same bits in every
+ * math mode.  `what` picks a plane; the totals are the five sums in that order, doubles folded in one fixed order
+ * that the level's geometry decides: the same bits from run to run, on any context, alone or in a batch.
+ * VM_E_STATE when the level holds no initialised state (the coarsest level; before vm_init_level; after
+ * vm_level_clear), VM_E_INVALID for a bad what / level / page / size or a NULL output.  The level is not changed. */
+enum { VM_ERR_SSIM = 0, VM_ERR_TPS, VM_ERR_UI, VM_ERR_TEMP, VM_ERR_ALL };
+/* the five totals of one level (UI/MdiEditor.cpp:1928-1933; morph.cu:730-761) */
+int  vm_level_energy(vm_pyr *pyr, int lvl, double *out5);
+/* the same for level `lvl` of n pyramids of one context and one geometry in ONE launch (UI/MdiEditor.cpp:1928-1933;
+ * morph.cu:730-761); out5n: n x 5, pair-major; each pair's bits are those of its own vm_level_energy */
+int  vm_level_energy_batch(vm_pyr **pyrs, int n, int lvl, double *out5n);
+/* one plane to the host, h rows of w floats, pitch in floats, 0 = tight (UI/MdiEditor.cpp:1928-1933; morph.cu:730-761) */
+int  vm_level_error_map(vm_pyr *pyr, int lvl, int what, float *plane, int pitch);
+/* the view itself (UI/MdiEditor.cpp:1928-1933; morph.cu:730-761): plane `what` sampled to w0 x h0 with the sampling of
+ * vm_upscale_result (MatchingThread.cpp:103-136; the plane is not rescaled by the size ratio), t = clamp(s * gain, 0, 1),
+ * heat ramp r = min(3t, 1), g = clamp(3t - 1, 0, 1), b = clamp(3t - 2, 0, 1), each byte (uint8)(c * 255 + 0.5);
+ * rgb: h0 rows of w0 RGB8 pixels, pitch in bytes (0 = tight), bytes beyond a row's 3 w0 are not written */
+int  vm_level_error_image(vm_pyr *pyr, int lvl, int what, float gain, int w0, int h0, uint8_t *rgb, int pitch_bytes);
+/* the same three for one page of a video level (UI/MdiEditor.cpp:1928-1933; morph.cu:730-761, the temporal term :752-759) */
+int  vm_video_energy(vm_video *v, int lvl, int page, double *out5);
+int  vm_video_error_map(vm_video *v, int lvl, int page, int what, float *plane, int pitch);
+int  vm_video_error_image(vm_video *v, int lvl, int page, int what, float gain, int w0, int h0, uint8_t *rgb,
+                          int pitch_bytes);
+
 /* ---- compositor ---------------------------------------------------------- */
 typedef struct vm_frame vm_frame;
 /* device-resident inputs of one output frame: the two Poisson-extended RGBA8

@@ -52,9 +52,10 @@ public:
                 int rc = vm_optimize_level(p, el - 1, _max_iter, &m_cb, fixed_work_ ? 1 : 0, &pr);
                 if (rc != VM_E_CANCELLED) check(rc);
                 progress[el] = pr;
+                energies[el] = m_pyramid[el].energy();
                 // morph.cu:1389-1391: a finished level is accounted as max_iter sweeps
                 _current_iter += (float)m_pyramid[el].width * m_pyramid[el].height * _max_iter;
-                check(vm_level_clear(p, el - 1));
+                if (!keep_state) check(vm_level_clear(p, el - 1));
                 _max_iter /= m_params.max_iter_drop_factor;
             }
         }
@@ -64,6 +65,10 @@ public:
     int _total_l, _current_l;
     float _total_iter, _current_iter, _max_iter;
     std::map<int, vm_progress> progress; // per level: what actually ran
+    std::map<int, std::array<double, 5>> energies; // per level, as it finishes: PyramidLevel::energy()
+    // true: skip the reference's clear_level (morph.cu:162), so that the error view of every level can still be read
+    // after the solve
+    bool keep_state = false;
 
 private:
     volatile int &m_cb;
@@ -92,6 +97,8 @@ public:
     }
 
     float percentage = 0.0f;
+    // per level the solve has finished: the five energy totals (Morph::energies)
+    const std::map<int, std::array<double, 5>> &energies() const { return gpu_morph.energies; }
 
 private:
     void solve() override { gpu_morph.calculate_halfway_parametrization(); } // MatchingThread.cpp:138-150

@@ -6,6 +6,7 @@
 #ifndef VMORPH_PYRAMID_HPP
 #define VMORPH_PYRAMID_HPP
 
+#include <array>
 #include <memory>
 #include <vector>
 
@@ -68,6 +69,12 @@ struct PyramidLevel {
     void set_v(const std::vector<float> &v);
     // any state array (VM_F_*), tight rows
     std::vector<float> field(int id) const;
+    // the error view (the reference only has the menu entry, UI/MdiEditor.cpp:1928-1933): the five energy totals
+    // (VM_ERR_SSIM .. VM_ERR_ALL), one plane of per-pixel terms (h * w floats) and its heat-ramp image at w0 x h0
+    // (h0 * w0 * 3 bytes); they throw while the level holds no initialised state
+    std::array<double, 5> energy() const;
+    std::vector<float> error_map(int what = VM_ERR_SSIM) const;
+    std::vector<unsigned char> error_image(int w0, int h0, int what = VM_ERR_SSIM, float gain = 1.0f) const;
 
 private:
     Pyramid *pyr_;
@@ -156,6 +163,24 @@ inline std::vector<float> PyramidLevel::get_v() const
 inline void PyramidLevel::set_v(const std::vector<float> &v)
 {
     check(vm_level_set_v(pyr_->handle(), el_ - 1, v.data(), 0));
+}
+inline std::array<double, 5> PyramidLevel::energy() const
+{
+    std::array<double, 5> e{};
+    check(vm_level_energy(pyr_->handle(), el_ - 1, e.data()));
+    return e;
+}
+inline std::vector<float> PyramidLevel::error_map(int what) const
+{
+    std::vector<float> out((size_t)width * height);
+    check(vm_level_error_map(pyr_->handle(), el_ - 1, what, out.data(), 0));
+    return out;
+}
+inline std::vector<unsigned char> PyramidLevel::error_image(int w0, int h0, int what, float gain) const
+{
+    std::vector<unsigned char> out((size_t)w0 * h0 * 3);
+    check(vm_level_error_image(pyr_->handle(), el_ - 1, what, gain, w0, h0, out.data(), 0));
+    return out;
 }
 inline std::vector<float> PyramidLevel::field(int id) const
 {

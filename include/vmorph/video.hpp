@@ -94,6 +94,26 @@ public:
         return v;
     }
 
+    // the error view of one page (as PyramidLevel's): energy totals, one plane, its heat-ramp image
+    std::array<double, 5> energy(int lvl, int page) const
+    {
+        std::array<double, 5> e{};
+        check(vm_video_energy(h_, lvl, page, e.data()));
+        return e;
+    }
+    std::vector<float> error_map(int lvl, int page, int what = VM_ERR_SSIM) const
+    {
+        std::vector<float> out((size_t)levels[lvl].width * levels[lvl].height);
+        check(vm_video_error_map(h_, lvl, page, what, out.data(), 0));
+        return out;
+    }
+    std::vector<unsigned char> error_image(int lvl, int page, int w0, int h0, int what = VM_ERR_SSIM, float gain = 1.0f) const
+    {
+        std::vector<unsigned char> out((size_t)w0 * h0 * 3);
+        check(vm_video_error_image(h_, lvl, page, what, gain, w0, h0, out.data(), 0));
+        return out;
+    }
+
     vm_video *handle() const { return h_; }
     Context &context() const { return ctx_; }
     int depth0() const { return depth0_; }

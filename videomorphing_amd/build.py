@@ -59,6 +59,8 @@ UNITS = [
     ("vm_flow.cpp", "vm_flow.o", ["-x", "hip"]),
     ("vm_track.hip", "vm_track_kernels.o", ["-ffp-contract=off"]),
     ("vm_track.cpp", "vm_track.o", ["-x", "hip"]),
+    ("vm_error.hip", "vm_error_kernels.o", ["-ffp-contract=off"]),
+    ("vm_error.cpp", "vm_error.o", ["-x", "hip"]),
     ("vm_sync.cpp", "vm_sync.o", ["-x", "hip"]),
     ("vm_video.cpp", "vm_video.o", ["-x", "hip"]),
     ("vm_pyramid_api.cpp", "vm_pyramid_api.o", ["-x", "hip"]),

@@ -18,6 +18,8 @@ MATH_EXACT, MATH_FAST, MATH_EXACT_FMA, MATH_REF_FASTMATH, MATH_REF_TEX8, MATH_RE
 REDUCE_ATOMIC, REDUCE_ORDERED = 0, 1          # vm_set_reduction
 DBG_MGB_QPATH = 3                             # vm_dbg_mgb_*: the quadratic path's system (1, 2: the sides of the extension)
 SWEEP_AUTO, SWEEP_TILE, SWEEP_SPLIT, SWEEP_STEP, SWEEP_SPARSE, SWEEP_PASS = 0, 1, 2, 3, 4, 5
+ERR_SSIM, ERR_TPS, ERR_UI, ERR_TEMP, ERR_ALL = 0, 1, 2, 3, 4   # planes / totals of the error view (vm_level_energy, ...)
+ERR_NAMES = ("ssim", "tps", "ui", "temp", "all")
 
 FIELDS = {  # name -> (id, channels)
     "img0": (0, 1), "img1": (1, 1), "v": (2, 2), "luma": (3, 2), "mean": (4, 2), "var": (5, 2),
@@ -49,6 +51,8 @@ SYMBOLS = [
     "vm_flow_params_default", "vm_optical_flow_rgb", "vm_optical_flow_luma", "vm_video_build_flows_rgb", "vm_sync_compute_flows",
     "vm_track_create", "vm_track_destroy", "vm_track_upload_frame", "vm_track_upload_flows", "vm_track_compute_flows",
     "vm_track_get_flows", "vm_track_propagate", "vm_video_build_flows_track",
+    "vm_level_energy", "vm_level_energy_batch", "vm_level_error_map", "vm_level_error_image",
+    "vm_video_energy", "vm_video_error_map", "vm_video_error_image",
 ]
 
 
@@ -231,6 +235,13 @@ def load():
         "vm_track_get_flows": [vp, i, i, vp, vp],
         "vm_track_propagate": [vp, vp, i, vp],
         "vm_video_build_flows_track": [vp, vp],
+        "vm_level_energy": [vp, i, C.POINTER(C.c_double)],
+        "vm_level_energy_batch": [C.POINTER(vp), i, i, C.POINTER(C.c_double)],
+        "vm_level_error_map": [vp, i, i, vp, i],
+        "vm_level_error_image": [vp, i, i, f, i, i, vp, i],
+        "vm_video_energy": [vp, i, i, C.POINTER(C.c_double)],
+        "vm_video_error_map": [vp, i, i, i, vp, i],
+        "vm_video_error_image": [vp, i, i, i, f, i, i, vp, i],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

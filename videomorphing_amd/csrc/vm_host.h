@@ -134,6 +134,12 @@ struct vm_ctx {
     // shift reduce (vm_mgb.h); mgb_ord: the ordered mode's partials, tickets and group sums of the current batch
     int reduction = 0;
     VmDev<char> mgb_ord;
+    // the error view (vm_error.cpp): jobs, workgroup partials and totals of the current call; arrival counters (zero between
+    // calls); the plane or image on its way to the host; pinned staging of the jobs (in) and the totals (out)
+    VmDev<char> err_ws;
+    VmDev<unsigned> err_tickets;
+    VmDev<char> err_out;
+    VmPinned<char> err_host;
     bool mgb_prof = false;
     double mgb_prof_us = 0, mgb_prof_unknown_launches = 0;
     int mgb_prof_launches = 0, mgb_prof_fused = 0;

@@ -20,6 +20,7 @@ import numpy as np
 
 from . import capi
 from .capi import BCOND_NONE, BCOND_CORNER, BCOND_BORDER, MATH_EXACT, MATH_FAST, REDUCE_ATOMIC, REDUCE_ORDERED  # noqa: F401
+from .capi import ERR_SSIM, ERR_TPS, ERR_UI, ERR_TEMP, ERR_ALL  # noqa: F401
 from . import synth
 
 
@@ -168,7 +169,34 @@ def _cons_array(cons):
     return arr, n
 
 
-class PyramidLevel(object):
+class _ErrorView(object):
+    """The error view of a level or a video page (the reference only has the menu entry,
+    UI/MdiEditor.cpp:1928-1933): _err(name) returns the C-ABI entry vm_{level,video}_<name> and the arguments that
+    address this level / page.  VmError(VM_E_STATE) while the level holds no initialised state."""
+
+    def energy(self):
+        """the five totals {"ssim", "tps", "ui", "temp", "all"} (float64, the same bits from run to run)"""
+        fn, at = self._err("energy")
+        out = (C.c_double * 5)()
+        capi.check(fn(*at, out))
+        return dict(zip(capi.ERR_NAMES, [float(x) for x in out]))
+
+    def error_map(self, what=ERR_SSIM):
+        """plane `what` (ERR_*) of the per-pixel energy terms, (h, w) float32"""
+        fn, at = self._err("error_map")
+        out = np.zeros((self.height, self.width), dtype=np.float32)
+        capi.check(fn(*at, int(what), out.ctypes.data, 0))
+        return out
+
+    def error_image(self, w0, h0, what=ERR_SSIM, gain=1.0):
+        """the heat-ramp image of plane `what` times `gain`, resized to w0 x h0: (h0, w0, 3) uint8"""
+        fn, at = self._err("error_image")
+        out = np.zeros((int(h0), int(w0), 3), dtype=np.uint8)
+        capi.check(fn(*at, int(what), float(gain), int(w0), int(h0), out.ctypes.data, 0))
+        return out
+
+
+class PyramidLevel(_ErrorView):
     """struct PyramidLevel, Pyramid.h:52-98 (geometry + device-state access)."""
 
     def __init__(self, pyr, el, w, h):
@@ -211,6 +239,9 @@ class PyramidLevel(object):
             out = np.zeros((self.height, self.width), dtype=np.float32)
         capi.check(L.vm_level_get_field(self._pyr._h, self._lvl(), fid, out.ctypes.data))
         return out
+
+    def _err(self, name):
+        return getattr(self._pyr._L, "vm_level_" + name), (self._pyr._h, self._lvl())
 
     def set_impmask(self, words):
         """test hook: overwrite the improving mask (the array field("impmask") returns), vm_dbg_level_set_mask"""
@@ -328,11 +359,15 @@ Pyramid.build_rgb = _pyramid_build_rgb
 class Morph(object):
     """class Morph, morph.h:10-31."""
 
-    def __init__(self, params, pyramid, run_flag=None, fixed_work=False):
+    def __init__(self, params, pyramid, run_flag=None, fixed_work=False, keep_state=False):
         self.m_params, self.m_pyramid = params, pyramid
         # bool& run_flag of the reference: a shared int the caller may clear
         self.m_cb = run_flag if run_flag is not None else C.c_int(1)
         self.fixed_work = bool(fixed_work)
+        # keep_state: skip the reference's clear_level (morph.cu:162) so that the error view of every level
+        # (PyramidLevel.energy / error_map / error_image) can still be read after the solve
+        self.keep_state = bool(keep_state)
+        self.energies = {}   # level -> the five totals (PyramidLevel.energy()), filled as each level finishes
         # ctor, morph.cu:122-141
         self._total_l = pyramid.size() - 1
         self._current_l = self._total_l
@@ -378,7 +413,9 @@ class Morph(object):
                                          candidates=pr.candidates, commits=pr.commits,
                                          evaluations=pr.evaluations,
                                          width=lv.width, height=lv.height)
-                capi.check(L.vm_level_clear(pyr._h, el - 1))
+                self.energies[el] = lv.energy()
+                if not self.keep_state:
+                    capi.check(L.vm_level_clear(pyr._h, el - 1))
                 self._max_iter /= P.max_iter_drop_factor
             self._current_l -= 1
         return True
@@ -464,10 +501,15 @@ class _SolverThread(object):
 class MatchingThread(_SolverThread):
     """class CMatchingThread, MatchingThread.h:7-37, on threading.Thread."""
 
-    def __init__(self, parameters, pyramids, fixed_work=False):
+    def __init__(self, parameters, pyramids, fixed_work=False, keep_state=False):
         _SolverThread.__init__(self)
         self._parameters, self._pyramids = parameters, pyramids
-        self.gpu_morph = Morph(parameters, pyramids, self._flag, fixed_work)
+        self.gpu_morph = Morph(parameters, pyramids, self._flag, fixed_work, keep_state)
+
+    @property
+    def energies(self):
+        """{level: the five energy totals}, one entry per level the solve has finished (Morph.energies)"""
+        return self.gpu_morph.energies
 
     def _solve(self):
         """MatchingThread.cpp:138-150"""
@@ -661,7 +703,7 @@ def video_constraints(P):
     return np.asarray(out, dtype=np.float32).reshape(-1, 6)
 
 
-class VideoPage(object):
+class VideoPage(_ErrorView):
     """One page of a PyramidLevel of depth > 1 (device-state access)."""
 
     def __init__(self, vid, lvl, page, w, h):
@@ -675,6 +717,9 @@ class VideoPage(object):
             raise capi.VmError(capi.VM_E_STATE, "this VideoPage outlived its VideoPyramid: keep a reference to the "
                                                 "VideoPyramid while its pages are in use")
         return v
+
+    def _err(self, name):
+        return getattr(self._vid._L, "vm_video_" + name), (self._vid._h, self._lvl, self._page)
 
     def field(self, name):
         fid, ch = capi.FIELDS[name]
@@ -813,6 +858,7 @@ class VideoMorph(object):
         self.fixed_work = bool(fixed_work)
         self._max_iter = float(params.max_iter)
         self.progress = {}
+        self.energies = {}   # level -> [the five totals of every page] (VideoPage.energy()), filled when the solve returns
 
     def calculate_halfway_parametrization(self):
         """morph.cu:150-168 with the page schedule of optimize_level (:1353-1441)"""
@@ -831,6 +877,8 @@ class VideoMorph(object):
                 self.progress[(l, t)] = dict(iters=pr.iters, iters_live=pr.iters_live, improving=pr.improving, commits=pr.commits,
                                              candidates=pr.candidates, elapsed_ms=pr.elapsed_ms)
                 k += 1
+            # (the levels of one vm_video_solve are pipelined inside the call: the totals are read once it is back)
+            self.energies[l] = [pg.energy() for pg in vid.pages[l]]
         return True
 
 
@@ -845,6 +893,11 @@ class VideoMatchingThread(_SolverThread):
         self.w0 = int(w0 if w0 is not None else pyramids.levels[0][0])
         self.h0 = int(h0 if h0 is not None else pyramids.levels[0][1])
         self.gpu_morph = VideoMorph(parameters, pyramids, self._flag, fixed_work)
+
+    @property
+    def energies(self):
+        """{level: [the five energy totals of every page]} (VideoMorph.energies)"""
+        return self.gpu_morph.energies
 
     def _solve(self):
         """MatchingThread.cpp:138-150"""
