@@ -32,6 +32,10 @@ int main(int argc, char **argv)
                e.step_min_cand, e.no_corun, e.no_tile_list, e.no_pass, e.tile_dense, e.dense128);
         return 0;
     }
+    if (argc > 1 && !strcmp(argv[1], "--env-dense-noint")) {
+        printf("%d\n", SweepSwitches::from_environment().dense_noint);
+        return 0;
+    }
     std::string line;
     while (std::getline(std::cin, line)) {
         std::istringstream in(line);
@@ -53,14 +57,17 @@ int main(int argc, char **argv)
             else if (k == "no_pass") sw.no_pass = atoi(v.c_str()) != 0;
             else if (k == "tile_dense") sw.tile_dense = atoi(v.c_str()) != 0;
             else if (k == "dense128") sw.dense128 = atoi(v.c_str());
+            else if (k == "dense_noint") sw.dense_noint = atoi(v.c_str());
             else return 2;
         }
         const SweepLevelPlan p = plan_level(q, sw);
         const SweepBatchPlan b = plan_batch(p, cand, tiles, may_pass != 0);
         printf("tiles=%d threads=%d parts=%d needs_ws=%d may_split=%d may_sparse=%d listed_ok=%d small_dense_ok=%d dense128=%d "
-               "want_pass=%d pass_switches=%d forced_split=%d sched=%d dense=%d step=%d use_tile_list=%d small_dense=%d\n",
+               "want_pass=%d pass_switches=%d forced_split=%d sched=%d dense=%d step=%d use_tile_list=%d small_dense=%d "
+               "no_interior=%d tile_form=%d\n",
                p.tiles, p.threads, p.parts, p.needs_ws, p.may_split, p.may_sparse, p.listed_ok, p.small_dense_ok, p.dense128,
-               p.want_pass, p.pass_switches, p.forced_split, (int)b.sched, b.dense, b.step, b.use_tile_list, b.small_dense);
+               p.want_pass, p.pass_switches, p.forced_split, (int)b.sched, b.dense, b.step, b.use_tile_list, b.small_dense,
+               b.no_interior, b.tile_form());
     }
     return 0;
 }
@@ -133,6 +140,56 @@ def test_dense_kernel_form_goes_by_the_level_size(plan_exe):
     _has(_plan(plan_exe, 960, 540), sched=0, dense=2, dense128=1)
     # ... never by the batch: 30 pairs of 480x270 keep the 256-VGPR form
     _has(_plan(plan_exe, 480, 270, n=30), dense=1, dense128=0)
+
+
+def test_small_levels_run_the_dense_kernel_without_its_interior_form(plan_exe):
+    """FAST, a dense batch that is not the 128-VGPR form: the form without the interior body up to 32 tiles per pass
+    (tile_form 3 is what the TILE launcher is told; `dense` stays 1)."""
+    _has(_plan(plan_exe, 276, 168, mode=TILE), tiles=32, sched=0, dense=1, no_interior=1, tile_form=3)  # 4 x 8
+    _has(_plan(plan_exe, 207, 231, mode=TILE), tiles=33, sched=0, dense=1, no_interior=0, tile_form=1)  # 3 x 11
+    _has(_plan(plan_exe, 240, 135, mode=TILE), tiles=28, sched=0, dense=1, no_interior=1, tile_form=3)
+    _has(_plan(plan_exe, 1920, 1080), sched=0, dense=2, no_interior=0, tile_form=2)
+    _has(_plan(plan_exe, 1920, 1080, dense128=0), sched=0, dense=1, no_interior=0, tile_form=1)
+    # a rule on the level, never on the batch: AUTO's TILE batches of many pairs, the dense ones of a pruned level
+    _has(_plan(plan_exe, 276, 168, n=3), sched=0, dense=1, no_interior=1, tile_form=3)
+    _has(_plan(plan_exe, 207, 231, n=30), sched=0, dense=1, no_interior=0, tile_form=1)
+    _has(_plan(plan_exe, 240, 135, cand=10, tiles=100, tile_dense=1), sched=0, dense=1, no_interior=1, tile_form=3)
+
+
+def test_the_no_interior_switch_and_what_it_never_touches(plan_exe):
+    levels = [(120, 68), (276, 168), (207, 231), (240, 135), (480, 270), (960, 540), (1920, 1080)]
+    # forced off: no level gets the form
+    for w, h in levels:
+        got = _plan(plan_exe, w, h, mode=TILE, dense_noint=0)
+        _has(got, no_interior=0, tile_form=got["dense"])
+    # forced on: every dense FAST batch that is not the 128-VGPR form gets it ...
+    for w, h in levels:
+        _has(_plan(plan_exe, w, h, mode=TILE, dense128=0, dense_noint=1), dense=1, no_interior=1, tile_form=3)
+    # ... and a batch planned as the 128-VGPR form never does, by the level's size or forced
+    for w, h in ((960, 540), (1920, 1080)):
+        _has(_plan(plan_exe, w, h, mode=TILE, dense_noint=1), dense128=1, dense=2, no_interior=0, tile_form=2)
+    _has(_plan(plan_exe, 120, 68, mode=TILE, dense128=1), dense=2, no_interior=0, tile_form=2)
+    _has(_plan(plan_exe, 120, 68, mode=TILE, dense128=1, dense_noint=1), dense=2, no_interior=0, tile_form=2)
+    # EXACT and the diagnostic arithmetics have one dense form
+    for m in (EXACT, capi.MATH_EXACT_FMA, capi.MATH_REF_FASTMATH, capi.MATH_REF_TEX8, capi.MATH_REF_TEX8_TRUNC):
+        _has(_plan(plan_exe, 240, 135, math=m, mode=TILE), dense=1, no_interior=0, tile_form=1)
+        _has(_plan(plan_exe, 240, 135, math=m, mode=TILE, dense_noint=1), dense=1, no_interior=0, tile_form=1)
+    # a lean batch is untouched
+    _has(_plan(plan_exe, 240, 135, mode=TILE, cand=10, tiles=100), sched=1, dense=0, no_interior=0, tile_form=0)
+    _has(_plan(plan_exe, 240, 135, mode=TILE, cand=10, tiles=100, dense_noint=1), sched=1, dense=0, no_interior=0, tile_form=0)
+    _has(_plan(plan_exe, 240, 135, cand=10, tiles=1, dense_noint=1), sched=3, dense=0, no_interior=0, tile_form=0)
+
+
+def test_the_no_interior_switch_comes_from_the_environment(plan_exe):
+    def dense_noint(**env):
+        e = {k: v for k, v in os.environ.items() if not k.startswith("VM_")}
+        e.update(env)
+        return int(subprocess.run([plan_exe, "--env-dense-noint"], env=e, capture_output=True, text=True, check=True).stdout)
+    assert dense_noint() == -1
+    assert dense_noint(VM_DENSE_NOINT="0") == 0
+    assert dense_noint(VM_DENSE_NOINT="1") == 1
+    assert dense_noint(VM_DENSE_NOINT="7") == 1
+    assert dense_noint(VM_DENSE_NOINT="x") == 0  # atoi
 
 
 def test_lean_regime_starts_below_a_tenth_of_the_pixels(plan_exe):

@@ -68,35 +68,6 @@ typedef __attribute__((address_space(1))) const float vm_g_cf32;
 // half of c -- a register that may be the destination of a load in flight)
 __device__ __forceinline__ int mad24(int a, int b, int c) { return __mul24(a, b) + c; }
 
-#ifdef VM_PROF
-// dev-only stage stamps of k_decide (10 ns ticks), wave 0 lane 0 of each workgroup
-__device__ unsigned long long vm_prof_buf[512 * 16 * 2];
-#define VM_PTSF(k)                                             \
-    if (tid == 0 && b < 256)                                   \
-    vm_prof_buf[8192 + 512 + b * 8 + (k)] = wall_clock64()
-#define VM_PTS(ph, k)                                          \
-    if (tid == 0 && b < 256 && (ph) < 4)                       \
-    vm_prof_buf[b * 32 + (ph) * 8 + (k)] = wall_clock64()
-// ... and of tile_sweep (TILE schedule): thread 0 of tiles 0..255 of the first pair
-#define VM_TTS(ph, k)                                                              \
-    if (threadIdx.x == 0 && blockIdx.x < 256 && blockIdx.z == 0)                   \
-    vm_prof_buf[blockIdx.x * 32 + (ph) * 8 + (k)] = wall_clock64()
-#define VM_TTSF(k)                                                                 \
-    if (threadIdx.x == 0 && blockIdx.x < 256 && blockIdx.z == 0)                   \
-    vm_prof_buf[8192 + 512 + blockIdx.x * 8 + (k)] = wall_clock64()
-#define VM_TS(i) ts[i] = wall_clock64()
-#define VM_TS_ARG , unsigned long long *ts
-#define VM_TS_PASS , ts
-#else
-#define VM_TS(i)
-#define VM_TS_ARG
-#define VM_TS_PASS
-#define VM_PTS(ph, k)
-#define VM_PTSF(k)
-#define VM_TTS(ph, k)
-#define VM_TTSF(k)
-#endif
-
 namespace {
 
 struct TileLds {
@@ -489,9 +460,8 @@ __device__ __forceinline__ void halves(float v, float &lo, float &hi)
 // agree bit for bit.  Returns true and the accepted step when the energy drops.
 template <class Energy, class Ring>
 __device__ __forceinline__ bool decide_with(const VmLevelView &L, const VmKParams &P, const PixelCtx &c,
-                                            const Energy &energy, const Ring &ring, float2 &step, uint32_t &n_eval VM_TS_ARG)
+                                            const Energy &energy, const Ring &ring, float2 &step, uint32_t &n_eval)
 {
-    VM_TS(4);
 #define ENERGY(DX, DY) (++n_eval, energy((DX), (DY)))
     // The energy is evaluated at exactly two places of the instruction stream (not at
     // the reference's seven): the sweep kernels must stay inside the instruction cache.
@@ -508,7 +478,6 @@ __device__ __forceinline__ bool decide_with(const VmLevelView &L, const VmKParam
     }
     gx = -gx;
     gy = -gy;
-    VM_TS(5);
     const float ng = fsqrt(gx * gx + gy * gy);
     if (ng == 0)
         return false;
@@ -519,7 +488,6 @@ __device__ __forceinline__ bool decide_with(const VmLevelView &L, const VmKParam
     fover_ring(L, ring, c.px, c.py, -1.0f, -c.v.x, -c.v.y, -gx, -gy, t_min);
     fover_ring(L, ring, c.px, c.py, 1.0f, c.v.x, c.v.y, gx, gy, t_min);
     float cc = fmaxf(t_min - P.eps, 0.0f);
-    VM_TS(6);
     // golden_section_search, morph.cu:885-947: step 0 and 1 evaluate the two initial
     // interior points b and x, later steps shrink the bracket
     const float R = 0.618033989f, C = 1.0f - R;
@@ -561,7 +529,6 @@ __device__ __forceinline__ bool decide_with(const VmLevelView &L, const VmKParam
         }
     }
 #undef ENERGY
-    VM_TS(7);
     const float tmin = fx < fb ? x : b, fmin = fx < fb ? fx : fb;
     if (!(fmin < 0))
         return false;
@@ -665,13 +632,13 @@ __device__ __forceinline__ bool decide_with64(const VmLevelView &L, const VmKPar
 // one lane (EXACT) or L lanes (FAST dense path) per pixel
 template <bool INTERIOR, int SMAX, int LF = 0, class Src>
 __device__ __forceinline__ bool decide(const VmLevelView &L, const VmKParams &P, const Src &src,
-                                       const PixelCtx &c, int sub, int Lf, float2 &step, uint32_t &n_eval VM_TS_ARG)
+                                       const PixelCtx &c, int sub, int Lf, float2 &step, uint32_t &n_eval)
 {
     NbCacheT<SMAX> nb;
     nb_load<INTERIOR, SMAX, LF>(nb, L, src, c, sub, Lf);
     return decide_with(
         L, P, c, [&](float dx, float dy) { return energy_change<INTERIOR, SMAX, LF>(L, P, src, nb, c, dx, dy, Lf); },
-        RingGlobal{L.v}, step, n_eval VM_TS_PASS);
+        RingGlobal{L.v}, step, n_eval);
 }
 
 #if VM_EXACT
@@ -736,13 +703,12 @@ __device__ __forceinline__ float energy_x32(const VmLevelView &L, const VmKParam
 
 template <class Src>
 __device__ __forceinline__ bool decide_x32(const VmLevelView &L, const VmKParams &P, const Src &src,
-                                           const PixelCtx &c, int sub, float2 &step, uint32_t &n_eval VM_TS_ARG)
+                                           const PixelCtx &c, int sub, float2 &step, uint32_t &n_eval)
 {
     NbX nb;
     nbx_load(nb, L, src, c, sub);
     return decide_with(
-        L, P, c, [&](float dx, float dy) { return energy_x32(L, P, nb, c, dx, dy); }, RingGlobal{L.v}, step,
-        n_eval VM_TS_PASS);
+        L, P, c, [&](float dx, float dy) { return energy_x32(L, P, nb, c, dx, dy); }, RingGlobal{L.v}, step, n_eval);
 }
 // ... with a whole wave per pixel (both halves hold the same neighbour sums)
 template <class Src>
@@ -957,9 +923,8 @@ __device__ __forceinline__ float fover32(const VmLevelView &L, const Ring &ring,
 template <bool INTERIOR, class Ring>
 __device__ __forceinline__ bool decide32(const VmLevelView &L, const VmKParams &P, const Nb1 &nb, const Ring &ring,
                                          const PixelCtx &c, int sub, float2 &step, float2 &luma,
-                                         uint32_t &n_eval VM_TS_ARG)
+                                         uint32_t &n_eval)
 {
-    VM_TS(4);
     n_eval += 4;
     const bool has_temp = L.temp_mask != nullptr; // uniform in the launch
     const float WT = has_temp ? P.w_temp * c.tmask * L.factor_d * L.inv_wh : 0.0f;
@@ -996,14 +961,12 @@ __device__ __forceinline__ bool decide32(const VmLevelView &L, const VmKParams &
     }
     gx = -gx;
     gy = -gy;
-    VM_TS(5);
     const float ng = fsqrt(gx * gx + gy * gy);
     if (ng == 0)
         return false;
     gx = fdiv(gx, ng);
     gy = fdiv(gy, ng);
     float cc = fmaxf(fover32(L, ring, c, gx, gy, sub) - P.eps, 0.0f);
-    VM_TS(6);
     // E(t) = WS change(t) + t (Q2 t + Q1)
     const float gg = gx * gx + gy * gy;
     const float WS = P.w_ssim * L.inv_wh, WU = P.w_ui * L.inv_wh;
@@ -1052,7 +1015,6 @@ __device__ __forceinline__ bool decide32(const VmLevelView &L, const VmKParams &
         lq = lt ? lf : olb;
     }
 #undef ELINE
-    VM_TS(7);
     const float tmin = fx < fb ? x : b, fmin = fx < fb ? fx : fb;
     if (!(fmin < 0))
         return false;
@@ -1493,7 +1455,6 @@ __device__ __forceinline__ bool tile_sweep(TileLds &S, const VmLevelView &L, con
                                            uint32_t *sp_list = nullptr, uint32_t *sp_val = nullptr, uint32_t *sp_cnt = nullptr,
                                            uint32_t sp_cap = 0)
 {
-    VM_TTSF(0);
     // --- improving-mask words of the tile and its ring of neighbour blocks ---
     const MaskGeom g = mask_geom(L, ox, oy);
     uint32_t mymask = 0;
@@ -1558,13 +1519,11 @@ __device__ __forceinline__ bool tile_sweep(TileLds &S, const VmLevelView &L, con
         }
     }
     __syncthreads();
-    VM_TTSF(1);
 
     bool tile_improving = false;
 
     for (int pi = 0; pi < 2; ++pi) {
         for (int pj = 0; pj < 2; ++pj) {
-            VM_TTS(pi * 2 + pj, 0);
             // ---- 1. candidates of this phase ----
             bool cand = false, hit = false;
             if (tid < 256) {
@@ -1581,15 +1540,8 @@ __device__ __forceinline__ bool tile_sweep(TileLds &S, const VmLevelView &L, con
             const int n_act = compact256(cand, tid, S.list, S.wave_cnt, hit, &any_hit);
             // no pixel of this phase in the mask: nothing to search, nothing to commit, no bit to clear
             // (a pruned tile visit is mostly such phases: 1.6 -> 0.9 us each)
-            if (!any_hit) {
-                VM_TTS(pi * 2 + pj, 1);
-                VM_TTS(pi * 2 + pj, 2);
-                VM_TTS(pi * 2 + pj, 3);
-                VM_TTS(pi * 2 + pj, 4);
-                VM_TTS(pi * 2 + pj, 5);
+            if (!any_hit)
                 continue;
-            }
-            VM_TTS(pi * 2 + pj, 1);
 
             if (n_act > 0) {
                 st_cand += n_act;
@@ -1616,20 +1568,17 @@ __device__ __forceinline__ bool tile_sweep(TileLds &S, const VmLevelView &L, con
                         LdsSrc src{&S, (ty * 2 + pi) * VM_HALO_W + (tx * 2 + pj)};
                         c.tps_b = S.tpsb[src.hc + 2 * VM_HALO_W + 2];
                         float2 step, luma;
-#ifdef VM_PROF
-                        unsigned long long ts[16];
-#endif
                         Nb1 nb;
                         bool ok;
                         uint32_t n_eval = 0;
                         if (wave_interior) {
                             nb1_load<true>(nb, L, src, c, sub);
                             ok = wide ? decide64<true>(L, P, nb, RingGlobal{L.v}, c, sub, (tid & 32) != 0, step, luma, n_eval)
-                                      : decide32<true>(L, P, nb, RingGlobal{L.v}, c, sub, step, luma, n_eval VM_TS_PASS);
+                                      : decide32<true>(L, P, nb, RingGlobal{L.v}, c, sub, step, luma, n_eval);
                         } else {
                             nb1_load<false>(nb, L, src, c, sub);
                             ok = wide ? decide64<false>(L, P, nb, RingGlobal{L.v}, c, sub, (tid & 32) != 0, step, luma, n_eval)
-                                      : decide32<false>(L, P, nb, RingGlobal{L.v}, c, sub, step, luma, n_eval VM_TS_PASS);
+                                      : decide32<false>(L, P, nb, RingGlobal{L.v}, c, sub, step, luma, n_eval);
                         }
                         if (writer)
                             atomicAdd(&S.n_eval, n_eval);
@@ -1666,12 +1615,9 @@ __device__ __forceinline__ bool tile_sweep(TileLds &S, const VmLevelView &L, con
                             LdsSrc src{&S, (ty * 2 + pi) * VM_HALO_W + (tx * 2 + pj)};
                             c.tps_b = S.tpsb[src.hc + 2 * VM_HALO_W + 2];
                             float2 step;
-#ifdef VM_PROF
-                            unsigned long long ts[16];
-#endif
                             uint32_t n_eval = 0;
                             const bool ok = wide ? decide_x64(L, P, src, c, sub, (tid & 32) != 0, step, n_eval)
-                                                 : decide_x32(L, P, src, c, sub, step, n_eval VM_TS_PASS);
+                                                 : decide_x32(L, P, src, c, sub, step, n_eval);
                             if (writer)
                                 atomicAdd(&S.n_eval, n_eval);
                             if (ok && writer) {
@@ -1709,12 +1655,9 @@ __device__ __forceinline__ bool tile_sweep(TileLds &S, const VmLevelView &L, con
                         LdsSrc src{&S, (ty * 2 + pi) * VM_HALO_W + (tx * 2 + pj)};
                         c.tps_b = S.tpsb[src.hc + 2 * VM_HALO_W + 2];
                         float2 step;
-#ifdef VM_PROF
-                        unsigned long long ts[16];
-#endif
                         uint32_t n_eval = 0;
-                        const bool ok = wave_interior ? decide<true, SMAX, MINF>(L, P, src, c, sub, Lf, step, n_eval VM_TS_PASS)
-                                                      : decide<false, SMAX, MINF>(L, P, src, c, sub, Lf, step, n_eval VM_TS_PASS);
+                        const bool ok = wave_interior ? decide<true, SMAX, MINF>(L, P, src, c, sub, Lf, step, n_eval)
+                                                      : decide<false, SMAX, MINF>(L, P, src, c, sub, Lf, step, n_eval);
                         if (sub == 0)
                             atomicAdd(&S.n_eval, n_eval);
                         if (ok && sub == 0) {
@@ -1725,9 +1668,7 @@ __device__ __forceinline__ bool tile_sweep(TileLds &S, const VmLevelView &L, con
                 }
                 }
             }
-            VM_TTS(pi * 2 + pj, 2);
             __syncthreads();
-            VM_TTS(pi * 2 + pj, 3);
 
             // ---- 3. commits ----
             const bool ok = tid < 256 && commit_own(S, L, g, tid, ox, oy, pi, pj);
@@ -1739,7 +1680,6 @@ __device__ __forceinline__ bool tile_sweep(TileLds &S, const VmLevelView &L, con
                 }
             }
             const int ncommit = __syncthreads_count(ok);
-            VM_TTS(pi * 2 + pj, 4);
             if (ncommit) {
                 tile_improving = true;
                 st_commit += ncommit;
@@ -1780,10 +1720,8 @@ __device__ __forceinline__ bool tile_sweep(TileLds &S, const VmLevelView &L, con
                 }
             }
             __syncthreads();
-            VM_TTS(pi * 2 + pj, 5);
         }
     }
-    VM_TTSF(2);
 
     // ---- SaveSSIM (morph.cu:1236-1256), tps.b and the owned mask words ----
     // (a pruned visit commits a pixel or two: only the cells those commits reached have changed)
@@ -1818,7 +1756,6 @@ __device__ __forceinline__ bool tile_sweep(TileLds &S, const VmLevelView &L, con
         }
     }
     improving = improving || tile_improving;
-    VM_TTSF(3);
     return true;
 }
 
@@ -2262,7 +2199,6 @@ __device__ __forceinline__ bool sv_phases(TileLds &S, SvPix &X, SparseLds &Q, co
             const int vpi = pi ^ ((oy - vy) & 1), vpj = pj ^ ((ox - vx) & 1);
             int *const ph_cnt = Q.ph_cnt[pj];
             uint32_t *const ph_cand = Q.ph_cand[pj], *const ph_commit = Q.ph_commit[pj];
-            VM_TTS(pi * 2 + pj, 0);
             // ---- 1. candidates of this phase ----
             bool cand = false, hit = false;
             uint32_t *mword = nullptr;
@@ -2292,7 +2228,6 @@ __device__ __forceinline__ bool sv_phases(TileLds &S, SvPix &X, SparseLds &Q, co
             const int n_act = (w0 & 0xFFFF) + (w1 & 0xFFFF) + (w2 & 0xFFFF) + (w3 & 0xFFFF);
             if (hit && !cand)
                 atomicAnd(mword, ~mbit); // a locked pixel in the mask
-            VM_TTS(pi * 2 + pj, 1);
             if (n_act > 0) {
                 st_cand += n_act;
                 // ---- 2. line searches on the pre-phase state: the lean search, a whole wave per candidate
@@ -2325,22 +2260,18 @@ __device__ __forceinline__ bool sv_phases(TileLds &S, SvPix &X, SparseLds &Q, co
                         }
                         c.tps_b = S.tpsb[pc];
                         const RingLds ring{X.v, pc};
-                        VM_TTS(pi * 2 + pj, 6);
                         float2 step, luma;
-#ifdef VM_PROF
-                        unsigned long long ts[16];
-#endif
                         Nb1 nb;
                         bool ok;
                         uint32_t n_eval = 0;
                         if (wave_interior) {
                             nb1_load<true>(nb, L, src, c, sub);
                             ok = wide ? decide64<true>(L, P, nb, ring, c, sub, (tid & 32) != 0, step, luma, n_eval)
-                                      : decide32<true>(L, P, nb, ring, c, sub, step, luma, n_eval VM_TS_PASS);
+                                      : decide32<true>(L, P, nb, ring, c, sub, step, luma, n_eval);
                         } else {
                             nb1_load<false>(nb, L, src, c, sub);
                             ok = wide ? decide64<false>(L, P, nb, ring, c, sub, (tid & 32) != 0, step, luma, n_eval)
-                                      : decide32<false>(L, P, nb, ring, c, sub, step, luma, n_eval VM_TS_PASS);
+                                      : decide32<false>(L, P, nb, ring, c, sub, step, luma, n_eval);
                         }
                         if (writer) {
                             atomicAdd(&S.n_eval, n_eval);
@@ -2369,9 +2300,7 @@ __device__ __forceinline__ bool sv_phases(TileLds &S, SvPix &X, SparseLds &Q, co
                     }
                 }
             }
-            VM_TTS(pi * 2 + pj, 2);
             __syncthreads();
-            VM_TTS(pi * 2 + pj, 3);
 
             // ---- 3. the cells gather the commits of the phase ----
             uint32_t cb[8];
@@ -2385,7 +2314,6 @@ __device__ __forceinline__ bool sv_phases(TileLds &S, SvPix &X, SparseLds &Q, co
                     ty1 = k;
                 }
             }
-            VM_TTS(pi * 2 + pj, 4);
             if (ncommit) {
                 tile_improving = true;
                 st_commit += ncommit;
@@ -2422,7 +2350,6 @@ __device__ __forceinline__ bool sv_phases(TileLds &S, SvPix &X, SparseLds &Q, co
                 }
             }
             __syncthreads();
-            VM_TTS(pi * 2 + pj, 5);
             if (!res || !(Q.unsafe & 1u)) // (uniform: written before the barrier above)
                 continue;
             // ---- a commit left the safe rectangle: move the virtual tile before the next phase ----
@@ -2564,7 +2491,6 @@ __global__ __launch_bounds__(VM_SWEEP_T) __attribute__((amdgpu_waves_per_eu(1)))
             const int offx = (pass & 1) ? VM_TILE_W : 0, offy = (pass & 2) ? VM_TILE_H : 0; // morph.cu:1382-1385
             const uint32_t *list = in_lds ? Q.wl[cur] : lists[cur];
             const bool pass_resident = resident; // (residency can end inside a pass, never begin)
-            VM_TTSF(4);
             // ---- 1. the tiles of this pass that a set mask bit reaches ----
             int ntl = 0;
             unsigned long long rtl = 0; // (resident) the <= 4 tiles, 16 bits each
@@ -2651,7 +2577,6 @@ __global__ __launch_bounds__(VM_SWEEP_T) __attribute__((amdgpu_waves_per_eu(1)))
                 __syncthreads();
                 ntl = (int)Q.ntl;
             }
-            VM_TTSF(5);
             // ---- 2. sweep them, one after the other (tiles of a pass touch disjoint state: any order) ----
             // (a few tiles: straight from the list; many: the bitmap, word by word -- walking all of its up to 46
             // words for the one tile of a cycling level was ~3 us of every pass)
@@ -2705,7 +2630,6 @@ __global__ __launch_bounds__(VM_SWEEP_T) __attribute__((amdgpu_waves_per_eu(1)))
                     __syncthreads(); // the tile's state and mask words are out before anything reads them
                 }
             }
-            VM_TTSF(6);
             if (resident)
                 continue; // the LDS copy of the words is the list
             if (pass_resident) {
@@ -2750,7 +2674,6 @@ __global__ __launch_bounds__(VM_SWEEP_T) __attribute__((amdgpu_waves_per_eu(1)))
                 }
                 cur ^= 1;
                 __syncthreads(); // Q.nnew is reset at the top of the next pass
-                VM_TTSF(7);
                 continue;
             }
             uint32_t *nlist = lists[cur ^ 1];
@@ -2831,11 +2754,6 @@ __global__ __launch_bounds__(VM_SWEEP_T) void SUF(k_decide)(const VmLevelView *_
 {
     __shared__ SplitLds S;
     const int tid = threadIdx.x, T = blockDim.x;
-#ifdef VM_PROF
-    unsigned long long ts[16];
-    for (int k = 0; k < 16; ++k) ts[k] = 0;
-    VM_TS(0);
-#endif
     const VmLevelView L = views[blockIdx.z];
     flags += (size_t)blockIdx.z * cap;
     stats += (size_t)blockIdx.z * cap * VM_STAT_WORDS;
@@ -2864,8 +2782,6 @@ __global__ __launch_bounds__(VM_SWEEP_T) void SUF(k_decide)(const VmLevelView *_
         S.n_eval = 0;
     if (!__syncthreads_or(mymask != 0))
         return;
-    VM_TS(1);
-    VM_TS(2);
 
     // every mask hit of the phase, in slot order: the list is the same in all `parts`
     // workgroups of the tile, entry i belongs to workgroup i % parts
@@ -2893,13 +2809,12 @@ __global__ __launch_bounds__(VM_SWEEP_T) void SUF(k_decide)(const VmLevelView *_
             PixelCtx c;
             c.idx = py * L.rs + px;
             if (!pixel_locked(L, P.bcond, px, py)) {
-                VM_TS(3);
                 ctx_load(c, L, S.tps, px, py);
                 c.tps_b = L.tps_b[c.idx];
                 GlbSrc src{&L, (py - 2) * L.rs + (px - 2)};
 #if VM_EXACT
                 (void)wave_interior;
-                const bool ok = decide_x32(L, P, src, c, sub, step, n_eval VM_TS_PASS);
+                const bool ok = decide_x32(L, P, src, c, sub, step, n_eval);
                 if (ok) { // the lumas commit_pixel_motion samples (morph.cu:997-1003)
                     const float nvx = c.v.x + step.x, nvy = c.v.y + step.y;
                     luma.x = tap(L.img0, L.w, L.h, L.rs, px - nvx + 0.5f, py - nvy + 0.5f);
@@ -2910,10 +2825,10 @@ __global__ __launch_bounds__(VM_SWEEP_T) void SUF(k_decide)(const VmLevelView *_
                 bool ok;
                 if (wave_interior) {
                     nb1_load<true>(nb, L, src, c, sub);
-                    ok = decide32<true>(L, P, nb, RingGlobal{L.v}, c, sub, step, luma, n_eval VM_TS_PASS);
+                    ok = decide32<true>(L, P, nb, RingGlobal{L.v}, c, sub, step, luma, n_eval);
                 } else {
                     nb1_load<false>(nb, L, src, c, sub);
-                    ok = decide32<false>(L, P, nb, RingGlobal{L.v}, c, sub, step, luma, n_eval VM_TS_PASS);
+                    ok = decide32<false>(L, P, nb, RingGlobal{L.v}, c, sub, step, luma, n_eval);
                 }
 #endif
                 if (ok)
@@ -2945,14 +2860,6 @@ __global__ __launch_bounds__(VM_SWEEP_T) void SUF(k_decide)(const VmLevelView *_
     __syncthreads();
     if (tid == 0 && S.n_eval)
         atomicAdd(&stats[iter_idx * VM_STAT_WORDS + 4], S.n_eval);
-#ifdef VM_PROF
-    VM_TS(8);
-    if ((tid & 63) == 0 && blockIdx.x < 512 && (tid >> 6) < 1) {
-        ts[9] = (unsigned long long)Lf;
-        ts[10] = (unsigned long long)n_mine;
-        for (int k = 0; k < 16; ++k) vm_prof_buf[blockIdx.x * 16 + k] = ts[k];
-    }
-#endif
 }
 
 __global__ __launch_bounds__(1024) void SUF(k_commit)(const VmLevelView *__restrict__ views, int cap, VmKParams P,
@@ -3214,11 +3121,6 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(T / 128))) vo
 {
     __shared__ StepLds S;
     const int tid = threadIdx.x;
-#ifdef VM_PROF
-    unsigned long long ts[16];
-    for (int k = 0; k < 16; ++k) ts[k] = 0;
-    VM_TS(0);
-#endif
     const VmLevelView L = views[blockIdx.z];
     flags += (size_t)blockIdx.z * cap;
     stats += (size_t)blockIdx.z * cap * VM_STAT_WORDS;
@@ -3403,7 +3305,6 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(T / 128))) vo
         S.n_eval = 0;
     }
     __syncthreads();
-    VM_TS(1);
     // the last phase's records: commit bits for the cell folds, and the mask words -- a committed
     // pixel sets its bit, a hit that did not move clears it.  (Mask bits further than 2 pixels
     // from the tile stay unfolded here: mask_hit never looks at them.)
@@ -3425,7 +3326,6 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(T / 128))) vo
         }
     }
     __syncthreads();
-    VM_TS(2);
 
     bool hit = false;
     if (tid < 256) {
@@ -3458,7 +3358,6 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(T / 128))) vo
         c.px = px;
         c.py = py;
         c.idx = py * L.rs + px;
-        VM_TS(3);
         // every lane takes part in the fold (its slot loops are wave-uniform); idle lanes fold
         // the pixel's own cell with no records
         ctx_load(c, L, S.tps, px, py);
@@ -3494,8 +3393,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(T / 128))) vo
                     (tid & 32) != 0, step, n_eval);
             else
                 ok = decide_with(
-                    L, P, c, [&](float dx, float dy) { return energy_x32(L, P, nb, c, dx, dy); }, RingGlobal{L.v}, step,
-                    n_eval VM_TS_PASS);
+                    L, P, c, [&](float dx, float dy) { return energy_x32(L, P, nb, c, dx, dy); }, RingGlobal{L.v}, step, n_eval);
             if (ok) { // the lumas commit_pixel_motion samples (morph.cu:997-1003)
                 const float nvx = c.v.x + step.x, nvy = c.v.y + step.y;
                 luma.x = tap(L.img0, L.w, L.h, L.rs, px - nvx + 0.5f, py - nvy + 0.5f);
@@ -3514,10 +3412,10 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(T / 128))) vo
                 }
             } else if (wave_interior) {
                 nb1_make<true>(nb, L, okc, qx, qy, m, q, cr, val);
-                ok = decide32<true>(L, P, nb, RingGlobal{L.v}, c, sub, step, luma, n_eval VM_TS_PASS);
+                ok = decide32<true>(L, P, nb, RingGlobal{L.v}, c, sub, step, luma, n_eval);
             } else {
                 nb1_make<false>(nb, L, okc, qx, qy, m, q, cr, val);
-                ok = decide32<false>(L, P, nb, RingGlobal{L.v}, c, sub, step, luma, n_eval VM_TS_PASS);
+                ok = decide32<false>(L, P, nb, RingGlobal{L.v}, c, sub, step, luma, n_eval);
             }
 #endif
             if (ok)
@@ -3541,14 +3439,6 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(T / 128))) vo
     }
     if (my_commits)
         atomicAdd(&S.n_commit, my_commits);
-#ifdef VM_PROF
-    VM_TS(8);
-    if ((tid & 63) == 0 && bid < 512 && (tid >> 6) < 1) {
-        ts[9] = 32;
-        ts[10] = (unsigned long long)n_mine;
-        for (int k = 0; k < 16; ++k) vm_prof_buf[bid * 16 + k] = ts[k];
-    }
-#endif
     __syncthreads();
     if (tid == 0) {
         const uint32_t nc = S.n_commit;
@@ -3700,10 +3590,6 @@ __global__ __launch_bounds__(VM_PASS_T) __attribute__((amdgpu_waves_per_eu(2, 2)
     const bool hi = (tid & 32) != 0;
     // workgroup -> (group, part): ids b, b + 8, ... of a 256-block chunk form one group
     const int b = (int)blockIdx.x, within = b & 255;
-#ifdef VM_PROF
-    if (tid == 0 && b < 256)
-        vm_prof_buf[8192 + b * 2] = wall_clock64();
-#endif
     // (force_wt & 4, a test switch: groups of 32 CONSECUTIVE ids instead -- every group then spans all eight
     // XCDs, which is what exercises the census, the write-back fence and the write-through hand-offs)
     const bool spread = (force_wt & 4) != 0;
@@ -3716,7 +3602,6 @@ __global__ __launch_bounds__(VM_PASS_T) __attribute__((amdgpu_waves_per_eu(2, 2)
     }
     const int pair = grp / ntiles, tile = grp - pair * ntiles;
     const VmLevelView L = views[pair];
-    VM_PTSF(0);
     flags += (size_t)pair * cap;
     uint32_t *const stats0 = stats;
     unsigned long long *const bar = (unsigned long long *)(sync + (size_t)grp * VM_PASS_SYNC_WORDS);
@@ -3752,7 +3637,6 @@ __global__ __launch_bounds__(VM_PASS_T) __attribute__((amdgpu_waves_per_eu(2, 2)
     // do not exist, and the reference's test (get_improve_mask_idx) sees them -- a pixel within 2
     // of such an edge stays a candidate for ever (measured: 684 line searches per iteration of a
     // converged 120x68 level, in the oracle and in every schedule).
-    VM_PTSF(1);
     bool live = ox < L.w && oy < L.h && prev_flag != 0 && err_before == 0;
     {
         uint32_t mine = 0;
@@ -3765,7 +3649,6 @@ __global__ __launch_bounds__(VM_PASS_T) __attribute__((amdgpu_waves_per_eu(2, 2)
         if (!__syncthreads_or(mine != 0))
             live = false;
     }
-    VM_PTSF(2);
     // the activity counts of the previous launch, added up by one wave of workgroup 0 (a plain
     // read-modify-write by one thread: nothing else touches that iteration's counters now)
     if (b == 0 && wave == 7 && prev_iter_idx >= 0)
@@ -3810,8 +3693,6 @@ __global__ __launch_bounds__(VM_PASS_T) __attribute__((amdgpu_waves_per_eu(2, 2)
     bool pure_known = false;                           // after the first barrier: the group's XCD census is in
     uint32_t rounds = 0;                               // barrier rounds behind us
     bool timed_out = false;
-    int prof_ph = 0;
-    (void)prof_ph;
 
     // Tile barrier: every store of this workgroup has left (vmcnt(0) per wave, then the workgroup
     // barrier), then one arrival per workgroup.  First round (and every round of a group spread
@@ -3822,7 +3703,6 @@ __global__ __launch_bounds__(VM_PASS_T) __attribute__((amdgpu_waves_per_eu(2, 2)
     auto tile_barrier = [&](bool first) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        VM_PTS(prof_ph, 5);
         if (wave == 0) {
             const bool by_flags = pure_known && !wt;
             const unsigned long long t0 = wall_clock64();
@@ -3865,7 +3745,6 @@ __global__ __launch_bounds__(VM_PASS_T) __attribute__((amdgpu_waves_per_eu(2, 2)
                 }
             }
         }
-        VM_PTS(prof_ph, 6);
         __syncthreads();
         ++rounds;
         if (S.go == 0)
@@ -3896,7 +3775,6 @@ __global__ __launch_bounds__(VM_PASS_T) __attribute__((amdgpu_waves_per_eu(2, 2)
         const int px = ox + tx * 2 + pj, py = oy + ty * 2 + pi;
         const bool in_img = px < L.w && py < L.h;
         const int spx = in_img ? px : ox, spy = in_img ? py : oy; // a safe pixel for the loads of an idle wave
-        VM_PTS(ph, 0);
         // ================= everything from memory in one round trip (no load depends on another): first every
         // byte offset, then the loads back to back.  (Address arithmetic between the loads costs a round trip
         // of its own as soon as it touches a register a load is still to fill -- the compiler's 32-bit
@@ -4042,10 +3920,6 @@ __global__ __launch_bounds__(VM_PASS_T) __attribute__((amdgpu_waves_per_eu(2, 2)
         if (!c_ok)
             ctag = 0;
 
-#ifdef VM_PROF
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // profiling build only: when have the loads landed?
-#endif
-        VM_PTS(ph, 1);
         // ================= the group's mask word: a committed pixel sets its bit, a hit that did not move clears it
         if (ph > 0) {
             const uint32_t setb = (uint32_t)__ballot(!hi && otag == want);
@@ -4132,7 +4006,6 @@ __global__ __launch_bounds__(VM_PASS_T) __attribute__((amdgpu_waves_per_eu(2, 2)
                 sto<float>(dbase, od_value + g4, val, wt);
             }
         }
-        VM_PTS(ph, 2);
         if (closing)
             break;
 
@@ -4153,7 +4026,6 @@ __global__ __launch_bounds__(VM_PASS_T) __attribute__((amdgpu_waves_per_eu(2, 2)
             }
             hit = hit && in_img;
         }
-        VM_PTS(ph, 3);
         if (hit) { // wave-uniform
             uint32_t state = 2;
             float2 step = make_float2(0, 0), luma = make_float2(0, 0);
@@ -4192,7 +4064,6 @@ __global__ __launch_bounds__(VM_PASS_T) __attribute__((amdgpu_waves_per_eu(2, 2)
                 if (ok)
                     state = 1;
             }
-            VM_PTS(ph, 4);
             my_eval += n_eval;
             if (lane == 0) {
                 if (state == 1) {
@@ -4209,9 +4080,7 @@ __global__ __launch_bounds__(VM_PASS_T) __attribute__((amdgpu_waves_per_eu(2, 2)
             if (state == 1)
                 ++my_commit;
         }
-        prof_ph = ph;
         tile_barrier(ph == 0);
-        VM_PTS(ph, 7);
         if (ph == 0 && !timed_out) {
             pure_known = true;
             if (!wt && S.wt) {
@@ -4238,10 +4107,6 @@ __global__ __launch_bounds__(VM_PASS_T) __attribute__((amdgpu_waves_per_eu(2, 2)
         *my_slot = make_uint4(S.n_cand, S.n_commit, S.n_eval, part == 0 ? 1u : 0u);
         if (b == 0)
             clock_probe(stats0 + (size_t)iter_idx * VM_STAT_WORDS, true);
-#ifdef VM_PROF
-        if (b < 256)
-            vm_prof_buf[8192 + b * 2 + 1] = wall_clock64();
-#endif
     }
 }
 
@@ -4262,15 +4127,9 @@ __global__ void SUF(k_next_iter)(int *iter_dev, int set, int value)
 
 // ---------------------------------------------------------------------------
 // launchers
-#if defined(VM_PROF) && !VM_EXACT
-extern "C" int vm_dbg_prof_read(void *dst, size_t bytes)
-{
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(vm_prof_buf), bytes);
-}
-#endif
-
 // `views`: device array of nbatch level views (frame pairs of one batch, same w x h);
-// flags/stats: nbatch rows of `cap` iterations
+// flags/stats: nbatch rows of `cap` iterations; dense (SweepBatchPlan::tile_form): 0 the lean kernel, 1 the dense
+// one, 2 its 128-VGPR form, 3 the dense one without the interior form -- FAST; the other arithmetics have one kernel
 void SUF(vm_launch_optimize)(const VmLevelView *views, int nbatch, int cap, int w, int h, const VmKParams &P,
                              const uint32_t *tables, int offx, int offy, uint32_t *flags, uint32_t *stats,
                              int iter_idx, int fixed_work, int threads, const int *iter_dev, int dense,
@@ -4296,18 +4155,7 @@ void SUF(vm_launch_optimize)(const VmLevelView *views, int nbatch, int cap, int 
                            iter_idx, fixed_work, iter_dev);
         return;
     }
-    // Levels of at most 32 tiles per pass (240x135 and below): most tiles touch the image border, so
-    // most tiles run the border form of the dense line search in some of their waves and wait for
-    // them; the interior form beside it only doubles the code the CU's waves execute at once.
-    // Without it (the same bits: the border form computes the same window counts at run time), us per
-    // dense pass (r03, tools/dev_dense.py): 30 x 120x68 187.5 -> 183.6, 30 x 240x135 623 -> 604, 3 x 240x135
-    // 182 -> 175; on large levels the interior form is what most waves run (1080p x 8 pairs, before the
-    // fixed fan-out: 36.6 ms per pass with it, 50.5 without).  A rule on the level, never on the batch.
-    // (This form also has no lean bodies, see tile_sweep: a phase of <= 16 candidates takes the two-lane
-    // search, so against the general kernel its results move by FAST rounding -- the same for a pair
-    // alone and in a batch, since the form follows from the level.)
-    static const char *noint = getenv("VM_DENSE_NOINT"); // dev switch: 0 / 1 = never / always
-    if (noint ? atoi(noint) != 0 : g.x * g.y <= 32) {
+    if (dense == 3) { // without the interior form (VM_NOINT_MAX_TILES, vm_sweep_plan.h)
         hipLaunchKernelGGL((SUF(k_optimize)<true, VM_SMAX, VM_MIN_FANOUT, false>), g, b, 0, s, views, cap, P, tables, offx, offy,
                            flags, stats, iter_idx, fixed_work, iter_dev);
         return;

@@ -35,6 +35,21 @@
 #ifndef VM_SPARSE_TILES
 #define VM_SPARSE_TILES 12 // SPARSE takes a pruned level over once <= this many tiles per iteration were active
 #endif
+// dense TILE sweeps, FAST, 256-VGPR kernel: levels of at most this many tiles per pass run the form without the
+// interior body.
+// Levels of at most 32 tiles per pass (240x135 and below): most tiles touch the image border, so
+// most tiles run the border form of the dense line search in some of their waves and wait for
+// them; the interior form beside it only doubles the code the CU's waves execute at once.
+// Without it (the same bits: the border form computes the same window counts at run time), us per
+// dense pass (r03, tools/dev_dense.py): 30 x 120x68 187.5 -> 183.6, 30 x 240x135 623 -> 604, 3 x 240x135
+// 182 -> 175; on large levels the interior form is what most waves run (1080p x 8 pairs, before the
+// fixed fan-out: 36.6 ms per pass with it, 50.5 without).  A rule on the level, never on the batch.
+// (This form also has no lean bodies, see tile_sweep: a phase of <= 16 candidates takes the two-lane
+// search, so against the general kernel its results move by FAST rounding -- the same for a pair
+// alone and in a batch, since the form follows from the level.)
+#ifndef VM_NOINT_MAX_TILES
+#define VM_NOINT_MAX_TILES 32
+#endif
 
 // tiles (= workgroups of a TILE launch per pair) of one of the four offset passes over a w x h level
 inline int vm_tiles_per_pass(int w, int h)
@@ -62,6 +77,7 @@ struct SweepSwitches {
     bool no_pass = false;      // VM_NO_PASS=1 turns the PASS schedule off, forced or not
     bool tile_dense = false;   // VM_TILE_DENSE: the dense TILE kernel whatever the counters say, and no SPARSE
     int dense128 = -1;         // VM_DENSE128=0 / 1 forces the 128-VGPR dense kernel off / on; -1: by the level's size
+    int dense_noint = -1;      // VM_DENSE_NOINT=0 / 1: never / always the dense kernel without the interior form; -1: by the level's size
 
     // the process' switches, read from the environment once
     static const SweepSwitches &from_environment()
@@ -76,6 +92,7 @@ struct SweepSwitches {
             s.no_pass = getenv("VM_NO_PASS") != nullptr;
             s.tile_dense = getenv("VM_TILE_DENSE") != nullptr;
             if (const char *e = getenv("VM_DENSE128")) s.dense128 = atoi(e) != 0;
+            if (const char *e = getenv("VM_DENSE_NOINT")) s.dense_noint = atoi(e) != 0;
             return s;
         }();
         return sw;
@@ -109,6 +126,7 @@ struct SweepLevelPlan {
     bool listed_ok = false;      // pruned TILE passes may take the listed form
     bool small_dense_ok = false; // dense TILE batches register with SmallDensePresence
     bool dense128 = false;
+    bool dense_noint = false;    // a dense batch that is not the 128-VGPR form runs the form without the interior body
     bool tile_dense = false;     // (the switch)
     bool want_pass = false;      // before the device has been asked: resident workgroups, the token
     int pass_switches = 0;
@@ -121,9 +139,13 @@ struct SweepLevelPlan {
 struct SweepBatchPlan {
     SweepSched sched = SCHED_TILE_DENSE;
     int dense = 1;              // TILE / SPARSE: 0 the lean kernel, 1 the dense one, 2 its 128-VGPR form
+    bool no_interior = false;   // TILE, dense == 1: the form without the interior body (VM_NOINT_MAX_TILES)
     bool step = false;          // sched == SCHED_STEP: one launch per phase (else the two-kernel SPLIT)
     bool use_tile_list = false; // TILE lean: the listed form
     bool small_dense = false;   // this batch launches small-level dense workgroups (SmallDensePresence)
+
+    // the `dense` argument of the TILE launcher: `dense`, or 3 for the dense kernel without the interior body
+    int tile_form() const { return no_interior ? 3 : dense; }
 };
 
 inline SweepLevelPlan plan_level(const SweepCall &q, const SweepSwitches &sw)
@@ -185,6 +207,8 @@ inline SweepLevelPlan plan_level(const SweepCall &q, const SweepSwitches &sw)
     // at the batch: a pair is solved by the same kernels alone and in a batch (FAST sums are
     // ordered by the lane fan-out).  VM_DENSE128=0 / 1 forces it (dev switch).
     p.dense128 = !p.exact && (sw.dense128 >= 0 ? sw.dense128 != 0 : p.tiles >= 256);
+    // (VM_NOINT_MAX_TILES) VM_DENSE_NOINT=0 / 1 forces it (dev switch)
+    p.dense_noint = !p.exact && (sw.dense_noint >= 0 ? sw.dense_noint != 0 : p.tiles <= VM_NOINT_MAX_TILES);
     p.tile_dense = sw.tile_dense;
     p.sparse_max_tiles = (double)sw.sparse_tiles;
     // PASS: the workgroups of a tile group spin at a barrier of their own, so every group of a
@@ -218,6 +242,7 @@ inline SweepBatchPlan plan_batch(const SweepLevelPlan &p, double cand_prev, doub
     b.step = split && !pass && !p.two_kernel;
     const bool lean_regime = cand_prev < p.lean_max_cand;
     b.dense = (p.exact || p.tile_dense || !lean_regime) ? (p.dense128 ? 2 : 1) : 0;
+    b.no_interior = b.dense == 1 && p.dense_noint;
     // SPARSE replaces the TILE launches of a pruned level once at most three tiles per pass
     // and pair are still active (measured on MI355X, 1080p: a no-op TILE iteration costs
     // 4 x 3.4 us, a no-op SPARSE iteration 4 x ~0.3 us; with more active tiles than that the

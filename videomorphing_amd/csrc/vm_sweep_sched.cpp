@@ -415,10 +415,11 @@ static int enqueue_tile(SweepRun &r)
         r.small_dense.leave();
     const int tile_threads = r.small_dense.in_flight() >= r.plan.corun_min_wgs ? 256 : r.plan.threads;
     uint32_t *const tile_list = r.b.use_tile_list ? c->tile_list.get() : nullptr;
+    const int form = r.b.tile_form();
     const int end = r.done + r.nb;
     int it0 = r.done;
     if (r.nb >= VM_GRAPH_ITERS) {
-        if (hipGraphExec_t ge = sweep_graph(c, c->math_mode, r.n, r.w, r.h, r.cap, r.fixed_work, tile_threads, r.b.dense, tile_list, r.P)) {
+        if (hipGraphExec_t ge = sweep_graph(c, c->math_mode, r.n, r.w, r.h, r.cap, r.fixed_work, tile_threads, form, tile_list, r.P)) {
             r.SL->next_iter(c->iter_dev.get(), 1, r.done, r.s);
             for (; it0 + VM_GRAPH_ITERS <= end; it0 += VM_GRAPH_ITERS) {
                 VM_HIP(hipGraphLaunch(ge, r.s));
@@ -428,7 +429,7 @@ static int enqueue_tile(SweepRun &r)
     }
     for (int it = it0; it < end; ++it)
         for (int k = 0; k < 4; ++k) {
-            r.SL->optimize(c->views.get(), r.n, r.cap, r.w, r.h, r.P, c->tables.get(), pass_offs[k][0], pass_offs[k][1], c->flags.get(), c->stats.get(), it, r.fixed_work, tile_threads, nullptr, r.b.dense, tile_list, r.s);
+            r.SL->optimize(c->views.get(), r.n, r.cap, r.w, r.h, r.P, c->tables.get(), pass_offs[k][0], pass_offs[k][1], c->flags.get(), c->stats.get(), it, r.fixed_work, tile_threads, nullptr, form, tile_list, r.s);
             ++r.launches;
         }
     return VM_OK;
