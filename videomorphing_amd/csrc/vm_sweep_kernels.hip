@@ -46,6 +46,9 @@
 // Commits are applied by a per-cell gather of the committed pixels' records in a
 // fixed order: deterministic, one owner per cell, no float atomics (the reference
 // uses 75 shared + 25 global float atomics per accepted pixel, morph.cu:951-1015).
+// Stages the schedules share by name: tile_cols / tile_rows / tile_ox / tile_oy (the tile grid of a pass), phase_px /
+// phase_py (the pixel of a slot), cell_count, window_row (lane -> window neighbour), commit_* (the records and new state
+// of a moved pixel), mask_update.  The line-search dispatch, the EXACT taps and the table staging are still per schedule.
 #include <algorithm>
 #include <type_traits>
 #include "vm_morph_common.h"
@@ -69,6 +72,26 @@ typedef __attribute__((address_space(1))) const float vm_g_cf32;
 __device__ __forceinline__ int mad24(int a, int b, int c) { return __mul24(a, b) + c; }
 
 namespace {
+
+// ---- small geometry names: the tile grid of a pass (morph.cu:1281-1290, 1382-1385), its phase pixels, the 5x5 window ----
+// tiles per row / column of a level of width w / height h
+__device__ __forceinline__ int tile_cols(int w) { return (w + VM_PITCH_X - 1) / VM_PITCH_X; }
+__device__ __forceinline__ int tile_rows(int h) { return (h + VM_PITCH_Y - 1) / VM_PITCH_Y; }
+// origin of tile t (row-major, gx tiles per row) of the pass offset by (offx, offy)
+__device__ __forceinline__ int tile_ox(int t, int gx, int offx) { return (t % gx) * VM_PITCH_X + offx; }
+__device__ __forceinline__ int tile_oy(int t, int gx, int offy) { return (t / gx) * VM_PITCH_Y + offy; }
+// the pixel of slot ty * 32 + tx of the tile at (ox, oy) in phase (pi, pj)
+__device__ __forceinline__ int phase_px(int ox, int slot, int pj) { return ox + (slot & 31) * 2 + pj; }
+__device__ __forceinline__ int phase_py(int oy, int slot, int pi) { return oy + (slot >> 5) * 2 + pi; }
+// thread tid of T stages its share of the 225 improving-mask table words (get_improve_mask_idx, morph.cu:621-646)
+__device__ __forceinline__ void stage_imp(uint32_t *imp, const uint32_t *tables, int tid, int T) { for (int k = tid; k < 225; k += T) imp[k] = tables[VM_TAB_IMP + k]; }
+// ... and of the 625 TPS kernel weights (25 border classes x 5 x 5)
+__device__ __forceinline__ void stage_tps(float *tps, const uint32_t *tables, int tid, int T) { for (int k = tid; k < 625; k += T) tps[k] = __uint_as_float(tables[VM_TAB_TPS + k]); }
+// in-image pixels of the 5x5 window of cell (qx, qy) of a w x h level: the `counter` of ssim()
+__device__ __forceinline__ float cell_count(int qy, int h, int qx, int w) { return (float)(window_count(qy, h) * window_count(qx, w)); }
+// row k / 5 of position k < 32 of a row-major 5x5 window (its column: k - 5 row); lane `sub` of a pixel's 32-lane
+// group owns window neighbour (px + column - 2, py + row - 2)
+__device__ __forceinline__ int window_row(int k) { return (k * 13) >> 6; }
 
 struct TileLds {
     float2 mean[VM_NCELL], var[VM_NCELL], tpsb[VM_NCELL];
@@ -119,6 +142,22 @@ __device__ __forceinline__ float temp_change(const PixelCtx &c, float dx, float 
     v_temp += fabsf(c.v.y + dy - c.tref.y) - fabsf(c.v.y - c.tref.y);
     return v_temp;
 }
+
+// commit_pixel_motion (morph.cu:990-1026), the pixel's own part: a pixel that moved by `step` from luma `ol` to `luma`
+// leaves the records rec_a = (d mean, d var) and rec_b = (d cross, step, 0) and gets a new ui.b and v
+__device__ __forceinline__ float4 commit_rec_a(float2 luma, float2 ol) { return make_float4(luma.x - ol.x, luma.y - ol.y, luma.x * luma.x - ol.x * ol.x, luma.y * luma.y - ol.y * ol.y); }
+__device__ __forceinline__ float2 commit_dmean(float2 luma, float2 ol) { return make_float2(commit_rec_a(luma, ol).x, commit_rec_a(luma, ol).y); }
+__device__ __forceinline__ float2 commit_dvar(float2 luma, float2 ol) { return make_float2(commit_rec_a(luma, ol).z, commit_rec_a(luma, ol).w); }
+__device__ __forceinline__ float commit_dcross(float lx, float ly, float ox, float oy) { return lx * ly - ox * oy; }
+__device__ __forceinline__ float2 commit_ui_b(float2 ui_b, float ui_axy, float2 step) { return make_float2(ui_b.x + 2 * step.x * ui_axy, ui_b.y + 2 * step.y * ui_axy); }
+__device__ __forceinline__ float2 commit_v(float2 v, float2 step) { return make_float2(v.x + step.x, v.y + step.y); }
+// the lumas commit_pixel_motion samples for a pixel whose motion is now (vx, vy) (morph.cu:997-1003)
+__device__ __forceinline__ float2 moved_lumas(const VmLevelView &L, int px, int py, float vx, float vy)
+{
+    return make_float2(tap(L.img0, L.w, L.h, L.rs, px - vx + 0.5f, py - vy + 0.5f), tap(L.img1, L.w, L.h, L.rs, px + vx + 0.5f, py + vy + 0.5f));
+}
+// the state of a record tag folded into a mask word: a committed pixel (1) sets its bit, a hit that did not move (2) clears it
+__device__ __forceinline__ uint32_t mask_update(uint32_t word, uint32_t bit, uint32_t state) { return state == 1u ? word | bit : state == 2u ? word & ~bit : word; }
 
 // where the 5x5 window sums of a pixel come from
 struct LdsSrc {
@@ -302,7 +341,7 @@ __device__ __forceinline__ void nb_load(NbCacheT<SMAX> &nb, const VmLevelView &L
         src.load(ok ? i : 2, ok ? jj : 2, m, q, cr, val);
         float n = 25.0f, in = 0.04f;
         if (!INTERIOR) {
-            n = ok ? (float)(window_count(qy, L.h) * window_count(qx, L.w)) : 25.0f;
+            n = ok ? cell_count(qy, L.h, qx, L.w) : 25.0f;
             in = n == 25.0f ? 0.04f : __builtin_amdgcn_rcpf(n);
             nb.N[j] = ok ? n : 0.0f; // 1/count is recomputed per evaluation: registers are scarcer than v_rcp
         }
@@ -659,11 +698,18 @@ struct NbX {
 template <class Src>
 __device__ __forceinline__ void nbx_load(NbX &nb, const VmLevelView &L, const Src &src, const PixelCtx &c, int sub)
 {
-    const int i = (sub * 13) >> 6, jj = sub - i * 5; // sub / 5, sub % 5 for sub < 32
+    const int i = window_row(sub), jj = sub - i * 5;
     const int qx = c.px + jj - 2, qy = c.py + i - 2;
     nb.ok = sub < 25 && qx >= 0 && qx < L.w && qy >= 0 && qy < L.h;
     src.load(nb.ok ? i : 2, nb.ok ? jj : 2, nb.m, nb.q, nb.cr, nb.val);
-    nb.counter = nb.ok ? (float)(window_count(qy, L.h) * window_count(qx, L.w)) : 25.0f;
+    nb.counter = nb.ok ? cell_count(qy, L.h, qx, L.w) : 25.0f;
+}
+
+// the same from a cell the caller has folded (STEP, PASS), as nb1_make
+__device__ __forceinline__ void nbx_make(NbX &nb, const VmLevelView &L, bool ok, int qx, int qy, const float2 &m, const float2 &q, float cr, float val)
+{
+    nb.ok = ok; nb.m = m; nb.q = q; nb.cr = cr; nb.val = val;
+    nb.counter = ok ? cell_count(qy, L.h, qx, L.w) : 25.0f;
 }
 
 __device__ __forceinline__ float energy_x32(const VmLevelView &L, const VmKParams &P, const NbX &nb,
@@ -752,7 +798,7 @@ template <bool INTERIOR>
 __device__ __forceinline__ bool nb1_cell(const VmLevelView &L, const PixelCtx &c, int sub, int &i, int &jj, int &qx,
                                          int &qy)
 {
-    i = (sub * 13) >> 6; // sub / 5 for sub < 32
+    i = window_row(sub);
     jj = sub - i * 5;
     qx = c.px + jj - 2;
     qy = c.py + i - 2;
@@ -765,7 +811,7 @@ __device__ __forceinline__ void nb1_make(Nb1 &nb, const VmLevelView &L, bool ok,
 {
     float n = 25.0f, in = 0.04f;
     if (!INTERIOR) {
-        n = ok ? (float)(window_count(qy, L.h) * window_count(qx, L.w)) : 25.0f;
+        n = ok ? cell_count(qy, L.h, qx, L.w) : 25.0f;
         in = n == 25.0f ? 0.04f : __builtin_amdgcn_rcpf(n);
     }
     (void)in;
@@ -1479,10 +1525,8 @@ __device__ __forceinline__ bool tile_sweep(TileLds &S, const VmLevelView &L, con
     if (!DENSE && tid < (VM_NCELL + 31) / 32)
         S.dirty[tid] = 0; // (ordered before the first gather by the barriers below)
     if (!tables_staged) { // TILE: per launch, after the early out; SPARSE: once per kernel
-        for (int k = tid; k < 625; k += T)
-            S.tps[k] = __uint_as_float(tables[VM_TAB_TPS + k]);
-        for (int k = tid; k < 225; k += T)
-            S.imp[k] = tables[VM_TAB_IMP + k];
+        stage_tps(S.tps, tables, tid, T);
+        stage_imp(S.imp, tables, tid, T);
     }
 
     // --- LoadSSIM (morph.cu:1214-1234) + the tile's tps.b ---
@@ -1527,7 +1571,7 @@ __device__ __forceinline__ bool tile_sweep(TileLds &S, const VmLevelView &L, con
             // ---- 1. candidates of this phase ----
             bool cand = false, hit = false;
             if (tid < 256) {
-                const int px = ox + (tid & 31) * 2 + pj, py = oy + (tid >> 5) * 2 + pi;
+                const int px = phase_px(ox, tid, pj), py = phase_py(oy, tid, pi);
                 int state = 0;
                 if (px < L.w && py < L.h && mask_hit(S.mask, S.imp, g, px, py)) {
                     state = 2; // in the mask: its bit is cleared unless it commits
@@ -1585,14 +1629,13 @@ __device__ __forceinline__ bool tile_sweep(TileLds &S, const VmLevelView &L, con
                         if (ok && writer) {
                             // commit_pixel_motion (morph.cu:990-1026), the pixel's own part, at once:
                             // nothing else of this phase reads its v, luma or ui.b (state 3)
-                            const float2 ol = c.old_luma;
                             S.d_step[slot] = step;
-                            S.d_mean[slot] = make_float2(luma.x - ol.x, luma.y - ol.y);
-                            S.d_var[slot] = make_float2(luma.x * luma.x - ol.x * ol.x, luma.y * luma.y - ol.y * ol.y);
-                            S.d_cross[slot] = luma.x * luma.y - ol.x * ol.y;
+                            S.d_mean[slot] = commit_dmean(luma, c.old_luma);
+                            S.d_var[slot] = commit_dvar(luma, c.old_luma);
+                            S.d_cross[slot] = commit_dcross(luma.x, luma.y, c.old_luma.x, c.old_luma.y);
                             L.luma[c.idx] = luma;
-                            L.ui_b[c.idx] = make_float2(c.ui_b.x + 2 * step.x * c.ui_axy, c.ui_b.y + 2 * step.y * c.ui_axy);
-                            L.v[c.idx] = make_float2(c.v.x + step.x, c.v.y + step.y);
+                            L.ui_b[c.idx] = commit_ui_b(c.ui_b, c.ui_axy, step);
+                            L.v[c.idx] = commit_v(c.v, step);
                             S.d_ok[slot] = 3;
                         }
                     }
@@ -1714,7 +1757,7 @@ __device__ __forceinline__ bool tile_sweep(TileLds &S, const VmLevelView &L, con
                         S.var[cell] = q;
                         S.cross[cell] = cr;
                         S.tpsb[cell] = tb;
-                        const float counter = (float)(window_count(qy, L.h) * window_count(qx, L.w));
+                        const float counter = cell_count(qy, L.h, qx, L.w);
                         S.value[cell] = ssim_value(m.x, m.y, q.x, q.y, cr, counter, P.ssim_clamp);
                     }
                 }
@@ -1820,7 +1863,7 @@ __global__ __launch_bounds__(VM_SWEEP_T) __attribute__((amdgpu_waves_per_eu(DENS
         return;
     if (tid == 0) {
         if (improving)
-            flags[iter_idx] = 1u; // every writer stores the same 1: no atomic needed (see k_step)
+            flags[iter_idx] = 1u; // every writer stores the same 1: no atomic needed (see k_step, at its *my_slot store)
         // per-iteration activity counters: active tiles, line searches, commits
         atomicAdd(&stats[iter_idx * VM_STAT_WORDS + 0], 1u);
         atomicAdd(&stats[iter_idx * VM_STAT_WORDS + 1], st_cand);
@@ -1863,7 +1906,7 @@ __global__ __launch_bounds__(256) void SUF(k_tile_scan)(const VmLevelView *__res
     if (!fixed_work && iter_idx > 0 && flags[(size_t)z * cap + iter_idx - 1] == 0)
         return; // converged in the previous iteration (sticky)
     const VmLevelView L = views[z];
-    const int gx = (L.w + VM_PITCH_X - 1) / VM_PITCH_X, gy = (L.h + VM_PITCH_Y - 1) / VM_PITCH_Y;
+    const int gx = tile_cols(L.w), gy = tile_rows(L.h);
     const int nwords = L.imp_rs * L.imp_rows;
     uint32_t *const stamp = tl + 4 * (size_t)cap + (size_t)z * tiles_stride;
     uint32_t *const entries = tl + 4 * (size_t)cap + (size_t)gridDim.z * tiles_stride;
@@ -1898,16 +1941,14 @@ __global__ __launch_bounds__(VM_SWEEP_T) __attribute__((amdgpu_waves_per_eu(4)))
     if (blockIdx.x >= cnt)
         return;
     const uint32_t *const entries = tl + 4 * (size_t)cap + (size_t)nbatch * tiles_stride;
-    for (int k = tid; k < 625; k += T)
-        S.tps[k] = __uint_as_float(tables[VM_TAB_TPS + k]);
-    for (int k = tid; k < 225; k += T)
-        S.imp[k] = tables[VM_TAB_IMP + k];
+    stage_tps(S.tps, tables, tid, T);
+    stage_imp(S.imp, tables, tid, T);
     for (uint32_t e = blockIdx.x; e < cnt; e += gridDim.x) {
         const uint32_t ent = entries[e];
         const int z = (int)(ent >> 16), t = (int)(ent & 0xFFFFu);
         const VmLevelView L = views[z];
-        const int gx = (L.w + VM_PITCH_X - 1) / VM_PITCH_X;
-        const int ox = (t % gx) * VM_PITCH_X + offx, oy = (t / gx) * VM_PITCH_Y + offy;
+        const int gx = tile_cols(L.w);
+        const int ox = tile_ox(t, gx, offx), oy = tile_oy(t, gx, offy);
         if (tid == 0)
             S.n_eval = 0; // ordered before its first use by the barriers of tile_sweep
         bool improving = false;
@@ -2281,14 +2322,13 @@ __device__ __forceinline__ bool sv_phases(TileLds &S, SvPix &X, SparseLds &Q, co
                                 // commit_pixel_motion (morph.cu:990-1026), the pixel's own part, at once: nothing
                                 // else of this phase reads its v, luma or ui.b; its record for the cells' gather;
                                 // its mask bit
-                                const float2 ol = c.old_luma;
                                 S.d_step[slot] = step;
-                                S.d_mean[slot] = make_float2(luma.x - ol.x, luma.y - ol.y);
-                                S.d_var[slot] = make_float2(luma.x * luma.x - ol.x * ol.x, luma.y * luma.y - ol.y * ol.y);
-                                S.d_cross[slot] = luma.x * luma.y - ol.x * ol.y;
+                                S.d_mean[slot] = commit_dmean(luma, c.old_luma);
+                                S.d_var[slot] = commit_dvar(luma, c.old_luma);
+                                S.d_cross[slot] = commit_dcross(luma.x, luma.y, c.old_luma.x, c.old_luma.y);
                                 X.luma[pc] = luma;
-                                X.uib[pc] = make_float2(c.ui_b.x + 2 * step.x * c.ui_axy, c.ui_b.y + 2 * step.y * c.ui_axy);
-                                X.v[pc] = make_float2(c.v.x + step.x, c.v.y + step.y);
+                                X.uib[pc] = commit_ui_b(c.ui_b, c.ui_axy, step);
+                                X.v[pc] = commit_v(c.v, step);
                                 atomicOr(&X.dirty[pc >> 5], 1u << (pc & 31));
                                 atomicOr(&ph_commit[ty], 1u << tx);
                                 atomicOr(mw, mb);
@@ -2345,7 +2385,7 @@ __device__ __forceinline__ bool sv_phases(TileLds &S, SvPix &X, SparseLds &Q, co
                     S.var[cell] = q;
                     S.cross[cell] = cr;
                     S.tpsb[cell] = tb;
-                    const float counter = (float)(window_count(qy, L.h) * window_count(qx, L.w));
+                    const float counter = cell_count(qy, L.h, qx, L.w);
                     S.value[cell] = ssim_value(m.x, m.y, q.x, q.y, cr, counter, P.ssim_clamp);
                 }
             }
@@ -2413,11 +2453,11 @@ __global__ __launch_bounds__(VM_SWEEP_T) __attribute__((amdgpu_waves_per_eu(1)))
     stats += (size_t)blockIdx.z * cap * VM_STAT_WORDS;
     if (!fixed_work && it0 > 0 && flags[it0 - 1] == 0)
         return; // converged in the previous iteration (sticky)
-    for (int k = tid; k < 625; k += T)
+    for (int k = tid; k < 625; k += T) // (stage_tps / stage_imp, spelled out: through the calls k_sparse<false> comes out different)
         S.tps[k] = __uint_as_float(tables[VM_TAB_TPS + k]);
     for (int k = tid; k < 225; k += T)
         S.imp[k] = tables[VM_TAB_IMP + k];
-    const int gx = (L.w + VM_PITCH_X - 1) / VM_PITCH_X, gy = (L.h + VM_PITCH_Y - 1) / VM_PITCH_Y;
+    const int gx = tile_cols(L.w), gy = tile_rows(L.h);
     const int ntw = (gx * gy + 31) / 32; // <= 256 (the host checks)
     const int nwords = L.imp_rs * L.imp_rows;
     uint32_t *const lists[2] = {L.sp_wl, L.sp_wl + nwords};
@@ -2502,7 +2542,7 @@ __global__ __launch_bounds__(VM_SWEEP_T) __attribute__((amdgpu_waves_per_eu(1)))
                 // rectangle + 2 meets the virtual tile, tested as tile_sweep's early out tests them
                 const int ax = V.vx - (VM_TILE_W + 1) - offx, bx = V.vx + (VM_TILE_W + 1) - offx;
                 const int ay = V.vy - (VM_TILE_H + 1) - offy, by = V.vy + (VM_TILE_H + 1) - offy;
-                const int c_lo = ax > 0 ? (ax + VM_PITCH_X - 1) / VM_PITCH_X : 0, r_lo = ay > 0 ? (ay + VM_PITCH_Y - 1) / VM_PITCH_Y : 0;
+                const int c_lo = ax > 0 ? (ax + VM_PITCH_X - 1) / VM_PITCH_X : 0, r_lo = ay > 0 ? (ay + VM_PITCH_Y - 1) / VM_PITCH_Y : 0; // first tile at or right of / below the edge
                 const int c_hi = bx >= 0 ? min(bx / VM_PITCH_X, gx - 1) : -1, r_hi = by >= 0 ? min(by / VM_PITCH_Y, gy - 1) : -1;
                 if (tid < 128) { // the <= 96 words of a window sit in waves 0 and 1
                     uint32_t mine = 0;
@@ -2585,7 +2625,7 @@ __global__ __launch_bounds__(VM_SWEEP_T) __attribute__((amdgpu_waves_per_eu(1)))
                 while (bits) {
                     const int t = pass_resident ? (int)((rtl >> (16 * wd)) & 0xFFFFu) : (ntl <= 64 ? Q.tl[wd] : wd * 32 + __ffs(bits) - 1);
                     bits &= bits - 1;
-                    const int ox = (t % gx) * VM_PITCH_X + offx, oy = (t / gx) * VM_PITCH_Y + offy;
+                    const int ox = tile_ox(t, gx, offx), oy = tile_oy(t, gx, offy);
                     bool visited;
 #if !VM_EXACT
                     if constexpr (LEAN) {
@@ -2696,7 +2736,7 @@ __global__ __launch_bounds__(VM_SWEEP_T) __attribute__((amdgpu_waves_per_eu(1)))
             } else {
                 for (int d = 0; d < nd; ++d) {
                     const int t = Q.done[d];
-                    const int ox = (t % gx) * VM_PITCH_X + offx, oy = (t / gx) * VM_PITCH_Y + offy;
+                    const int ox = tile_ox(t, gx, offx), oy = tile_oy(t, gx, offy);
                     const MaskGeom g = mask_geom(L, ox, oy);
                     if (tid < g.nbx * g.nby) {
                         const int mx = tid % g.nbx, my = tid / g.nbx;
@@ -2760,8 +2800,8 @@ __global__ __launch_bounds__(VM_SWEEP_T) void SUF(k_decide)(const VmLevelView *_
     if (!fixed_work && iter_idx > 0 && flags[iter_idx - 1] == 0)
         return;
     const int part = blockIdx.x % parts, tile = blockIdx.x / parts;
-    const int gxn = (L.w + VM_PITCH_X - 1) / VM_PITCH_X;
-    const int ox = (tile % gxn) * VM_PITCH_X + offx, oy = (tile / gxn) * VM_PITCH_Y + offy;
+    const int gxn = tile_cols(L.w);
+    const int ox = tile_ox(tile, gxn, offx), oy = tile_oy(tile, gxn, offy);
     if (ox >= L.w || oy >= L.h)
         return;
     const MaskGeom g = mask_geom(L, ox, oy);
@@ -2772,8 +2812,7 @@ __global__ __launch_bounds__(VM_SWEEP_T) void SUF(k_decide)(const VmLevelView *_
         mymask = L.impmask[(g.by0 + my + 1) * L.imp_rs + (g.bx0 + mx + 1)];
         S.mask[my][mx] = mymask;
     }
-    for (int k = tid; k < 225; k += T)
-        S.imp[k] = tables[VM_TAB_IMP + k];
+    stage_imp(S.imp, tables, tid, T);
     if (tid >= 256 && tid < 256 + 25) // ctx_load only needs the centre weight of each border class
         S.tps[(tid - 256) * 25 + 12] = __uint_as_float(tables[VM_TAB_TPS + (tid - 256) * 25 + 12]);
     if (T < 512 && tid < 25)
@@ -2787,7 +2826,7 @@ __global__ __launch_bounds__(VM_SWEEP_T) void SUF(k_decide)(const VmLevelView *_
     // workgroups of the tile, entry i belongs to workgroup i % parts
     bool hit = false;
     if (tid < 256) {
-        const int px = ox + (tid & 31) * 2 + pj, py = oy + (tid >> 5) * 2 + pi;
+        const int px = phase_px(ox, tid, pj), py = phase_py(oy, tid, pi);
         hit = px < L.w && py < L.h && mask_hit(S.mask, S.imp, g, px, py);
     }
     const int n_hit = compact256(hit, tid, S.list, S.wave_cnt);
@@ -2800,7 +2839,7 @@ __global__ __launch_bounds__(VM_SWEEP_T) void SUF(k_decide)(const VmLevelView *_
     for (int base = 0; base < n_mine; base += slots) {
         const int m = base + grp;
         const int slot = S.list[part + parts * min(m, n_mine - 1)];
-        const int px = ox + (slot & 31) * 2 + pj, py = oy + (slot >> 5) * 2 + pi;
+        const int px = phase_px(ox, slot, pj), py = phase_py(oy, slot, pi);
         const bool wave_interior = __all(m >= n_mine || is_interior(L, px, py));
         if (m < n_mine) {
             uint32_t state = 2;
@@ -2815,11 +2854,8 @@ __global__ __launch_bounds__(VM_SWEEP_T) void SUF(k_decide)(const VmLevelView *_
 #if VM_EXACT
                 (void)wave_interior;
                 const bool ok = decide_x32(L, P, src, c, sub, step, n_eval);
-                if (ok) { // the lumas commit_pixel_motion samples (morph.cu:997-1003)
-                    const float nvx = c.v.x + step.x, nvy = c.v.y + step.y;
-                    luma.x = tap(L.img0, L.w, L.h, L.rs, px - nvx + 0.5f, py - nvy + 0.5f);
-                    luma.y = tap(L.img1, L.w, L.h, L.rs, px + nvx + 0.5f, py + nvy + 0.5f);
-                }
+                if (ok)
+                    luma = moved_lumas(L, px, py, c.v.x + step.x, c.v.y + step.y);
 #else
                 Nb1 nb;
                 bool ok;
@@ -2841,14 +2877,13 @@ __global__ __launch_bounds__(VM_SWEEP_T) void SUF(k_decide)(const VmLevelView *_
                 if (state == 1) {
                     // commit_pixel_motion (morph.cu:990-1026), the pixel's own part
                     const float2 ol = c.old_luma;
-                    ra = make_float4(luma.x - ol.x, luma.y - ol.y, luma.x * luma.x - ol.x * ol.x,
-                                     luma.y * luma.y - ol.y * ol.y);
-                    rb.x = luma.x * luma.y - ol.x * ol.y;
+                    ra = commit_rec_a(luma, ol);
+                    rb.x = commit_dcross(luma.x, luma.y, ol.x, ol.y);
                     rb.y = step.x;
                     rb.z = step.y;
                     L.luma[c.idx] = luma;
-                    L.ui_b[c.idx] = make_float2(c.ui_b.x + 2 * step.x * c.ui_axy, c.ui_b.y + 2 * step.y * c.ui_axy);
-                    L.v[c.idx] = make_float2(c.v.x + step.x, c.v.y + step.y);
+                    L.ui_b[c.idx] = commit_ui_b(c.ui_b, c.ui_axy, step);
+                    L.v[c.idx] = commit_v(c.v, step);
                     L.rec_a[c.idx] = ra;
                 }
                 if (state == 1)
@@ -2885,7 +2920,7 @@ __global__ __launch_bounds__(1024) void SUF(k_commit)(const VmLevelView *__restr
     uint32_t bit = 0;
     int mcx = 0, mcy = 0;
     if (tid < 256) {
-        const int px = ox + (tid & 31) * 2 + pj, py = oy + (tid >> 5) * 2 + pi;
+        const int px = phase_px(ox, tid, pj), py = phase_py(oy, tid, pi);
         if (px < L.w && py < L.h) {
             const uint32_t r = L.rec_tag[py * L.rs + px];
             const float4 rb = L.rec_b[py * L.rs + px];
@@ -2908,8 +2943,7 @@ __global__ __launch_bounds__(1024) void SUF(k_commit)(const VmLevelView *__restr
         const int k = tid - 256, mx = k % g.nbx, my = k / g.nbx;
         S.mask[my][mx] = L.impmask[(g.by0 + my + 1) * L.imp_rs + (g.bx0 + mx + 1)];
     }
-    for (int k = tid; k < 625; k += T)
-        S.tps[k] = __uint_as_float(tables[VM_TAB_TPS + k]);
+    stage_tps(S.tps, tables, tid, T);
     float2 cm[2], cq[2], ctb[2];
     float ccr[2];
     int cgi[2];
@@ -2954,7 +2988,7 @@ __global__ __launch_bounds__(1024) void SUF(k_commit)(const VmLevelView *__restr
             L.cross[gi] = cr;
             L.tps_b[gi] = tb;
             const int qx = ox + rx, qy = oy + ry;
-            const float counter = (float)(window_count(qy, L.h) * window_count(qx, L.w));
+            const float counter = cell_count(qy, L.h, qx, L.w);
             L.value[gi] = ssim_value(m.x, m.y, q.x, q.y, cr, counter, P.ssim_clamp);
         }
     }
@@ -2965,7 +2999,7 @@ __global__ __launch_bounds__(1024) void SUF(k_commit)(const VmLevelView *__restr
     }
     if (tid == 0) {
         if (ncommit)
-            flags[iter_idx] = 1u; // every writer stores the same 1: no atomic needed (see k_step)
+            flags[iter_idx] = 1u; // every writer stores the same 1: no atomic needed (see k_step, at its *my_slot store)
         atomicAdd(&stats[iter_idx * VM_STAT_WORDS + 3], 1u); // tile-phases with records
         atomicAdd(&stats[iter_idx * VM_STAT_WORDS + 1], (uint32_t)n_rec);
         atomicAdd(&stats[iter_idx * VM_STAT_WORDS + 2], (uint32_t)ncommit);
@@ -2979,7 +3013,7 @@ __global__ __launch_bounds__(1024) void SUF(k_commit)(const VmLevelView *__restr
 // a step reads copy `src` (state before the records of phase s-1 were folded in) and
 //  - its FOLD workgroups (one per 64x16 block of the level, geometry-free) write
 //    sums + records(s-1) -> copy `dst`, whole level;
-//  - its DECIDE workgroups (tiles x parts, as k_decide) fold the same records privately,
+//  - its DECIDE workgroups (tiles x parts: tile_ox / tile_oy and the candidate list of k_decide) fold the same records privately,
 //    per lane, into the one window cell the lane owns, run the 32-lane line search and
 //    write the pixel's own state + records(s).
 // Folding is defined by image coordinates only -- a record of epoch s-1 reaches every
@@ -3085,7 +3119,7 @@ __device__ __forceinline__ bool fold_cell(const VmLevelView &L, const float4 *__
 #endif
             bidx[k] = b;
             const int bb = max(b, 0);
-            const int dy = (bb * 13) >> 6, dx = bb - dy * 5;
+            const int dy = window_row(bb), dx = bb - dy * 5;
             const int rsafe = b >= 0 ? (qy + dy - 2) * L.rs + (qx + dx - 2) : qy * L.rs + qx;
             ra[k] = rec_load<COH>(r_a + rsafe);
             rb[k] = rec_load<COH>(r_b + rsafe);
@@ -3095,7 +3129,7 @@ __device__ __forceinline__ bool fold_cell(const VmLevelView &L, const float4 *__
             const int b = bidx[k];
             if (b < 0)
                 continue;
-            const int dy = (b * 13) >> 6, dx = b - dy * 5;
+            const int dy = window_row(b), dx = b - dy * 5;
             const int x = qx + dx - 2, y = qy + dy - 2;
             m.x += ra[k].x;
             m.y += ra[k].y;
@@ -3141,8 +3175,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(T / 128))) vo
     float4 *w_a = w1 ? L.rec_a2 : L.rec_a, *w_b = w1 ? L.rec_b2 : L.rec_b;
     const uint32_t want = (pe << 2) | 1u;
 
-    for (int k = tid; k < 625; k += T)
-        S.tps[k] = __uint_as_float(tables[VM_TAB_TPS + k]);
+    stage_tps(S.tps, tables, tid, T);
     if (tid < VM_STEP_BH * 4)
         S.bits[tid >> 2][tid & 3] = 0;
 
@@ -3184,22 +3217,17 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(T / 128))) vo
             const int my = wi / L.imp_rs, mx = wi - my * L.imp_rs;
             uint32_t word = s_imp[wi];
             if (mx >= 1 && my >= 1 && (mx - 1) * 5 < L.w && (my - 1) * 5 < L.h) {
-                // a committed pixel sets its bit, a hit that did not move clears it
                 uint32_t tw[25];
 #pragma unroll
                 for (int k = 0; k < 25; ++k) {
-                    const int dy = (k * 13) >> 6, dx = k - dy * 5;
+                    const int dy = window_row(k), dx = k - dy * 5;
                     const int x = (mx - 1) * 5 + dx, y = (my - 1) * 5 + dy;
                     tw[k] = (x < L.w && y < L.h) ? r_tag[y * L.rs + x] : 0u;
                 }
 #pragma unroll
                 for (int k = 0; k < 25; ++k)
-                    if ((tw[k] >> 2) == pe) {
-                        if ((tw[k] & 3u) == 1u)
-                            word |= 1u << k;
-                        else if ((tw[k] & 3u) == 2u)
-                            word &= ~(1u << k);
-                    }
+                    if ((tw[k] >> 2) == pe)
+                        word = mask_update(word, 1u << k, tw[k] & 3u);
             }
             d_imp[wi] = word;
         }
@@ -3223,7 +3251,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(T / 128))) vo
             if (!in)
                 continue;
             if (touched) {
-                const float counter = (float)(window_count(qy, L.h) * window_count(qx, L.w));
+                const float counter = cell_count(qy, L.h, qx, L.w);
                 val = ssim_value(m.x, m.y, q.x, q.y, cr, counter, P.ssim_clamp);
             } else if (in_place) {
                 continue;
@@ -3236,7 +3264,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(T / 128))) vo
             d_value[gi] = val;
         }
         // Activity counters: a decide workgroup leaves its counts in a slot (a plain store); the
-        // first fold workgroup of the NEXT launch adds them up.  Five agent-scope atomics per
+        // first fold workgroup of the NEXT launch adds them up (PASS: pass_sum_slots, which says where the two differ).  Five agent-scope atomics per
         // workgroup on one line were 0.8 us of every launch (they drain at memory, and the launch
         // cannot end before they have).
         if (blockIdx.x == 0 && prev_iter_idx >= 0) {
@@ -3279,8 +3307,8 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(T / 128))) vo
         return;
     }
     const int part = bid % parts, tile = bid / parts;
-    const int gxn = (L.w + VM_PITCH_X - 1) / VM_PITCH_X;
-    const int ox = (tile % gxn) * VM_PITCH_X + offx, oy = (tile / gxn) * VM_PITCH_Y + offy;
+    const int gxn = tile_cols(L.w);
+    const int ox = tile_ox(tile, gxn, offx), oy = tile_oy(tile, gxn, offy);
     if (ox >= L.w || oy >= L.h) {
         if (tid == 0)
             *my_slot = make_uint4(0, 0, 0, 0);
@@ -3298,8 +3326,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(T / 128))) vo
     }
     if (tid < g.nbx * g.nby)
         S.mask[tid / g.nbx][tid % g.nbx] = s_imp[(g.by0 + tid / g.nbx + 1) * L.imp_rs + (g.bx0 + tid % g.nbx + 1)];
-    for (int k = tid; k < 225; k += T)
-        S.imp[k] = tables[VM_TAB_IMP + k];
+    stage_imp(S.imp, tables, tid, T);
     if (tid == 0) {
         S.n_commit = 0;
         S.n_eval = 0;
@@ -3329,7 +3356,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(T / 128))) vo
 
     bool hit = false;
     if (tid < 256) {
-        const int px = ox + (tid & 31) * 2 + pj, py = oy + (tid >> 5) * 2 + pi;
+        const int px = phase_px(ox, tid, pj), py = phase_py(oy, tid, pi);
         hit = px < L.w && py < L.h && mask_hit(S.mask, S.imp, g, px, py);
     }
     const int n_hit = compact256(hit, tid, S.list, S.wave_cnt);
@@ -3348,7 +3375,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(T / 128))) vo
     for (int base = 0; base < n_mine; base += slots) {
         const int mi = base + grp;
         const int slot = S.list[part + parts * min(mi, n_mine - 1)];
-        const int px = ox + (slot & 31) * 2 + pj, py = oy + (slot >> 5) * 2 + pi;
+        const int px = phase_px(ox, slot, pj), py = phase_py(oy, slot, pi);
         const bool wave_interior = __all(mi >= n_mine || is_interior(L, px, py));
         const bool live = mi < n_mine && !pixel_locked(L, P.bcond, px, py);
         uint32_t state = 2;
@@ -3362,7 +3389,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(T / 128))) vo
         // the pixel's own cell with no records
         ctx_load(c, L, S.tps, px, py);
         // the lane's window cell: sums of copy `src` + the records of the last phase
-        const int i = (sub * 13) >> 6, jj = sub - i * 5; // lane sub < 25 owns neighbour (sub % 5 - 2, sub / 5 - 2)
+        const int i = window_row(sub), jj = sub - i * 5;
         const int qx = px + jj - 2, qy = py + i - 2;
         const bool okc = sub < 25 && qx >= 0 && qx < L.w && qy >= 0 && qy < L.h;
         const int cx = okc ? qx : px, cy = okc ? qy : py, gi = cy * L.rs + cx;
@@ -3370,7 +3397,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(T / 128))) vo
         float cr = s_cross[gi], val = s_value[gi];
         const uint32_t hits = live && okc ? cell_hits(S.bits, bx0, by0, cx, cy) : 0u;
         if (fold_cell(L, r_a, r_b, S.tps, hits, cx, cy, m, q, cr, tb, P.commit_order)) {
-            const float counter = (float)(window_count(cy, L.h) * window_count(cx, L.w));
+            const float counter = cell_count(cy, L.h, cx, L.w);
             val = ssim_value(m.x, m.y, q.x, q.y, cr, counter, P.ssim_clamp);
         }
         // tps.b of the pixel itself is the folded value of its own cell (lane 12)
@@ -3381,12 +3408,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(T / 128))) vo
 #if VM_EXACT
             (void)wave_interior;
             NbX nb;
-            nb.ok = okc;
-            nb.m = m;
-            nb.q = q;
-            nb.cr = cr;
-            nb.val = val;
-            nb.counter = okc ? (float)(window_count(qy, L.h) * window_count(qx, L.w)) : 25.0f;
+            nbx_make(nb, L, okc, qx, qy, m, q, cr, val);
             if (wide)
                 ok = decide_with64(
                     L, P, c, [&](float dx, float dy) { return energy_x32(L, P, nb, c, dx, dy); }, RingGlobal{L.v},
@@ -3394,11 +3416,8 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(T / 128))) vo
             else
                 ok = decide_with(
                     L, P, c, [&](float dx, float dy) { return energy_x32(L, P, nb, c, dx, dy); }, RingGlobal{L.v}, step, n_eval);
-            if (ok) { // the lumas commit_pixel_motion samples (morph.cu:997-1003)
-                const float nvx = c.v.x + step.x, nvy = c.v.y + step.y;
-                luma.x = tap(L.img0, L.w, L.h, L.rs, px - nvx + 0.5f, py - nvy + 0.5f);
-                luma.y = tap(L.img1, L.w, L.h, L.rs, px + nvx + 0.5f, py + nvy + 0.5f);
-            }
+            if (ok)
+                luma = moved_lumas(L, px, py, c.v.x + step.x, c.v.y + step.y);
 #else
             Nb1 nb;
             if (wide) {
@@ -3425,13 +3444,11 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(T / 128))) vo
             if (n_eval)
                 atomicAdd(&S.n_eval, n_eval);
             if (state == 1) {
-                const float2 ol = c.old_luma;
-                w_a[c.idx] = make_float4(luma.x - ol.x, luma.y - ol.y, luma.x * luma.x - ol.x * ol.x,
-                                         luma.y * luma.y - ol.y * ol.y);
-                w_b[c.idx] = make_float4(luma.x * luma.y - ol.x * ol.y, step.x, step.y, 0.0f);
+                w_a[c.idx] = commit_rec_a(luma, c.old_luma);
+                w_b[c.idx] = make_float4(commit_dcross(luma.x, luma.y, c.old_luma.x, c.old_luma.y), step.x, step.y, 0.0f);
                 L.luma[c.idx] = luma;
-                L.ui_b[c.idx] = make_float2(c.ui_b.x + 2 * step.x * c.ui_axy, c.ui_b.y + 2 * step.y * c.ui_axy);
-                L.v[c.idx] = make_float2(c.v.x + step.x, c.v.y + step.y);
+                L.ui_b[c.idx] = commit_ui_b(c.ui_b, c.ui_axy, step);
+                L.v[c.idx] = commit_v(c.v, step);
                 ++my_commits;
             }
             w_tag[c.idx] = (epoch << 2) | state;
@@ -3546,7 +3563,9 @@ template <class T> __device__ __forceinline__ void sto(const char *base, uint32_
 #define VM_PASS_TIMEOUT_TICKS 200000000ull // 2 s of the 100 MHz wall clock
 
 // one wave adds the per-workgroup count slots of a finished PASS launch into the counters of
-// iteration `it`, pair by pair (slot k belongs to group (k >> 8) * 8 + (k & 7))
+// iteration `it`, pair by pair (slot k belongs to group (k >> 8) * 8 + (k & 7)).  Not the slot fold of k_step: there a launch
+// holds one pair per blockIdx.z, a whole workgroup sums all `nslot` slots through LDS atomics and the fourth word counts
+// tile-phases (st[3]); here a launch holds all pairs, slots go by group -> pair, one wave sums with shuffles, the fourth is tile visits (st[0]).
 __device__ __forceinline__ void pass_sum_slots(uint32_t *stats0, const uint32_t *slots, int it, int nslot, int ntiles,
                                                int ngroups, int cap, int lane, bool spread)
 {
@@ -3606,8 +3625,8 @@ __global__ __launch_bounds__(VM_PASS_T) __attribute__((amdgpu_waves_per_eu(2, 2)
     uint32_t *const stats0 = stats;
     unsigned long long *const bar = (unsigned long long *)(sync + (size_t)grp * VM_PASS_SYNC_WORDS);
     uint32_t *const flg = sync + (size_t)grp * VM_PASS_SYNC_WORDS + 32;
-    const int gxn = (L.w + VM_PITCH_X - 1) / VM_PITCH_X;
-    const int ox = (tile % gxn) * VM_PITCH_X + offx, oy = (tile / gxn) * VM_PITCH_Y + offy;
+    const int gxn = tile_cols(L.w);
+    const int ox = tile_ox(tile, gxn, offx), oy = tile_oy(tile, gxn, offy);
     const MaskGeom g = mask_geom(L, ox, oy);
     // (requested before the tables are copied: one round trip for both)
     uint32_t early_word = 0;
@@ -3616,10 +3635,8 @@ __global__ __launch_bounds__(VM_PASS_T) __attribute__((amdgpu_waves_per_eu(2, 2)
     const uint32_t prev_flag = (!fixed_work && iter_idx > 0) ? flags[iter_idx - 1] : 1u;
     // a barrier of an earlier launch of this batch timed out: the host will discard the batch -- do not wait again
     const uint32_t err_before = ldc(err);
-    for (int k = tid; k < 625; k += VM_PASS_T)
-        S.tps[k] = __uint_as_float(tables[VM_TAB_TPS + k]);
-    for (int k = tid; k < 225; k += VM_PASS_T)
-        S.imp[k] = tables[VM_TAB_IMP + k];
+    stage_tps(S.tps, tables, tid, VM_PASS_T);
+    stage_imp(S.imp, tables, tid, VM_PASS_T);
     if (tid == 0) {
         S.n_cand = S.n_commit = S.n_eval = 0;
         S.go = 1;
@@ -3854,7 +3871,7 @@ __global__ __launch_bounds__(VM_PASS_T) __attribute__((amdgpu_waves_per_eu(2, 2)
         const int phx = 2 + 2 * tx + pj, phy = 2 + 2 * ty + pi;
         const int ohx0 = tx == 0 ? 0 : phx, ohx1 = tx == 31 ? VM_HALO_W - 1 : phx + 1;
         const int ohy0 = ty == 0 ? 0 : phy, ohy1 = ty == 7 ? VM_HALO_H - 1 : phy + 1;
-        const int wi_ = (sub * 13) >> 6, wj_ = sub - wi_ * 5;
+        const int wi_ = window_row(sub), wj_ = sub - wi_ * 5;
         int chx, chy;
         if (sub < 25) {
             chx = phx + wj_ - 2;
@@ -3993,7 +4010,7 @@ __global__ __launch_bounds__(VM_PASS_T) __attribute__((amdgpu_waves_per_eu(2, 2)
                 __builtin_amdgcn_wave_barrier();
             }
             if (touched) {
-                const float counter = (float)(window_count(qy, L.h) * window_count(qx, L.w));
+                const float counter = cell_count(qy, L.h, qx, L.w);
                 val = ssim_value(m.x, m.y, q.x, q.y, cr, counter, P.ssim_clamp);
             }
             // the cells this slot owns go to the other copy of the sums
@@ -4037,20 +4054,17 @@ __global__ __launch_bounds__(VM_PASS_T) __attribute__((amdgpu_waves_per_eu(2, 2)
                 c.tps_b.y = __shfl(tb.y, 12, 32);
                 bool ok;
 #if VM_EXACT
-                NbX nb;
+                NbX nb; // (nbx_make, spelled out: through the call this kernel's code comes out different)
                 nb.ok = okc;
                 nb.m = m;
                 nb.q = q;
                 nb.cr = cr;
                 nb.val = val;
-                nb.counter = okc ? (float)(window_count(qy, L.h) * window_count(qx, L.w)) : 25.0f;
+                nb.counter = okc ? cell_count(qy, L.h, qx, L.w) : 25.0f;
                 ok = decide_with64(
                     L, P, c, [&](float dx, float dy) { return energy_x32(L, P, nb, c, dx, dy); }, ring, hi, step, n_eval);
-                if (ok) { // the lumas commit_pixel_motion samples (morph.cu:997-1003)
-                    const float nvx = c.v.x + step.x, nvy = c.v.y + step.y;
-                    luma.x = tap(L.img0, L.w, L.h, L.rs, px - nvx + 0.5f, py - nvy + 0.5f);
-                    luma.y = tap(L.img1, L.w, L.h, L.rs, px + nvx + 0.5f, py + nvy + 0.5f);
-                }
+                if (ok)
+                    luma = moved_lumas(L, px, py, c.v.x + step.x, c.v.y + step.y);
 #else
                 Nb1 nb;
                 if (is_interior(L, px, py)) { // wave-uniform: one pixel per wave
@@ -4068,12 +4082,11 @@ __global__ __launch_bounds__(VM_PASS_T) __attribute__((amdgpu_waves_per_eu(2, 2)
             if (lane == 0) {
                 if (state == 1) {
                     const float2 ol = c.old_luma;
-                    sto<float4>(wb, o_wa + (p4 << 2), make_float4(luma.x - ol.x, luma.y - ol.y, luma.x * luma.x - ol.x * ol.x,
-                                                                luma.y * luma.y - ol.y * ol.y), wt);
-                    sto<float4>(wb, o_wb + (p4 << 2), make_float4(luma.x * luma.y - ol.x * ol.y, step.x, step.y, 0.0f), wt);
+                    sto<float4>(wb, o_wa + (p4 << 2), commit_rec_a(luma, ol), wt);
+                    sto<float4>(wb, o_wb + (p4 << 2), make_float4(commit_dcross(luma.x, luma.y, ol.x, ol.y), step.x, step.y, 0.0f), wt);
                     sto<float2>(sb, o_luma + p8, luma, wt);
-                    sto<float2>(sb, o_uib + p8, make_float2(c.ui_b.x + 2 * step.x * c.ui_axy, c.ui_b.y + 2 * step.y * c.ui_axy), wt);
-                    sto<float2>(sb, p8, make_float2(c.v.x + step.x, c.v.y + step.y), wt);
+                    sto<float2>(sb, o_uib + p8, commit_ui_b(c.ui_b, c.ui_axy, step), wt);
+                    sto<float2>(sb, p8, make_float2(c.v.x + step.x, c.v.y + step.y), wt); // (commit_v: through the call the EXACT builds come out different)
                 }
                 sto<uint32_t>(wb, o_wtag + p4, (epoch << 2) | state, wt);
             }
@@ -4103,7 +4116,7 @@ __global__ __launch_bounds__(VM_PASS_T) __attribute__((amdgpu_waves_per_eu(2, 2)
     __syncthreads();
     if (tid == 0) {
         if (S.n_commit)
-            flags[iter_idx] = 1u; // every writer stores the same 1 (see k_step)
+            flags[iter_idx] = 1u; // every writer stores the same 1 (see k_step, at its *my_slot store)
         *my_slot = make_uint4(S.n_cand, S.n_commit, S.n_eval, part == 0 ? 1u : 0u);
         if (b == 0)
             clock_probe(stats0 + (size_t)iter_idx * VM_STAT_WORDS, true);
