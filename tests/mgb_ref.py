@@ -1,4 +1,5 @@
-"""Plain numpy statement of the compositor's linear solver (videomorphing_amd/csrc/vm_mgb.h): the hierarchy, one V cycle
+"""Plain numpy statement of the compositor's linear solver (videomorphing_amd/csrc/vm_mgb.h, its host rules
+vm_mgb_plan.h): the hierarchy, one V cycle
 z = M^-1 r stage by stage, and the preconditioned CG around it.  Written from the header's description, not from the kernels'
 structure: whole-grid arrays, one half-sweep at a time, nothing tiled, nothing fused, nothing "in differences".
 
@@ -10,7 +11,7 @@ h x (w - 1); ws[y, x] of (x, y) - (x, y + 1), shape (h - 1) x w.
 """
 import numpy as np
 
-# vm_mgb.h
+# vm_mgb_plan.h
 COARSEST = 64            # VM_MGB_COARSEST: the hierarchy ends at a grid of at most this many cells ...
 MAXLEV = 14              # VM_MGB_MAXLEV: ... or at this many levels
 COARSE_SWEEPS = 2        # VM_MGB_COARSE_SWEEPS: symmetric sweeps each way on the coarsest grid
@@ -19,7 +20,8 @@ NU_POISSON, NU_QPATH = (1, 1, 2), (1,)             # VM_MGB_NU_POISSON / _QPATH
 
 
 # ---------------------------------------------------------------------------
-# the rules of the driver (vm_poisson_api.cpp), restated
+# the rules of the hierarchy (vm_mgb_plan.h: mg_sizes, mg_tail_level, mg_nu, mg_parse_nu), restated; tests/test_mgb_plan.py
+# compares the two without a device
 
 def sizes(w, h):
     """(w, h) per level: halved, rounding up, until <= COARSEST cells or MAXLEV levels"""
@@ -233,7 +235,8 @@ def half_steps(levels, r, nu):
 
 def pcg(levels, B, X0, nu, tol, max_it=60):
     """the device's iteration: x from X0, r = B - A x, z = M^-1 r, p = z + beta p, q = A p, alpha = r.z / p.q per channel;
-    stops at the first iteration count N whose worst channel of sqrt(r.r / b.b) is <= tol.  Dot products are float64
+    stops at the first iteration count N whose worst channel of sqrt(r.r / b.b) is <= tol (the device looks at the
+    residual at the cadence of vm_mgb_plan.h: MgbStop and can stop up to three iterations later).  Dot products are float64
     sums of `dtype` vectors, alpha and beta are rounded to `dtype`, as on the device.  Returns (N or -1, [rel after 0, 1,
     ... iterations], x)"""
     L = levels[0]

@@ -1,6 +1,6 @@
 """Shared by tests/test_reduction_mode.py and tests/test_gpu_reduction_mode.py: the digest of an extended frame, the inputs
 of the 2304x1464 compositor cases, the script a fresh child process solves one frame with, and a HOST RESTATEMENT of the
-ordered reduction's arrival counting and fold order (videomorphing_amd/csrc/vm_mgb.h: VmMgbOrd)."""
+ordered reduction's arrival counting and fold order (videomorphing_amd/csrc/vm_mgb_plan.h: VmMgbOrd)."""
 import hashlib
 import struct
 

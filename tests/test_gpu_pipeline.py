@@ -378,7 +378,7 @@ print("CYCLE_OK", i1, i2, qi, worst, dq)
 
 @pytest.mark.parametrize("nu", ["1", "2", "2,1,3", "1,2,1,2"])
 def test_poisson_cycle_variants(nu):
-    """the multigrid cycle's sweeps per level are a build-time choice per kind of system (vm_mgb.h: VM_MGB_NU_POISSON /
+    """the multigrid cycle's sweeps per level are a build-time choice per kind of system (vm_mgb_plan.h: VM_MGB_NU_POISSON /
     _QPATH); VM_MGB_NU overrides it per process.  Every combination the kernels offer -- one or two red-black sweeps each
     way in the tile kernels of level 0 and of the coarser levels, one to nine in the tail -- is the same preconditioned
     CG on the same system: both sides of a frame with holes within one colour level of the oracle's CG, the quadratic

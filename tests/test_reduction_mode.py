@@ -110,14 +110,22 @@ def test_ordered_fold_restated_on_the_host():
     assert len(sums) > 1
 
 
-def test_ordered_storage_fits_every_producer():
-    """the room mgb_solve gives a system -- cap = max(ceil(gx gy / 4), gx ceil(gy / 4)) producing workgroups -- covers the
-    streaming kernels' groups of four blocks and the tile kernels' tiles, whatever the type map (stated here from the
-    grid alone, as the host does)"""
-    for w, h in ((2304, 1464), (1920, 1080), (64, 4), (65, 5), (2, 2), (510, 300), (4096, 2200)):
-        gx, gy = (w + 63) // 64, (h + 3) // 4
-        cap = max((gx * gy + 3) // 4, gx * ((gy + 3) // 4))
+def test_ordered_storage_fits_every_producer(tmp_path):
+    """the room the solver gives a system (vm_mgb_plan.h: MgbOrdLayout, asked of the header itself) -- cap producing
+    workgroups in gcap groups -- covers the streaming kernels' groups of four blocks and the tile kernels' tiles, whatever
+    the type map (from the grid alone, as the host states it)"""
+    src = tmp_path / "ord.cpp"
+    src.write_text('#include "vm_mgb_plan.h"\n#include <cstdio>\n'
+                   'int main() { for (int gx, gy; scanf("%d %d", &gx, &gy) == 2;) { const MgbOrdLayout Y(gx, gy); printf("%d %d\\n", Y.cap, Y.gcap); } }\n')
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "videomorphing_amd", "csrc"), str(src), "-o", str(tmp_path / "ord")])
+    grids = [((w + 63) // 64, (h + 3) // 4) for w, h in ((2304, 1464), (1920, 1080), (64, 4), (65, 5), (2, 2), (510, 300), (4096, 2200))]
+    out = subprocess.run([str(tmp_path / "ord")], input="".join("%d %d\n" % g for g in grids), capture_output=True, text=True, check=True).stdout
+    caps = [tuple(int(x) for x in l.split()) for l in out.splitlines()]
+    assert len(caps) == len(grids)
+    for (gx, gy), (cap, gcap) in zip(grids, caps):
         for nblocks in (0, 1, gx * gy // 2, gx * gy):
             assert (nblocks + 3) // 4 <= cap
         assert gx * ((gy + 3) // 4) <= cap          # every tile of the grid
+        assert gcap * RC.GROUP >= cap > (gcap - 1) * RC.GROUP
+    assert grids[0] == (36, 366) and caps[0][0] == 3312
     assert max((36 * 366 + 3) // 4, 36 * 92) == 3312

@@ -28,15 +28,7 @@
 #define VM_MGB_H
 
 #include "vm_internal.h"
-
-#define VM_MGB_MAXLEV 14
-#define VM_MGB_SLOTS 8          // dot-product accumulators are spread over 8 lines: same-address double atomics serialise in the L2
-#define VM_MGB_MAXSYS 64
-
-// a vector entry in memory: three colour channels, 12 bytes (dwordx3 loads / stores: a quarter less traffic than float4)
-struct VmV3 {
-    float x, y, z;
-};
+#include "vm_mgb_plan.h"     // the constants, VmV3, VmMgbScalars, VmMgbOrd and every host rule that needs no HIP
 
 // One grid of one system's hierarchy:
 //   (A u)(p) = dg(p) u(p) - we(p) u(p + x) - we(p - x) u(p - x) - ws(p) u(p + y) - ws(p - y) u(p - y)
@@ -63,41 +55,6 @@ struct VmMgbLevel {
     int *ntiles;
 };
 
-struct VmMgbScalars {
-    double bb[VM_MGB_SLOTS][16];        // [slot][channel], one 128-byte line per slot
-    double rr[2][VM_MGB_SLOTS][16];     // [iteration parity] ...
-    double rz[2][VM_MGB_SLOTS][16];
-    double pq[2][VM_MGB_SLOTS][16];
-};
-
-// ---------------------------------------------------------------------------
-// ORDERED reduction (vm_set_reduction(ctx, VM_REDUCE_ORDERED); the default, VM_REDUCE_ATOMIC, is the slots above).
-// Every dot product of the PCG becomes a fold in ONE fixed order that is a function of the system alone:
-//   * a producing workgroup is entry i of the system's OWN list of the launch -- i < n, n = ceil(nblocks / MGB_G) in the
-//     streaming kernels (init, dirspmv, update, dot_rz), n = ntiles of level 0 in the tile kernels (the fused update in
-//     the restriction, the prolongation) -- and leaves the three channel sums of its cells (the same shuffle tree and
-//     wave order as the default) in part[acc][i].  Workgroups the launch holds beyond n (the grid is the batch's
-//     maximum) publish nothing and take no ticket;
-//   * workgroups i with the same i / VM_MGB_ORD_GROUP share an arrival ticket; the one that arrives LAST adds the
-//     group's partials in ascending i from zero into gpart[acc][i / VM_MGB_ORD_GROUP] and resets the ticket.  Nobody
-//     waits for anybody;
-//   * the consumers -- the NEXT launch, where the default sums its slots, and the host's stop test -- fold the
-//     ng = ceil(n / VM_MGB_ORD_GROUP) group partials: on the device lane j of 32 adds entries j, j + 32, ... in ascending
-//     order from zero and the 32 lanes are joined by a butterfly (xor 16, 8, 4, 2, 1); the host adds entries 0 .. ng - 1
-//     in ascending order (bb and rr, which only the host reads).
-// gridDim, the batch-mates, the system's index, the stream and the context do not enter.  The fused and the separate
-// update partition level 0 by tiles and by blocks: their ordered bits may differ (VM_MGB_FUSE_MIN_SYS is a dev switch).
-#define VM_MGB_ORD_GROUP 32
-#define VM_MGB_ORD_TSTRIDE 32   // words between tickets: one 128-byte line each
-enum { VM_MGB_ACC_BB = 0, VM_MGB_ACC_RR = 1, VM_MGB_ACC_RZ = 3, VM_MGB_ACC_PQ = 5, VM_MGB_NACC = 7 };   // + the iteration's parity
-struct VmMgbOrd {               // one system's storage (device), constant during a solve
-    int cap, gcap;              // producing workgroups / groups there is room for
-    double *part;               // [VM_MGB_NACC][cap][4]: a workgroup's channel sums (written through, read by its group's last arriver)
-    double *gpart;              // [VM_MGB_NACC][gcap][4]: the groups' sums
-    unsigned *ticket;           // [VM_MGB_NACC][gcap] x VM_MGB_ORD_TSTRIDE words, zero between launches
-    int *ng;                    // [VM_MGB_NACC]: groups of the launch that last produced the accumulator
-};
-
 struct VmMgbSys {
     int nlev;
     VmMgbLevel lv[VM_MGB_MAXLEV];
@@ -111,31 +68,6 @@ struct VmMgbSys {
         const VmMgbOrd *ord; // VM_REDUCE_ORDERED (the kernels' ORD = true instantiations)
     };
 };
-
-#define VM_MGB_COARSEST 64      // the hierarchy ends at a grid of at most this many cells ...
-// Red-black sweeps each way per level, from level 0 on (comma list, the last entry repeats; vm_poisson_api.cpp: mg_nu).
-// Measured on the 2304 x 1464 canvas, tol 1e-5 / 1e-6 (tools/exp/nu_sweep.sh, nu_ab.sh on one box; tools/exp/mg_prototype.py
-// is the CPU model that predicted the iteration counts), ms per frame in 4-frame batches in the bench line's setting:
-//   1 everywhere      11 / 13 iterations   2.20 / 2.52
-//   1, 1, 2           9 / 10               2.00 / 2.17   <- the extra sweeps go where the cycle is launch-bound, not byte-bound
-//   2 everywhere      7-8 / 8              as slow as 1 everywhere: level 0's wider window costs what the iterations save
-// The quadratic path's whole-grid system (1920 x 1080, tol 1e-4, a solved field) stays at 1 everywhere: 1.72 ms (8 iterations)
-// against 2.02 (8) with 1, 1, 2 and 1.89 (6) with 2 everywhere.
-#ifndef VM_MGB_NU_POISSON
-#define VM_MGB_NU_POISSON 1, 1, 2
-#define VM_MGB_NU_QPATH 1
-#endif
-#define VM_MGB_COARSE_SWEEPS 2  // ... which gets this many symmetric Gauss-Seidel sweeps each way (R B R B, B R B R) from zero
-// the tail of the cycle -- every level from `tail` on -- runs in ONE workgroup with the iterates in LDS: the levels'
-// cell counts must fit these pools: all of them (a float4 iterate + a float2 of edge weights per cell) / all but the first
-// (a float4 right-hand side): 120 + 32 KB of the CU's 160 KB of LDS
-#ifndef VM_MGB_TAIL_X
-#define VM_MGB_TAIL_X 5120
-#define VM_MGB_TAIL_B 2048
-#endif
-// ... and no level of the tail may hold more than this many PAIRS of cells, ceil(w / 2) h (the tail's threads are dealt
-// pairs, three each)
-#define VM_MGB_TAIL_PAIRS 3072
 
 // set-up: level 0 from the type map, Galerkin coarsening (2x2 aggregates, edge weights x 1/2), block flags on the way
 void vm_mgb_launch_level0(const VmMgbSys *sys, int nsys, int gx, int gy, hipStream_t s);

@@ -1,65 +1,15 @@
 // vm_poisson_api.cpp -- C-ABI of the Poisson boundary extension
 // (CPoissonExt::run body for one side, Algorithm/PoissonExt.cpp:19-41) and the
-// quadratic path of a frame.
+// quadratic path of a frame.  The launcher of the batched solver: its rules -- hierarchy, workspace layout, host folds,
+// stop rule -- are vm_mgb_plan.h's.
 #include "vm_host.h"
 #include "vm_mgb.h"
 #include "vm_poisson.h"
 
-#include <cmath>
-#include <cstdlib>
 #include <cstring>
 #include <mutex>
-#include <utility>
+#include <type_traits>
 #include <vector>
-
-namespace {
-
-// grid sizes: halve (rounding up) down to a grid of at most VM_MGB_COARSEST cells
-std::vector<std::pair<int, int>> mg_sizes(int w, int h)
-{
-    std::vector<std::pair<int, int>> v{{w, h}};
-    while ((size_t)v.back().first * v.back().second > VM_MGB_COARSEST && (int)v.size() < VM_MGB_MAXLEV)
-        v.push_back({(v.back().first + 1) / 2, (v.back().second + 1) / 2});
-    return v;
-}
-
-// the first level of the cycle's one-workgroup tail: from there on all iterates fit VM_MGB_TAIL_X cells of LDS and all
-// right-hand sides but the first VM_MGB_TAIL_B
-int mg_tail_level(const std::vector<std::pair<int, int>> &sz)
-{
-    size_t below = 0;       // cells of the levels after l
-    int l = (int)sz.size() - 1;
-    while (l > 0) {
-        const size_t here = (size_t)sz[l].first * sz[l].second, up = (size_t)sz[l - 1].first * sz[l - 1].second;
-        if (below + here + up > VM_MGB_TAIL_X || below + here > VM_MGB_TAIL_B ||
-            (size_t)((sz[l - 1].first + 1) / 2) * sz[l - 1].second > VM_MGB_TAIL_PAIRS)
-            break;
-        below += here;
-        --l;
-    }
-    return l;
-}
-
-// red-black sweeps each way on level l of the cycle (VmMgbLevel::nu), by kind of system: VM_MGB_NU_POISSON / _QPATH
-// (vm_mgb.h: measured choices).  VM_MGB_NU = "a,b,c" overrides both for experiments: sweeps per level from level 0 on, the
-// last entry repeats; 1 or 2 on the levels the tile kernels sweep (larger values are cut to 2 there), 1 .. 9 inside the
-// one-workgroup tail
-int mg_nu(int l, bool in_tail, bool qpath)
-{
-    static const std::vector<int> env = [] {
-        std::vector<int> t;
-        if (const char *e = getenv("VM_MGB_NU"))
-            for (const char *q = e; *q; ++q)
-                if (*q >= '1' && *q <= '9') t.push_back(*q - '0');
-        return t;
-    }();
-    static const std::vector<int> poisson{VM_MGB_NU_POISSON}, path{VM_MGB_NU_QPATH};
-    const std::vector<int> &table = !env.empty() ? env : qpath ? path : poisson;
-    const int nu = table[std::min((size_t)l, table.size() - 1)];
-    return in_tail ? nu : std::min(nu, 2);
-}
-
-} // namespace
 
 // ---------------------------------------------------------------------------
 // The solver: multigrid-preconditioned CG, batched over systems (a system = one side of one frame), swept over the
@@ -73,163 +23,50 @@ struct MgbWork {          // one system's device workspace, carved from f->pws2[
     char *xcoarse;        // the x arrays of levels >= 1, contiguous (cleared per extension)
     size_t xcoarse_bytes;
     VmV3 *Xbest;          // optional (mgb_carve qpath): the iterate with the smallest residual seen near the tolerance
-    int *counts;          // nblocks per level, then ntiles per level (device)
     int tail;             // first level of the cycle's one-workgroup tail
-    VmV3 *r1;             // second buffer of the PCG residual, for ...
-    bool fused;           // ... the PCG update riding in the level-0 restriction (the residual ping-pongs between S.R[0] and S.R[1]):
-                          // can this system's hierarchy do it (mgb_carve); whether a solve does: mgb_solve
+    VmV3 *r1;             // second buffer of the PCG residual, for the PCG update riding in the level-0 restriction (the
+                          // residual ping-pongs between S.R[0] and S.R[1]); whether a solve does: mgb_setup
 };
 
-size_t mgb_bytes(int w, int h, bool with_best = false)
-{
-    const auto sz = mg_sizes(w, h);
-    const size_t N0 = (size_t)w * h;
-    size_t need = 2 * vm_align256(N0) + vm_align256(sizeof(VmMgbScalars)) + vm_align256(2 * VM_MGB_MAXLEV * sizeof(int)) + 5 * vm_align256(N0 * 12);
-    for (size_t l = 0; l < sz.size(); ++l) {
-        const size_t N = (size_t)sz[l].first * sz[l].second;
-        const size_t nb = (size_t)((sz[l].first + 63) / 64) * ((sz[l].second + 3) / 4);
-        need += (l ? 4 * vm_align256(N * 4) : 0) + 2 * vm_align256(N * 12) + vm_align256((N + 1) / 2 * 12) + 3 * vm_align256(nb * 4);
-    }
-    return need + (with_best ? vm_align256(N0 * 12) : 0);
-}
+size_t mgb_bytes(int w, int h, bool with_best = false) { return MgbLayout(w, h, with_best).bytes; }
 
+// pointers into a workspace at b, by the layout; qpath: the quadratic path's system (its sweeps per level, and room for the
+// best iterate)
 void mgb_carve(MgbWork &W, int w, int h, char *b, bool qpath = false)
 {
-    const auto sz = mg_sizes(w, h);
-    const size_t N0 = (size_t)w * h;
-    W.type = (uint8_t *)b; b += vm_align256(N0);
+    const MgbLayout A(w, h, qpath);
+    const std::vector<int> &nu = mg_nu_table(MgbSwitches::from_environment(), qpath);
+    auto at = [b](auto *&p, size_t off) { p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(b + off); };
+    int *counts;        // nblocks per level, then ntiles per level (device)
+    at(W.type, A.type); at(W.S.sc, A.sc); at(counts, A.counts);
+    at(W.S.X, A.X); at(W.S.P[0], A.P[0]); at(W.S.P[1], A.P[1]); at(W.S.Q, A.Q); at(W.r1, A.r1);
     W.S.type = W.type;
-    W.S.sc = (VmMgbScalars *)b; b += vm_align256(sizeof(VmMgbScalars));
-    W.counts = (int *)b; b += vm_align256(2 * VM_MGB_MAXLEV * sizeof(int));
-    W.tail = mg_tail_level(sz);
-    W.S.X = (VmV3 *)b; b += vm_align256(N0 * 12);
-    W.S.P[0] = (VmV3 *)b; b += vm_align256(N0 * 12);
-    W.S.P[1] = (VmV3 *)b; b += vm_align256(N0 * 12);
-    W.S.Q = (VmV3 *)b; b += vm_align256(N0 * 12);
-    VmV3 *const r1 = (VmV3 *)b; b += vm_align256(N0 * 12);
-    W.S.nlev = (int)sz.size();
-    for (size_t l = 0; l < sz.size(); ++l) {
+    W.tail = A.tail;
+    W.S.nlev = A.nlev;
+    for (int l = 0; l < A.nlev; ++l) {
+        const MgbLevelLayout &O = A.lv[l];
         VmMgbLevel &L = W.S.lv[l];
-        L.w = sz[l].first; L.h = sz[l].second;
-        L.gx = (L.w + 63) / 64; L.gy = (L.h + 3) / 4;
-        const size_t N = (size_t)L.w * L.h, nb = (size_t)L.gx * L.gy;
+        L.w = O.w; L.h = O.h;
+        L.gx = O.gx; L.gy = O.gy;
         L.info = nullptr;
         L.we = L.ws = L.dg = L.k = nullptr;
         if (l == 0) {                       // one byte of operator per cell
-            L.info = (uint8_t *)b; b += vm_align256(N);
+            at(L.info, O.info);
         } else {
-            L.we = (float *)b; b += vm_align256(N * 4);
-            L.ws = (float *)b; b += vm_align256(N * 4);
-            L.dg = (float *)b; b += vm_align256(N * 4);
-            L.k = (float *)b; b += vm_align256(N * 4);
+            at(L.we, O.we); at(L.ws, O.ws); at(L.dg, O.dg); at(L.k, O.k);
         }
-        L.b = (VmV3 *)b; b += vm_align256(N * 12);
-        L.nu = mg_nu((int)l, (int)l >= W.tail, qpath);
-        L.xr = (VmV3 *)b; b += vm_align256((N + 1) / 2 * 12);
-        L.flags = (uint32_t *)b; b += vm_align256(nb * 4);
-        L.blocks = (uint32_t *)b; b += vm_align256(nb * 4);
-        L.nblocks = W.counts + l;
-        L.tiles = (uint32_t *)b; b += vm_align256(nb * 4);
-        L.ntiles = W.counts + VM_MGB_MAXLEV + l;
+        at(L.b, O.b); at(L.xr, O.xr); at(L.x, O.x);
+        at(L.flags, O.flags); at(L.blocks, O.blocks); at(L.tiles, O.tiles);
+        L.nu = mg_nu(nu, l, l >= A.tail);
+        L.nblocks = counts + l;
+        L.ntiles = counts + VM_MGB_MAXLEV + l;
     }
-    // the x arrays last and together: level 0's (z), then the coarse ones, which are cleared per extension (a
-    // fine cell may read the correction of a coarse cell that is no unknown and sits in a block nobody sweeps)
-    W.S.lv[0].x = (VmV3 *)b; b += vm_align256(N0 * 12);
-    W.xcoarse = b;
-    for (size_t l = 1; l < sz.size(); ++l) {
-        W.S.lv[l].x = (VmV3 *)b;
-        b += vm_align256((size_t)sz[l].first * sz[l].second * 12);
-    }
-    W.xcoarse_bytes = (size_t)(b - W.xcoarse);
-    W.Xbest = qpath ? (VmV3 *)b : nullptr;     // (the quadratic path keeps the best iterate seen: mgb_solve)
-    // The PCG update can ride in the level-0 restriction wherever that kernel exists in its one-sweep form: level 0 swept by
-    // the tile kernels (not inside the tail) with one sweep each way
-    W.fused = W.tail > 0 && W.S.lv[0].nu == 1;
-    W.r1 = r1;
+    at(W.xcoarse, A.xcoarse);
+    W.xcoarse_bytes = A.xcoarse_bytes;
+    W.Xbest = nullptr;
+    if (qpath) at(W.Xbest, A.xbest);       // (the quadratic path keeps the best iterate seen: MgbStop)
     W.S.R[0] = W.S.R[1] = W.S.lv[0].b;
 }
-
-// z = M^-1 r of every active system: one V cycle (sweeps per level: VmMgbLevel::nu); iteration k's r.z lands in rz[k & 1].
-// nb / nt: blocks / tiles per level (the largest count among the systems).  In two halves, because the residual norm
-// of iteration k - 1 comes out of the FIRST kernel of iteration k when the update rides in the level-0 restriction:
-//   mgb_iter_head(k): the PCG update of iteration k - 1 (k >= 1) -- inside the level-0 restriction of cycle k (fused), or
-//                     k_mgb_update by itself -- after which x, r and r.r of k completed iterations stand in memory;
-//   mgb_iter_rest(k): the rest of cycle k and p = z + beta p, q = A p.
-void mgb_iter_head(const VmMgbSys *dev, int nsys, bool fused, const std::vector<int> &nb, const std::vector<int> &nt, int k, uint64_t active,
-                   bool ord, hipStream_t s)
-{
-    if (fused)
-        vm_mgb_launch_restrict(dev, nsys, 0, 1, nt[0], k, k > 0, active, ord, s);
-    else if (k > 0)
-        vm_mgb_launch_update(dev, nsys, nb[0], k - 1, active, ord, s);
-}
-
-void mgb_iter_rest(const VmMgbSys *dev, int nsys, const MgbWork &W0, bool fused, const std::vector<int> &nb, const std::vector<int> &nt, int k,
-                   uint64_t active, bool ord, hipStream_t s)
-{
-    const int tail = W0.tail;       // levels tail .. nlev - 1 run in one workgroup
-    for (int l = fused ? 1 : 0; l < tail; ++l)
-        vm_mgb_launch_restrict(dev, nsys, l, W0.S.lv[l].nu, nt[l], k, false, active, false, s);
-    vm_mgb_launch_tail(dev, nsys, tail, active, s);
-    if (tail == 0)
-        vm_mgb_launch_dot_rz(dev, nsys, nb[0], k, active, ord, s);
-    for (int l = tail - 1; l >= 0; --l)
-        vm_mgb_launch_prolong(dev, nsys, l, W0.S.lv[l].nu, nt[l], k, active, ord && l == 0, s);
-    vm_mgb_launch_dirspmv(dev, nsys, nb[0], k, active, ord, s);
-}
-
-double mgb_rel(const VmMgbScalars &h, int par)
-{
-    double worst = 0;
-    for (int c = 0; c < 3; ++c) {
-        double bb = 0, rr = 0;
-        for (int k = 0; k < VM_MGB_SLOTS; ++k) { bb += h.bb[k][c]; rr += h.rr[par][k][c]; }
-        if (!(bb == bb) || !(rr == rr) || std::isinf(bb) || std::isinf(rr)) return -1;
-        if (bb > 0) worst = std::max(worst, std::sqrt(rr / bb));
-    }
-    return worst;
-}
-
-// The ordered mode's storage of one system, as the host sees it (vm_mgb.h: VmMgbOrd).  The head -- the descriptor, the
-// group counts and the group sums of the accumulators the HOST reads (bb, rr[0], rr[1]: the first three) -- is what a
-// residual check reads back.
-struct MgbOrdLayout {
-    int cap, gcap;
-    size_t o_ng, o_gpart, head, o_ticket, o_part, bytes;    // offsets from the system's base; head = bytes of a read-back
-    MgbOrdLayout(int gx, int gy)
-    {
-        // producing workgroups of a launch at most: groups of MGB_G = 4 blocks (streaming kernels), tiles of four block rows
-        cap = std::max((gx * gy + 3) / 4, gx * ((gy + 3) / 4));
-        gcap = (cap + VM_MGB_ORD_GROUP - 1) / VM_MGB_ORD_GROUP;
-        o_ng = vm_align256(sizeof(VmMgbOrd));
-        o_gpart = o_ng + vm_align256(VM_MGB_NACC * sizeof(int));
-        head = o_gpart + (size_t)(VM_MGB_ACC_RR + 2) * gcap * 4 * sizeof(double);
-        o_ticket = o_gpart + vm_align256((size_t)VM_MGB_NACC * gcap * 4 * sizeof(double));
-        o_part = o_ticket + vm_align256((size_t)VM_MGB_NACC * gcap * VM_MGB_ORD_TSTRIDE * sizeof(unsigned));
-        bytes = o_part + vm_align256((size_t)VM_MGB_NACC * cap * 4 * sizeof(double));
-    }
-};
-
-// ... and the stop test's two totals from a read-back head: group sums 0 .. ng - 1 in ascending order from zero
-double mgb_rel_ordered(const char *head, const MgbOrdLayout &Y, int par)
-{
-    const int *ng = (const int *)(head + Y.o_ng);
-    const double *gp = (const double *)(head + Y.o_gpart);
-    auto total = [&](int acc, int c) {
-        double t = 0;
-        for (int g = 0; g < std::min(ng[acc], Y.gcap); ++g) t += gp[((size_t)acc * Y.gcap + g) * 4 + c];
-        return t;
-    };
-    double worst = 0;
-    for (int c = 0; c < 3; ++c) {
-        const double bb = total(VM_MGB_ACC_BB, c), rr = total(VM_MGB_ACC_RR + par, c);
-        if (!(bb == bb) || !(rr == rr) || std::isinf(bb) || std::isinf(rr)) return -1;
-        if (bb > 0) worst = std::max(worst, std::sqrt(rr / bb));
-    }
-    return worst;
-}
-
-} // namespace
 
 // What mgb_setup leaves for the iterations of one batch: where the context keeps the batch's descriptors, scalars and
 // ordered-mode storage, and the block / tile counts per level (the largest among the systems)
@@ -241,13 +78,41 @@ struct MgbBatch {
     int nlev = 0;
     MgbOrdLayout Y{1, 1};
     std::vector<char> ord_head;        // the systems' descriptors going up, then their read-back heads
+    std::vector<VmMgbScalars> sc_host; // ... and the read-back scalars of the default mode (mgb_look)
     std::vector<int> cnt, nb, nt;      // cnt: every system's counts as mgb_carve lays them out (nblocks, then ntiles per level)
 };
+
+// z = M^-1 r of every active system: one V cycle (sweeps per level: VmMgbLevel::nu); iteration k's r.z lands in rz[k & 1].
+// B.nb / nt: blocks / tiles per level (the largest count among the systems).  In two halves, because the residual norm
+// of iteration k - 1 comes out of the FIRST kernel of iteration k when the update rides in the level-0 restriction:
+//   mgb_iter_head(k): the PCG update of iteration k - 1 (k >= 1) -- inside the level-0 restriction of cycle k (fused), or
+//                     k_mgb_update by itself -- after which x, r and r.r of k completed iterations stand in memory;
+//   mgb_iter_rest(k): the rest of cycle k and p = z + beta p, q = A p.
+void mgb_iter_head(const MgbBatch &B, int nsys, int k, uint64_t active, hipStream_t s)
+{
+    if (B.fused)
+        vm_mgb_launch_restrict(B.dev, nsys, 0, 1, B.nt[0], k, k > 0, active, B.ord, s);
+    else if (k > 0)
+        vm_mgb_launch_update(B.dev, nsys, B.nb[0], k - 1, active, B.ord, s);
+}
+
+void mgb_iter_rest(const MgbBatch &B, int nsys, const MgbWork &W0, int k, uint64_t active, hipStream_t s)
+{
+    const int tail = W0.tail;       // levels tail .. nlev - 1 run in one workgroup
+    for (int l = B.fused ? 1 : 0; l < tail; ++l)
+        vm_mgb_launch_restrict(B.dev, nsys, l, W0.S.lv[l].nu, B.nt[l], k, false, active, false, s);
+    vm_mgb_launch_tail(B.dev, nsys, tail, active, s);
+    if (tail == 0)
+        vm_mgb_launch_dot_rz(B.dev, nsys, B.nb[0], k, active, B.ord, s);
+    for (int l = tail - 1; l >= 0; --l)
+        vm_mgb_launch_prolong(B.dev, nsys, l, W0.S.lv[l].nu, B.nt[l], k, active, B.ord && l == 0, s);
+    vm_mgb_launch_dirspmv(B.dev, nsys, B.nb[0], k, active, B.ord, s);
+}
 
 // The set-up of a batch: nsys systems of one size whose workspaces are carved and whose type maps are enqueued on the
 // context's stream.  Descriptors up, scalars and ordered-mode storage cleared, the hierarchy (level 0, coarsening) and its
 // block / tile lists built, their counts read back.
-static int mgb_setup(vm_ctx *c, std::vector<MgbWork> &W, int nsys, MgbBatch &B)
+int mgb_setup(vm_ctx *c, std::vector<MgbWork> &W, int nsys, MgbBatch &B)
 {
     hipStream_t s = c->stream;
     if (int rc = c->mgb_sys.reserve(VM_MGB_MAXSYS)) return rc;
@@ -270,13 +135,7 @@ static int mgb_setup(vm_ctx *c, std::vector<MgbWork> &W, int nsys, MgbBatch &B)
         if (int rc = c->mgb_ord.reserve((size_t)nsys * Y.bytes)) return rc;
         ord_dev = B.ord_dev = c->mgb_ord.get();
     }
-    // The PCG update rides in the level-0 restriction wherever the hierarchy allows it.  Measured on the 2304 x 1464 canvas
-    // (tools/exp/fuse_ab.sh, ms per frame at 1e-5, fused against the separate k_mgb_update): 8 systems per batch 1.61 / 1.70,
-    // 4 systems 1.95 / 1.99, 2 systems 2.49 / 2.51, one system 1.78 / 1.81 per side (with the fused kernel's loads issued cell
-    // by cell it lost on one and two systems, 2.56 / 2.49: vm_mgb.hip).  Same arithmetic either way.
-    // VM_MGB_FUSE_MIN_SYS (dev switch): the smallest batch that fuses (0: never).
-    static const int fuse_min = [] { const char *e = getenv("VM_MGB_FUSE_MIN_SYS"); return e ? atoi(e) : 1; }();
-    const bool fused = B.fused = W[0].fused && fuse_min > 0 && nsys >= fuse_min;
+    const bool fused = B.fused = mgb_fused(W[0].tail, W[0].S.lv[0].nu, MgbSwitches::from_environment().fuse_min, nsys);
     for (int i = 0; i < nsys; ++i) {
         W[i].S.R[1] = fused ? W[i].r1 : W[i].S.R[0];
         hs[i] = W[i].S;
@@ -322,114 +181,80 @@ static int mgb_setup(vm_ctx *c, std::vector<MgbWork> &W, int nsys, MgbBatch &B)
     return VM_OK;
 }
 
+// The look at the systems due after `it` completed iterations (mgb_iter_head(it) has been enqueued: x, r, r.r are theirs):
+// one read-back of the span that holds them, then what each one's stop rule asks for (MgbStop::observe) -- the copy that
+// keeps or brings back its best iterate, its bit of `active` cleared
+int mgb_look(vm_ctx *c, std::vector<MgbWork> &W, MgbBatch &B, std::vector<MgbStop> &stop, int it, float tol, int max_it, uint64_t &active)
+{
+    hipStream_t s = c->stream;
+    const MgbOrdLayout &Y = B.Y;
+    const MgbSpan due = mgb_due_span(stop, active, it);
+    if (due.hi < due.lo) return VM_OK;
+    const size_t n_due = (size_t)(due.hi - due.lo + 1), x_bytes = (size_t)W[0].S.lv[0].w * W[0].S.lv[0].h * sizeof(VmV3);
+    if (B.ord)
+        VM_HIP(hipMemcpy2DAsync(&B.ord_head[(size_t)due.lo * Y.head], Y.head, B.ord_dev + (size_t)due.lo * Y.bytes, Y.bytes, Y.head, n_due,
+                                hipMemcpyDeviceToHost, s));
+    else
+        VM_HIP(hipMemcpyAsync(&B.sc_host[due.lo], B.sc_dev + due.lo, n_due * sizeof(VmMgbScalars), hipMemcpyDeviceToHost, s));
+    VM_HIP(hipStreamSynchronize(s));
+    for (int i = due.lo; i <= due.hi; ++i) {
+        if (!((active >> i) & 1) || !stop[i].due(it)) continue;
+        // it == 0: parity 1, where k_mgb_init left r.r
+        const int par = (it - 1) & 1;
+        const double worst = B.ord ? mgb_rel_ordered(&B.ord_head[(size_t)i * Y.head], Y, par) : mgb_rel(B.sc_host[i], par);
+        const int verdict = stop[i].observe(it, worst, tol, max_it, W[i].Xbest != nullptr);
+        if (verdict & MGB_BREAKDOWN)
+            return vm_fail(VM_E_NUMERIC, it == 0 ? "multigrid PCG: the right-hand side is not finite" : "multigrid PCG broke down (NaN)");
+        if (verdict & MGB_SAVE_BEST) VM_HIP(hipMemcpyAsync(W[i].Xbest, W[i].S.X, x_bytes, hipMemcpyDeviceToDevice, s));
+        if (verdict & MGB_STOP) active &= ~(1ull << i);
+        if (verdict & MGB_RESTORE_BEST) VM_HIP(hipMemcpyAsync(W[i].S.X, W[i].Xbest, x_bytes, hipMemcpyDeviceToDevice, s));
+    }
+    return VM_OK;
+}
+
 // The batched PCG proper: nsys systems of one size whose workspaces are carved, whose type maps, right-hand sides
 // (lv[0].b) and initial guesses (X) are enqueued on the context's stream.  Leaves every system's solution in its X
 // (the iterate it stopped at; the best one seen near the tolerance if the workspace was carved with room for it), its
 // iteration count and relative residual in iters / rels.
-static int mgb_solve(vm_ctx *c, std::vector<MgbWork> &W, int nsys, float tol, int max_it, int *iters, double *rels)
+int mgb_solve(vm_ctx *c, std::vector<MgbWork> &W, int nsys, float tol, int max_it, int *iters, double *rels)
 {
     hipStream_t s = c->stream;
-    const size_t N0 = (size_t)W[0].S.lv[0].w * W[0].S.lv[0].h;
     MgbBatch B;
     if (int rc = mgb_setup(c, W, nsys, B)) return rc;
-    VmMgbSys *const dev = B.dev;
-    VmMgbScalars *const sc_dev = B.sc_dev;
-    char *const ord_dev = B.ord_dev;
-    const bool ord = B.ord, fused = B.fused;
-    const MgbOrdLayout &Y = B.Y;
-    std::vector<char> &ord_head = B.ord_head;
-    const std::vector<int> &nb = B.nb, &nt = B.nt;
-    if (nb[0] == 0) {                       // no unknown anywhere: nothing to extend
+    if (B.nb[0] == 0) {                     // no unknown anywhere: nothing to extend
         for (int i = 0; i < nsys; ++i) { iters[i] = 0; rels[i] = 0; }
         return VM_OK;
     }
     uint64_t active = nsys == 64 ? ~0ull : ((1ull << nsys) - 1);
-    vm_mgb_launch_init(dev, nsys, nb[0], active, ord, s);
-    std::vector<VmMgbScalars> h(nsys);
-    std::vector<double> best(nsys, 1e300);
-    std::vector<int> best_it(nsys, 0), next_check(nsys, 0), saved(nsys, 0);
+    vm_mgb_launch_init(B.dev, nsys, B.nb[0], active, B.ord, s);
+    B.sc_host.resize(nsys);
+    std::vector<MgbStop> stop(nsys);
     std::vector<std::pair<VmEvent, VmEvent>> prof_ev;
     std::vector<int> prof_sys;
-    int it = 0;
-    // A system's residual is looked at every 4 iterations (a read drains the stream) until it is within a factor 30
-    // of the tolerance -- the cycle gains a decade in two to three iterations -- and every iteration from there: a solve
-    // stops at the iteration that reaches the tolerance instead of up to three later.  The cadence is the SYSTEM's own
-    // (next_check): where it stops, and so what it pastes, does not depend on its batch-mates.
-    // check(it): the systems due after `it` completed iterations (mgb_iter_head(it) has been enqueued: x, r, r.r are theirs)
-    auto check = [&](int it) -> int {
-        int lo = nsys, hi = -1;          // the systems looked at now: one read-back of the span that holds them
-        for (int i = 0; i < nsys; ++i)
-            if (((active >> i) & 1) && next_check[i] == it) { lo = std::min(lo, i); hi = i; }
-        if (hi < lo) return VM_OK;
-        if (ord)
-            VM_HIP(hipMemcpy2DAsync(&ord_head[(size_t)lo * Y.head], Y.head, ord_dev + (size_t)lo * Y.bytes, Y.bytes, Y.head, (size_t)(hi - lo + 1),
-                                    hipMemcpyDeviceToHost, s));
-        else
-            VM_HIP(hipMemcpyAsync(&h[lo], sc_dev + lo, (size_t)(hi - lo + 1) * sizeof(VmMgbScalars), hipMemcpyDeviceToHost, s));
-        VM_HIP(hipStreamSynchronize(s));
-        for (int i = 0; i < nsys; ++i) {
-            if (!((active >> i) & 1) || next_check[i] != it) continue;
-            // it == 0: parity 1, where k_mgb_init left r.r
-            const double worst = ord ? mgb_rel_ordered(&ord_head[(size_t)i * Y.head], Y, (it - 1) & 1) : mgb_rel(h[i], (it - 1) & 1);
-            if (worst < 0)
-                return vm_fail(VM_E_NUMERIC, it == 0 ? "multigrid PCG: the right-hand side is not finite" : "multigrid PCG broke down (NaN)");
-            if (worst < best[i]) {
-                best[i] = worst;
-                best_it[i] = it;
-                // A system with room for it (the quadratic path: float32 attains 1e-4 .. 1e-5 there, the recursively updated
-                // residual passes below what the stored iterate attains and the iteration then drifts) keeps the best
-                // iterate seen at a check near the tolerance
-                if (W[i].Xbest && worst <= 30.0 * tol) {
-                    VM_HIP(hipMemcpyAsync(W[i].Xbest, W[i].S.X, N0 * sizeof(VmV3), hipMemcpyDeviceToDevice, s));
-                    saved[i] = 1;
-                }
-            }
-            // a system stops when it reaches the tolerance -- or gives up: no better residual for 12 iterations, a
-            // residual 1000 times the best one seen, max_it.  It then holds its best iterate if it kept one, else its
-            // CURRENT iterate, and reports that iterate's residual (the callers turn a residual above the tolerance into
-            // VM_E_NUMERIC)
-            if (worst <= tol || it >= max_it || it - best_it[i] >= 12 || worst > 1e3 * best[i]) {
-                active &= ~(1ull << i);
-                if (saved[i] && best_it[i] != it) {
-                    VM_HIP(hipMemcpyAsync(W[i].S.X, W[i].Xbest, N0 * sizeof(VmV3), hipMemcpyDeviceToDevice, s));
-                } else {
-                    best[i] = worst;
-                    best_it[i] = it;
-                }
-            }
-            next_check[i] = std::min(max_it, it + (best[i] <= 30.0 * tol ? 1 : 4));
-        }
-        return VM_OK;
-    };
-    {
-        const int rc = check(0);
-        if (rc != VM_OK) return rc;
-    }
-    while (active) {
-        if (c->mgb_prof && it > 0) {     // the probe of vm_dbg_poisson_profile: events around the launch that carries the update
+    if (int rc = mgb_look(c, W, B, stop, 0, tol, max_it, active)) return rc;
+    for (int it = 0; active; ++it) {
+        const bool probe = c->mgb_prof && it > 0;       // vm_dbg_poisson_profile: events around the launch that carries the update
+        if (probe) {
             prof_ev.emplace_back();
-            VmEvent &e0 = prof_ev.back().first, &e1 = prof_ev.back().second;
-            if (int rc = e0.create()) return rc;
-            if (int rc = e1.create()) return rc;
-            VM_HIP(hipEventRecord(e0.get(), s));
-            mgb_iter_head(dev, nsys, fused, nb, nt, it, active, ord, s);
-            VM_HIP(hipEventRecord(e1.get(), s));
+            if (int rc = prof_ev.back().first.create()) return rc;
+            if (int rc = prof_ev.back().second.create()) return rc;
+            VM_HIP(hipEventRecord(prof_ev.back().first.get(), s));
+        }
+        mgb_iter_head(B, nsys, it, active, s);
+        if (probe) {
+            VM_HIP(hipEventRecord(prof_ev.back().second.get(), s));
             prof_sys.push_back(__builtin_popcountll(active));
-        } else {
-            mgb_iter_head(dev, nsys, fused, nb, nt, it, active, ord, s);
         }
         if (it > 0) {
-            const int rc = check(it);
-            if (rc != VM_OK) return rc;
+            if (int rc = mgb_look(c, W, B, stop, it, tol, max_it, active)) return rc;
             if (!active) break;
         }
-        mgb_iter_rest(dev, nsys, W[0], fused, nb, nt, it, active, ord, s);
-        ++it;
+        mgb_iter_rest(B, nsys, W[0], it, active, s);
         VM_HIP(hipGetLastError());
     }
     for (int i = 0; i < nsys; ++i) {
-        iters[i] = best_it[i];
-        rels[i] = best[i];
+        iters[i] = stop[i].best_it;
+        rels[i] = stop[i].best;
     }
     if (!prof_ev.empty()) {
         VM_HIP(hipStreamSynchronize(s));
@@ -438,13 +263,47 @@ static int mgb_solve(vm_ctx *c, std::vector<MgbWork> &W, int nsys, float tol, in
             if (hipEventElapsedTime(&ms, prof_ev[k].first.get(), prof_ev[k].second.get()) == hipSuccess) {
                 c->mgb_prof_us += 1e3 * ms;
                 c->mgb_prof_launches += 1;
-                c->mgb_prof_fused += fused ? 1 : 0;
+                c->mgb_prof_fused += B.fused ? 1 : 0;
                 c->mgb_prof_unknown_launches += prof_sys[k];        // active systems of that launch (x unknowns per system: the caller's)
             }
         }
     }
     return VM_OK;
 }
+
+// What the entry points that solve share.  `solve(its, rel)` enqueues a solve of n systems on the context's stream and leaves
+// their iteration counts and residuals; it runs between the context's two events, whose distance goes to *elapsed_ms.
+// iters / rel_res (n entries each, optional) get the systems' results; `worst` is the system with the largest residual,
+// which the caller turns into VM_E_NUMERIC if it is above the tolerance.
+struct MgbResult {
+    std::vector<int> its;
+    std::vector<double> rel;
+    int worst = 0;
+};
+
+template <class Solve>
+int mgb_timed(vm_ctx *c, int n, Solve &&solve, int *iters, float *rel_res, float *elapsed_ms, MgbResult &R)
+{
+    hipStream_t s = c->stream;
+    R.its.assign(n, 0);
+    R.rel.assign(n, 0.0);
+    VM_HIP(hipEventRecord(c->ev0.get(), s));
+    if (int rc = solve(R.its.data(), R.rel.data())) return rc;
+    VM_HIP(hipGetLastError());
+    VM_HIP(hipEventRecord(c->ev1.get(), s));
+    VM_HIP(hipEventSynchronize(c->ev1.get()));
+    float ms = 0;
+    VM_HIP(hipEventElapsedTime(&ms, c->ev0.get(), c->ev1.get()));
+    if (elapsed_ms) *elapsed_ms = ms;
+    for (int i = 0; i < n; ++i) {
+        if (iters) iters[i] = R.its[i];
+        if (rel_res) rel_res[i] = (float)R.rel[i];
+        if (R.rel[i] > R.rel[R.worst]) R.worst = i;
+    }
+    return VM_OK;
+}
+
+} // namespace
 
 // Diagnostic (bench.py's roofline of the compositor's HBM-bound kernel, measured live as the contract asks: HIP events on
 // the stream the kernel is launched on): on != 0 arms the probe and clears its sums; on == 0 disarms it and returns the
@@ -526,22 +385,11 @@ extern "C" int vm_poisson_extend(vm_frame *f, int side, float tol, int max_it, i
         return vm_fail(VM_E_INVALID, "vm_poisson_extend: bad argument");
     VM_ENTER_LOCKED(f);
     vm_ctx *c = f->ctx;
-    hipStream_t s = c->stream;
-    VM_HIP(hipEventRecord(c->ev0.get(), s));
-    int total_it = 0;
-    double rel = 0;
-    int rc = poisson_solve_batch(c, &f, &side, 1, tol, max_it, &total_it, &rel);
-    if (rc != VM_OK) return rc;
-    VM_HIP(hipGetLastError());
-    VM_HIP(hipEventRecord(c->ev1.get(), s));
-    VM_HIP(hipEventSynchronize(c->ev1.get()));
-    float ms = 0;
-    VM_HIP(hipEventElapsedTime(&ms, c->ev0.get(), c->ev1.get()));
-    if (iters) *iters = total_it;
-    if (rel_res) *rel_res = (float)rel;
-    if (elapsed_ms) *elapsed_ms = ms;
-    if (rel > tol)
-        return vm_fail(VM_E_NUMERIC, "vm_poisson_extend: residual %.3g after %d iterations (tol %.3g)", rel, total_it, (double)tol);
+    MgbResult R;
+    auto solve = [&](int *its, double *rel) { return poisson_solve_batch(c, &f, &side, 1, tol, max_it, its, rel); };
+    if (int rc = mgb_timed(c, 1, solve, iters, rel_res, elapsed_ms, R)) return rc;
+    if (R.rel[0] > tol)
+        return vm_fail(VM_E_NUMERIC, "vm_poisson_extend: residual %.3g after %d iterations (tol %.3g)", R.rel[0], R.its[0], (double)tol);
     return VM_OK;
 }
 
@@ -563,29 +411,16 @@ extern "C" int vm_poisson_extend_frames(vm_frame *const *frames, int n, float to
     }
     VM_ENTER_LOCKED(frames[0]);
     vm_ctx *c = frames[0]->ctx;
-    hipStream_t s = c->stream;
     std::vector<vm_frame *> fr(2 * n);
-    std::vector<int> sd(2 * n), its(2 * n, 0);
-    std::vector<double> rel(2 * n, 0.0);
+    std::vector<int> sd(2 * n);
     for (int i = 0; i < n; ++i) { fr[2 * i] = fr[2 * i + 1] = frames[i]; sd[2 * i] = 1; sd[2 * i + 1] = 2; }
-    VM_HIP(hipEventRecord(c->ev0.get(), s));
-    int rc = poisson_solve_batch(c, fr.data(), sd.data(), 2 * n, tol, max_it, its.data(), rel.data());
-    if (rc != VM_OK) return rc;
-    VM_HIP(hipEventRecord(c->ev1.get(), s));
-    VM_HIP(hipEventSynchronize(c->ev1.get()));
-    float ms = 0;
-    VM_HIP(hipEventElapsedTime(&ms, c->ev0.get(), c->ev1.get()));
-    if (elapsed_ms) *elapsed_ms = ms;
-    double worst = 0;
-    int at = 0;
-    for (int i = 0; i < 2 * n; ++i) {
-        if (iters) iters[i] = its[i];
-        if (rel_res) rel_res[i] = (float)rel[i];
-        if (rel[i] > worst) { worst = rel[i]; at = i; }
-    }
-    if (worst > tol)
+    MgbResult R;
+    auto solve = [&](int *its, double *rel) { return poisson_solve_batch(c, fr.data(), sd.data(), 2 * n, tol, max_it, its, rel); };
+    if (int rc = mgb_timed(c, 2 * n, solve, iters, rel_res, elapsed_ms, R)) return rc;
+    const int at = R.worst;
+    if (R.rel[at] > tol)
         return vm_fail(VM_E_NUMERIC, "vm_poisson_extend_frames: residual %.3g after %d iterations on side %d of frame %d (tol %.3g)",
-                       worst, its[at], at % 2 + 1, at / 2, (double)tol);
+                       R.rel[at], R.its[at], at % 2 + 1, at / 2, (double)tol);
     return VM_OK;
 }
 
@@ -694,8 +529,8 @@ extern "C" int vm_dbg_mgb_cycle(vm_frame *f, int which, const float *r_in, float
         return VM_OK;
     }
     VM_HIP(hipMemcpyAsync(L.b, r_in, N0 * sizeof(VmV3), hipMemcpyHostToDevice, s));      // the residual of iteration 0: R[0]
-    mgb_iter_head(B.dev, 1, B.fused, B.nb, B.nt, 0, 1ull, B.ord, s);
-    mgb_iter_rest(B.dev, 1, W[0], B.fused, B.nb, B.nt, 0, 1ull, B.ord, s);
+    mgb_iter_head(B, 1, 0, 1ull, s);
+    mgb_iter_rest(B, 1, W[0], 0, 1ull, s);
     VM_HIP(hipGetLastError());
     std::vector<uint8_t> info(N0);
     if (int rc = mgb_dbg_download(info.data(), L.info, N0, s)) return rc;
@@ -724,10 +559,8 @@ extern "C" int vm_frame_quadratic_path(vm_frame *f, float tol, int max_it, int *
         return vm_fail(VM_E_INVALID, "vm_frame_quadratic_path: needs a frame of at least 2x2 pixels");
     vm_ctx *c = f->ctx;
     hipStream_t s = c->stream;
-    int it = 0;
-    double rel = 0;
-    VM_HIP(hipEventRecord(c->ev0.get(), s));
-    {
+    MgbResult R;
+    auto solve = [&](int *its, double *rel) {
         // the batched solver on the whole grid (mgb_system)
         std::vector<MgbWork> W(1);
         int rc = mgb_system(f, VM_DBG_MGB_QPATH, W[0], false);
@@ -742,23 +575,17 @@ extern "C" int vm_frame_quadratic_path(vm_frame *f, float tol, int max_it, int *
         vm_qpath_launch_sum3(W[0].S.lv[0].b, f->w, f->h, sums, ord_part, s);
         vm_qpath_launch_shift3(W[0].S.lv[0].b, f->w, f->h, sums, nullptr, 0, s);
         VM_HIP(hipGetLastError());
-        rc = mgb_solve(c, W, 1, tol, max_it, &it, &rel);
+        rc = mgb_solve(c, W, 1, tol, max_it, its, rel);
         if (rc != VM_OK) return rc;
         VM_HIP(hipMemsetAsync(W[0].S.sc, 0, sizeof(VmMgbScalars), s));
         vm_qpath_launch_sum3(W[0].S.X, f->w, f->h, sums, ord_part, s);
         vm_qpath_launch_shift3(W[0].S.X, f->w, f->h, sums, f->u.get(), f->rs, s);
-    }
-    f->u_zero = false;
-    VM_HIP(hipGetLastError());
-    VM_HIP(hipEventRecord(c->ev1.get(), s));
-    VM_HIP(hipEventSynchronize(c->ev1.get()));
-    float ms = 0;
-    VM_HIP(hipEventElapsedTime(&ms, c->ev0.get(), c->ev1.get()));
-    if (iters) *iters = it;
-    if (rel_res) *rel_res = (float)rel;
-    if (elapsed_ms) *elapsed_ms = ms;
-    if (rel > tol)
-        return vm_fail(VM_E_NUMERIC, "vm_frame_quadratic_path: residual %.3g after %d iterations (tol %.3g)", rel, it, (double)tol);
+        f->u_zero = false;
+        return (int)VM_OK;
+    };
+    if (int rc = mgb_timed(c, 1, solve, iters, rel_res, elapsed_ms, R)) return rc;
+    if (R.rel[0] > tol)
+        return vm_fail(VM_E_NUMERIC, "vm_frame_quadratic_path: residual %.3g after %d iterations (tol %.3g)", R.rel[0], R.its[0], (double)tol);
     return VM_OK;
 }
 
