@@ -437,6 +437,29 @@ int  vm_render_halfway(vm_frame *f, float color_fa, float geo_fa, int color_from
 /* same, output left on the device (for timing / chaining) */
 int  vm_render_halfway_dev(vm_frame *f, float color_fa, float geo_fa, int color_from,
                            float *elapsed_ms);
+/* What the fixed point of vm_render_halfway (kernel_render_halfway_image, Algorithm/render.cu:16-60; the per-frame
+ * call of UI/RenderWidget.cpp:229-266) knows besides a colour.  After its 20 rounds an output pixel holds (px, py), the
+ * blended v and, if the frame has a path, u -- the renderer's float32 expressions in the renderer's order:
+ *   map0 = (px - v.x, py - v.y), map1 = (px + v.x, py + v.y): where the pixel samples image 0 and image 1, in image
+ *     pixels (pixel centre i is i; the renderer adds ex + 0.5f to these).  At geo_fa = 0 map1 is the forward map image
+ *     0 -> image 1, at geo_fa = 1 map0 the backward map.  Tight (h, w, 2) floats each;
+ *   resid = fmaxf(|px20 - px19|, |py20 - py19|): the move of the last round, tight (h, w) floats;
+ *   flags, tight (h, w) bytes: bit 0 set when 0 <= map0.x <= w - 1 && 0 <= map0.y <= h - 1, bit 1 the same for map1 (a NaN
+ *     coordinate fails the comparisons).
+ * Any output may be NULL, not all four (VM_E_INVALID).  The frame is not changed. */
+int  vm_frame_sampling_maps(vm_frame *f, float geo_fa, float *map0_xy, float *map1_xy, float *resid, uint8_t *flags);
+/* Two w x h float32 layers of 1..4 interleaved channels (h rows of pitch_floats, 0 = tight) -- a matte, a depth or UV pass,
+ * a float plate -- kept on the device beside the canvases render.cu:16-60 samples (UI/RenderWidget.cpp:229-266 uploads
+ * only those).  Storage is allocated on the first upload; uploading again replaces the layers and may change `channels`. */
+int  vm_frame_upload_layers(vm_frame *f, int channels, const float *layer0, const float *layer1, int pitch_floats);
+/* The layers through the morph (the chain of render.cu:16-60, UI/RenderWidget.cpp:229-266): layer k is sampled at
+ * (mapk.x + 0.5f, mapk.y + 0.5f) with the field taps' bilinear expression, per channel (1-a)(1-b) t00 + a(1-b) t10 +
+ * (1-a)b t01 + ab t11 from left to right, indices clamped to the layer: no Poisson extension, the edge texel repeats
+ * (flags of vm_frame_sampling_maps tell where).  color_from 0: c0, 2: c1, 1: c0 * (1 - color_fa) + c1 * color_fa in float32.
+ * out: (h, w, channels) floats, pitch in floats (0 = tight).  VM_E_STATE on a frame that holds no layers. */
+int  vm_render_layers(vm_frame *f, float color_fa, float geo_fa, int color_from, float *out, int pitch_floats);
+/* same (render.cu:16-60, UI/RenderWidget.cpp:229-266), output left on the device (for timing) */
+int  vm_render_layers_dev(vm_frame *f, float color_fa, float geo_fa, int color_from, float *elapsed_ms);
 /* CPoissonExt::prepare + poissonExtend for one side (1 or 2) of the frame,
  * Algorithm/PoissonExt.cpp:49-362, on the device-resident canvases: matrix-free
  * multigrid-preconditioned CG instead of MKL DSS.  iters/rel_res may be NULL. */

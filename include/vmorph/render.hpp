@@ -72,11 +72,47 @@ public:
         return out;
     }
 
+    // where every output pixel of render_halfway_image at geo_fa samples image 0 and image 1 (vm_frame_sampling_maps):
+    // the renderer's fixed point (render.cu:16-60) with its two positions kept
+    struct SamplingMaps {
+        std::vector<float> map0, map1;      // (h, w, 2): image pixels, pixel centre i is i
+        std::vector<float> resid;           // (h, w): the move of the last round
+        std::vector<unsigned char> flags;   // (h, w): bit 0 / 1: map0 / map1 inside the image
+    };
+    SamplingMaps sampling_maps(float geo_fa)
+    {
+        const size_t n = (size_t)w_ * h_;
+        SamplingMaps m{std::vector<float>(2 * n), std::vector<float>(2 * n), std::vector<float>(n), std::vector<unsigned char>(n)};
+        check(vm_frame_sampling_maps(f_, geo_fa, m.map0.data(), m.map1.data(), m.resid.data(), m.flags.data()));
+        return m;
+    }
+    // two (h, w, channels) float layers, channels in 1..4, kept on the device for render_layers
+    void upload_layers(int channels, const float *layer0, const float *layer1, int pitch_floats = 0)
+    {
+        check(vm_frame_upload_layers(f_, channels, layer0, layer1, pitch_floats));
+        channels_ = channels;
+    }
+    // the layers through the morph: (h, w, channels) floats
+    std::vector<float> render_layers(float color_fa, float geo_fa, int color_from)
+    {
+        std::vector<float> out((size_t)w_ * h_ * (channels_ ? channels_ : 1));
+        check(vm_render_layers(f_, color_fa, geo_fa, color_from, out.data(), 0));
+        return out;
+    }
+    // ... left on the device: the kernel's milliseconds
+    float render_layers_dev(float color_fa, float geo_fa, int color_from)
+    {
+        float ms = 0;
+        check(vm_render_layers_dev(f_, color_fa, geo_fa, color_from, &ms));
+        return ms;
+    }
+
     vm_frame *handle() const { return f_; }
 
 private:
     vm_frame *f_ = nullptr;
     int w_, h_, ex_;
+    int channels_ = 0;
 };
 
 // CPoissonExt::run's loop body (PoissonExt.cpp:24-36) for several frames of one context at once: both sides of every

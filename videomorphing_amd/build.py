@@ -50,6 +50,8 @@ UNITS = [
     # "off": 1-2 % on the sweep kernels, profiles/r02_notes.md)
     ("vm_sweep_kernels.hip", "vm_sweep_kernels_fast.o", ["-DVM_EXACT=0", "-ffp-contract=off"]),
     ("vm_render.hip", "vm_render.o", ["-ffp-contract=off"]),
+    ("vm_warp.hip", "vm_warp_kernels.o", ["-ffp-contract=off"]),
+    ("vm_warp.cpp", "vm_warp.o", ["-x", "hip"]),
     ("vm_poisson.hip", "vm_poisson.o", ["-ffp-contract=off"]),
     ("vm_mgb.hip", "vm_mgb.o", ["-ffp-contract=fast"]),
     ("vm_pyramid.hip", "vm_pyramid.o", ["-ffp-contract=off"]),

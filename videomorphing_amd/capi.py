@@ -53,6 +53,7 @@ SYMBOLS = [
     "vm_track_get_flows", "vm_track_propagate", "vm_video_build_flows_track",
     "vm_level_energy", "vm_level_energy_batch", "vm_level_error_map", "vm_level_error_image",
     "vm_video_energy", "vm_video_error_map", "vm_video_error_image",
+    "vm_frame_sampling_maps", "vm_frame_upload_layers", "vm_render_layers", "vm_render_layers_dev",
 ]
 
 
@@ -242,6 +243,10 @@ def load():
         "vm_video_energy": [vp, i, i, C.POINTER(C.c_double)],
         "vm_video_error_map": [vp, i, i, i, vp, i],
         "vm_video_error_image": [vp, i, i, i, f, i, i, vp, i],
+        "vm_frame_sampling_maps": [vp, f, vp, vp, vp, vp],
+        "vm_frame_upload_layers": [vp, i, vp, vp, i],
+        "vm_render_layers": [vp, f, f, i, vp, i],
+        "vm_render_layers_dev": [vp, f, f, i, C.POINTER(f)],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

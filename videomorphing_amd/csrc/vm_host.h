@@ -217,6 +217,13 @@ struct vm_frame {
     // solver workspace (allocated on first use), pws2[side - 1]: one per side (both sides of a frame are in flight
     // together); the quadratic path uses side 1's
     VmDev<char> pws2[2];
+    // float layers carried through the morph (vm_frame_upload_layers, vm_warp.cpp), allocated on the first upload: two tight
+    // (h, w, layer_ch) images, the second at layer_off floats; layer_ch == 0: the frame holds none
+    VmDev<float> layers;
+    int layer_ch = 0;
+    size_t layer_off = 0;
+    // what the warp kernels write before it goes to the host (the maps, or the rendered layers), allocated on first use
+    VmDev<char> warp_out;
 };
 
 // The one destroy path of the objects that live on a context's device (pyramid, video, frame, sync).  With the device

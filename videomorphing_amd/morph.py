@@ -596,6 +596,39 @@ class Frame(object):
         capi.check(self._L.vm_render_halfway_dev(self._h, color_fa, geo_fa, color_from, C.byref(ms)))
         return ms.value
 
+    def sampling_maps(self, geo_fa):
+        """where every output pixel of render_halfway at geo_fa samples image 0 and image 1, and how well that is
+        founded (vm_frame_sampling_maps): (map0 (h, w, 2) float32, map1 (h, w, 2) float32, resid (h, w) float32 -- the
+        move of the fixed point's last round --, flags (h, w) uint8 -- bit 0 / 1: map0 / map1 inside the image).  At
+        geo_fa = 0 map1 is the forward map image 0 -> image 1, at geo_fa = 1 map0 the backward map."""
+        m0 = np.empty((self.h, self.w, 2), dtype=np.float32)
+        m1 = np.empty((self.h, self.w, 2), dtype=np.float32)
+        resid = np.empty((self.h, self.w), dtype=np.float32)
+        flags = np.empty((self.h, self.w), dtype=np.uint8)
+        capi.check(self._L.vm_frame_sampling_maps(self._h, float(geo_fa), m0.ctypes.data, m1.ctypes.data,
+                                                  resid.ctypes.data, flags.ctypes.data))
+        return m0, m1, resid, flags
+
+    def upload_layers(self, l0, l1):
+        """two float32 layers, (h, w) or (h, w, C) with C in 1..4 (a matte, a depth or UV pass, a float plate), kept on
+        the device for render_layers (vm_frame_upload_layers); uploading again replaces them"""
+        a0, a1 = np.ascontiguousarray(l0, dtype=np.float32), np.ascontiguousarray(l1, dtype=np.float32)
+        assert a0.shape == a1.shape and a0.shape[:2] == (self.h, self.w) and a0.ndim in (2, 3)
+        self._layer_shape = a0.shape
+        capi.check(self._L.vm_frame_upload_layers(self._h, 1 if a0.ndim == 2 else a0.shape[2], a0.ctypes.data, a1.ctypes.data, 0))
+
+    def render_layers(self, color_fa, geo_fa, color_from):
+        """the uploaded layers through the morph (vm_render_layers): float32 of the shape they were uploaded in"""
+        shape = getattr(self, "_layer_shape", (self.h, self.w))       # (no upload: the call answers VM_E_STATE)
+        out = np.empty(shape, dtype=np.float32)
+        capi.check(self._L.vm_render_layers(self._h, color_fa, geo_fa, color_from, out.ctypes.data, 0))
+        return out
+
+    def render_layers_dev(self, color_fa, geo_fa, color_from):
+        ms = C.c_float(0)
+        capi.check(self._L.vm_render_layers_dev(self._h, color_fa, geo_fa, color_from, C.byref(ms)))
+        return ms.value
+
     def quadratic_path(self, tol=1e-4, max_it=200):
         """CQuadraticPath::optimize for this frame's v (QuadraticPath.cpp:24-223); the result
         stays in the frame for render_halfway.  Returns (iterations, residual, ms)."""
