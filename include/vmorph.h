@@ -460,6 +460,52 @@ int  vm_frame_upload_layers(vm_frame *f, int channels, const float *layer0, cons
 int  vm_render_layers(vm_frame *f, float color_fa, float geo_fa, int color_from, float *out, int pitch_floats);
 /* same (render.cu:16-60, UI/RenderWidget.cpp:229-266), output left on the device (for timing) */
 int  vm_render_layers_dev(vm_frame *f, float color_fa, float geo_fa, int color_from, float *elapsed_ms);
+/* ---- transition control: where the morph happens when ---------------------
+ * The calls above take one geo_fa and one color_fa for the whole frame.  A frame may instead hold a SCHEDULE: two planes
+ * of w x h float pairs (t0, t1) in the halfway domain (the domain of v), one for the geometry and one for the colour.  A
+ * texel starts its transition at time t0 and ends it at t1.  For a call at time t with ease e every texel's rate is, in
+ * float32 and in this order (the division correctly rounded):
+ *   d = t1 - t0;  s = d > 0 ? fminf(fmaxf((t - t0) / d, 0), 1) : (t >= t0 ? 1 : 0)
+ *   rate = e == VM_EASE_SMOOTH ? (s * s) * (3 - 2 * s) : s
+ * which gives the rate planes G (geometry) and K (colour); t is not clamped.  Both are sampled at the tap positions of
+ * the chain of kernel_render_halfway_image (Algorithm/render.cu:16-60) with the field taps' index and clamp arithmetic, in
+ * lerp form: r0 = t00 + a (t10 - t00), r1 = t01 + a (t11 - t01), r = r0 + b (r1 - r0) (a constant plane gives its value
+ * exactly).  The chain is the renderer's with g = tapr(G, p) in the place of geo_fa, taken anew (undamped) at every p:
+ *   p = q, V = tap(v, p), U = tap(u, p), g = tapr(G, p);  20 rounds: s1 = 2 g - 1, s2 = 4 g - 4 g g,
+ *   p = (q - s1 V) - s2 U, V = 0.8 tap(v, p) + (1 - 0.8) V, U likewise, g = tapr(G, p);  then k = tapr(K, p) in the
+ *   place of color_fa.
+ * The geometric rate belongs to the halfway-domain point p the chain looks for, not to the output pixel: uniform frames
+ * mixed by a matte on the host tear at every rate gradient, this does not.  With the schedule (0, 1) everywhere and
+ * VM_EASE_LINEAR, G is exactly t for t in [0, 1] and every call below gives the bits of its uniform counterpart at
+ * geo_fa = color_fa = t.  A discontinuous schedule can keep the chain from settling (a hard step t1 == t0 across a lead
+ * ramp: a resid of several pixels at the seam): that is the caller's business, resid of vm_frame_transition_maps reports it. */
+#define VM_EASE_LINEAR 0
+#define VM_EASE_SMOOTH 1
+/* The schedule (render.cu:16-60; stored beside what UI/RenderWidget.cpp:229-266 uploads per frame): (h, w, 2) floats
+ * each, h rows of pitch_floats (0 = tight).  Either plane may be NULL: uniform (0, 1); both NULL: VM_E_INVALID.  Kept on
+ * the device beside the layers; a new upload replaces it. */
+int  vm_frame_upload_schedule(vm_frame *f, const float *geo_t0t1, const float *color_t0t1, int pitch_floats);
+/* the frame holds no schedule from here on (render.cu:16-60, UI/RenderWidget.cpp:229-266: the calls below answer VM_E_STATE) */
+int  vm_frame_clear_schedule(vm_frame *f);
+/* vm_render_halfway under the schedule at time t (render.cu:16-60, UI/RenderWidget.cpp:229-266): RGB8 from the
+ * Poisson-extended canvases with the renderer's tail (+ ex + 0.5f, the blend c0 * (1 - k) + c1 * k for color_from 1, + 0.5
+ * in double, truncation).  rgb_out: h rows of w RGB8 pixels, pitch in bytes (0 = tight).  VM_E_STATE without a schedule;
+ * VM_E_INVALID for an ease other than VM_EASE_LINEAR / VM_EASE_SMOOTH, a color_from outside 0..2, a pitch below the row,
+ * a NULL output.  The frame's v, path, canvases and layers are not changed by any of the calls of this section. */
+int  vm_render_transition(vm_frame *f, float t, int ease, int color_from, uint8_t *rgb_out, int pitch_bytes);
+/* same (render.cu:16-60, UI/RenderWidget.cpp:229-266), output left on the device (for timing) */
+int  vm_render_transition_dev(vm_frame *f, float t, int ease, int color_from, float *elapsed_ms);
+/* vm_render_layers under the schedule (render.cu:16-60, UI/RenderWidget.cpp:229-266): the layers of vm_frame_upload_layers
+ * through the same chain, blended with k.  out: (h, w, channels) floats, pitch in floats (0 = tight).  VM_E_STATE without a
+ * schedule or without layers. */
+int  vm_render_transition_layers(vm_frame *f, float t, int ease, int color_from, float *out, int pitch_floats);
+/* same (render.cu:16-60, UI/RenderWidget.cpp:229-266), output left on the device (for timing) */
+int  vm_render_transition_layers_dev(vm_frame *f, float t, int ease, int color_from, float *elapsed_ms);
+/* vm_frame_sampling_maps under the schedule (render.cu:16-60, UI/RenderWidget.cpp:229-266): its four outputs, and
+ * rates_gk, tight (h, w, 2) floats: (g, k) as they stand after round 20.  Any output may be NULL, not all five
+ * (VM_E_INVALID). */
+int  vm_frame_transition_maps(vm_frame *f, float t, int ease, float *map0_xy, float *map1_xy, float *resid, uint8_t *flags,
+                              float *rates_gk);
 /* CPoissonExt::prepare + poissonExtend for one side (1 or 2) of the frame,
  * Algorithm/PoissonExt.cpp:49-362, on the device-resident canvases: matrix-free
  * multigrid-preconditioned CG instead of MKL DSS.  iters/rel_res may be NULL. */

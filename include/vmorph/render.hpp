@@ -107,6 +107,55 @@ public:
         return ms;
     }
 
+    // transition control: where the morph happens when.  Two (h, w, 2) planes of (t0, t1) in the halfway domain, for the
+    // geometry and the colour (either may be nullptr: uniform (0, 1)); kept on the device until replaced or cleared
+    void upload_schedule(const float *geo_t0t1, const float *color_t0t1, int pitch_floats = 0)
+    {
+        check(vm_frame_upload_schedule(f_, geo_t0t1, color_t0t1, pitch_floats));
+    }
+    void clear_schedule() { check(vm_frame_clear_schedule(f_)); }
+    // render_halfway_image under the schedule at time t (vm_render_transition): the chain of render.cu:16-60 with the
+    // per-texel rates in the place of geo_fa and color_fa
+    std::vector<unsigned char> render_transition(float t, int ease = VM_EASE_LINEAR, int color_from = 1)
+    {
+        std::vector<unsigned char> out((size_t)w_ * h_ * 3);
+        check(vm_render_transition(f_, t, ease, color_from, out.data(), 0));
+        return out;
+    }
+    float render_transition_dev(float t, int ease = VM_EASE_LINEAR, int color_from = 1)
+    {
+        float ms = 0;
+        check(vm_render_transition_dev(f_, t, ease, color_from, &ms));
+        return ms;
+    }
+    // the layers under the schedule: (h, w, channels) floats
+    std::vector<float> render_transition_layers(float t, int ease = VM_EASE_LINEAR, int color_from = 1)
+    {
+        std::vector<float> out((size_t)w_ * h_ * (channels_ ? channels_ : 1));
+        check(vm_render_transition_layers(f_, t, ease, color_from, out.data(), 0));
+        return out;
+    }
+    float render_transition_layers_dev(float t, int ease = VM_EASE_LINEAR, int color_from = 1)
+    {
+        float ms = 0;
+        check(vm_render_transition_layers_dev(f_, t, ease, color_from, &ms));
+        return ms;
+    }
+    // sampling_maps under the schedule, and the rates (g, k) every output pixel ended with
+    struct TransitionMaps {
+        SamplingMaps maps;
+        std::vector<float> rates;           // (h, w, 2): the geometric and the colour rate after the last round
+    };
+    TransitionMaps transition_maps(float t, int ease = VM_EASE_LINEAR)
+    {
+        const size_t n = (size_t)w_ * h_;
+        TransitionMaps m{{std::vector<float>(2 * n), std::vector<float>(2 * n), std::vector<float>(n), std::vector<unsigned char>(n)},
+                         std::vector<float>(2 * n)};
+        check(vm_frame_transition_maps(f_, t, ease, m.maps.map0.data(), m.maps.map1.data(), m.maps.resid.data(), m.maps.flags.data(),
+                                       m.rates.data()));
+        return m;
+    }
+
     vm_frame *handle() const { return f_; }
 
 private:

@@ -20,6 +20,7 @@ DBG_MGB_QPATH = 3                             # vm_dbg_mgb_*: the quadratic path
 SWEEP_AUTO, SWEEP_TILE, SWEEP_SPLIT, SWEEP_STEP, SWEEP_SPARSE, SWEEP_PASS = 0, 1, 2, 3, 4, 5
 ERR_SSIM, ERR_TPS, ERR_UI, ERR_TEMP, ERR_ALL = 0, 1, 2, 3, 4   # planes / totals of the error view (vm_level_energy, ...)
 ERR_NAMES = ("ssim", "tps", "ui", "temp", "all")
+EASE_LINEAR, EASE_SMOOTH = 0, 1               # the ramp of a transition schedule (vm_render_transition, ...)
 
 FIELDS = {  # name -> (id, channels)
     "img0": (0, 1), "img1": (1, 1), "v": (2, 2), "luma": (3, 2), "mean": (4, 2), "var": (5, 2),
@@ -54,6 +55,8 @@ SYMBOLS = [
     "vm_level_energy", "vm_level_energy_batch", "vm_level_error_map", "vm_level_error_image",
     "vm_video_energy", "vm_video_error_map", "vm_video_error_image",
     "vm_frame_sampling_maps", "vm_frame_upload_layers", "vm_render_layers", "vm_render_layers_dev",
+    "vm_frame_upload_schedule", "vm_frame_clear_schedule", "vm_render_transition", "vm_render_transition_dev",
+    "vm_render_transition_layers", "vm_render_transition_layers_dev", "vm_frame_transition_maps",
 ]
 
 
@@ -247,6 +250,13 @@ def load():
         "vm_frame_upload_layers": [vp, i, vp, vp, i],
         "vm_render_layers": [vp, f, f, i, vp, i],
         "vm_render_layers_dev": [vp, f, f, i, C.POINTER(f)],
+        "vm_frame_upload_schedule": [vp, vp, vp, i],
+        "vm_frame_clear_schedule": [vp],
+        "vm_render_transition": [vp, f, i, i, vp, i],
+        "vm_render_transition_dev": [vp, f, i, i, C.POINTER(f)],
+        "vm_render_transition_layers": [vp, f, i, i, vp, i],
+        "vm_render_transition_layers_dev": [vp, f, i, i, C.POINTER(f)],
+        "vm_frame_transition_maps": [vp, f, i, vp, vp, vp, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

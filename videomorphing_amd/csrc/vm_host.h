@@ -224,6 +224,10 @@ struct vm_frame {
     size_t layer_off = 0;
     // what the warp kernels write before it goes to the host (the maps, or the rendered layers), allocated on first use
     VmDev<char> warp_out;
+    // the transition schedule (vm_frame_upload_schedule, vm_warp.cpp), allocated on the first upload: the geometry plane and
+    // the colour plane of h x rs pairs (t0, t1), then the scratch plane of the same size a call ramps its rates into
+    VmDev<float2> sched;
+    bool has_sched = false;
 };
 
 // The one destroy path of the objects that live on a context's device (pyramid, video, frame, sync).  With the device

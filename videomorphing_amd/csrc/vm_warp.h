@@ -4,11 +4,37 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../../include/vmorph.h"
 
 // The renderer's chain with other tails.  channels == 0: the sampling maps into map0 / map1 / resid / flags (tight (h, w);
 // any may be NULL); 1..4: the two tight (h, w, channels) layers through the morph into out.
 void vm_launch_warp(int w, int h, int rs, float color_fa, float geo_fa, int color_from, const float2 *v, const float2 *u,
                     float2 *map0, float2 *map1, float *resid, uint8_t *flags, int channels, const float *layer0,
                     const float *layer1, float *out, hipStream_t s);
+
+// The same chain under a transition schedule (vm_warp.hip): geo_fa / color_fa are per-texel rates ramped from
+// the schedule planes (h x rs pairs (t0, t1), geometry and colour) at time t with `ease`, by a pre-pass, into `rates`,
+// the call's scratch plane of h x rs pairs.  channels == 0: the maps tail and rates_out (tight (h, w, 2), may be NULL); 1..4: the layers
+// into out; VM_WARP_CANVAS: RGB8 from the extended canvases into rgb (h rows of 3 w bytes).
+enum { VM_WARP_CANVAS = -1 };
+struct VmTransition {
+    int w, h, rs;
+    float t;
+    int ease, color_from;
+    const float2 *v, *u;
+    const float2 *sched_geo, *sched_color;
+    float2 *rates;
+    int channels;
+    float2 *map0, *map1;
+    float *resid;
+    uint8_t *flags;
+    float2 *rates_out;
+    const float *layer0, *layer1;
+    float *out;
+    const uchar4 *ext0, *ext1;
+    int ex;
+    uint8_t *rgb;
+};
+void vm_launch_transition(const VmTransition &T, hipStream_t s);
 
 #endif

@@ -629,6 +629,59 @@ class Frame(object):
         capi.check(self._L.vm_render_layers_dev(self._h, color_fa, geo_fa, color_from, C.byref(ms)))
         return ms.value
 
+    def upload_schedule(self, geo=None, color=None):
+        """the transition schedule (vm_frame_upload_schedule): (h, w, 2) float32 planes of (t0, t1) in the halfway
+        domain for the geometry and the colour (videomorphing_amd.transition builds them); one of them may be None:
+        uniform (0, 1).  Uploading again replaces the schedule."""
+        def ptr(a):
+            if a is None:
+                return None, None
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            assert a.shape == (self.h, self.w, 2)
+            return a, a.ctypes.data
+        ag, pg = ptr(geo)
+        ac, pc = ptr(color)
+        capi.check(self._L.vm_frame_upload_schedule(self._h, pg, pc, 0))
+
+    def clear_schedule(self):
+        capi.check(self._L.vm_frame_clear_schedule(self._h))
+
+    def render_transition(self, t, ease=capi.EASE_LINEAR, color_from=1):
+        """render_halfway under the schedule at time t (vm_render_transition) -> (h, w, 3) uint8"""
+        out = np.zeros((self.h, self.w, 3), dtype=np.uint8)
+        capi.check(self._L.vm_render_transition(self._h, float(t), int(ease), int(color_from), out.ctypes.data, 0))
+        return out
+
+    def render_transition_dev(self, t, ease=capi.EASE_LINEAR, color_from=1):
+        ms = C.c_float(0)
+        capi.check(self._L.vm_render_transition_dev(self._h, float(t), int(ease), int(color_from), C.byref(ms)))
+        return ms.value
+
+    def render_transition_layers(self, t, ease=capi.EASE_LINEAR, color_from=1):
+        """the uploaded layers under the schedule at time t (vm_render_transition_layers): float32 of the shape they
+        were uploaded in"""
+        shape = getattr(self, "_layer_shape", (self.h, self.w))       # (no upload: the call answers VM_E_STATE)
+        out = np.empty(shape, dtype=np.float32)
+        capi.check(self._L.vm_render_transition_layers(self._h, float(t), int(ease), int(color_from), out.ctypes.data, 0))
+        return out
+
+    def render_transition_layers_dev(self, t, ease=capi.EASE_LINEAR, color_from=1):
+        ms = C.c_float(0)
+        capi.check(self._L.vm_render_transition_layers_dev(self._h, float(t), int(ease), int(color_from), C.byref(ms)))
+        return ms.value
+
+    def transition_maps(self, t, ease=capi.EASE_LINEAR):
+        """sampling_maps under the schedule at time t (vm_frame_transition_maps): (map0, map1, resid, flags, rates) --
+        rates (h, w, 2) float32: the geometric and the colour rate (g, k) of every output pixel after the last round"""
+        m0 = np.empty((self.h, self.w, 2), dtype=np.float32)
+        m1 = np.empty((self.h, self.w, 2), dtype=np.float32)
+        resid = np.empty((self.h, self.w), dtype=np.float32)
+        flags = np.empty((self.h, self.w), dtype=np.uint8)
+        rates = np.empty((self.h, self.w, 2), dtype=np.float32)
+        capi.check(self._L.vm_frame_transition_maps(self._h, float(t), int(ease), m0.ctypes.data, m1.ctypes.data,
+                                                    resid.ctypes.data, flags.ctypes.data, rates.ctypes.data))
+        return m0, m1, resid, flags, rates
+
     def quadratic_path(self, tol=1e-4, max_it=200):
         """CQuadraticPath::optimize for this frame's v (QuadraticPath.cpp:24-223); the result
         stays in the frame for render_halfway.  Returns (iterations, residual, ms)."""
