@@ -230,17 +230,10 @@ extern "C" int vm_upscale_result(vm_pyr *p, int lvl, int w0, int h0, float *out,
 static int render_dev(vm_frame *f, float color_fa, float geo_fa, int color_from, float *ms)
 {
     if (color_from < 0 || color_from > 2) return vm_fail(VM_E_INVALID, "vm_render_halfway: color_from %d", color_from);
-    vm_ctx *c = f->ctx;
-    if (ms) VM_HIP(hipEventRecord(c->ev0.get(), c->stream));
-    vm_launch_render(f->out.get(), f->w * 3, f->w, f->h, f->rs, f->ex, color_fa, geo_fa, color_from,
-                     f->ext[0].get(), f->ext[1].get(), f->v.get(), f->u_zero ? nullptr : f->u.get(), c->stream);
-    VM_HIP(hipGetLastError());
-    if (ms) {
-        VM_HIP(hipEventRecord(c->ev1.get(), c->stream));
-        VM_HIP(hipEventSynchronize(c->ev1.get()));
-        VM_HIP(hipEventElapsedTime(ms, c->ev0.get(), c->ev1.get()));
-    }
-    return VM_OK;
+    return vm_timed_launch(f->ctx, ms, [&] {
+        vm_launch_render(f->out.get(), f->w * 3, f->w, f->h, f->rs, f->ex, color_fa, geo_fa, color_from, f->ext[0].get(),
+                         f->ext[1].get(), f->v.get(), f->u_zero ? nullptr : f->u.get(), f->ctx->stream);
+    });
 }
 
 extern "C" int vm_render_halfway_dev(vm_frame *f, float color_fa, float geo_fa, int color_from, float *ms)

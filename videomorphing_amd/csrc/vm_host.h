@@ -145,6 +145,21 @@ struct vm_ctx {
     int mgb_prof_launches = 0, mgb_prof_fused = 0;
 };
 
+// A launch on the context's stream, timed by HIP events if `ms` is given: ev0, fn() (which enqueues), the launch error,
+// then ev1 recorded and waited for and the elapsed time read.  Without `ms` nothing is waited for.
+template <class F> int vm_timed_launch(vm_ctx *c, float *ms, F fn)
+{
+    if (ms) VM_HIP(hipEventRecord(c->ev0.get(), c->stream));
+    fn();
+    VM_HIP(hipGetLastError());
+    if (ms) {
+        VM_HIP(hipEventRecord(c->ev1.get(), c->stream));
+        VM_HIP(hipEventSynchronize(c->ev1.get()));
+        VM_HIP(hipEventElapsedTime(ms, c->ev0.get(), c->ev1.get()));
+    }
+    return VM_OK;
+}
+
 struct vm_level {
     int w = 0, h = 0, rs = 0, imp_rs = 0, imp_rows = 0;
     VmDev<char> slab;

@@ -6,30 +6,38 @@
 
 static const float2 *path_of(vm_frame *f) { return f->u_zero ? nullptr : f->u.get(); }
 
+// A maps call: its N optional outputs one after the other in warp_out (256-byte aligned each; a NULL output takes no room
+// and gets a NULL device pointer), launch(dev) enqueued on s, the outputs copied to the host, drained on return.
+template <int N, class F> static int maps_call(vm_frame *f, void *const (&host)[N], const size_t (&bytes)[N], hipStream_t s, F launch)
+{
+    size_t off[N], total = 0;
+    for (int k = 0; k < N; ++k) {
+        off[k] = total;
+        if (host[k]) total += vm_align256(bytes[k]);
+    }
+    if (int rc = f->warp_out.reserve(total, s)) return rc;
+    void *dev[N];
+    for (int k = 0; k < N; ++k) dev[k] = host[k] ? f->warp_out.get() + off[k] : nullptr;
+    launch(dev);
+    VM_HIP(hipGetLastError());
+    for (int k = 0; k < N; ++k)
+        if (host[k]) VM_HIP(hipMemcpyAsync(host[k], dev[k], bytes[k], hipMemcpyDeviceToHost, s));
+    VM_HIP(hipStreamSynchronize(s));
+    return VM_OK;
+}
+
 extern "C" int vm_frame_sampling_maps(vm_frame *f, float geo_fa, float *map0_xy, float *map1_xy, float *resid, uint8_t *flags)
 {
     VM_ENTER(f);
     if (!map0_xy && !map1_xy && !resid && !flags) return vm_fail(VM_E_INVALID, "%s: every output is NULL", __func__);
     hipStream_t s = f->ctx->stream;
-    // the outputs asked for, one after the other in the staging buffer (256-byte aligned each)
     const size_t n = (size_t)f->w * f->h;
-    void *host[4] = {map0_xy, map1_xy, resid, flags};
+    void *const host[4] = {map0_xy, map1_xy, resid, flags};
     const size_t bytes[4] = {n * 8, n * 8, n * 4, n};
-    size_t off[4], total = 0;
-    for (int k = 0; k < 4; ++k) {
-        off[k] = total;
-        if (host[k]) total += vm_align256(bytes[k]);
-    }
-    if (int rc = f->warp_out.reserve(total, s)) return rc;
-    char *d = f->warp_out.get();
-    vm_launch_warp(f->w, f->h, f->rs, 0.0f, geo_fa, 0, f->v.get(), path_of(f), map0_xy ? (float2 *)(d + off[0]) : nullptr,
-                   map1_xy ? (float2 *)(d + off[1]) : nullptr, resid ? (float *)(d + off[2]) : nullptr,
-                   flags ? (uint8_t *)(d + off[3]) : nullptr, 0, nullptr, nullptr, nullptr, s);
-    VM_HIP(hipGetLastError());
-    for (int k = 0; k < 4; ++k)
-        if (host[k]) VM_HIP(hipMemcpyAsync(host[k], d + off[k], bytes[k], hipMemcpyDeviceToHost, s));
-    VM_HIP(hipStreamSynchronize(s));
-    return VM_OK;
+    return maps_call(f, host, bytes, s, [&](void *const *dev) {
+        vm_launch_warp(f->w, f->h, f->rs, 0.0f, geo_fa, 0, f->v.get(), path_of(f), (float2 *)dev[0], (float2 *)dev[1], (float *)dev[2],
+                       (uint8_t *)dev[3], 0, nullptr, nullptr, nullptr, s);
+    });
 }
 
 extern "C" int vm_frame_upload_layers(vm_frame *f, int channels, const float *layer0, const float *layer1, int pitch_floats)
@@ -58,16 +66,10 @@ static int layers_dev(vm_frame *f, const char *fn, float color_fa, float geo_fa,
     if (!f->layer_ch) return vm_fail(VM_E_STATE, "%s: the frame holds no layers (vm_frame_upload_layers)", fn);
     vm_ctx *c = f->ctx;
     if (int rc = f->warp_out.reserve((size_t)f->w * f->h * f->layer_ch * 4, c->stream)) return rc;
-    if (ms) VM_HIP(hipEventRecord(c->ev0.get(), c->stream));
-    vm_launch_warp(f->w, f->h, f->rs, color_fa, geo_fa, color_from, f->v.get(), path_of(f), nullptr, nullptr, nullptr, nullptr,
-                   f->layer_ch, f->layers.get(), f->layers.get() + f->layer_off, (float *)f->warp_out.get(), c->stream);
-    VM_HIP(hipGetLastError());
-    if (ms) {
-        VM_HIP(hipEventRecord(c->ev1.get(), c->stream));
-        VM_HIP(hipEventSynchronize(c->ev1.get()));
-        VM_HIP(hipEventElapsedTime(ms, c->ev0.get(), c->ev1.get()));
-    }
-    return VM_OK;
+    return vm_timed_launch(c, ms, [&] {
+        vm_launch_warp(f->w, f->h, f->rs, color_fa, geo_fa, color_from, f->v.get(), path_of(f), nullptr, nullptr, nullptr, nullptr,
+                       f->layer_ch, f->layers.get(), f->layers.get() + f->layer_off, (float *)f->warp_out.get(), c->stream);
+    });
 }
 
 extern "C" int vm_render_layers_dev(vm_frame *f, float color_fa, float geo_fa, int color_from, float *elapsed_ms)
@@ -155,15 +157,7 @@ static int transition_dev(vm_frame *f, const char *fn, float t, int ease, int co
         T.channels = VM_WARP_CANVAS;
         T.ext0 = f->ext[0].get(); T.ext1 = f->ext[1].get(); T.ex = f->ex; T.rgb = (uint8_t *)f->warp_out.get();
     }
-    if (ms) VM_HIP(hipEventRecord(c->ev0.get(), c->stream));
-    vm_launch_transition(T, c->stream);
-    VM_HIP(hipGetLastError());
-    if (ms) {
-        VM_HIP(hipEventRecord(c->ev1.get(), c->stream));
-        VM_HIP(hipEventSynchronize(c->ev1.get()));
-        VM_HIP(hipEventElapsedTime(ms, c->ev0.get(), c->ev1.get()));
-    }
-    return VM_OK;
+    return vm_timed_launch(c, ms, [&] { vm_launch_transition(T, c->stream); });
 }
 
 extern "C" int vm_render_transition_dev(vm_frame *f, float t, int ease, int color_from, float *elapsed_ms)
@@ -214,27 +208,13 @@ extern "C" int vm_frame_transition_maps(vm_frame *f, float t, int ease, float *m
     VmTransition T;
     if (int rc = transition_args(f, __func__, t, ease, 0, &T)) return rc;
     hipStream_t s = f->ctx->stream;
-    // the outputs asked for, one after the other in the staging buffer (256-byte aligned each)
     const size_t n = (size_t)f->w * f->h;
-    void *host[5] = {map0_xy, map1_xy, resid, flags, rates_gk};
+    void *const host[5] = {map0_xy, map1_xy, resid, flags, rates_gk};
     const size_t bytes[5] = {n * 8, n * 8, n * 4, n, n * 8};
-    size_t off[5], total = 0;
-    for (int k = 0; k < 5; ++k) {
-        off[k] = total;
-        if (host[k]) total += vm_align256(bytes[k]);
-    }
-    if (int rc = f->warp_out.reserve(total, s)) return rc;
-    char *d = f->warp_out.get();
-    T.channels = 0;
-    T.map0 = map0_xy ? (float2 *)(d + off[0]) : nullptr;
-    T.map1 = map1_xy ? (float2 *)(d + off[1]) : nullptr;
-    T.resid = resid ? (float *)(d + off[2]) : nullptr;
-    T.flags = flags ? (uint8_t *)(d + off[3]) : nullptr;
-    T.rates_out = rates_gk ? (float2 *)(d + off[4]) : nullptr;
-    vm_launch_transition(T, s);
-    VM_HIP(hipGetLastError());
-    for (int k = 0; k < 5; ++k)
-        if (host[k]) VM_HIP(hipMemcpyAsync(host[k], d + off[k], bytes[k], hipMemcpyDeviceToHost, s));
-    VM_HIP(hipStreamSynchronize(s));
-    return VM_OK;
+    return maps_call(f, host, bytes, s, [&](void *const *dev) {
+        T.channels = 0;
+        T.map0 = (float2 *)dev[0]; T.map1 = (float2 *)dev[1]; T.resid = (float *)dev[2]; T.flags = (uint8_t *)dev[3];
+        T.rates_out = (float2 *)dev[4];
+        vm_launch_transition(T, s);
+    });
 }

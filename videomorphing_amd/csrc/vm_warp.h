@@ -1,10 +1,15 @@
-// vm_warp.h -- the launcher of vm_warp.hip, called from vm_warp.cpp.
+// vm_warp.h -- the launchers of vm_warp.hip, called from vm_warp.cpp, and the switch between the chain's two forms.
 #ifndef VM_WARP_H
 #define VM_WARP_H
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/vmorph.h"
+
+// Which form of the chain (vm_chain.h) a field of pitch rs and h rows takes, for the launchers of vm_render.hip (where it is
+// defined) and vm_warp.hip: the window form, unless VM_RENDER=plain asks for the plain kernels (A/B runs) or the field is
+// out of the window form's reach.
+bool vm_render_window_form(int rs, int h);
 
 // The renderer's chain with other tails.  channels == 0: the sampling maps into map0 / map1 / resid / flags (tight (h, w);
 // any may be NULL); 1..4: the two tight (h, w, channels) layers through the morph into out.
