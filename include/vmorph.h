@@ -506,6 +506,36 @@ int  vm_render_transition_layers_dev(vm_frame *f, float t, int ease, int color_f
  * (VM_E_INVALID). */
 int  vm_frame_transition_maps(vm_frame *f, float t, int ease, float *map0_xy, float *map1_xy, float *resid, uint8_t *flags,
                               float *rates_gk);
+/* ---- motion blur: the morph integrated over a shutter ----------------------
+ * A frame rendered at one instant is sharp however fast its content moves; a sequence of them strobes.  A shutter call
+ * walks the chain of kernel_render_halfway_image (Algorithm/render.cu:16-60) at N = samples times per output pixel, in one
+ * launch, and returns the mean of the samples' colours.  In float32, in this order (the divisions correctly rounded), for
+ * s = 0 .. N - 1:
+ *   f   = ((float)s + 0.5f) / (float)N
+ *   t_s = fminf(fmaxf(geo_open + (geo_close - geo_open) * f, 0), 1)
+ *   c_s = the colour of the uniform call at geo_fa = t_s, before its rounding: the taps at (map0, map1)_s blended by
+ *         color_from with the call's one color_fa (the colour fraction stays fixed over the exposure: a dissolve is not motion)
+ *   acc = acc + c_s                              (acc starts at +0)
+ * and the result is acc / (float)N.  The times are clamped, so a shutter open across t = 0 or t = 1 holds still outside
+ * the morph; geo_close < geo_open is legal.  With samples = 1 and geo_open == geo_close == g in [0, 1] a call gives the bits
+ * of its uniform counterpart at geo_fa = g.  Every call of this section answers VM_E_INVALID for samples outside 1..64, a
+ * color_from outside 0..2, a pitch below the row or a NULL output, and changes nothing of the frame (v, path, canvases,
+ * layers, schedule).  The schedule of the section above is not consulted. */
+/* vm_render_halfway over the shutter (render.cu:16-60, UI/RenderWidget.cpp:229-266): RGB8 from the Poisson-extended
+ * canvases, (uint8)((double)(acc / (float)N) + 0.5) per channel.  rgb_out: h rows of w RGB8 pixels, pitch in bytes (0 = tight). */
+int  vm_render_shutter(vm_frame *f, float color_fa, float geo_open, float geo_close, int samples, int color_from,
+                       uint8_t *rgb_out, int pitch_bytes);
+/* same (render.cu:16-60, UI/RenderWidget.cpp:229-266), output left on the device (for timing) */
+int  vm_render_shutter_dev(vm_frame *f, float color_fa, float geo_open, float geo_close, int samples, int color_from,
+                           float *elapsed_ms);
+/* vm_render_layers over the shutter (render.cu:16-60, UI/RenderWidget.cpp:229-266): the layers of vm_frame_upload_layers
+ * through the same sample times, so that a matte blurs exactly as its plate does.  out: (h, w, channels) floats, pitch in
+ * floats (0 = tight).  VM_E_STATE on a frame that holds no layers. */
+int  vm_render_shutter_layers(vm_frame *f, float color_fa, float geo_open, float geo_close, int samples, int color_from,
+                              float *out, int pitch_floats);
+/* same (render.cu:16-60, UI/RenderWidget.cpp:229-266), output left on the device (for timing) */
+int  vm_render_shutter_layers_dev(vm_frame *f, float color_fa, float geo_open, float geo_close, int samples, int color_from,
+                                  float *elapsed_ms);
 /* CPoissonExt::prepare + poissonExtend for one side (1 or 2) of the frame,
  * Algorithm/PoissonExt.cpp:49-362, on the device-resident canvases: matrix-free
  * multigrid-preconditioned CG instead of MKL DSS.  iters/rel_res may be NULL. */

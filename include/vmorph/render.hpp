@@ -141,6 +141,33 @@ public:
         check(vm_render_transition_layers_dev(f_, t, ease, color_from, &ms));
         return ms;
     }
+    // motion blur: render_halfway_image integrated over a shutter (vm_render_shutter) -- the mean over `samples` (1..64)
+    // times between geo_open and geo_close, each clamped to [0, 1], taken in float32 before the one rounding
+    std::vector<unsigned char> render_shutter(float color_fa, float geo_open, float geo_close, int samples, int color_from = 1)
+    {
+        std::vector<unsigned char> out((size_t)w_ * h_ * 3);
+        check(vm_render_shutter(f_, color_fa, geo_open, geo_close, samples, color_from, out.data(), 0));
+        return out;
+    }
+    float render_shutter_dev(float color_fa, float geo_open, float geo_close, int samples, int color_from = 1)
+    {
+        float ms = 0;
+        check(vm_render_shutter_dev(f_, color_fa, geo_open, geo_close, samples, color_from, &ms));
+        return ms;
+    }
+    // the layers through the same shutter: (h, w, channels) floats
+    std::vector<float> render_shutter_layers(float color_fa, float geo_open, float geo_close, int samples, int color_from = 1)
+    {
+        std::vector<float> out((size_t)w_ * h_ * (channels_ ? channels_ : 1));
+        check(vm_render_shutter_layers(f_, color_fa, geo_open, geo_close, samples, color_from, out.data(), 0));
+        return out;
+    }
+    float render_shutter_layers_dev(float color_fa, float geo_open, float geo_close, int samples, int color_from = 1)
+    {
+        float ms = 0;
+        check(vm_render_shutter_layers_dev(f_, color_fa, geo_open, geo_close, samples, color_from, &ms));
+        return ms;
+    }
     // sampling_maps under the schedule, and the rates (g, k) every output pixel ended with
     struct TransitionMaps {
         SamplingMaps maps;

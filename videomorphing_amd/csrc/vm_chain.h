@@ -1,6 +1,6 @@
 // vm_chain.h -- the compositor's fixed-point chain (kernel_render_halfway_image, Algorithm/render.cu:16-60), stated once
-// for the units that walk it: vm_render.hip (RGB8 from the extended canvases) and vm_warp.hip (sampling maps, float
-// layers, transition control).  A kernel walks the window form (the product path: taps served from an LDS window;
+// for the units that walk it: vm_render.hip (RGB8 from the extended canvases), vm_warp.hip (sampling maps, float
+// layers, transition control) and vm_shutter.hip (both tails over the sample times of a shutter).  A kernel walks the window form (the product path: taps served from an LDS window;
 // vm_chain_win.h, included in the kernel's body) or calls chain_plain (VM_RENDER=plain, and fields of 4 GiB and more),
 // returns if the chain gave its thread no pixel, and runs its own tail on the Landing.  Everything is float32 in tap2's
 // expressions and order; the units are compiled with -ffp-contract=off.  Every function here is inlined into the kernel

@@ -1,5 +1,6 @@
 // vm_chain_win.h -- the window form of the compositor's chain (vm_chain.h), stated once as the statements a window kernel
-// includes at the top of its body: k_render_win (vm_render.hip) and k_warp_win (vm_warp.hip).  It is no function because
+// includes at the top of its body -- k_render_win (vm_render.hip) and k_warp_win (vm_warp.hip) -- or of its sample loop's
+// (k_shutter_win, vm_shutter.hip).  It is no function because
 // the compiler lays a kernel out differently once this body sits behind any function boundary, a lambda included (the
 // fallback's float2 gathers stay whole, the vectoriser pairs other operations, and the sum after the inside / outside
 // split of the tap is emitted once instead of once per side): k_warp_win<true, CANVAS, true> lost 1.5 us of 100 that way.
@@ -9,6 +10,13 @@
 // const float2 *vf, *uf, *rates (rates is read only if RATES); namespace vm_chain.  It leaves int x, y (the pixel) and
 // Landing L, and returns from the kernel for a thread without a pixel (the whole workgroup past the last tile, or a
 // pixel outside the image -- after the barrier).  Everything else stays inside its block.
+//
+// A kernel that walks the chain several times in a loop (vm_shutter.hip) defines, before it includes this,
+//   VM_CHAIN_WIN_NO_PIXEL        what a thread without a pixel does after the barrier (default: return; in a loop the
+//                                thread has to stay for the barriers of the rounds to come)
+//   VM_CHAIN_WIN_STAGE(ox, oy)   whether the window is staged at (ox, oy), workgroup-uniform (default: true; in a loop
+//                                the barrier before a restaging belongs to it, and a window that has not moved may stay)
+// The defaults leave the statements below what they were.
 //
 // The window form: the plain chain with the 21 dependent taps of v (and u, and the rates) served from LDS and lean index
 // arithmetic.  Measured (round 5, profiles/r05_notes.md): the plain loop costs 4.0 us per iteration and 1080p frame at
@@ -25,6 +33,12 @@
 // to the XCDs in contiguous bands (a workgroup's id modulo 8 is its XCD); the grid is ((ntiles + 7) / 8) * 8 workgroups
 // of RW x RH threads.  RATES: (G, K) is staged like v in a third window, g of the last tap steers the next round, the
 // four K texels and fractions of the last tap are kept and k is formed once, after round 20.
+#ifndef VM_CHAIN_WIN_NO_PIXEL
+#define VM_CHAIN_WIN_NO_PIXEL return
+#endif
+#ifndef VM_CHAIN_WIN_STAGE
+#define VM_CHAIN_WIN_STAGE(ox, oy) true
+#endif
     int x, y;
     Landing L;
     {
@@ -58,19 +72,21 @@
             oy = by - (int)rintf(dy) - RR;
         }
         // staged with CLAMPED source coordinates: every index below is within the field
-        for (int i = tid; i < WH * WW; i += RW * RH) {
-            const int wy = i / WW, wx = i - wy * WW;
-            const int src = min(max(oy + wy, 0), hm1) * rs + min(max(ox + wx, 0), wm1);
-            win_v[i] = vf[src];
-            if (HAS_U)
-                win_u[i] = uf[src];
-            if constexpr (RATES)
-                win_r[i] = rate_at(rates, (uint32_t)src << 3);
+        if (VM_CHAIN_WIN_STAGE(ox, oy)) {
+            for (int i = tid; i < WH * WW; i += RW * RH) {
+                const int wy = i / WW, wx = i - wy * WW;
+                const int src = min(max(oy + wy, 0), hm1) * rs + min(max(ox + wx, 0), wm1);
+                win_v[i] = vf[src];
+                if (HAS_U)
+                    win_u[i] = uf[src];
+                if constexpr (RATES)
+                    win_r[i] = rate_at(rates, (uint32_t)src << 3);
+            }
+            __syncthreads();
         }
-        __syncthreads();
         x = bx + threadIdx.x; y = by + threadIdx.y;
         if (x >= w || y >= h)
-            return;
+            VM_CHAIN_WIN_NO_PIXEL;
         const float qx = (float)x, qy = (float)y;
         float px = qx, py = qy, lx = qx, ly = qy;
         float2 v, u = make_float2(0.0f, 0.0f);

@@ -1,0 +1,203 @@
+// vm_shutter.hip -- motion blur for gfx950: the compositor's chain (kernel_render_halfway_image, Algorithm/render.cu:16-60;
+// vm_chain.h, vm_chain_win.h) walked at the N sample times of a shutter per output pixel, the samples' colours summed in
+// registers and stored once.  One launch per call, whatever N is.
+//
+// In float32, without contraction, for s = 0 .. N - 1 (1 <= N <= 64):
+//   f   = ((float)s + 0.5f) / (float)N                                     correctly rounded division
+//   t_s = fminf(fmaxf(geo_open + (geo_close - geo_open) * f, 0), 1)        a shutter across t = 0 or 1 holds still outside
+//   (map0, map1)_s = the chain at geo_fa = t_s
+//   c_s = the tail of the uniform call on them: the canvas taps of vm_render.hip (+ ex, then + 0.5f, tap_rgb's weights) or
+//         the layer taps of vm_warp.hip, blended by color_from with the call's one color_fa (a dissolve is not motion)
+//   acc = acc + c_s                                                        acc starts at +0, in sample order
+// and the pixel is (uint8)((double)(acc / (float)N) + 0.5) per channel for the canvases, acc / (float)N for layers.  With
+// N = 1 and geo_open == geo_close == g in [0, 1] that is the uniform call's result at g, bit for bit.
+//
+// The window form restages its LDS window sample by sample, because the window's origin follows t_s: a barrier before the
+// restaging (every tap of the sample before has been served) as well as the one after it, and a thread without a pixel
+// stays in the loop for both.  Two consecutive samples whose windows have the same origin share the staged texels -- the
+// window holds exact texels, the bits cannot change -- which is the usual case for a short shutter (VM_SHUTTER_SKIP=0
+// restages always: the A/B of profiles/shutter.md).
+#include "vm_chain.h"
+#include "vm_layer_tap.h"
+#include "vm_shutter.h"
+#include "vm_warp.h"     // vm_render_window_form
+
+#ifndef VM_SHUTTER_SKIP
+#define VM_SHUTTER_SKIP 1
+#endif
+
+namespace {
+
+using namespace vm_chain;
+
+constexpr int CANVAS = VM_SHUTTER_CANVAS;
+template <int C> constexpr int NACC = C == CANVAS ? 3 : C;      // accumulators per pixel
+
+__device__ __forceinline__ float sample_time(float open, float close, int s, float n)
+{
+    const float f = __fdiv_rn((float)s + 0.5f, n);
+    return fminf(fmaxf(open + (close - open) * f, 0.0f), 1.0f);
+}
+
+// A uniform value the sample loop takes from its scalar register anew in every round.  Hoisted out of the loop, what is
+// derived from it -- (float)w, (float)N, 1 - color_fa, the tile's pixel, the first tap's indices and weights: some twenty
+// values -- is held in vector registers across the chain and the tails, which costs the window kernels their eighth wave;
+// re-derived it is a handful of instructions beside the 21 taps.
+template <class T> __device__ __forceinline__ T per_sample(T v)
+{
+    asm volatile("" : "+s"(v));
+    return v;
+}
+
+// acc += c_s: the uniform tails' taps and blend on the Landing of sample s
+template <int C> __device__ __forceinline__ void add_sample(const VmShutter &A, const Landing &L, float (&acc)[NACC<C>])
+{
+    const float m0x = L.px - L.v.x, m0y = L.py - L.v.y;
+    const float m1x = L.px + L.v.x, m1y = L.py + L.v.y;
+    const float color_fa = per_sample(A.color_fa);
+    if constexpr (C == CANVAS) {
+        const int cw = A.w + 2 * A.ex, ch = A.h + 2 * A.ex, ex = A.ex;
+        float3 c;
+        if (A.color_from == 0) {
+            c = tap_rgb(A.ext0, cw, ch, m0x + ex + 0.5f, m0y + ex + 0.5f);
+        } else if (A.color_from == 2) {
+            c = tap_rgb(A.ext1, cw, ch, m1x + ex + 0.5f, m1y + ex + 0.5f);
+        } else {
+            const float3 c0 = tap_rgb(A.ext0, cw, ch, m0x + ex + 0.5f, m0y + ex + 0.5f);
+            const float3 c1 = tap_rgb(A.ext1, cw, ch, m1x + ex + 0.5f, m1y + ex + 0.5f);
+            c.x = c0.x * (1 - color_fa) + c1.x * color_fa;
+            c.y = c0.y * (1 - color_fa) + c1.y * color_fa;
+            c.z = c0.z * (1 - color_fa) + c1.z * color_fa;
+        }
+        acc[0] = acc[0] + c.x; acc[1] = acc[1] + c.y; acc[2] = acc[2] + c.z;
+    } else {
+        Texel<C> r;
+        if (A.color_from == 0) {
+            r = tap_layer<C>(A.layer0, A.w, A.h, m0x + 0.5f, m0y + 0.5f);
+        } else if (A.color_from == 2) {
+            r = tap_layer<C>(A.layer1, A.w, A.h, m1x + 0.5f, m1y + 0.5f);
+        } else {
+            Texel<C> c0 = tap_layer<C>(A.layer0, A.w, A.h, m0x + 0.5f, m0y + 0.5f);
+            // 3 and 4 channels: side 1 is tapped after side 0's texels are summed (side 1's position passes through a
+            // statement that stands behind the one side 0's sums pass through), or eight texels of C registers are live
+            // at once: 55 / 56 registers instead of 70 / 72
+            float n1x = m1x, n1y = m1y;
+            if constexpr (C >= 3) {
+#pragma unroll
+                for (int k = 0; k < C; ++k)
+                    asm volatile("" : "+v"(c0.c[k]));
+                asm volatile("" : "+v"(n1x), "+v"(n1y));
+            }
+            const Texel<C> c1 = tap_layer<C>(A.layer1, A.w, A.h, n1x + 0.5f, n1y + 0.5f);
+#pragma unroll
+            for (int k = 0; k < C; ++k)
+                r.c[k] = c0.c[k] * (1 - color_fa) + c1.c[k] * color_fa;
+        }
+#pragma unroll
+        for (int k = 0; k < C; ++k)
+            acc[k] = acc[k] + r.c[k];
+    }
+}
+
+// the one store of pixel (x, y): the mean, rounded the renderer's way for the canvases
+template <int C> __device__ __forceinline__ void store_mean(const VmShutter &A, int x, int y, const float (&acc)[NACC<C>], float n)
+{
+    const size_t at = (size_t)y * A.w + x;
+    if constexpr (C == CANVAS) {
+        uint8_t *o = A.rgb + 3 * at;
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            o[k] = (uint8_t)((double)__fdiv_rn(acc[k], n) + 0.5);
+    } else {
+        Texel<C> r;
+#pragma unroll
+        for (int k = 0; k < C; ++k)
+            r.c[k] = __fdiv_rn(acc[k], n);
+        texel_store<C>(A.out, at, r);
+    }
+}
+
+// the plain form: one pixel per thread, every tap a global gather
+template <int C> __global__ __launch_bounds__(256) void k_shutter(const VmShutter A)
+{
+    const float n = (float)A.samples;
+    float acc[NACC<C>] = {};
+    int x = 0, y = 0;
+    for (int s = 0; s < A.samples; ++s) {
+        Landing L;
+        if (!chain_plain<false>(A.w, A.h, A.rs, sample_time(A.geo_open, A.geo_close, s, n), A.vf, A.uf, nullptr, x, y, L))
+            return;
+        add_sample<C>(A, L, acc);
+    }
+    store_mean<C>(A, x, y, acc, n);
+}
+
+// whether sample s stages the window at (ox, oy), for the whole workgroup: not if the sample before left it there; the
+// barrier before a restaging is taken here (every tap of the sample before has been served)
+__device__ __forceinline__ bool restage(int s, int ox, int oy, int &at_x, int &at_y)
+{
+    ox = __builtin_amdgcn_readfirstlane(ox); oy = __builtin_amdgcn_readfirstlane(oy);
+    if (VM_SHUTTER_SKIP && s && ox == at_x && oy == at_y)
+        return false;
+    if (s)
+        __syncthreads();
+    at_x = ox; at_y = oy;
+    return true;
+}
+
+// the window form.  The chain's statements stand in the sample loop: a thread without a pixel goes on to the next
+// sample's barriers, only the workgroup past the last tile leaves.  (x, y) belong to the chain's statements, so the one
+// store stands behind the last sample inside the loop.
+#define VM_CHAIN_WIN_NO_PIXEL continue
+#define VM_CHAIN_WIN_STAGE(ox, oy) restage(s, ox, oy, at_x, at_y)
+template <bool HAS_U, int C> __global__ __launch_bounds__(RW * RH) void k_shutter_win(const VmShutter A)
+{
+    constexpr bool RATES = false;       // (a shutter under a transition schedule: one rate plane per sample)
+    const float2 *rates = nullptr;
+    const int rs = A.rs, ntiles = A.ntiles;
+    const float2 *__restrict__ vf = A.vf, *__restrict__ uf = A.uf;
+    float acc[NACC<C>] = {};
+    int at_x = 0, at_y = 0;             // where the staged window is (read from the second sample on: restage())
+    for (int s = 0; s < A.samples; ++s) {
+        const int w = per_sample(A.w), h = per_sample(A.h), tiles_x = per_sample(A.tiles_x);
+        const float n = (float)per_sample(A.samples);
+        // (geo_open alone: close - open is then formed per sample, and close is read from its scalar register)
+        const float geo_fa = sample_time(per_sample(A.geo_open), A.geo_close, s, n);
+#include "vm_chain_win.h"
+        add_sample<C>(A, L, acc);
+        if (s == A.samples - 1)
+            store_mean<C>(A, x, y, acc, n);
+    }
+}
+#undef VM_CHAIN_WIN_NO_PIXEL
+#undef VM_CHAIN_WIN_STAGE
+
+template <int C> void launch(VmShutter &A, hipStream_t s)
+{
+    if (!vm_render_window_form(A.rs, A.h)) {
+        dim3 b(64, 4), g((A.w + 63) / 64, (A.h + 3) / 4);
+        hipLaunchKernelGGL((k_shutter<C>), g, b, 0, s, A);
+        return;
+    }
+    A.tiles_x = (A.w + RW - 1) / RW;
+    A.ntiles = A.tiles_x * ((A.h + RH - 1) / RH);
+    dim3 b(RW, RH), g(((A.ntiles + 7) / 8) * 8);
+    if (A.uf)
+        hipLaunchKernelGGL((k_shutter_win<true, C>), g, b, 0, s, A);
+    else
+        hipLaunchKernelGGL((k_shutter_win<false, C>), g, b, 0, s, A);
+}
+
+} // namespace
+
+void vm_launch_shutter(const VmShutter &S, hipStream_t s)
+{
+    VmShutter A = S;
+    switch (A.channels) {
+    case 1: launch<1>(A, s); break;
+    case 2: launch<2>(A, s); break;
+    case 3: launch<3>(A, s); break;
+    case 4: launch<4>(A, s); break;
+    default: launch<CANVAS>(A, s); break;
+    }
+}

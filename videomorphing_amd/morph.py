@@ -682,6 +682,35 @@ class Frame(object):
                                                     resid.ctypes.data, flags.ctypes.data, rates.ctypes.data))
         return m0, m1, resid, flags, rates
 
+    def render_shutter(self, color_fa, geo_open, geo_close, samples, color_from=1):
+        """render_halfway with motion blur (vm_render_shutter): the mean over `samples` (1..64) times between geo_open
+        and geo_close, each clamped to [0, 1], taken in float32 before the one rounding -> (h, w, 3) uint8"""
+        out = np.zeros((self.h, self.w, 3), dtype=np.uint8)
+        capi.check(self._L.vm_render_shutter(self._h, float(color_fa), float(geo_open), float(geo_close), int(samples),
+                                             int(color_from), out.ctypes.data, 0))
+        return out
+
+    def render_shutter_dev(self, color_fa, geo_open, geo_close, samples, color_from=1):
+        ms = C.c_float(0)
+        capi.check(self._L.vm_render_shutter_dev(self._h, float(color_fa), float(geo_open), float(geo_close), int(samples),
+                                                 int(color_from), C.byref(ms)))
+        return ms.value
+
+    def render_shutter_layers(self, color_fa, geo_open, geo_close, samples, color_from=1):
+        """the uploaded layers through the same shutter (vm_render_shutter_layers): float32 of the shape they were
+        uploaded in -- a matte blurs exactly as its plate does"""
+        shape = getattr(self, "_layer_shape", (self.h, self.w))       # (no upload: the call answers VM_E_STATE)
+        out = np.empty(shape, dtype=np.float32)
+        capi.check(self._L.vm_render_shutter_layers(self._h, float(color_fa), float(geo_open), float(geo_close), int(samples),
+                                                    int(color_from), out.ctypes.data, 0))
+        return out
+
+    def render_shutter_layers_dev(self, color_fa, geo_open, geo_close, samples, color_from=1):
+        ms = C.c_float(0)
+        capi.check(self._L.vm_render_shutter_layers_dev(self._h, float(color_fa), float(geo_open), float(geo_close),
+                                                        int(samples), int(color_from), C.byref(ms)))
+        return ms.value
+
     def quadratic_path(self, tol=1e-4, max_it=200):
         """CQuadraticPath::optimize for this frame's v (QuadraticPath.cpp:24-223); the result
         stays in the frame for render_halfway.  Returns (iterations, residual, ms)."""
