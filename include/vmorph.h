@@ -520,7 +520,7 @@ int  vm_frame_transition_maps(vm_frame *f, float t, int ease, float *map0_xy, fl
  * the morph; geo_close < geo_open is legal.  With samples = 1 and geo_open == geo_close == g in [0, 1] a call gives the bits
  * of its uniform counterpart at geo_fa = g.  Every call of this section answers VM_E_INVALID for samples outside 1..64, a
  * color_from outside 0..2, a pitch below the row or a NULL output, and changes nothing of the frame (v, path, canvases,
- * layers, schedule).  The schedule of the section above is not consulted. */
+ * layers, schedule).  The schedule of the section above is not consulted (the section below does). */
 /* vm_render_halfway over the shutter (render.cu:16-60, UI/RenderWidget.cpp:229-266): RGB8 from the Poisson-extended
  * canvases, (uint8)((double)(acc / (float)N) + 0.5) per channel.  rgb_out: h rows of w RGB8 pixels, pitch in bytes (0 = tight). */
 int  vm_render_shutter(vm_frame *f, float color_fa, float geo_open, float geo_close, int samples, int color_from,
@@ -536,6 +536,41 @@ int  vm_render_shutter_layers(vm_frame *f, float color_fa, float geo_open, float
 /* same (render.cu:16-60, UI/RenderWidget.cpp:229-266), output left on the device (for timing) */
 int  vm_render_shutter_layers_dev(vm_frame *f, float color_fa, float geo_open, float geo_close, int samples, int color_from,
                                   float *elapsed_ms);
+/* ---- motion blur under a transition schedule ------------------------------
+ * The two sections above together: the shutter of a frame that holds a schedule.  The geometry schedule is ramped anew at
+ * every sample time, the colour schedule once, at t_color (the colour time stays fixed over the exposure: a dissolve is
+ * not motion).  In float32, in this order (the divisions correctly rounded), with ramp, tapr and the chain as the
+ * transition section states them, N = samples:
+ *   K   = ramp(schedule_colour, t_color, ease)
+ *   for s = 0 .. N - 1:
+ *     f   = ((float)s + 0.5f) / (float)N
+ *     t_s = t_open + (t_close - t_open) * f      (not clamped: ramp clamps per texel, as for vm_render_transition's t)
+ *     G_s = ramp(schedule_geometry, t_s, ease)
+ *     p_s, V_s = the chain under G_s;  k_s = tapr(K, p_s)
+ *     c_s = the colour of vm_render_transition / vm_render_transition_layers on them before its rounding, blended by
+ *           color_from with k_s
+ *     acc = acc + c_s                            (acc starts at +0)
+ * and the result is acc / (float)N.  With samples = 1 and t_open == t_close == t_color == t a call gives the bits of its
+ * transition counterpart at t; with the schedule (0, 1) on both planes and VM_EASE_LINEAR it gives the bits of its shutter
+ * counterpart at color_fa = t_color in [0, 1], geo_open = t_open, geo_close = t_close.  t_close < t_open is legal.  Every
+ * call of this section answers VM_E_INVALID for samples outside 1..64, an ease other than VM_EASE_LINEAR /
+ * VM_EASE_SMOOTH, a color_from outside 0..2, a pitch below the row or a NULL output, and VM_E_STATE on a frame without a
+ * schedule.  The frame's v, path, canvases, layers and schedule are not changed; no device memory depends on samples. */
+/* vm_render_transition over the shutter (render.cu:16-60, UI/RenderWidget.cpp:229-266): RGB8 from the Poisson-extended
+ * canvases, (uint8)((double)(acc / (float)N) + 0.5) per channel.  rgb_out: h rows of w RGB8 pixels, pitch in bytes (0 = tight). */
+int  vm_render_transition_shutter(vm_frame *f, float t_open, float t_close, int samples, float t_color, int ease, int color_from,
+                                  uint8_t *rgb_out, int pitch_bytes);
+/* same (render.cu:16-60, UI/RenderWidget.cpp:229-266), output left on the device (for timing) */
+int  vm_render_transition_shutter_dev(vm_frame *f, float t_open, float t_close, int samples, float t_color, int ease,
+                                      int color_from, float *elapsed_ms);
+/* vm_render_transition_layers over the shutter (render.cu:16-60, UI/RenderWidget.cpp:229-266): the layers of
+ * vm_frame_upload_layers through the same sample times and rates, so that a matte stays in step with its plate.  out:
+ * (h, w, channels) floats, pitch in floats (0 = tight).  VM_E_STATE on a frame that holds no layers. */
+int  vm_render_transition_shutter_layers(vm_frame *f, float t_open, float t_close, int samples, float t_color, int ease,
+                                         int color_from, float *out, int pitch_floats);
+/* same (render.cu:16-60, UI/RenderWidget.cpp:229-266), output left on the device (for timing) */
+int  vm_render_transition_shutter_layers_dev(vm_frame *f, float t_open, float t_close, int samples, float t_color, int ease,
+                                             int color_from, float *elapsed_ms);
 /* CPoissonExt::prepare + poissonExtend for one side (1 or 2) of the frame,
  * Algorithm/PoissonExt.cpp:49-362, on the device-resident canvases: matrix-free
  * multigrid-preconditioned CG instead of MKL DSS.  iters/rel_res may be NULL. */

@@ -168,6 +168,37 @@ public:
         check(vm_render_shutter_layers_dev(f_, color_fa, geo_open, geo_close, samples, color_from, &ms));
         return ms;
     }
+    // motion blur under the schedule (vm_render_transition_shutter): the mean over `samples` (1..64) times between t_open
+    // and t_close, the geometry schedule ramped at each of them, the colour schedule once at t_color
+    std::vector<unsigned char> render_transition_shutter(float t_open, float t_close, int samples, float t_color,
+                                                         int ease = VM_EASE_LINEAR, int color_from = 1)
+    {
+        std::vector<unsigned char> out((size_t)w_ * h_ * 3);
+        check(vm_render_transition_shutter(f_, t_open, t_close, samples, t_color, ease, color_from, out.data(), 0));
+        return out;
+    }
+    float render_transition_shutter_dev(float t_open, float t_close, int samples, float t_color, int ease = VM_EASE_LINEAR,
+                                        int color_from = 1)
+    {
+        float ms = 0;
+        check(vm_render_transition_shutter_dev(f_, t_open, t_close, samples, t_color, ease, color_from, &ms));
+        return ms;
+    }
+    // the layers through the same shutter and schedule: (h, w, channels) floats
+    std::vector<float> render_transition_shutter_layers(float t_open, float t_close, int samples, float t_color,
+                                                        int ease = VM_EASE_LINEAR, int color_from = 1)
+    {
+        std::vector<float> out((size_t)w_ * h_ * (channels_ ? channels_ : 1));
+        check(vm_render_transition_shutter_layers(f_, t_open, t_close, samples, t_color, ease, color_from, out.data(), 0));
+        return out;
+    }
+    float render_transition_shutter_layers_dev(float t_open, float t_close, int samples, float t_color, int ease = VM_EASE_LINEAR,
+                                               int color_from = 1)
+    {
+        float ms = 0;
+        check(vm_render_transition_shutter_layers_dev(f_, t_open, t_close, samples, t_color, ease, color_from, &ms));
+        return ms;
+    }
     // sampling_maps under the schedule, and the rates (g, k) every output pixel ended with
     struct TransitionMaps {
         SamplingMaps maps;

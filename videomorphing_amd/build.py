@@ -54,6 +54,8 @@ UNITS = [
     ("vm_warp.cpp", "vm_warp.o", ["-x", "hip"]),
     ("vm_shutter.hip", "vm_shutter_kernels.o", ["-ffp-contract=off"]),
     ("vm_shutter.cpp", "vm_shutter.o", ["-x", "hip"]),
+    ("vm_tshutter.hip", "vm_tshutter_kernels.o", ["-ffp-contract=off"]),
+    ("vm_tshutter.cpp", "vm_tshutter.o", ["-x", "hip"]),
     ("vm_poisson.hip", "vm_poisson.o", ["-ffp-contract=off"]),
     ("vm_mgb.hip", "vm_mgb.o", ["-ffp-contract=fast"]),
     ("vm_pyramid.hip", "vm_pyramid.o", ["-ffp-contract=off"]),

@@ -58,6 +58,8 @@ SYMBOLS = [
     "vm_frame_upload_schedule", "vm_frame_clear_schedule", "vm_render_transition", "vm_render_transition_dev",
     "vm_render_transition_layers", "vm_render_transition_layers_dev", "vm_frame_transition_maps",
     "vm_render_shutter", "vm_render_shutter_dev", "vm_render_shutter_layers", "vm_render_shutter_layers_dev",
+    "vm_render_transition_shutter", "vm_render_transition_shutter_dev", "vm_render_transition_shutter_layers",
+    "vm_render_transition_shutter_layers_dev",
 ]
 
 
@@ -262,6 +264,10 @@ def load():
         "vm_render_shutter_dev": [vp, f, f, f, i, i, C.POINTER(f)],
         "vm_render_shutter_layers": [vp, f, f, f, i, i, vp, i],
         "vm_render_shutter_layers_dev": [vp, f, f, f, i, i, C.POINTER(f)],
+        "vm_render_transition_shutter": [vp, f, f, i, f, i, i, vp, i],
+        "vm_render_transition_shutter_dev": [vp, f, f, i, f, i, i, C.POINTER(f)],
+        "vm_render_transition_shutter_layers": [vp, f, f, i, f, i, i, vp, i],
+        "vm_render_transition_shutter_layers_dev": [vp, f, f, i, f, i, i, C.POINTER(f)],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

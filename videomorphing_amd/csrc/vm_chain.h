@@ -1,6 +1,6 @@
 // vm_chain.h -- the compositor's fixed-point chain (kernel_render_halfway_image, Algorithm/render.cu:16-60), stated once
 // for the units that walk it: vm_render.hip (RGB8 from the extended canvases), vm_warp.hip (sampling maps, float
-// layers, transition control) and vm_shutter.hip (both tails over the sample times of a shutter).  A kernel walks the window form (the product path: taps served from an LDS window;
+// layers, transition control), vm_shutter.hip (both tails over the sample times of a shutter) and vm_tshutter.hip (the same under a schedule).  A kernel walks the window form (the product path: taps served from an LDS window;
 // vm_chain_win.h, included in the kernel's body) or calls chain_plain (VM_RENDER=plain, and fields of 4 GiB and more),
 // returns if the chain gave its thread no pixel, and runs its own tail on the Landing.  Everything is float32 in tap2's
 // expressions and order; the units are compiled with -ffp-contract=off.  Every function here is inlined into the kernel
@@ -90,12 +90,21 @@ __device__ __forceinline__ float2 tapr(const float2 *rates, int w, int h, int rs
     return make_float2(lerp2(t00.x, t10.x, t01.x, t11.x, t.a, t.b), lerp2(t00.y, t10.y, t01.y, t11.y, t.a, t.b));
 }
 
+// the same on rates that are no stored plane: anything with a rate_texel(rates, 64-bit index) of its own (vm_ramp.h)
+template <class Rates> __device__ __forceinline__ float2 tapr(const Rates &rates, int w, int h, int rs, float x, float y)
+{
+    const Tap t = tap_at(w, h, (size_t)rs, x, y);
+    const float2 t00 = rate_texel(rates, t.i00), t10 = rate_texel(rates, t.i10), t01 = rate_texel(rates, t.i01), t11 = rate_texel(rates, t.i11);
+    return make_float2(lerp2(t00.x, t10.x, t01.x, t11.x, t.a, t.b), lerp2(t00.y, t10.y, t01.y, t11.y, t.a, t.b));
+}
+
 // ---------------------------------------------------------------------------
 // the plain form: pixel (x, y) of a 64 x 4 block, every tap a global gather.  RATES (transition control):
 // g = tapr(G, p) replaces geo_fa round by round, k = tapr(K, p20) is left for the tail.  false: no pixel for this thread.
-template <bool RATES>
+// Rates: const float2 * (or nullptr without RATES), or what the second tapr takes.
+template <bool RATES, class Rates>
 __device__ __forceinline__ bool chain_plain(int w, int h, int rs, float geo_fa, const float2 *vf,
-                                            const float2 *uf, const float2 *rates, int &x, int &y, Landing &L)
+                                            const float2 *uf, Rates rates, int &x, int &y, Landing &L)
 {
     x = blockIdx.x * 64 + threadIdx.x; y = blockIdx.y * 4 + threadIdx.y;
     if (x >= w || y >= h)

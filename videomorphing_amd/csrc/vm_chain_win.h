@@ -1,13 +1,14 @@
 // vm_chain_win.h -- the window form of the compositor's chain (vm_chain.h), stated once as the statements a window kernel
 // includes at the top of its body -- k_render_win (vm_render.hip) and k_warp_win (vm_warp.hip) -- or of its sample loop's
-// (k_shutter_win, vm_shutter.hip).  It is no function because
+// (k_shutter_win, vm_shutter.hip; k_tblur_win, vm_tshutter.hip).  It is no function because
 // the compiler lays a kernel out differently once this body sits behind any function boundary, a lambda included (the
 // fallback's float2 gathers stay whole, the vectoriser pairs other operations, and the sum after the inside / outside
 // split of the tap is emitted once instead of once per side): k_warp_win<true, CANVAS, true> lost 1.5 us of 100 that way.
 // Included like this every window kernel keeps the loop it had when each unit carried its own copy.
 //
 // In scope where it is included: constexpr bool HAS_U, RATES; int w, h, rs, tiles_x, ntiles; float geo_fa;
-// const float2 *vf, *uf, *rates (rates is read only if RATES); namespace vm_chain.  It leaves int x, y (the pixel) and
+// const float2 *vf, *uf, *rates (rates is read only if RATES, and only through rate_at: vm_tshutter.hip puts a Ramped of
+// vm_ramp.h there); namespace vm_chain.  It leaves int x, y (the pixel) and
 // Landing L, and returns from the kernel for a thread without a pixel (the whole workgroup past the last tile, or a
 // pixel outside the image -- after the barrier).  Everything else stays inside its block.
 //
@@ -16,6 +17,8 @@
 //                                thread has to stay for the barriers of the rounds to come)
 //   VM_CHAIN_WIN_STAGE(ox, oy)   whether the window is staged at (ox, oy), workgroup-uniform (default: true; in a loop
 //                                the barrier before a restaging belongs to it, and a window that has not moved may stay)
+//   VM_CHAIN_WIN_STAGE_FIELD     whether a staging copies v and u, workgroup-uniform (default: true; vm_tshutter.hip stages
+//                                the rates at every sample, v and u only where the window has moved)
 // The defaults leave the statements below what they were.
 //
 // The window form: the plain chain with the 21 dependent taps of v (and u, and the rates) served from LDS and lean index
@@ -38,6 +41,9 @@
 #endif
 #ifndef VM_CHAIN_WIN_STAGE
 #define VM_CHAIN_WIN_STAGE(ox, oy) true
+#endif
+#ifndef VM_CHAIN_WIN_STAGE_FIELD
+#define VM_CHAIN_WIN_STAGE_FIELD true
 #endif
     int x, y;
     Landing L;
@@ -76,9 +82,11 @@
             for (int i = tid; i < WH * WW; i += RW * RH) {
                 const int wy = i / WW, wx = i - wy * WW;
                 const int src = min(max(oy + wy, 0), hm1) * rs + min(max(ox + wx, 0), wm1);
-                win_v[i] = vf[src];
-                if (HAS_U)
-                    win_u[i] = uf[src];
+                if (VM_CHAIN_WIN_STAGE_FIELD) {
+                    win_v[i] = vf[src];
+                    if (HAS_U)
+                        win_u[i] = uf[src];
+                }
                 if constexpr (RATES)
                     win_r[i] = rate_at(rates, (uint32_t)src << 3);
             }

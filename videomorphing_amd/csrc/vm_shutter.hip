@@ -18,8 +18,7 @@
 // window holds exact texels, the bits cannot change -- which is the usual case for a short shutter (VM_SHUTTER_SKIP=0
 // restages always: the A/B of profiles/shutter.md).
 #include "vm_chain.h"
-#include "vm_layer_tap.h"
-#include "vm_shutter.h"
+#include "vm_shutter_tail.h"
 #include "vm_warp.h"     // vm_render_window_form
 
 #ifndef VM_SHUTTER_SKIP
@@ -30,91 +29,10 @@ namespace {
 
 using namespace vm_chain;
 
-constexpr int CANVAS = VM_SHUTTER_CANVAS;
-template <int C> constexpr int NACC = C == CANVAS ? 3 : C;      // accumulators per pixel
-
 __device__ __forceinline__ float sample_time(float open, float close, int s, float n)
 {
-    const float f = __fdiv_rn((float)s + 0.5f, n);
+    const float f = sample_fraction(s, n);
     return fminf(fmaxf(open + (close - open) * f, 0.0f), 1.0f);
-}
-
-// A uniform value the sample loop takes from its scalar register anew in every round.  Hoisted out of the loop, what is
-// derived from it -- (float)w, (float)N, 1 - color_fa, the tile's pixel, the first tap's indices and weights: some twenty
-// values -- is held in vector registers across the chain and the tails, which costs the window kernels their eighth wave;
-// re-derived it is a handful of instructions beside the 21 taps.
-template <class T> __device__ __forceinline__ T per_sample(T v)
-{
-    asm volatile("" : "+s"(v));
-    return v;
-}
-
-// acc += c_s: the uniform tails' taps and blend on the Landing of sample s
-template <int C> __device__ __forceinline__ void add_sample(const VmShutter &A, const Landing &L, float (&acc)[NACC<C>])
-{
-    const float m0x = L.px - L.v.x, m0y = L.py - L.v.y;
-    const float m1x = L.px + L.v.x, m1y = L.py + L.v.y;
-    const float color_fa = per_sample(A.color_fa);
-    if constexpr (C == CANVAS) {
-        const int cw = A.w + 2 * A.ex, ch = A.h + 2 * A.ex, ex = A.ex;
-        float3 c;
-        if (A.color_from == 0) {
-            c = tap_rgb(A.ext0, cw, ch, m0x + ex + 0.5f, m0y + ex + 0.5f);
-        } else if (A.color_from == 2) {
-            c = tap_rgb(A.ext1, cw, ch, m1x + ex + 0.5f, m1y + ex + 0.5f);
-        } else {
-            const float3 c0 = tap_rgb(A.ext0, cw, ch, m0x + ex + 0.5f, m0y + ex + 0.5f);
-            const float3 c1 = tap_rgb(A.ext1, cw, ch, m1x + ex + 0.5f, m1y + ex + 0.5f);
-            c.x = c0.x * (1 - color_fa) + c1.x * color_fa;
-            c.y = c0.y * (1 - color_fa) + c1.y * color_fa;
-            c.z = c0.z * (1 - color_fa) + c1.z * color_fa;
-        }
-        acc[0] = acc[0] + c.x; acc[1] = acc[1] + c.y; acc[2] = acc[2] + c.z;
-    } else {
-        Texel<C> r;
-        if (A.color_from == 0) {
-            r = tap_layer<C>(A.layer0, A.w, A.h, m0x + 0.5f, m0y + 0.5f);
-        } else if (A.color_from == 2) {
-            r = tap_layer<C>(A.layer1, A.w, A.h, m1x + 0.5f, m1y + 0.5f);
-        } else {
-            Texel<C> c0 = tap_layer<C>(A.layer0, A.w, A.h, m0x + 0.5f, m0y + 0.5f);
-            // 3 and 4 channels: side 1 is tapped after side 0's texels are summed (side 1's position passes through a
-            // statement that stands behind the one side 0's sums pass through), or eight texels of C registers are live
-            // at once: 55 / 56 registers instead of 70 / 72
-            float n1x = m1x, n1y = m1y;
-            if constexpr (C >= 3) {
-#pragma unroll
-                for (int k = 0; k < C; ++k)
-                    asm volatile("" : "+v"(c0.c[k]));
-                asm volatile("" : "+v"(n1x), "+v"(n1y));
-            }
-            const Texel<C> c1 = tap_layer<C>(A.layer1, A.w, A.h, n1x + 0.5f, n1y + 0.5f);
-#pragma unroll
-            for (int k = 0; k < C; ++k)
-                r.c[k] = c0.c[k] * (1 - color_fa) + c1.c[k] * color_fa;
-        }
-#pragma unroll
-        for (int k = 0; k < C; ++k)
-            acc[k] = acc[k] + r.c[k];
-    }
-}
-
-// the one store of pixel (x, y): the mean, rounded the renderer's way for the canvases
-template <int C> __device__ __forceinline__ void store_mean(const VmShutter &A, int x, int y, const float (&acc)[NACC<C>], float n)
-{
-    const size_t at = (size_t)y * A.w + x;
-    if constexpr (C == CANVAS) {
-        uint8_t *o = A.rgb + 3 * at;
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-            o[k] = (uint8_t)((double)__fdiv_rn(acc[k], n) + 0.5);
-    } else {
-        Texel<C> r;
-#pragma unroll
-        for (int k = 0; k < C; ++k)
-            r.c[k] = __fdiv_rn(acc[k], n);
-        texel_store<C>(A.out, at, r);
-    }
 }
 
 // the plain form: one pixel per thread, every tap a global gather
@@ -127,7 +45,7 @@ template <int C> __global__ __launch_bounds__(256) void k_shutter(const VmShutte
         Landing L;
         if (!chain_plain<false>(A.w, A.h, A.rs, sample_time(A.geo_open, A.geo_close, s, n), A.vf, A.uf, nullptr, x, y, L))
             return;
-        add_sample<C>(A, L, acc);
+        add_sample<C>(A, L, per_sample(A.color_fa), acc);
     }
     store_mean<C>(A, x, y, acc, n);
 }
@@ -152,7 +70,7 @@ __device__ __forceinline__ bool restage(int s, int ox, int oy, int &at_x, int &a
 #define VM_CHAIN_WIN_STAGE(ox, oy) restage(s, ox, oy, at_x, at_y)
 template <bool HAS_U, int C> __global__ __launch_bounds__(RW * RH) void k_shutter_win(const VmShutter A)
 {
-    constexpr bool RATES = false;       // (a shutter under a transition schedule: one rate plane per sample)
+    constexpr bool RATES = false;       // (a shutter under a transition schedule is vm_tshutter.hip: RATES, ramped per sample)
     const float2 *rates = nullptr;
     const int rs = A.rs, ntiles = A.ntiles;
     const float2 *__restrict__ vf = A.vf, *__restrict__ uf = A.uf;
@@ -164,7 +82,7 @@ template <bool HAS_U, int C> __global__ __launch_bounds__(RW * RH) void k_shutte
         // (geo_open alone: close - open is then formed per sample, and close is read from its scalar register)
         const float geo_fa = sample_time(per_sample(A.geo_open), A.geo_close, s, n);
 #include "vm_chain_win.h"
-        add_sample<C>(A, L, acc);
+        add_sample<C>(A, L, per_sample(A.color_fa), acc);
         if (s == A.samples - 1)
             store_mean<C>(A, x, y, acc, n);
     }

@@ -41,5 +41,8 @@ struct VmTransition {
     uint8_t *rgb;
 };
 void vm_launch_transition(const VmTransition &T, hipStream_t s);
+// the pre-pass alone: T's two schedule planes ramped at T.t with T.ease into T.rates (vm_tshutter.hip takes its colour
+// rates from it)
+void vm_launch_rates(const VmTransition &T, hipStream_t s);
 
 #endif

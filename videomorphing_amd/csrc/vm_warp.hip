@@ -25,6 +25,7 @@
 // the uniform instantiations (RATES == false).  A third tail, CANVAS, is the renderer's own: RGB8 from the extended canvases.
 #include "vm_chain.h"
 #include "vm_layer_tap.h"
+#include "vm_ramp.h"
 #include "vm_warp.h"
 
 namespace {
@@ -56,14 +57,6 @@ struct VmWarpArgs {
     int ex;
     uint8_t *rgb;
 };
-
-// the ramp of one texel's schedule (t0, t1) at time t
-__device__ __forceinline__ float ramp(float2 s, float t, int ease)
-{
-    const float d = s.y - s.x;
-    const float r = d > 0.0f ? fminf(fmaxf(__fdiv_rn(t - s.x, d), 0.0f), 1.0f) : (t >= s.x ? 1.0f : 0.0f);
-    return ease == VM_EASE_SMOOTH ? (r * r) * (3.0f - 2.0f * r) : r;
-}
 
 // the pre-pass of a transition call: the two schedule planes ramped per texel into the call's (G, K) plane (all three of
 // the field's pitch).  Ramping while staging instead -- every workgroup the cells it stages, a tap outside the window its
@@ -186,6 +179,12 @@ void vm_launch_warp(int w, int h, int rs, float color_fa, float geo_fa, int colo
     launch_tail<false>(A, channels, vm_render_window_form(rs, h), s);
 }
 
+void vm_launch_rates(const VmTransition &T, hipStream_t s)
+{
+    dim3 b(64, 4), g((T.w + 63) / 64, (T.h + 3) / 4);
+    hipLaunchKernelGGL(k_rates, g, b, 0, s, T.rates, T.sched_geo, T.sched_color, T.w, T.h, T.rs, T.t, T.ease);
+}
+
 void vm_launch_transition(const VmTransition &T, hipStream_t s)
 {
     VmWarpArgs A{};
@@ -196,7 +195,6 @@ void vm_launch_transition(const VmTransition &T, hipStream_t s)
     A.map0 = T.map0; A.map1 = T.map1; A.resid = T.resid; A.flags = T.flags; A.rates_out = T.rates_out;
     A.layer0 = T.layer0; A.layer1 = T.layer1; A.out = T.out;
     A.ext0 = T.ext0; A.ext1 = T.ext1; A.ex = T.ex; A.rgb = T.rgb;
-    dim3 b(64, 4), g((T.w + 63) / 64, (T.h + 3) / 4);
-    hipLaunchKernelGGL(k_rates, g, b, 0, s, T.rates, T.sched_geo, T.sched_color, T.w, T.h, T.rs, T.t, T.ease);
+    vm_launch_rates(T, s);
     launch_tail<true>(A, T.channels, vm_render_window_form(T.rs, T.h), s);
 }

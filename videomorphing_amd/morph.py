@@ -711,6 +711,47 @@ class Frame(object):
                                                         int(samples), int(color_from), C.byref(ms)))
         return ms.value
 
+    @staticmethod
+    def _shutter_color_time(t_open, t_close, t_color):
+        """t_color of the transition shutter calls; None: the float32 midpoint (t_open + t_close) * 0.5, formed here"""
+        if t_color is not None:
+            return float(t_color)
+        return float((np.float32(t_open) + np.float32(t_close)) * np.float32(0.5))
+
+    def render_transition_shutter(self, t_open, t_close, samples, t_color=None, ease=capi.EASE_LINEAR, color_from=1):
+        """render_transition with motion blur (vm_render_transition_shutter): the mean over `samples` (1..64) times
+        between t_open and t_close, the geometry schedule ramped at each of them, the colour schedule once at t_color
+        (None: the float32 midpoint (t_open + t_close) * 0.5, formed on the host) -> (h, w, 3) uint8"""
+        out = np.zeros((self.h, self.w, 3), dtype=np.uint8)
+        tc = self._shutter_color_time(t_open, t_close, t_color)
+        capi.check(self._L.vm_render_transition_shutter(self._h, float(t_open), float(t_close), int(samples), tc, int(ease),
+                                                        int(color_from), out.ctypes.data, 0))
+        return out
+
+    def render_transition_shutter_dev(self, t_open, t_close, samples, t_color=None, ease=capi.EASE_LINEAR, color_from=1):
+        ms = C.c_float(0)
+        tc = self._shutter_color_time(t_open, t_close, t_color)
+        capi.check(self._L.vm_render_transition_shutter_dev(self._h, float(t_open), float(t_close), int(samples), tc, int(ease),
+                                                            int(color_from), C.byref(ms)))
+        return ms.value
+
+    def render_transition_shutter_layers(self, t_open, t_close, samples, t_color=None, ease=capi.EASE_LINEAR, color_from=1):
+        """the uploaded layers through the same shutter under the schedule (vm_render_transition_shutter_layers): float32
+        of the shape they were uploaded in; t_color None: the float32 midpoint, as above"""
+        shape = getattr(self, "_layer_shape", (self.h, self.w))       # (no upload: the call answers VM_E_STATE)
+        out = np.empty(shape, dtype=np.float32)
+        tc = self._shutter_color_time(t_open, t_close, t_color)
+        capi.check(self._L.vm_render_transition_shutter_layers(self._h, float(t_open), float(t_close), int(samples), tc, int(ease),
+                                                               int(color_from), out.ctypes.data, 0))
+        return out
+
+    def render_transition_shutter_layers_dev(self, t_open, t_close, samples, t_color=None, ease=capi.EASE_LINEAR, color_from=1):
+        ms = C.c_float(0)
+        tc = self._shutter_color_time(t_open, t_close, t_color)
+        capi.check(self._L.vm_render_transition_shutter_layers_dev(self._h, float(t_open), float(t_close), int(samples), tc,
+                                                                   int(ease), int(color_from), C.byref(ms)))
+        return ms.value
+
     def quadratic_path(self, tol=1e-4, max_it=200):
         """CQuadraticPath::optimize for this frame's v (QuadraticPath.cpp:24-223); the result
         stays in the frame for render_halfway.  Returns (iterations, residual, ms)."""
