@@ -870,11 +870,10 @@ __device__ __forceinline__ int med3i(int x, int lo, int hi)
 }
 
 // tex2D(linear, clamp) of both images at p -+ (vx, vy) (the arithmetic of tap(), the four
-// products summed in quad order)
-// ... in two halves, so that the texel loads of independent evaluations (the four of the
-// gradient) can be in flight together: the lane's texel and its corner weight,
-__device__ __forceinline__ void taps32_issue(const VmLevelView &L, const TapLane &t, const PixelCtx &c, float vx,
-                                             float vy, float &texel, float &wgt)
+// products summed in quad order).
+// The byte offset of the lane's texel from img0 (clamped to the image) and the lane's corner weight
+__device__ __forceinline__ uint32_t taps32_addr(const VmLevelView &L, const TapLane &t, const PixelCtx &c, float vx,
+                                                float vy, float &wgt)
 {
     const float xb = fmaf(t.sgn, vx, (float)c.px), yb = fmaf(t.sgn, vy, (float)c.py);
     float fi = floorf(xb), fj = floorf(yb);
@@ -882,10 +881,37 @@ __device__ __forceinline__ void taps32_issue(const VmLevelView &L, const TapLane
     fi = __builtin_amdgcn_fmed3f(fi, -1.0f, (float)L.w);
     fj = __builtin_amdgcn_fmed3f(fj, -1.0f, (float)L.h);
     const int i = med3i((int)fi + t.cx, 0, L.w - 1), j = med3i((int)fj + t.cy, 0, L.h - 1);
+    wgt = fmaf(t.wxs, a, t.wxo) * fmaf(t.wys, b, t.wyo);
+    return (uint32_t)(t.imgoff + j * L.rs + i) << 2;
+}
+// The taps in two halves, so that the texel loads of independent evaluations (the four of the
+// gradient) can be in flight together: the lane's texel and its corner weight,
+__device__ __forceinline__ void taps32_issue(const VmLevelView &L, const TapLane &t, const PixelCtx &c, float vx,
+                                             float vy, float &texel, float &wgt)
+{
     // (a global load off the image base + an unsigned 32-bit byte offset: the images are read-only,
     // both sit in the level's slab)
-    texel = *(vm_g_cf32 *)((const char *)L.img0 + ((uint32_t)(t.imgoff + j * L.rs + i) << 2));
-    wgt = fmaf(t.wxs, a, t.wxo) * fmaf(t.wys, b, t.wyo);
+    texel = *(vm_g_cf32 *)((const char *)L.img0 + taps32_addr(L, t, c, vx, vy, wgt));
+}
+// The texel a lane fetched last in this pixel's line search, keyed by its byte offset (after clamping, so the border
+// needs no case of its own).  Golden section closes in on t = 0: after the first few steps a lane's corner texel is
+// the one it loaded a round earlier, and a lone wave has nothing to put under that load.  A lane whose offset repeats
+// issues no load; when no lane of the wave does, the wait that follows has nothing to wait for.  The images are
+// read-only for the whole launch, so the kept value is the value a load would return.
+struct TexelKeep {
+    uint32_t off = 0xFFFFFFFFu; // no texel sits there: offsets are multiples of 4
+    float texel = 0.0f;
+};
+// taps32_issue for the evaluations along a search line, which follow one another: the load only where the offset moved
+__device__ __forceinline__ void taps32_issue(const VmLevelView &L, const TapLane &t, const PixelCtx &c, float vx,
+                                             float vy, TexelKeep &keep, float &texel, float &wgt)
+{
+    const uint32_t off = taps32_addr(L, t, c, vx, vy, wgt);
+    if (off != keep.off) {
+        keep.texel = *(vm_g_cf32 *)((const char *)L.img0 + off);
+        keep.off = off;
+    }
+    texel = keep.texel;
 }
 // ... then the quad sums and the exchange between the two images' quads
 __device__ __forceinline__ void taps32_finish(const TapLane &t, float texel, float wgt, float &lx, float &ly)
@@ -897,11 +923,12 @@ __device__ __forceinline__ void taps32_finish(const TapLane &t, float texel, flo
     lx = t.odd ? o : r;
     ly = t.odd ? r : o;
 }
+// (the evaluations along the search line: one after the other, the lane's last texel kept)
 __device__ __forceinline__ void taps32(const VmLevelView &L, const TapLane &t, const PixelCtx &c, float vx, float vy,
-                                       float &lx, float &ly)
+                                       TexelKeep &keep, float &lx, float &ly)
 {
     float texel, wgt;
-    taps32_issue(L, t, c, vx, vy, texel, wgt);
+    taps32_issue(L, t, c, vx, vy, keep, texel, wgt);
     taps32_finish(t, texel, wgt, lx, ly);
 }
 
@@ -1020,11 +1047,12 @@ __device__ __forceinline__ bool decide32(const VmLevelView &L, const VmKParams &
     const float Q1 = WU * (c.ui_b.x * gx + c.ui_b.y * gy) + P.w_tps * (c.tps_b.x * gx + c.tps_b.y * gy);
     // temporal term along the line: WT (|v + g t - ref|_1 - |v - ref|_1)
     const float T0 = fabsf(c.v.x - c.tref.x) + fabsf(c.v.y - c.tref.y);
+    TexelKeep keep; // of this pixel's search: filled by the first evaluation
 #define ELINE(T_, F_, LUM_)                                                            \
     {                                                                                  \
         const float nvx_ = fmaf(gx, (T_), c.v.x), nvy_ = fmaf(gy, (T_), c.v.y);        \
         ++n_eval;                                                                      \
-        taps32(L, tl, c, nvx_, nvy_, lx, ly);                                          \
+        taps32(L, tl, c, nvx_, nvy_, keep, lx, ly);                                    \
         (F_) = fmaf(WS, change32<INTERIOR>(P, nb, c, lx, ly), (T_) * fmaf(Q2, (T_), Q1)); \
         if (has_temp)                                                                  \
             (F_) = fmaf(WT, (fabsf(nvx_ - c.tref.x) + fabsf(nvy_ - c.tref.y)) - T0, (F_)); \
@@ -1142,11 +1170,12 @@ __device__ __forceinline__ bool decide64(const VmLevelView &L, const VmKParams &
     const float Q2 = (WU * c.ui_axy + P.w_tps * c.tps_axy) * gg;
     const float Q1 = WU * (c.ui_b.x * gx + c.ui_b.y * gy) + P.w_tps * (c.tps_b.x * gx + c.tps_b.y * gy);
     const float T0 = fabsf(c.v.x - c.tref.x) + fabsf(c.v.y - c.tref.y);
+    TexelKeep keep; // of this pixel's search: filled by the first evaluation
     // the energy at t of this half; f and the lumas of both halves come back
 #define ELINE2(T_, FLO_, FHI_, LLO_, LHI_)                                              \
     {                                                                                  \
         const float nvx_ = fmaf(gx, (T_), c.v.x), nvy_ = fmaf(gy, (T_), c.v.y);        \
-        taps32(L, tl, c, nvx_, nvy_, lx, ly);                                          \
+        taps32(L, tl, c, nvx_, nvy_, keep, lx, ly);                                    \
         float f_ = fmaf(WS, change32<INTERIOR>(P, nb, c, lx, ly), (T_) * fmaf(Q2, (T_), Q1)); \
         if (has_temp)                                                                  \
             f_ = fmaf(WT, (fabsf(nvx_ - c.tref.x) + fabsf(nvy_ - c.tref.y)) - T0, f_); \
