@@ -571,6 +571,51 @@ int  vm_render_transition_shutter_layers(vm_frame *f, float t_open, float t_clos
 /* same (render.cu:16-60, UI/RenderWidget.cpp:229-266), output left on the device (for timing) */
 int  vm_render_transition_shutter_layers_dev(vm_frame *f, float t_open, float t_close, int samples, float t_color, int ease,
                                              int color_from, float *elapsed_ms);
+/* ---- viewports: any window of the morph at any size, supersampled ----------
+ * The calls above render the w x h grid of the field, one chain per pixel from the pixel's centre.  A viewport call lays an
+ * out_w x out_h grid freely over the halfway domain -- a zoom, a pan, a proxy, a delivery size, overscan into the
+ * Poisson-extended canvases -- and starts the chain of kernel_render_halfway_image (Algorithm/render.cu:16-60) from a
+ * regular nx x ny grid of sub-sample points inside every output pixel, in one launch, and returns the mean of the samples'
+ * colours.  Coordinates are pixel-EDGE: field pixel i covers [i, i + 1), its centre is i + 0.5. */
+typedef struct vm_viewport {
+    float x0, y0;           /* top-left corner of the output in field coordinates */
+    float step_x, step_y;   /* field pixels per output pixel (1 = native, 0.5 = 2x enlargement, 2 = half size) */
+    int   out_w, out_h;     /* output size, 1..32768 each */
+    int   nx, ny;           /* sub-samples per output pixel, a regular nx x ny grid; 1 <= nx * ny <= 64 */
+} vm_viewport;
+/* In float32, in this order (the divisions correctly rounded), for output pixel (X, Y) and sub-sample s = j * nx + i
+ * (i fastest, s = 0 .. N - 1, N = nx * ny):
+ *   fx = ((float)i + 0.5f) / (float)nx             fy = ((float)j + 0.5f) / (float)ny
+ *   qx = (x0 + ((float)X + fx) * step_x) - 0.5f    qy = (y0 + ((float)Y + fy) * step_y) - 0.5f
+ *   (p, V)_s = the chain as vm_frame_sampling_maps states it, with q = (qx, qy) in the place of the pixel, at the call's
+ *              geo_fa (not clamped)
+ *   c_s = the colour of the uniform call on (map0, map1)_s = (p - V, p + V) before its rounding, blended by color_from
+ *         with the call's color_fa
+ *   acc = acc + c_s                                (acc starts at +0)
+ * and the result is acc / (float)N.  The field, the path, the canvases and the layers are read outside [0, w) x [0, h) as
+ * the chain reads them wherever a warp leaves the image (clamped taps), so a viewport may lie partly or wholly outside the
+ * field.  {0, 0, 1, 1, w, h, 1, 1} gives the bits of the uniform call; integer x0, y0 with step 1 and one sample give the
+ * corresponding slice of it; with a zero field and no path {0, 0, 2, 2, w / 2, h / 2, 2, 2} reads exactly the four texels
+ * of every 2 x 2 block: an exact box reduction.  Every call of this section answers VM_E_INVALID for a NULL viewport or
+ * output, a non-finite x0, y0 or step, a step that is not > 0, out_w or out_h outside 1..32768, nx < 1, ny < 1 or
+ * nx * ny > 64, a color_from outside 0..2 or a pitch below the output's row, and changes nothing of the frame (v, path,
+ * canvases, layers, schedule); no device memory depends on nx * ny.  Not in this section, deliberately: viewport calls under
+ * a transition schedule or over a shutter, and viewport sampling maps (the schedule is not consulted). */
+/* vm_render_halfway through a viewport (render.cu:16-60, UI/RenderWidget.cpp:229-266): RGB8 from the Poisson-extended
+ * canvases, (uint8)((double)(acc / (float)N) + 0.5) per channel.  rgb_out: out_h rows of out_w RGB8 pixels, pitch in bytes
+ * (0 = tight). */
+int  vm_render_viewport(vm_frame *f, const vm_viewport *vp, float color_fa, float geo_fa, int color_from, uint8_t *rgb_out,
+                        int pitch_bytes);
+/* same (render.cu:16-60, UI/RenderWidget.cpp:229-266), output left on the device (for timing) */
+int  vm_render_viewport_dev(vm_frame *f, const vm_viewport *vp, float color_fa, float geo_fa, int color_from, float *elapsed_ms);
+/* vm_render_layers through a viewport (render.cu:16-60, UI/RenderWidget.cpp:229-266): the layers of vm_frame_upload_layers
+ * from the same sub-sample points, so that a matte is filtered exactly as its plate is.  out: (out_h, out_w, channels)
+ * floats, pitch in floats (0 = tight).  VM_E_STATE on a frame that holds no layers. */
+int  vm_render_viewport_layers(vm_frame *f, const vm_viewport *vp, float color_fa, float geo_fa, int color_from, float *out,
+                               int pitch_floats);
+/* same (render.cu:16-60, UI/RenderWidget.cpp:229-266), output left on the device (for timing) */
+int  vm_render_viewport_layers_dev(vm_frame *f, const vm_viewport *vp, float color_fa, float geo_fa, int color_from,
+                                   float *elapsed_ms);
 /* CPoissonExt::prepare + poissonExtend for one side (1 or 2) of the frame,
  * Algorithm/PoissonExt.cpp:49-362, on the device-resident canvases: matrix-free
  * multigrid-preconditioned CG instead of MKL DSS.  iters/rel_res may be NULL. */

@@ -23,6 +23,35 @@ inline std::vector<unsigned char> make_extended(const unsigned char *rgb, int w,
     return can;
 }
 
+// A viewport of the morph (vm_viewport): where an out_w x out_h grid lies over the halfway domain, in pixel-EDGE
+// coordinates (field pixel i covers [i, i + 1)), and how many sub-samples every output pixel takes.  The constructors
+// compute in double and round once, as the Python facade's do.
+struct Viewport : vm_viewport {
+    Viewport(double x0_, double y0_, double step_x_, double step_y_, int out_w_, int out_h_, int nx_ = 1, int ny_ = 1)
+        : vm_viewport{(float)x0_, (float)y0_, (float)step_x_, (float)step_y_, out_w_, out_h_, nx_, ny_} {}
+    // the frame itself: the bits of render_halfway_image
+    static Viewport identity(int w, int h) { return Viewport(0.0, 0.0, 1.0, 1.0, w, h); }
+    // a w x h window at native scale with its corner at (x, y)
+    static Viewport crop(double x, double y, int w, int h) { return Viewport(x, y, 1.0, 1.0, w, h); }
+    // the whole w x h frame at another size
+    static Viewport fit(int w, int h, int out_w, int out_h) { return Viewport(0.0, 0.0, (double)w / out_w, (double)h / out_h, out_w, out_h); }
+    // an out_w x out_h window centred on (cx, cy), `factor` times enlarged
+    static Viewport zoom(double cx, double cy, double factor, int out_w, int out_h)
+    {
+        const double step = 1.0 / factor;
+        return Viewport(cx - 0.5 * out_w * step, cy - 0.5 * out_h * step, step, step, out_w, out_h);
+    }
+    // the w x h frame and `margin` pixels beyond every edge
+    static Viewport overscan(int w, int h, int margin) { return Viewport(-(double)margin, -(double)margin, 1.0, 1.0, w + 2 * margin, h + 2 * margin); }
+    // the same viewport with nx x ny sub-samples per output pixel (ny 0: nx)
+    Viewport supersampled(int nx_, int ny_ = 0) const
+    {
+        Viewport v = *this;
+        v.nx = nx_; v.ny = ny_ ? ny_ : nx_;
+        return v;
+    }
+};
+
 class Frame {
 public:
     Frame(Context &ctx, int w, int h, int ex) : w_(w), h_(h), ex_(ex) { check(vm_frame_create(ctx.handle(), w, h, ex, &f_)); }
@@ -199,6 +228,33 @@ public:
         check(vm_render_transition_shutter_layers_dev(f_, t_open, t_close, samples, t_color, ease, color_from, &ms));
         return ms;
     }
+    // any viewport of the morph at any size, supersampled (vm_render_viewport): every pixel of the vp.out_w x vp.out_h grid
+    // the mean of vp.nx x vp.ny chains of render.cu:16-60, taken in float32 before the one rounding: (out_h, out_w, 3) bytes
+    std::vector<unsigned char> render_viewport(const Viewport &vp, float color_fa, float geo_fa, int color_from = 1)
+    {
+        std::vector<unsigned char> out(viewport_pixels(vp) * 3);
+        check(vm_render_viewport(f_, &vp, color_fa, geo_fa, color_from, out.data(), 0));
+        return out;
+    }
+    float render_viewport_dev(const Viewport &vp, float color_fa, float geo_fa, int color_from = 1)
+    {
+        float ms = 0;
+        check(vm_render_viewport_dev(f_, &vp, color_fa, geo_fa, color_from, &ms));
+        return ms;
+    }
+    // the layers through the same viewport: (out_h, out_w, channels) floats
+    std::vector<float> render_viewport_layers(const Viewport &vp, float color_fa, float geo_fa, int color_from = 1)
+    {
+        std::vector<float> out(viewport_pixels(vp) * (channels_ ? channels_ : 1));
+        check(vm_render_viewport_layers(f_, &vp, color_fa, geo_fa, color_from, out.data(), 0));
+        return out;
+    }
+    float render_viewport_layers_dev(const Viewport &vp, float color_fa, float geo_fa, int color_from = 1)
+    {
+        float ms = 0;
+        check(vm_render_viewport_layers_dev(f_, &vp, color_fa, geo_fa, color_from, &ms));
+        return ms;
+    }
     // sampling_maps under the schedule, and the rates (g, k) every output pixel ended with
     struct TransitionMaps {
         SamplingMaps maps;
@@ -217,6 +273,12 @@ public:
     vm_frame *handle() const { return f_; }
 
 private:
+    // the pixels of a viewport's output (one for a viewport the library will refuse)
+    static size_t viewport_pixels(const vm_viewport &vp)
+    {
+        const bool ok = vp.out_w >= 1 && vp.out_w <= 32768 && vp.out_h >= 1 && vp.out_h <= 32768;
+        return ok ? (size_t)vp.out_w * vp.out_h : 1;
+    }
     vm_frame *f_ = nullptr;
     int w_, h_, ex_;
     int channels_ = 0;

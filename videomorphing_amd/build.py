@@ -56,6 +56,8 @@ UNITS = [
     ("vm_shutter.cpp", "vm_shutter.o", ["-x", "hip"]),
     ("vm_tshutter.hip", "vm_tshutter_kernels.o", ["-ffp-contract=off"]),
     ("vm_tshutter.cpp", "vm_tshutter.o", ["-x", "hip"]),
+    ("vm_viewport.hip", "vm_viewport_kernels.o", ["-ffp-contract=off"]),
+    ("vm_viewport.cpp", "vm_viewport.o", ["-x", "hip"]),
     ("vm_poisson.hip", "vm_poisson.o", ["-ffp-contract=off"]),
     ("vm_mgb.hip", "vm_mgb.o", ["-ffp-contract=fast"]),
     ("vm_pyramid.hip", "vm_pyramid.o", ["-ffp-contract=off"]),

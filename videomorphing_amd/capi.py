@@ -60,6 +60,7 @@ SYMBOLS = [
     "vm_render_shutter", "vm_render_shutter_dev", "vm_render_shutter_layers", "vm_render_shutter_layers_dev",
     "vm_render_transition_shutter", "vm_render_transition_shutter_dev", "vm_render_transition_shutter_layers",
     "vm_render_transition_shutter_layers_dev",
+    "vm_render_viewport", "vm_render_viewport_dev", "vm_render_viewport_layers", "vm_render_viewport_layers_dev",
 ]
 
 
@@ -78,6 +79,12 @@ class Constraint(C.Structure):
 class VideoConstraint(C.Structure):
     _fields_ = [("lx", C.c_float), ("ly", C.c_float), ("rx", C.c_float), ("ry", C.c_float),
                 ("weight", C.c_float), ("frame", C.c_int)]
+
+
+class ViewportStruct(C.Structure):
+    """vm_viewport (videomorphing_amd.viewport.Viewport builds and checks one)"""
+    _fields_ = [("x0", C.c_float), ("y0", C.c_float), ("step_x", C.c_float), ("step_y", C.c_float),
+                ("out_w", C.c_int), ("out_h", C.c_int), ("nx", C.c_int), ("ny", C.c_int)]
 
 
 class Progress(C.Structure):
@@ -268,6 +275,10 @@ def load():
         "vm_render_transition_shutter_dev": [vp, f, f, i, f, i, i, C.POINTER(f)],
         "vm_render_transition_shutter_layers": [vp, f, f, i, f, i, i, vp, i],
         "vm_render_transition_shutter_layers_dev": [vp, f, f, i, f, i, i, C.POINTER(f)],
+        "vm_render_viewport": [vp, C.POINTER(ViewportStruct), f, f, i, vp, i],
+        "vm_render_viewport_dev": [vp, C.POINTER(ViewportStruct), f, f, i, C.POINTER(f)],
+        "vm_render_viewport_layers": [vp, C.POINTER(ViewportStruct), f, f, i, vp, i],
+        "vm_render_viewport_layers_dev": [vp, C.POINTER(ViewportStruct), f, f, i, C.POINTER(f)],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

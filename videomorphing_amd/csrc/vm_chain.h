@@ -1,6 +1,6 @@
 // vm_chain.h -- the compositor's fixed-point chain (kernel_render_halfway_image, Algorithm/render.cu:16-60), stated once
 // for the units that walk it: vm_render.hip (RGB8 from the extended canvases), vm_warp.hip (sampling maps, float
-// layers, transition control), vm_shutter.hip (both tails over the sample times of a shutter) and vm_tshutter.hip (the same under a schedule).  A kernel walks the window form (the product path: taps served from an LDS window;
+// layers, transition control), vm_shutter.hip (both tails over the sample times of a shutter), vm_tshutter.hip (the same under a schedule) and vm_viewport.hip (both tails from the sub-sample points of a viewport).  A kernel walks the window form (the product path: taps served from an LDS window;
 // vm_chain_win.h, included in the kernel's body) or calls chain_plain (VM_RENDER=plain, and fields of 4 GiB and more),
 // returns if the chain gave its thread no pixel, and runs its own tail on the Landing.  Everything is float32 in tap2's
 // expressions and order; the units are compiled with -ffp-contract=off.  Every function here is inlined into the kernel
@@ -140,6 +140,44 @@ __device__ __forceinline__ bool chain_plain(int w, int h, int rs, float geo_fa, 
     L.v = v;
     L.g = gk.x; L.k = gk.y;
     return true;
+}
+
+// the plain form from any point q of the halfway domain in the place of the pixel (a pixel's centre i is q = i; the
+// viewport kernels of vm_viewport.hip start between pixels, and own their output grid): chain_plain's statements, stated
+// beside it and not under it, because chain_plain's callers compile to other (equivalent) code once it calls this.
+template <bool RATES, class Rates>
+__device__ __forceinline__ void chain_plain_from(int w, int h, int rs, float geo_fa, const float2 *vf, const float2 *uf,
+                                                 Rates rates, const float qx, const float qy, Landing &L)
+{
+    const float alpha = 0.8f;
+    float s1 = 2 * geo_fa - 1;
+    float s2 = 4 * geo_fa - 4 * geo_fa * geo_fa;
+    L.px = qx; L.py = qy;
+    L.lx = qx; L.ly = qy;
+    float2 v = tap2(vf, w, h, rs, L.px + 0.5f, L.py + 0.5f);
+    float2 u = uf ? tap2(uf, w, h, rs, L.px + 0.5f, L.py + 0.5f) : make_float2(0.0f, 0.0f);
+    float2 gk = make_float2(0.0f, 0.0f);
+    if constexpr (RATES) gk = tapr(rates, w, h, rs, L.px + 0.5f, L.py + 0.5f);
+    for (int i = 0; i < VM_RENDER_ITERS; ++i) {
+        L.lx = L.px; L.ly = L.py;
+        if constexpr (RATES) {
+            s1 = 2 * gk.x - 1;
+            s2 = 4 * gk.x - 4 * gk.x * gk.x;
+        }
+        L.px = qx - s1 * v.x - s2 * u.x;
+        L.py = qy - s1 * v.y - s2 * u.y;
+        float2 t = tap2(vf, w, h, rs, L.px + 0.5f, L.py + 0.5f);
+        v.x = alpha * t.x + (1 - alpha) * v.x;
+        v.y = alpha * t.y + (1 - alpha) * v.y;
+        if (uf) {       // (a zero path stays zero: alpha * 0 + (1 - alpha) * 0)
+            t = tap2(uf, w, h, rs, L.px + 0.5f, L.py + 0.5f);
+            u.x = alpha * t.x + (1 - alpha) * u.x;
+            u.y = alpha * t.y + (1 - alpha) * u.y;
+        }
+        if constexpr (RATES) gk = tapr(rates, w, h, rs, L.px + 0.5f, L.py + 0.5f);
+    }
+    L.v = v;
+    L.g = gk.x; L.k = gk.y;
 }
 
 // ---------------------------------------------------------------------------

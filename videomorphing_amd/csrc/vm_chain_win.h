@@ -1,6 +1,6 @@
 // vm_chain_win.h -- the window form of the compositor's chain (vm_chain.h), stated once as the statements a window kernel
 // includes at the top of its body -- k_render_win (vm_render.hip) and k_warp_win (vm_warp.hip) -- or of its sample loop's
-// (k_shutter_win, vm_shutter.hip; k_tblur_win, vm_tshutter.hip).  It is no function because
+// (k_shutter_win, vm_shutter.hip; k_tblur_win, vm_tshutter.hip; k_viewport_win, vm_viewport.hip).  It is no function because
 // the compiler lays a kernel out differently once this body sits behind any function boundary, a lambda included (the
 // fallback's float2 gathers stay whole, the vectoriser pairs other operations, and the sum after the inside / outside
 // split of the tap is emitted once instead of once per side): k_warp_win<true, CANVAS, true> lost 1.5 us of 100 that way.
@@ -19,6 +19,14 @@
 //                                the barrier before a restaging belongs to it, and a window that has not moved may stay)
 //   VM_CHAIN_WIN_STAGE_FIELD     whether a staging copies v and u, workgroup-uniform (default: true; vm_tshutter.hip stages
 //                                the rates at every sample, v and u only where the window has moved)
+// A kernel whose output grid is not the field's (vm_viewport.hip: x, y, tiles_x and ntiles then count OUTPUT pixels and
+// tiles, w, h and rs stay the field's) defines
+//   VM_CHAIN_WIN_Q_X, _Q_Y           the point q of the halfway domain the chain of output pixel (x, y) starts from
+//                                    (default: (float)x, (float)y, the pixel's centre)
+//   VM_CHAIN_WIN_ORIGIN_X, _Y        the field cell the tile's footprint begins at, from which the window is placed
+//   VM_CHAIN_WIN_CENTRE_X, _Y        and the cell at its centre, within the field, whose warp displaces the window
+//                                    (defaults: bx, by and min(bx + RW / 2, wm1), min(by + RH / 2, hm1): the tile itself)
+//   VM_CHAIN_WIN_OUTSIDE             whether output pixel (x, y) is no pixel (default: x >= w || y >= h)
 // The defaults leave the statements below what they were.
 //
 // The window form: the plain chain with the 21 dependent taps of v (and u, and the rates) served from LDS and lean index
@@ -45,6 +53,19 @@
 #ifndef VM_CHAIN_WIN_STAGE_FIELD
 #define VM_CHAIN_WIN_STAGE_FIELD true
 #endif
+#ifndef VM_CHAIN_WIN_Q_X
+#define VM_CHAIN_WIN_Q_X (float)x
+#define VM_CHAIN_WIN_Q_Y (float)y
+#endif
+#ifndef VM_CHAIN_WIN_ORIGIN_X
+#define VM_CHAIN_WIN_ORIGIN_X bx
+#define VM_CHAIN_WIN_ORIGIN_Y by
+#define VM_CHAIN_WIN_CENTRE_X min(bx + RW / 2, wm1)
+#define VM_CHAIN_WIN_CENTRE_Y min(by + RH / 2, hm1)
+#endif
+#ifndef VM_CHAIN_WIN_OUTSIDE
+#define VM_CHAIN_WIN_OUTSIDE x >= w || y >= h
+#endif
     int x, y;
     Landing L;
     {
@@ -64,7 +85,7 @@
         float s2 = 4 * geo_fa - 4 * geo_fa * geo_fa;
         int ox, oy;
         {
-            const int cx = min(bx + RW / 2, wm1), cy = min(by + RH / 2, hm1);
+            const int cx = VM_CHAIN_WIN_CENTRE_X, cy = VM_CHAIN_WIN_CENTRE_Y;
             const float2 vc = vf[cy * rs + cx];
             const float2 uc = HAS_U ? uf[cy * rs + cx] : make_float2(0.0f, 0.0f);
             if constexpr (RATES) {             // the window goes where the centre's own rate sends it
@@ -74,8 +95,8 @@
             }
             // (a non-finite or absurd centre puts the window nowhere useful: every tap then takes the global path)
             const float dx = __builtin_amdgcn_fmed3f(s1 * vc.x + s2 * uc.x, -1e6f, 1e6f), dy = __builtin_amdgcn_fmed3f(s1 * vc.y + s2 * uc.y, -1e6f, 1e6f);
-            ox = bx - (int)rintf(dx) - RR;
-            oy = by - (int)rintf(dy) - RR;
+            ox = VM_CHAIN_WIN_ORIGIN_X - (int)rintf(dx) - RR;
+            oy = VM_CHAIN_WIN_ORIGIN_Y - (int)rintf(dy) - RR;
         }
         // staged with CLAMPED source coordinates: every index below is within the field
         if (VM_CHAIN_WIN_STAGE(ox, oy)) {
@@ -93,9 +114,9 @@
             __syncthreads();
         }
         x = bx + threadIdx.x; y = by + threadIdx.y;
-        if (x >= w || y >= h)
+        if (VM_CHAIN_WIN_OUTSIDE)
             VM_CHAIN_WIN_NO_PIXEL;
-        const float qx = (float)x, qy = (float)y;
+        const float qx = VM_CHAIN_WIN_Q_X, qy = VM_CHAIN_WIN_Q_Y;
         float px = qx, py = qy, lx = qx, ly = qy;
         float2 v, u = make_float2(0.0f, 0.0f);
         const LdsWords wv = (LdsWords)win_v, wu = (LdsWords)win_u, wr = (LdsWords)win_r;

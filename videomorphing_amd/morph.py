@@ -712,6 +712,43 @@ class Frame(object):
         return ms.value
 
     @staticmethod
+    def _viewport_grid(s):
+        """(out_h, out_w) of a vm_viewport; one the library will refuse gets a buffer of one pixel"""
+        ok = 1 <= s.out_w <= 32768 and 1 <= s.out_h <= 32768
+        return (s.out_h, s.out_w) if ok else (1, 1)
+
+    def render_viewport(self, vp, color_fa, geo_fa, color_from=1):
+        """render_halfway through a viewport (vm_render_viewport; vp: a videomorphing_amd.viewport.Viewport): any window
+        of the morph at any size, every output pixel the mean of vp.nx x vp.ny chains taken in float32 before the one
+        rounding -> (vp.out_h, vp.out_w, 3) uint8.  The library checks the viewport (VmError, VM_E_INVALID)."""
+        s = vp.struct()
+        out = np.zeros(self._viewport_grid(s) + (3,), dtype=np.uint8)
+        capi.check(self._L.vm_render_viewport(self._h, C.byref(s), float(color_fa), float(geo_fa), int(color_from),
+                                              out.ctypes.data, 0))
+        return out
+
+    def render_viewport_dev(self, vp, color_fa, geo_fa, color_from=1):
+        ms, s = C.c_float(0), vp.struct()
+        capi.check(self._L.vm_render_viewport_dev(self._h, C.byref(s), float(color_fa), float(geo_fa), int(color_from), C.byref(ms)))
+        return ms.value
+
+    def render_viewport_layers(self, vp, color_fa, geo_fa, color_from=1):
+        """the uploaded layers through the same viewport (vm_render_viewport_layers): float32 (vp.out_h, vp.out_w) or
+        (vp.out_h, vp.out_w, C) as they were uploaded -- a matte is filtered exactly as its plate is"""
+        s = vp.struct()
+        shape = getattr(self, "_layer_shape", (self.h, self.w))       # (no upload: the call answers VM_E_STATE)
+        out = np.empty(self._viewport_grid(s) + tuple(shape[2:]), dtype=np.float32)
+        capi.check(self._L.vm_render_viewport_layers(self._h, C.byref(s), float(color_fa), float(geo_fa), int(color_from),
+                                                     out.ctypes.data, 0))
+        return out
+
+    def render_viewport_layers_dev(self, vp, color_fa, geo_fa, color_from=1):
+        ms, s = C.c_float(0), vp.struct()
+        capi.check(self._L.vm_render_viewport_layers_dev(self._h, C.byref(s), float(color_fa), float(geo_fa), int(color_from),
+                                                         C.byref(ms)))
+        return ms.value
+
+    @staticmethod
     def _shutter_color_time(t_open, t_close, t_color):
         """t_color of the transition shutter calls; None: the float32 midpoint (t_open + t_close) * 0.5, formed here"""
         if t_color is not None:
