@@ -581,7 +581,7 @@ __device__ __forceinline__ bool decide_with(const VmLevelView &L, const VmKParam
 // if the coming comparison repeats the last (the next point's position depends on that one bit
 // only).  Every evaluation that is USED is the one decide_with makes at that step, with the same
 // arguments: bit-identical results; n_eval counts the search's evaluations.  (The FAST lean path
-// has its own copy, decide64, which also carries the lumas along.)
+// has its own copy, decide64, which also samples the lumas of the accepted point.)
 template <class Energy, class Ring>
 __device__ __forceinline__ bool decide_with64(const VmLevelView &L, const VmKParams &P, const PixelCtx &c,
                                               const Energy &energy, const Ring &ring, bool hi, float2 &step,
@@ -869,6 +869,15 @@ __device__ __forceinline__ int med3i(int x, int lo, int hi)
     return r;
 }
 
+// med3i(x, 0, hi) with a bound all lanes share (a level's w - 1, h - 1): the instruction takes the bound from its
+// scalar register and the zero as a constant, where three vector operands cost a copy of the bound per use
+__device__ __forceinline__ int clamp0(int hi, int x)
+{
+    int r;
+    asm("v_med3_i32 %0, %1, 0, %2" : "=v"(r) : "v"(x), "s"(hi));
+    return r;
+}
+
 // tex2D(linear, clamp) of both images at p -+ (vx, vy) (the arithmetic of tap(), the four
 // products summed in quad order).
 // The byte offset of the lane's texel from img0 (clamped to the image) and the lane's corner weight
@@ -880,7 +889,7 @@ __device__ __forceinline__ uint32_t taps32_addr(const VmLevelView &L, const TapL
     const float a = xb - fi, b = yb - fj;
     fi = __builtin_amdgcn_fmed3f(fi, -1.0f, (float)L.w);
     fj = __builtin_amdgcn_fmed3f(fj, -1.0f, (float)L.h);
-    const int i = med3i((int)fi + t.cx, 0, L.w - 1), j = med3i((int)fj + t.cy, 0, L.h - 1);
+    const int i = clamp0(L.w - 1, (int)fi + t.cx), j = clamp0(L.h - 1, (int)fj + t.cy);
     wgt = fmaf(t.wxs, a, t.wxo) * fmaf(t.wys, b, t.wyo);
     return (uint32_t)(t.imgoff + j * L.rs + i) << 2;
 }
@@ -930,6 +939,16 @@ __device__ __forceinline__ void taps32(const VmLevelView &L, const TapLane &t, c
     float texel, wgt;
     taps32_issue(L, t, c, vx, vy, keep, texel, wgt);
     taps32_finish(t, texel, wgt, lx, ly);
+}
+// The lumas of the accepted point t of the search line v + g t: the taps once more, where the search evaluated them.
+// b and x of the golden section are bit copies of the t their evaluation was made at, so fmaf(g, t, v) is the point
+// of that evaluation and these are its lumas, bit for bit -- not a sample at v + step, which rounds differently: the
+// lumas FAST commits are the line's.  (The search does not carry lumas through its rounds: a quarter of the searches
+// commit, no round needs them, and the lane's kept texel is normally the one this evaluation wants.)
+__device__ __forceinline__ void line_lumas(const VmLevelView &L, const TapLane &t, const PixelCtx &c, float gx, float gy,
+                                           float tmin, TexelKeep &keep, float2 &luma)
+{
+    taps32(L, t, c, fmaf(gx, tmin, c.v.x), fmaf(gy, tmin, c.v.y), keep, luma.x, luma.y);
 }
 
 // sum over the window of (stored SSIM value - value with the pixel's lumas replaced by
@@ -1048,7 +1067,7 @@ __device__ __forceinline__ bool decide32(const VmLevelView &L, const VmKParams &
     // temporal term along the line: WT (|v + g t - ref|_1 - |v - ref|_1)
     const float T0 = fabsf(c.v.x - c.tref.x) + fabsf(c.v.y - c.tref.y);
     TexelKeep keep; // of this pixel's search: filled by the first evaluation
-#define ELINE(T_, F_, LUM_)                                                            \
+#define ELINE(T_, F_)                                                                  \
     {                                                                                  \
         const float nvx_ = fmaf(gx, (T_), c.v.x), nvy_ = fmaf(gy, (T_), c.v.y);        \
         ++n_eval;                                                                      \
@@ -1056,16 +1075,14 @@ __device__ __forceinline__ bool decide32(const VmLevelView &L, const VmKParams &
         (F_) = fmaf(WS, change32<INTERIOR>(P, nb, c, lx, ly), (T_) * fmaf(Q2, (T_), Q1)); \
         if (has_temp)                                                                  \
             (F_) = fmaf(WT, (fabsf(nvx_ - c.tref.x) + fabsf(nvy_ - c.tref.y)) - T0, (F_)); \
-        (LUM_) = make_float2(lx, ly);                                                  \
     }
     // golden_section_search, morph.cu:885-947
     const float R = 0.618033989f, C = 1.0f - R;
     float a = 0;
     float b = cc * C, x = b * R + cc * C;
     float fb, fx;
-    float2 lb, lq; // lumas at b and at x
-    ELINE(b, fb, lb);
-    ELINE(x, fx, lq);
+    ELINE(b, fb);
+    ELINE(x, fx);
 #pragma unroll 1
     for (;;) {
         if (!(cc - a > P.eps))
@@ -1077,23 +1094,19 @@ __device__ __forceinline__ bool decide32(const VmLevelView &L, const VmKParams &
         cc = lt ? cc : x;
         const float xn = p * R + qv * C;
         float f;
-        float2 lf;
-        ELINE(xn, f, lf);
+        ELINE(xn, f);
         const float ob = b, ofb = fb;
-        const float2 olb = lb;
         b = lt ? x : xn;
         x = lt ? xn : ob;
         fb = lt ? fx : f;
         fx = lt ? f : ofb;
-        lb = lt ? lq : lf;
-        lq = lt ? lf : olb;
     }
 #undef ELINE
     const float tmin = fx < fb ? x : b, fmin = fx < fb ? fx : fb;
     if (!(fmin < 0))
         return false;
     step = make_float2(gx * tmin, gy * tmin);
-    luma = fx < fb ? lq : lb;
+    line_lumas(L, tl, c, gx, gy, tmin, keep, luma);
     return true;
 }
 
@@ -1171,8 +1184,8 @@ __device__ __forceinline__ bool decide64(const VmLevelView &L, const VmKParams &
     const float Q1 = WU * (c.ui_b.x * gx + c.ui_b.y * gy) + P.w_tps * (c.tps_b.x * gx + c.tps_b.y * gy);
     const float T0 = fabsf(c.v.x - c.tref.x) + fabsf(c.v.y - c.tref.y);
     TexelKeep keep; // of this pixel's search: filled by the first evaluation
-    // the energy at t of this half; f and the lumas of both halves come back
-#define ELINE2(T_, FLO_, FHI_, LLO_, LHI_)                                              \
+    // the energy at t of this half; f of both halves comes back
+#define ELINE2(T_, FLO_, FHI_)                                                         \
     {                                                                                  \
         const float nvx_ = fmaf(gx, (T_), c.v.x), nvy_ = fmaf(gy, (T_), c.v.y);        \
         taps32(L, tl, c, nvx_, nvy_, keep, lx, ly);                                    \
@@ -1180,16 +1193,13 @@ __device__ __forceinline__ bool decide64(const VmLevelView &L, const VmKParams &
         if (has_temp)                                                                  \
             f_ = fmaf(WT, (fabsf(nvx_ - c.tref.x) + fabsf(nvy_ - c.tref.y)) - T0, f_); \
         halves(f_, (FLO_), (FHI_));                                                    \
-        halves(lx, (LLO_).x, (LHI_).x);                                                \
-        halves(ly, (LLO_).y, (LHI_).y);                                                \
     }
     // golden_section_search, morph.cu:885-947
     const float R = 0.618033989f, C = 1.0f - R;
     float a = 0;
     float b = cc * C, x = b * R + cc * C;
     float fb, fx;
-    float2 lb, lq; // lumas at b and at x
-    ELINE2(hi ? x : b, fb, fx, lb, lq);
+    ELINE2(hi ? x : b, fb, fx);
     n_eval += 2;
 #pragma unroll 1
     for (;;) {
@@ -1209,32 +1219,25 @@ __device__ __forceinline__ bool decide64(const VmLevelView &L, const VmKParams &
         const float p2 = G ? x1 : b1, q2 = G ? cc1 : a1;
         const float xn2 = p2 * R + q2 * C;
         float f1, f2;
-        float2 l1, l2;
-        ELINE2(hi ? xn2 : xn, f1, f2, l1, l2);
+        ELINE2(hi ? xn2 : xn, f1, f2);
         ++n_eval;
         {
             const float nfb = lt ? fx : f1, nfx = lt ? f1 : fb;
-            const float2 nlb = lt ? lq : l1, nlq = lt ? l1 : lb;
             a = a1;
             cc = cc1;
             b = b1;
             x = x1;
             fb = nfb;
             fx = nfx;
-            lb = nlb;
-            lq = nlq;
         }
         if (cc - a > P.eps && (fx < fb) == G) { // the guess held: f2 is the next step's evaluation
             const float ob = b, ofb = fb;
-            const float2 olb = lb;
             a = G ? b : a;
             cc = G ? cc : x;
             b = G ? x : xn2;
             x = G ? xn2 : ob;
             fb = G ? fx : f2;
             fx = G ? f2 : ofb;
-            lb = G ? lq : l2;
-            lq = G ? l2 : olb;
             ++n_eval;
         }
     }
@@ -1243,7 +1246,7 @@ __device__ __forceinline__ bool decide64(const VmLevelView &L, const VmKParams &
     if (!(fmin < 0))
         return false;
     step = make_float2(gx * tmin, gy * tmin);
-    luma = fx < fb ? lq : lb;
+    line_lumas(L, tl, c, gx, gy, tmin, keep, luma); // both halves at the same point
     return true;
 }
 #endif
@@ -1640,7 +1643,9 @@ __device__ __forceinline__ bool tile_sweep(TileLds &S, const VmLevelView &L, con
                         ctx_load(c, L, S.tps, px, py);
                         LdsSrc src{&S, (ty * 2 + pi) * VM_HALO_W + (tx * 2 + pj)};
                         c.tps_b = S.tpsb[src.hc + 2 * VM_HALO_W + 2];
-                        float2 step, luma;
+                        // (defined on every path, the four search bodies below included: left undefined where a search
+                        // fails, they cost the lean kernels 64 bytes of scratch per lane and the dense ones 16)
+                        float2 step = make_float2(0, 0), luma = make_float2(0, 0);
                         Nb1 nb;
                         bool ok;
                         uint32_t n_eval = 0;
