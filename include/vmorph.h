@@ -599,8 +599,8 @@ typedef struct vm_viewport {
  * of every 2 x 2 block: an exact box reduction.  Every call of this section answers VM_E_INVALID for a NULL viewport or
  * output, a non-finite x0, y0 or step, a step that is not > 0, out_w or out_h outside 1..32768, nx < 1, ny < 1 or
  * nx * ny > 64, a color_from outside 0..2 or a pitch below the output's row, and changes nothing of the frame (v, path,
- * canvases, layers, schedule); no device memory depends on nx * ny.  Not in this section, deliberately: viewport calls under
- * a transition schedule or over a shutter, and viewport sampling maps (the schedule is not consulted). */
+ * canvases, layers, schedule); no device memory depends on nx * ny.  Not in this section, deliberately: viewport sampling
+ * maps.  The schedule is not consulted here (the section after this one does). */
 /* vm_render_halfway through a viewport (render.cu:16-60, UI/RenderWidget.cpp:229-266): RGB8 from the Poisson-extended
  * canvases, (uint8)((double)(acc / (float)N) + 0.5) per channel.  rgb_out: out_h rows of out_w RGB8 pixels, pitch in bytes
  * (0 = tight). */
@@ -616,6 +616,68 @@ int  vm_render_viewport_layers(vm_frame *f, const vm_viewport *vp, float color_f
 /* same (render.cu:16-60, UI/RenderWidget.cpp:229-266), output left on the device (for timing) */
 int  vm_render_viewport_layers_dev(vm_frame *f, const vm_viewport *vp, float color_fa, float geo_fa, int color_from,
                                    float *elapsed_ms);
+/* ---- viewports over a shutter, uniformly and under a transition schedule ----
+ * The viewport section composed with the two motion-blur sections: a viewer that zooms into a motion-blurred frame, a
+ * half-size proxy of a wipe, a delivery at another size with a shutter, an overscan render of a frame that holds a
+ * schedule.  Every output pixel is the mean of the chain of kernel_render_halfway_image (Algorithm/render.cu:16-60) from
+ * its nx x ny sub-sample points at each of T = samples times, in one launch.  In float32, in this order (the divisions
+ * correctly rounded), with N = nx * ny; time sample tau = 0 .. T - 1 is the OUTER loop, sub-sample s = j * nx + i = 0 .. N - 1
+ * the INNER one, i fastest:
+ *   f_tau = ((float)tau + 0.5f) / (float)T
+ *   q     = (qx, qy) of the viewport section for (X, Y, i, j), unchanged
+ *   uniform (vm_render_viewport_shutter*):
+ *     t_tau  = fminf(fmaxf(geo_open + (geo_close - geo_open) * f_tau, 0), 1)
+ *     (p, V) = the chain from q at geo_fa = t_tau
+ *     c      = the colour of the uniform call on (p - V, p + V) before its rounding, blended by color_from with color_fa
+ *   scheduled (vm_render_viewport_transition_shutter*):
+ *     K      = ramp(schedule_colour, t_color, ease)                     once per call
+ *     t_tau  = t_open + (t_close - t_open) * f_tau                      (not clamped: ramp clamps per texel)
+ *     (p, V) = the chain from q under G_tau = ramp(schedule_geometry, t_tau, ease), g = tapr(G_tau, p) anew at every p
+ *     k      = tapr(K, p)
+ *     c      = the colour of the transition call on (p - V, p + V) before its rounding, blended by color_from with k
+ *   acc = acc + c                                                       (acc starts at +0, in loop order)
+ * and the result is acc / (float)(T * N).  Reads outside the field are the chain's clamped taps, as in the viewport section.
+ * With samples = 1 and geo_open == geo_close == g in [0, 1] a uniform call gives the bits of its viewport counterpart at
+ * geo_fa = g; with {0, 0, 1, 1, w, h, 1, 1} a call gives the bits of its shutter counterpart; with the schedule (0, 1) on both
+ * planes and VM_EASE_LINEAR a scheduled call gives the bits of the uniform one at color_fa = t_color in [0, 1].  A viewport
+ * under a schedule at one instant t is a scheduled call with samples = 1 and t_open == t_close == t_color == t; it has no
+ * entry points of its own.  Every call of this section answers VM_E_INVALID for anything the viewport section or the
+ * shutter sections refuse -- a NULL viewport or output, a non-finite x0, y0 or step, a step that is not > 0, out_w or out_h
+ * outside 1..32768, nx < 1, ny < 1 or nx * ny > 64, samples outside 1..64, a color_from outside 0..2, an ease other than
+ * VM_EASE_LINEAR / VM_EASE_SMOOTH (scheduled), a pitch below the output's row -- and for samples * nx * ny > 256 (a 4 x 4
+ * grid at 16 times: a condition of this interface); VM_E_STATE for a scheduled call on a frame without a schedule and for a
+ * layer call on a frame without layers.  The frame's v, path, canvases, layers and schedule are not changed; no device
+ * memory depends on samples or nx * ny. */
+/* vm_render_viewport over the shutter (render.cu:16-60, UI/RenderWidget.cpp:229-266): RGB8 from the Poisson-extended
+ * canvases, (uint8)((double)(acc / (float)(T * N)) + 0.5) per channel.  rgb_out: out_h rows of out_w RGB8 pixels, pitch in
+ * bytes (0 = tight). */
+int  vm_render_viewport_shutter(vm_frame *f, const vm_viewport *vp, float color_fa, float geo_open, float geo_close, int samples,
+                                int color_from, uint8_t *rgb_out, int pitch_bytes);
+/* same (render.cu:16-60, UI/RenderWidget.cpp:229-266), output left on the device (for timing) */
+int  vm_render_viewport_shutter_dev(vm_frame *f, const vm_viewport *vp, float color_fa, float geo_open, float geo_close,
+                                    int samples, int color_from, float *elapsed_ms);
+/* vm_render_viewport_layers over the shutter (render.cu:16-60, UI/RenderWidget.cpp:229-266): the layers of
+ * vm_frame_upload_layers from the same points at the same times.  out: (out_h, out_w, channels) floats, pitch in floats
+ * (0 = tight). */
+int  vm_render_viewport_shutter_layers(vm_frame *f, const vm_viewport *vp, float color_fa, float geo_open, float geo_close,
+                                       int samples, int color_from, float *out, int pitch_floats);
+/* same (render.cu:16-60, UI/RenderWidget.cpp:229-266), output left on the device (for timing) */
+int  vm_render_viewport_shutter_layers_dev(vm_frame *f, const vm_viewport *vp, float color_fa, float geo_open, float geo_close,
+                                           int samples, int color_from, float *elapsed_ms);
+/* vm_render_transition_shutter through a viewport (render.cu:16-60, UI/RenderWidget.cpp:229-266): RGB8 from the
+ * Poisson-extended canvases under the schedule.  rgb_out: out_h rows of out_w RGB8 pixels, pitch in bytes (0 = tight). */
+int  vm_render_viewport_transition_shutter(vm_frame *f, const vm_viewport *vp, float t_open, float t_close, int samples,
+                                           float t_color, int ease, int color_from, uint8_t *rgb_out, int pitch_bytes);
+/* same (render.cu:16-60, UI/RenderWidget.cpp:229-266), output left on the device (for timing) */
+int  vm_render_viewport_transition_shutter_dev(vm_frame *f, const vm_viewport *vp, float t_open, float t_close, int samples,
+                                               float t_color, int ease, int color_from, float *elapsed_ms);
+/* vm_render_transition_shutter_layers through a viewport (render.cu:16-60, UI/RenderWidget.cpp:229-266): the layers of
+ * vm_frame_upload_layers under the same rates.  out: (out_h, out_w, channels) floats, pitch in floats (0 = tight). */
+int  vm_render_viewport_transition_shutter_layers(vm_frame *f, const vm_viewport *vp, float t_open, float t_close, int samples,
+                                                  float t_color, int ease, int color_from, float *out, int pitch_floats);
+/* same (render.cu:16-60, UI/RenderWidget.cpp:229-266), output left on the device (for timing) */
+int  vm_render_viewport_transition_shutter_layers_dev(vm_frame *f, const vm_viewport *vp, float t_open, float t_close,
+                                                      int samples, float t_color, int ease, int color_from, float *elapsed_ms);
 /* CPoissonExt::prepare + poissonExtend for one side (1 or 2) of the frame,
  * Algorithm/PoissonExt.cpp:49-362, on the device-resident canvases: matrix-free
  * multigrid-preconditioned CG instead of MKL DSS.  iters/rel_res may be NULL. */

@@ -255,6 +255,74 @@ public:
         check(vm_render_viewport_layers_dev(f_, &vp, color_fa, geo_fa, color_from, &ms));
         return ms;
     }
+    // a viewport over a shutter (vm_render_viewport_shutter): every output pixel the mean of its vp.nx x vp.ny chains at
+    // each of `samples` times between geo_open and geo_close; samples * vp.nx * vp.ny may be 256 at most
+    std::vector<unsigned char> render_viewport_shutter(const Viewport &vp, float color_fa, float geo_open, float geo_close,
+                                                       int samples, int color_from = 1)
+    {
+        std::vector<unsigned char> out(viewport_pixels(vp) * 3);
+        check(vm_render_viewport_shutter(f_, &vp, color_fa, geo_open, geo_close, samples, color_from, out.data(), 0));
+        return out;
+    }
+    float render_viewport_shutter_dev(const Viewport &vp, float color_fa, float geo_open, float geo_close, int samples,
+                                      int color_from = 1)
+    {
+        float ms = 0;
+        check(vm_render_viewport_shutter_dev(f_, &vp, color_fa, geo_open, geo_close, samples, color_from, &ms));
+        return ms;
+    }
+    // the layers through the same viewport over the same shutter: (out_h, out_w, channels) floats
+    std::vector<float> render_viewport_shutter_layers(const Viewport &vp, float color_fa, float geo_open, float geo_close,
+                                                      int samples, int color_from = 1)
+    {
+        std::vector<float> out(viewport_pixels(vp) * (channels_ ? channels_ : 1));
+        check(vm_render_viewport_shutter_layers(f_, &vp, color_fa, geo_open, geo_close, samples, color_from, out.data(), 0));
+        return out;
+    }
+    float render_viewport_shutter_layers_dev(const Viewport &vp, float color_fa, float geo_open, float geo_close, int samples,
+                                             int color_from = 1)
+    {
+        float ms = 0;
+        check(vm_render_viewport_shutter_layers_dev(f_, &vp, color_fa, geo_open, geo_close, samples, color_from, &ms));
+        return ms;
+    }
+    // a viewport over a shutter under the schedule (vm_render_viewport_transition_shutter): the geometry schedule ramped at
+    // each of `samples` times between t_open and t_close, the colour schedule once at t_color
+    std::vector<unsigned char> render_viewport_transition_shutter(const Viewport &vp, float t_open, float t_close, int samples,
+                                                                  float t_color, int ease = VM_EASE_LINEAR, int color_from = 1)
+    {
+        std::vector<unsigned char> out(viewport_pixels(vp) * 3);
+        check(vm_render_viewport_transition_shutter(f_, &vp, t_open, t_close, samples, t_color, ease, color_from, out.data(), 0));
+        return out;
+    }
+    float render_viewport_transition_shutter_dev(const Viewport &vp, float t_open, float t_close, int samples, float t_color,
+                                                 int ease = VM_EASE_LINEAR, int color_from = 1)
+    {
+        float ms = 0;
+        check(vm_render_viewport_transition_shutter_dev(f_, &vp, t_open, t_close, samples, t_color, ease, color_from, &ms));
+        return ms;
+    }
+    // the layers through the same viewport, shutter and schedule: (out_h, out_w, channels) floats
+    std::vector<float> render_viewport_transition_shutter_layers(const Viewport &vp, float t_open, float t_close, int samples,
+                                                                 float t_color, int ease = VM_EASE_LINEAR, int color_from = 1)
+    {
+        std::vector<float> out(viewport_pixels(vp) * (channels_ ? channels_ : 1));
+        check(vm_render_viewport_transition_shutter_layers(f_, &vp, t_open, t_close, samples, t_color, ease, color_from,
+                                                           out.data(), 0));
+        return out;
+    }
+    float render_viewport_transition_shutter_layers_dev(const Viewport &vp, float t_open, float t_close, int samples,
+                                                        float t_color, int ease = VM_EASE_LINEAR, int color_from = 1)
+    {
+        float ms = 0;
+        check(vm_render_viewport_transition_shutter_layers_dev(f_, &vp, t_open, t_close, samples, t_color, ease, color_from, &ms));
+        return ms;
+    }
+    // a viewport under the schedule at the one instant t: one sample, t_open == t_close == t_color == t
+    std::vector<unsigned char> render_viewport_transition(const Viewport &vp, float t, int ease = VM_EASE_LINEAR, int color_from = 1)
+    {
+        return render_viewport_transition_shutter(vp, t, t, 1, t, ease, color_from);
+    }
     // sampling_maps under the schedule, and the rates (g, k) every output pixel ended with
     struct TransitionMaps {
         SamplingMaps maps;

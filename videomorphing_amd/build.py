@@ -58,6 +58,8 @@ UNITS = [
     ("vm_tshutter.cpp", "vm_tshutter.o", ["-x", "hip"]),
     ("vm_viewport.hip", "vm_viewport_kernels.o", ["-ffp-contract=off"]),
     ("vm_viewport.cpp", "vm_viewport.o", ["-x", "hip"]),
+    ("vm_vshutter.hip", "vm_vshutter_kernels.o", ["-ffp-contract=off"]),
+    ("vm_vshutter.cpp", "vm_vshutter.o", ["-x", "hip"]),
     ("vm_poisson.hip", "vm_poisson.o", ["-ffp-contract=off"]),
     ("vm_mgb.hip", "vm_mgb.o", ["-ffp-contract=fast"]),
     ("vm_pyramid.hip", "vm_pyramid.o", ["-ffp-contract=off"]),

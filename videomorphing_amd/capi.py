@@ -61,6 +61,10 @@ SYMBOLS = [
     "vm_render_transition_shutter", "vm_render_transition_shutter_dev", "vm_render_transition_shutter_layers",
     "vm_render_transition_shutter_layers_dev",
     "vm_render_viewport", "vm_render_viewport_dev", "vm_render_viewport_layers", "vm_render_viewport_layers_dev",
+    "vm_render_viewport_shutter", "vm_render_viewport_shutter_dev", "vm_render_viewport_shutter_layers",
+    "vm_render_viewport_shutter_layers_dev",
+    "vm_render_viewport_transition_shutter", "vm_render_viewport_transition_shutter_dev",
+    "vm_render_viewport_transition_shutter_layers", "vm_render_viewport_transition_shutter_layers_dev",
 ]
 
 
@@ -279,6 +283,14 @@ def load():
         "vm_render_viewport_dev": [vp, C.POINTER(ViewportStruct), f, f, i, C.POINTER(f)],
         "vm_render_viewport_layers": [vp, C.POINTER(ViewportStruct), f, f, i, vp, i],
         "vm_render_viewport_layers_dev": [vp, C.POINTER(ViewportStruct), f, f, i, C.POINTER(f)],
+        "vm_render_viewport_shutter": [vp, C.POINTER(ViewportStruct), f, f, f, i, i, vp, i],
+        "vm_render_viewport_shutter_dev": [vp, C.POINTER(ViewportStruct), f, f, f, i, i, C.POINTER(f)],
+        "vm_render_viewport_shutter_layers": [vp, C.POINTER(ViewportStruct), f, f, f, i, i, vp, i],
+        "vm_render_viewport_shutter_layers_dev": [vp, C.POINTER(ViewportStruct), f, f, f, i, i, C.POINTER(f)],
+        "vm_render_viewport_transition_shutter": [vp, C.POINTER(ViewportStruct), f, f, i, f, i, i, vp, i],
+        "vm_render_viewport_transition_shutter_dev": [vp, C.POINTER(ViewportStruct), f, f, i, f, i, i, C.POINTER(f)],
+        "vm_render_viewport_transition_shutter_layers": [vp, C.POINTER(ViewportStruct), f, f, i, f, i, i, vp, i],
+        "vm_render_viewport_transition_shutter_layers_dev": [vp, C.POINTER(ViewportStruct), f, f, i, f, i, i, C.POINTER(f)],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

@@ -1,6 +1,7 @@
 // vm_chain_win.h -- the window form of the compositor's chain (vm_chain.h), stated once as the statements a window kernel
 // includes at the top of its body -- k_render_win (vm_render.hip) and k_warp_win (vm_warp.hip) -- or of its sample loop's
-// (k_shutter_win, vm_shutter.hip; k_tblur_win, vm_tshutter.hip; k_viewport_win, vm_viewport.hip).  It is no function because
+// (k_shutter_win, vm_shutter.hip; k_tblur_win, vm_tshutter.hip; k_viewport_win, vm_viewport.hip; k_vblur_win,
+// vm_vshutter.hip, with the hooks of all three).  It is no function because
 // the compiler lays a kernel out differently once this body sits behind any function boundary, a lambda included (the
 // fallback's float2 gathers stay whole, the vectoriser pairs other operations, and the sum after the inside / outside
 // split of the tap is emitted once instead of once per side): k_warp_win<true, CANVAS, true> lost 1.5 us of 100 that way.

@@ -282,6 +282,9 @@ int vm_level_copy_v(vm_ctx *c, vm_level &l, hipMemcpyKind kind, const float *v, 
 int vm_pitch_resolve(const char *fn, int *pitch, size_t unit, size_t row_bytes);
 int vm_copy_pitched(const char *fn, hipMemcpyKind kind, void *dev, size_t dev_pitch_bytes, const void *host, int pitch,
                     size_t unit, size_t row_bytes, int h, hipStream_t s);
+// What every call that takes a vm_viewport checks of it and of its colour source (vm_viewport.cpp; include/vmorph.h's
+// viewport section lists the refusals): VM_OK, or VM_E_INVALID with fn's message.
+int vm_viewport_check(const char *fn, const vm_viewport *vp, int color_from);
 // the sweep of one level (vm_sweep_sched.cpp)
 int vm_iteration_cap(float max_iter, int *cap);
 int vm_optimize_levels(vm_ctx *c, vm_level **lv, int n, float max_iter, volatile const int *run_flag,

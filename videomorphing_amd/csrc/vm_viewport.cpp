@@ -7,8 +7,8 @@
 
 enum { VM_VIEWPORT_MAX_SIDE = 32768, VM_VIEWPORT_MAX_SAMPLES = 64 };
 
-// what every viewport call checks of its viewport and colour source
-static int viewport_check(const char *fn, const vm_viewport *vp, int color_from)
+// what every viewport call checks of its viewport and colour source (vm_host.h: vm_vshutter.cpp checks the same)
+int vm_viewport_check(const char *fn, const vm_viewport *vp, int color_from)
 {
     if (!vp) return vm_fail(VM_E_INVALID, "%s: viewport is NULL", fn);
     if (!std::isfinite(vp->x0) || !std::isfinite(vp->y0))
@@ -60,7 +60,7 @@ extern "C" int vm_render_viewport_dev(vm_frame *f, const vm_viewport *vp, float 
                                       float *elapsed_ms)
 {
     VM_ENTER(f);
-    if (int rc = viewport_check(__func__, vp, color_from)) return rc;
+    if (int rc = vm_viewport_check(__func__, vp, color_from)) return rc;
     return viewport_dev(f, __func__, vp, color_fa, geo_fa, color_from, false, elapsed_ms);
 }
 
@@ -68,7 +68,7 @@ extern "C" int vm_render_viewport_layers_dev(vm_frame *f, const vm_viewport *vp,
                                              float *elapsed_ms)
 {
     VM_ENTER(f);
-    if (int rc = viewport_check(__func__, vp, color_from)) return rc;
+    if (int rc = vm_viewport_check(__func__, vp, color_from)) return rc;
     return viewport_dev(f, __func__, vp, color_fa, geo_fa, color_from, true, elapsed_ms);
 }
 
@@ -77,7 +77,7 @@ extern "C" int vm_render_viewport(vm_frame *f, const vm_viewport *vp, float colo
 {
     VM_ENTER(f);
     if (!rgb_out) return vm_fail(VM_E_INVALID, "%s: output is NULL", __func__);
-    if (int rc = viewport_check(__func__, vp, color_from)) return rc;
+    if (int rc = vm_viewport_check(__func__, vp, color_from)) return rc;
     const size_t row = viewport_row(f, vp, false);
     if (int rc = vm_pitch_resolve(__func__, &pitch_bytes, 1, row)) return rc;
     if (int rc = viewport_dev(f, __func__, vp, color_fa, geo_fa, color_from, false, nullptr)) return rc;
@@ -92,7 +92,7 @@ extern "C" int vm_render_viewport_layers(vm_frame *f, const vm_viewport *vp, flo
 {
     VM_ENTER(f);
     if (!out) return vm_fail(VM_E_INVALID, "%s: output is NULL", __func__);
-    if (int rc = viewport_check(__func__, vp, color_from)) return rc;
+    if (int rc = vm_viewport_check(__func__, vp, color_from)) return rc;
     // (before the pitch is judged: its row depends on the layers)
     if (!f->layer_ch) return vm_fail(VM_E_STATE, "%s: the frame holds no layers (vm_frame_upload_layers)", __func__);
     const size_t row = viewport_row(f, vp, true);

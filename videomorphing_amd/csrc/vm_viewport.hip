@@ -75,7 +75,7 @@ template <int C> __global__ __launch_bounds__(256) void k_viewport(const VmViewp
 #define VM_CHAIN_WIN_OUTSIDE x >= per_sample(A.out_w) || y >= per_sample(A.out_h)
 template <bool HAS_U, int C> __global__ __launch_bounds__(RW * RH) void k_viewport_win(const VmViewport A)
 {
-    constexpr bool RATES = false;       // (a viewport under a transition schedule is a tail choice to come)
+    constexpr bool RATES = false;       // (a viewport under a transition schedule or over a shutter is vm_vshutter.hip)
     const float2 *rates = nullptr;
     const int rs = A.rs, ntiles = A.ntiles;
     const float2 *__restrict__ vf = A.vf, *__restrict__ uf = A.uf;

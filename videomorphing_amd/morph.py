@@ -748,6 +748,75 @@ class Frame(object):
                                                          C.byref(ms)))
         return ms.value
 
+    def _viewport_shutter(self, name, s, args, layers):
+        """one vm_render_viewport_[transition_]shutter[_layers] call into a host array of the viewport's grid"""
+        if layers:
+            shape = getattr(self, "_layer_shape", (self.h, self.w))       # (no upload: the call answers VM_E_STATE)
+            out = np.empty(self._viewport_grid(s) + tuple(shape[2:]), dtype=np.float32)
+        else:
+            out = np.zeros(self._viewport_grid(s) + (3,), dtype=np.uint8)
+        capi.check(getattr(self._L, name)(self._h, C.byref(s), *args, out.ctypes.data, 0))
+        return out
+
+    def _viewport_shutter_dev(self, name, s, args):
+        ms = C.c_float(0)
+        capi.check(getattr(self._L, name)(self._h, C.byref(s), *args, C.byref(ms)))
+        return ms.value
+
+    def render_viewport_shutter(self, vp, color_fa, geo_open, geo_close, samples, color_from=1):
+        """render_viewport with motion blur (vm_render_viewport_shutter): every output pixel the mean of its vp.nx x vp.ny
+        chains at each of `samples` (1..64) times between geo_open and geo_close, each clamped to [0, 1], taken in float32
+        before the one rounding -> (vp.out_h, vp.out_w, 3) uint8.  samples * vp.nx * vp.ny may be 256 at most; the library
+        checks that and the viewport (VmError, VM_E_INVALID)."""
+        args = (float(color_fa), float(geo_open), float(geo_close), int(samples), int(color_from))
+        return self._viewport_shutter("vm_render_viewport_shutter", vp.struct(), args, False)
+
+    def render_viewport_shutter_dev(self, vp, color_fa, geo_open, geo_close, samples, color_from=1):
+        args = (float(color_fa), float(geo_open), float(geo_close), int(samples), int(color_from))
+        return self._viewport_shutter_dev("vm_render_viewport_shutter_dev", vp.struct(), args)
+
+    def render_viewport_shutter_layers(self, vp, color_fa, geo_open, geo_close, samples, color_from=1):
+        """the uploaded layers through the same viewport over the same shutter (vm_render_viewport_shutter_layers):
+        float32 (vp.out_h, vp.out_w) or (vp.out_h, vp.out_w, C) as they were uploaded"""
+        args = (float(color_fa), float(geo_open), float(geo_close), int(samples), int(color_from))
+        return self._viewport_shutter("vm_render_viewport_shutter_layers", vp.struct(), args, True)
+
+    def render_viewport_shutter_layers_dev(self, vp, color_fa, geo_open, geo_close, samples, color_from=1):
+        args = (float(color_fa), float(geo_open), float(geo_close), int(samples), int(color_from))
+        return self._viewport_shutter_dev("vm_render_viewport_shutter_layers_dev", vp.struct(), args)
+
+    def _scheduled_args(self, t_open, t_close, samples, t_color, ease, color_from):
+        tc = self._shutter_color_time(t_open, t_close, t_color)
+        return (float(t_open), float(t_close), int(samples), tc, int(ease), int(color_from))
+
+    def render_viewport_transition_shutter(self, vp, t_open, t_close, samples, t_color=None, ease=capi.EASE_LINEAR, color_from=1):
+        """render_transition_shutter through a viewport (vm_render_viewport_transition_shutter): the geometry schedule
+        ramped at each of `samples` times between t_open and t_close, the colour schedule once at t_color (None: the
+        float32 midpoint, formed on the host), from the vp.nx x vp.ny sub-sample points of every output pixel ->
+        (vp.out_h, vp.out_w, 3) uint8"""
+        args = self._scheduled_args(t_open, t_close, samples, t_color, ease, color_from)
+        return self._viewport_shutter("vm_render_viewport_transition_shutter", vp.struct(), args, False)
+
+    def render_viewport_transition_shutter_dev(self, vp, t_open, t_close, samples, t_color=None, ease=capi.EASE_LINEAR, color_from=1):
+        args = self._scheduled_args(t_open, t_close, samples, t_color, ease, color_from)
+        return self._viewport_shutter_dev("vm_render_viewport_transition_shutter_dev", vp.struct(), args)
+
+    def render_viewport_transition_shutter_layers(self, vp, t_open, t_close, samples, t_color=None, ease=capi.EASE_LINEAR,
+                                                  color_from=1):
+        """the uploaded layers through the same viewport, shutter and rates (vm_render_viewport_transition_shutter_layers)"""
+        args = self._scheduled_args(t_open, t_close, samples, t_color, ease, color_from)
+        return self._viewport_shutter("vm_render_viewport_transition_shutter_layers", vp.struct(), args, True)
+
+    def render_viewport_transition_shutter_layers_dev(self, vp, t_open, t_close, samples, t_color=None, ease=capi.EASE_LINEAR,
+                                                      color_from=1):
+        args = self._scheduled_args(t_open, t_close, samples, t_color, ease, color_from)
+        return self._viewport_shutter_dev("vm_render_viewport_transition_shutter_layers_dev", vp.struct(), args)
+
+    def render_viewport_transition(self, vp, t, ease=capi.EASE_LINEAR, color_from=1):
+        """render_transition through a viewport: the frame under its schedule at the one instant t, which is
+        render_viewport_transition_shutter with samples = 1 and t_open == t_close == t_color == t"""
+        return self.render_viewport_transition_shutter(vp, t, t, 1, t, ease, color_from)
+
     @staticmethod
     def _shutter_color_time(t_open, t_close, t_color):
         """t_color of the transition shutter calls; None: the float32 midpoint (t_open + t_close) * 0.5, formed here"""
