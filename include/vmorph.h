@@ -214,6 +214,14 @@ int  vm_dbg_sparse_resident_visits(vm_ctx *ctx);
  * L2).  The first call only arms the recording (xcc_of_block is filled with 0xFF); placement
  * is a matter of speed, never of correctness. */
 int  vm_dbg_pass_placement(vm_ctx *ctx, uint8_t *xcc_of_block, int n);
+/* Test hook of the wave-wide line search of the FAST sweeps (decide64): the control flow of its golden-section
+ * search alone -- initial pair, regime loop, generic loop, final choice, the same text the sweep kernels expand --
+ * with the energy f(t) = (A (t - t0)) (t - t0) + B in place of the taps and the SSIM change.  n cases (1 to 65536)
+ * in one launch, a wave each; params: cc, A, t0, B per case (4 n floats, host; cc in [0, 16]), eps in [2^-10, 1]
+ * (the bounds keep the search finite).  out, per case 20 words (host): the bits of tmin and of fmin, the count of
+ * used evaluations, then the bits of the used evaluation points in order (at most 17, the rest 0).  It moves no
+ * texture and touches no level state.  Bad arguments: VM_E_INVALID. */
+int  vm_dbg_golden(vm_ctx *ctx, int n, const float *params, float eps, uint32_t *out);
 /* Do the streams of two contexts of one device run side by side?  (The reference has one device context and one stream,
  * UI/MdiEditor.cpp:54-75; a host of this library keeps several: solver streams, compositor lanes.)  The HIP runtime
  * multiplexes a process's streams onto GPU_MAX_HW_QUEUES hardware queues, and two streams on one queue run their kernels

@@ -277,6 +277,29 @@ extern "C" int vm_dbg_pass_placement(vm_ctx *c, uint8_t *xcc_of_block, int n)
     return VM_OK;
 }
 
+extern "C" int vm_dbg_golden(vm_ctx *c, int n, const float *params, float eps, uint32_t *out)
+{
+    if (!params || !out || n < 1 || n > 65536) return vm_fail(VM_E_INVALID, "vm_dbg_golden: bad argument");
+    if (!(eps >= 1.0f / 1024.0f && eps <= 1.0f)) return vm_fail(VM_E_INVALID, "vm_dbg_golden: eps %g (2^-10 to 1)", (double)eps);
+    for (int k = 0; k < n; ++k)
+        if (!(params[4 * k] >= 0.0f && params[4 * k] <= 16.0f))
+            return vm_fail(VM_E_INVALID, "vm_dbg_golden: cc of case %d is %g (0 to 16)", k, (double)params[4 * k]);
+    VM_ENTER_LOCKED(c);
+    VmDev<float> in;
+    VmDev<uint32_t> res;
+    const size_t words = (size_t)n * VM_DBG_GOLDEN_WORDS;
+    if (int rc = in.reserve((size_t)4 * n)) return rc;
+    if (int rc = res.reserve(words)) return rc;
+    hipStream_t s = c->stream;
+    VM_HIP(hipMemcpyAsync(in.get(), params, (size_t)4 * n * sizeof(float), hipMemcpyHostToDevice, s));
+    VM_HIP(hipMemsetAsync(res.get(), 0, words * sizeof(uint32_t), s));
+    vm_launch_dbg_golden_fast(n, in.get(), eps, res.get(), s);
+    VM_HIP(hipGetLastError());
+    VM_HIP(hipMemcpyAsync(out, res.get(), words * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    VM_HIP(hipStreamSynchronize(s));
+    return VM_OK;
+}
+
 extern "C" int vm_set_tuning(vm_ctx *c, int sweep_mode, int threads, int parts)
 {
     if (!c || sweep_mode < VM_SWEEP_AUTO || sweep_mode > VM_SWEEP_PASS || threads < 0 || parts < 0 ||

@@ -128,6 +128,11 @@ VM_DECL_LAUNCHERS(reffm)  // sweeps only (-DVM_EXACT=3 -ffp-contract=fast): VM_M
 VM_DECL_LAUNCHERS(tex8)   // sweeps, init_level, upsample (-DVM_EXACT=4 -ffp-contract=off): VM_MATH_REF_TEX8
 VM_DECL_LAUNCHERS(tex8t)  // the same with truncated weights (-DVM_EXACT=5): VM_MATH_REF_TEX8_TRUNC
 
+// vm_dbg_golden (FAST sweeps only): the wave-wide golden-section search on a synthetic energy, a wave per case;
+// VM_DBG_GOLDEN_WORDS result words per case (tmin, fmin, n_eval, up to 17 points)
+#define VM_DBG_GOLDEN_WORDS 20
+void vm_launch_dbg_golden_fast(int n, const float *in, float eps, uint32_t *out, hipStream_t s);
+
 // compositor / result delivery (single arithmetic mode)
 void vm_launch_upscale(float2 *dst, int w0, int h0, int dpitch, const float2 *v, int w, int h,
                        int rs, hipStream_t s);

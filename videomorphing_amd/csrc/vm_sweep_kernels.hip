@@ -1110,6 +1110,98 @@ __device__ __forceinline__ bool decide32(const VmLevelView &L, const VmKParams &
     return true;
 }
 
+// golden_section_search (morph.cu:885-947) on [0, CC_] with the two halves of a wave side by side, stated once for
+// decide64 and for vm_dbg_golden (a macro, not a function: calls change this unit's code generation).
+// EVAL2_(t, flo, fhi): the energy at this half's t; flo / fhi come back as the lower / the upper half's value.
+// TRACE_(t): a point whose evaluation the search USES, in the order decide32 makes them (GOLDEN64_NO_TRACE: nothing).
+// CC_ (the interval's upper end, consumed) and NEVAL_ are lvalues; TMIN_ / FMIN_ receive the final choice.  All values
+// are uniform over the wave, so neither loop diverges.
+//   initial pair: b and x side by side.
+//   regime loop: while the comparison says "not lower at x" and a is the +0 it started as.  Then qv = a = +0 and
+//     xn = b R + 0 C = b R (b R > 0 whenever cc > eps; the product rounds as the generic form's does), the repeat guess
+//     gives xn2 = xn R + 0 C = xn R, cc - a = cc, and a step is the shift cc <- x <- b <- xn, fx <- fb <- f1.  A round
+//     whose guess held makes two of them (the second with xn2, f2): one select per variable between the single and the
+//     double shift, none on lt or G.  The points of a round do not depend on its energies.  Entered at most once, from
+//     the top; left for good the first time fx < fb.  (A round whose guess fails is the loop's last: the loop test that
+//     follows it is the guess-held test.)  On the 120x68 level of the 1080p pair every search starts here, 98.9 % of
+//     all rounds run here and 5 % of the searches leave (profiles/line_search_regime.md).
+//   generic loop: per round the point the search needs now AND the point it needs next if the coming comparison goes
+//     the way this one went.  It continues from the regime loop's state; a is 0 until its first "lower at x" step.
+#define GOLDEN64_NO_TRACE(T_)
+#define GOLDEN64(EVAL2_, TRACE_, CC_, EPS_, HI_, NEVAL_, TMIN_, FMIN_)                                                 \
+    {                                                                                                                  \
+        const float R = 0.618033989f, C = 1.0f - R;                                                                    \
+        float a = 0;                                                                                                   \
+        float b = (CC_) * C, x = b * R + (CC_) * C;                                                                    \
+        float fb, fx;                                                                                                  \
+        EVAL2_((HI_) ? x : b, fb, fx);                                                                                 \
+        TRACE_(b)                                                                                                      \
+        TRACE_(x)                                                                                                      \
+        (NEVAL_) += 2;                                                                                                 \
+        _Pragma("unroll 1") while ((CC_) > (EPS_) && !(fx < fb))                                                       \
+        {                                                                                                              \
+            const float xn = b * R, xn2 = xn * R;                                                                      \
+            float f1, f2;                                                                                              \
+            EVAL2_((HI_) ? xn2 : xn, f1, f2);                                                                          \
+            TRACE_(xn)                                                                                                 \
+            /* after the step (cc, x, b) <- (x, b, xn), (fx, fb) <- (fb, f1): does the search go on, the same way? */  \
+            const bool held = x > (EPS_) && !(fb < f1);                                                                \
+            if (held) { /* the guess held: f2 is the next step's evaluation, two shifts in one */                      \
+                TRACE_(xn2)                                                                                            \
+            }                                                                                                          \
+            (NEVAL_) += held ? 2 : 1;                                                                                  \
+            (CC_) = held ? b : x;                                                                                      \
+            x = held ? xn : b;                                                                                         \
+            b = held ? xn2 : xn;                                                                                       \
+            fx = held ? f1 : fb;                                                                                       \
+            fb = held ? f2 : f1;                                                                                       \
+        }                                                                                                              \
+        _Pragma("unroll 1") for (;;)                                                                                   \
+        {                                                                                                              \
+            if (!((CC_) - a > (EPS_)))                                                                                 \
+                break;                                                                                                 \
+            const bool lt = fx < fb;                                                                                   \
+            /* this step: [a, cc] <- [b, cc], b <- x  or  [a, cc] <- [a, x], x <- b;  one new point xn */              \
+            const float p = lt ? x : b, qv = lt ? (CC_) : a;                                                           \
+            const float a1 = lt ? b : a, cc1 = lt ? (CC_) : x;                                                         \
+            const float xn = p * R + qv * C;                                                                           \
+            const float b1 = lt ? x : xn, x1 = lt ? xn : b;                                                            \
+            /* the step after it, should its comparison fall like this one did.  The guess: the comparison repeats. */ \
+            /* Measured on the 120x68 level of the 1080p pair it holds for 99 % of the steps (most accepted moves */   \
+            /* are small: the search keeps shrinking towards 0); a parabola through the three known points */          \
+            /* predicted no better and cost more. */                                                                   \
+            const bool G = lt;                                                                                         \
+            const float p2 = G ? x1 : b1, q2 = G ? cc1 : a1;                                                           \
+            const float xn2 = p2 * R + q2 * C;                                                                         \
+            float f1, f2;                                                                                              \
+            EVAL2_((HI_) ? xn2 : xn, f1, f2);                                                                          \
+            TRACE_(xn)                                                                                                 \
+            ++(NEVAL_);                                                                                                \
+            {                                                                                                          \
+                const float nfb = lt ? fx : f1, nfx = lt ? f1 : fb;                                                    \
+                a = a1;                                                                                                \
+                (CC_) = cc1;                                                                                           \
+                b = b1;                                                                                                \
+                x = x1;                                                                                                \
+                fb = nfb;                                                                                              \
+                fx = nfx;                                                                                              \
+            }                                                                                                          \
+            if ((CC_) - a > (EPS_) && (fx < fb) == G) { /* the guess held: f2 is the next step's evaluation */         \
+                TRACE_(xn2)                                                                                            \
+                const float ob = b, ofb = fb;                                                                          \
+                a = G ? b : a;                                                                                         \
+                (CC_) = G ? (CC_) : x;                                                                                 \
+                b = G ? x : xn2;                                                                                       \
+                x = G ? xn2 : ob;                                                                                      \
+                fb = G ? fx : f2;                                                                                      \
+                fx = G ? f2 : ofb;                                                                                     \
+                ++(NEVAL_);                                                                                            \
+            }                                                                                                          \
+        }                                                                                                              \
+        (TMIN_) = fx < fb ? x : b;                                                                                     \
+        (FMIN_) = fx < fb ? fx : fb;                                                                                   \
+    }
+
 // decide32 with a whole wave per pixel: the line search is a chain of dependent energy
 // evaluations (the only thing a launch-bound small level waits for), and the chip is idle there,
 // so the two halves of the wave evaluate two points at once --
@@ -1121,6 +1213,11 @@ __device__ __forceinline__ bool decide32(const VmLevelView &L, const VmKParams &
 // Every evaluation that is USED is the one decide32 makes at that step (same point, same
 // arithmetic, same lanes' roles), so the result is bit-identical to decide32's; n_eval counts
 // the search's evaluations, not the speculative ones.
+// The rounds are two loops (GOLDEN64 above).  Most searches shrink towards 0: the comparison says "not lower at x",
+// the interval's lower end a is still the +0 it started as.  While that lasts the bookkeeping of a round is two
+// multiplies and the shifts of (cc, x, b) and (fx, fb), without the selects on the comparison and on the guess -- the
+// regime loop, 114-117 instructions a round against 130 / 139.  The first time the energy at x is the lower one the
+// search falls into the generic loop with its state as it stands, and stays there.
 // (Round 4 tried FOUR points per round -- the wave's four 16-lane rows, two window neighbours per lane, the two
 // 16-lane trees of the 32-lane sum side by side: the gradient in one round, two golden-section steps per round
 // for certain and a third under the same guess; bit-identical, all schedule-equality tests green.  Measured: no
@@ -1194,55 +1291,9 @@ __device__ __forceinline__ bool decide64(const VmLevelView &L, const VmKParams &
             f_ = fmaf(WT, (fabsf(nvx_ - c.tref.x) + fabsf(nvy_ - c.tref.y)) - T0, f_); \
         halves(f_, (FLO_), (FHI_));                                                    \
     }
-    // golden_section_search, morph.cu:885-947
-    const float R = 0.618033989f, C = 1.0f - R;
-    float a = 0;
-    float b = cc * C, x = b * R + cc * C;
-    float fb, fx;
-    ELINE2(hi ? x : b, fb, fx);
-    n_eval += 2;
-#pragma unroll 1
-    for (;;) {
-        if (!(cc - a > P.eps))
-            break;
-        const bool lt = fx < fb;
-        // this step: [a, cc] <- [b, cc], b <- x  or  [a, cc] <- [a, x], x <- b;  one new point xn
-        const float p = lt ? x : b, qv = lt ? cc : a;
-        const float a1 = lt ? b : a, cc1 = lt ? cc : x;
-        const float xn = p * R + qv * C;
-        const float b1 = lt ? x : xn, x1 = lt ? xn : b;
-        // the step after it, should its comparison fall like this one did
-        // The guess: the comparison repeats.  Measured on the 120x68 level of the 1080p pair it
-        // holds for 99 % of the steps (most accepted moves are small: the search keeps shrinking
-        // towards 0); a parabola through the three known points predicted no better and cost more.
-        const bool G = lt;
-        const float p2 = G ? x1 : b1, q2 = G ? cc1 : a1;
-        const float xn2 = p2 * R + q2 * C;
-        float f1, f2;
-        ELINE2(hi ? xn2 : xn, f1, f2);
-        ++n_eval;
-        {
-            const float nfb = lt ? fx : f1, nfx = lt ? f1 : fb;
-            a = a1;
-            cc = cc1;
-            b = b1;
-            x = x1;
-            fb = nfb;
-            fx = nfx;
-        }
-        if (cc - a > P.eps && (fx < fb) == G) { // the guess held: f2 is the next step's evaluation
-            const float ob = b, ofb = fb;
-            a = G ? b : a;
-            cc = G ? cc : x;
-            b = G ? x : xn2;
-            x = G ? xn2 : ob;
-            fb = G ? fx : f2;
-            fx = G ? f2 : ofb;
-            ++n_eval;
-        }
-    }
+    float tmin, fmin;
+    GOLDEN64(ELINE2, GOLDEN64_NO_TRACE, cc, P.eps, hi, n_eval, tmin, fmin)
 #undef ELINE2
-    const float tmin = fx < fb ? x : b, fmin = fx < fb ? fx : fb;
     if (!(fmin < 0))
         return false;
     step = make_float2(gx * tmin, gy * tmin);
@@ -4170,6 +4221,44 @@ __global__ void SUF(k_next_iter)(int *iter_dev, int set, int value)
         *iter_dev = set ? value : *iter_dev + value;
 }
 
+#if !VM_EXACT
+// vm_dbg_golden: the control flow of decide64's search on its own, one wave per case.  The search is GOLDEN64 as
+// decide64 expands it; the energy is f(t) = (A (t - t0)) (t - t0) + B in place of the taps and the SSIM change (each
+// half evaluates its own point, halves() exchanges the values).  in: cc, A, t0, B of case k at in[4 k ..]; out, per
+// case VM_DBG_GOLDEN_WORDS words: the bits of tmin and fmin, n_eval, then the bits of the used points in order.
+__global__ __launch_bounds__(64) void SUF(k_dbg_golden)(const float *__restrict__ in, float eps, uint32_t *__restrict__ out)
+{
+    const int k = (int)blockIdx.x;
+    const bool hi = (threadIdx.x & 32) != 0;
+    float cc = in[4 * k];
+    const float A = in[4 * k + 1], t0 = in[4 * k + 2], B = in[4 * k + 3];
+    uint32_t *o = out + (size_t)k * VM_DBG_GOLDEN_WORDS;
+    uint32_t n_eval = 0;
+    int n_pt = 0;
+#define EGOLDEN(T_, FLO_, FHI_)                     \
+    {                                               \
+        const float d_ = (T_) - t0;                 \
+        const float f_ = (A * d_) * d_ + B;         \
+        halves(f_, (FLO_), (FHI_));                 \
+    }
+#define TGOLDEN(T_)                                             \
+    {                                                           \
+        if (threadIdx.x == 0 && n_pt < VM_DBG_GOLDEN_WORDS - 3) \
+            o[3 + n_pt] = __float_as_uint(T_);                  \
+        ++n_pt;                                                 \
+    }
+    float tmin, fmin;
+    GOLDEN64(EGOLDEN, TGOLDEN, cc, eps, hi, n_eval, tmin, fmin)
+#undef EGOLDEN
+#undef TGOLDEN
+    if (threadIdx.x == 0) {
+        o[0] = __float_as_uint(tmin);
+        o[1] = __float_as_uint(fmin);
+        o[2] = n_eval;
+    }
+}
+#endif
+
 } // namespace
 
 // ---------------------------------------------------------------------------
@@ -4312,3 +4401,11 @@ int SUF(vm_pass_resident_blocks)(int device)
     }
     return per_cu * pr.multiProcessorCount;
 }
+
+#if !VM_EXACT
+// vm_dbg_golden: n searches in one launch, a wave each (`in`: 4 n floats, `out`: n x VM_DBG_GOLDEN_WORDS words, device)
+void vm_launch_dbg_golden_fast(int n, const float *in, float eps, uint32_t *out, hipStream_t s)
+{
+    hipLaunchKernelGGL(SUF(k_dbg_golden), dim3(n), dim3(64), 0, s, in, eps, out);
+}
+#endif
