@@ -438,6 +438,10 @@ int  vm_host_register(void *ptr, uint64_t bytes);
 int  vm_host_unregister(void *ptr);
 /* ... and frame `frame` of vm_video_result (above), computed on the device */
 int  vm_frame_set_v_from_video(vm_frame *f, vm_video *v, int lvl, int frame);
+/* The render calls -- every vm_render_* from here to the viewports over a shutter, and each one's _dev twin -- refuse in
+ * one order: the handle (VM_E_INVALID); a NULL output of a call that downloads (VM_E_INVALID); the arguments -- viewport,
+ * samples, samples * nx * ny, ease, color_from (VM_E_INVALID); the frame's state -- no schedule, then no layers
+ * (VM_E_STATE); a pitch below the row (VM_E_INVALID).  Of two faults at once the earlier one answers. */
 /* render_halfway_image, Algorithm/render.cu:62-96 (UI/RenderWidget.h:52-57);
  * rgb_out: h rows of w RGB8 pixels, pitch in bytes (0 = tight) */
 int  vm_render_halfway(vm_frame *f, float color_fa, float geo_fa, int color_from,

@@ -95,11 +95,7 @@ public:
     }
     // render_halfway_image(out, rowstride, w, h, ex, color_fa, geo_fa, color_from, ...)
     std::vector<unsigned char> render_halfway_image(float color_fa, float geo_fa, int color_from)
-    {
-        std::vector<unsigned char> out((size_t)w_ * h_ * 3);
-        check(vm_render_halfway(f_, color_fa, geo_fa, color_from, out.data(), 0));
-        return out;
-    }
+    { return rendered<unsigned char>(rgb_bytes(), vm_render_halfway, color_fa, geo_fa, color_from); }
 
     // where every output pixel of render_halfway_image at geo_fa samples image 0 and image 1 (vm_frame_sampling_maps):
     // the renderer's fixed point (render.cu:16-60) with its two positions kept
@@ -123,18 +119,10 @@ public:
     }
     // the layers through the morph: (h, w, channels) floats
     std::vector<float> render_layers(float color_fa, float geo_fa, int color_from)
-    {
-        std::vector<float> out((size_t)w_ * h_ * (channels_ ? channels_ : 1));
-        check(vm_render_layers(f_, color_fa, geo_fa, color_from, out.data(), 0));
-        return out;
-    }
+    { return rendered<float>(layer_floats(), vm_render_layers, color_fa, geo_fa, color_from); }
     // ... left on the device: the kernel's milliseconds
     float render_layers_dev(float color_fa, float geo_fa, int color_from)
-    {
-        float ms = 0;
-        check(vm_render_layers_dev(f_, color_fa, geo_fa, color_from, &ms));
-        return ms;
-    }
+    { return timed(vm_render_layers_dev, color_fa, geo_fa, color_from); }
 
     // transition control: where the morph happens when.  Two (h, w, 2) planes of (t0, t1) in the halfway domain, for the
     // geometry and the colour (either may be nullptr: uniform (0, 1)); kept on the device until replaced or cleared
@@ -146,178 +134,81 @@ public:
     // render_halfway_image under the schedule at time t (vm_render_transition): the chain of render.cu:16-60 with the
     // per-texel rates in the place of geo_fa and color_fa
     std::vector<unsigned char> render_transition(float t, int ease = VM_EASE_LINEAR, int color_from = 1)
-    {
-        std::vector<unsigned char> out((size_t)w_ * h_ * 3);
-        check(vm_render_transition(f_, t, ease, color_from, out.data(), 0));
-        return out;
-    }
+    { return rendered<unsigned char>(rgb_bytes(), vm_render_transition, t, ease, color_from); }
     float render_transition_dev(float t, int ease = VM_EASE_LINEAR, int color_from = 1)
-    {
-        float ms = 0;
-        check(vm_render_transition_dev(f_, t, ease, color_from, &ms));
-        return ms;
-    }
+    { return timed(vm_render_transition_dev, t, ease, color_from); }
     // the layers under the schedule: (h, w, channels) floats
     std::vector<float> render_transition_layers(float t, int ease = VM_EASE_LINEAR, int color_from = 1)
-    {
-        std::vector<float> out((size_t)w_ * h_ * (channels_ ? channels_ : 1));
-        check(vm_render_transition_layers(f_, t, ease, color_from, out.data(), 0));
-        return out;
-    }
+    { return rendered<float>(layer_floats(), vm_render_transition_layers, t, ease, color_from); }
     float render_transition_layers_dev(float t, int ease = VM_EASE_LINEAR, int color_from = 1)
-    {
-        float ms = 0;
-        check(vm_render_transition_layers_dev(f_, t, ease, color_from, &ms));
-        return ms;
-    }
+    { return timed(vm_render_transition_layers_dev, t, ease, color_from); }
     // motion blur: render_halfway_image integrated over a shutter (vm_render_shutter) -- the mean over `samples` (1..64)
     // times between geo_open and geo_close, each clamped to [0, 1], taken in float32 before the one rounding
     std::vector<unsigned char> render_shutter(float color_fa, float geo_open, float geo_close, int samples, int color_from = 1)
-    {
-        std::vector<unsigned char> out((size_t)w_ * h_ * 3);
-        check(vm_render_shutter(f_, color_fa, geo_open, geo_close, samples, color_from, out.data(), 0));
-        return out;
-    }
+    { return rendered<unsigned char>(rgb_bytes(), vm_render_shutter, color_fa, geo_open, geo_close, samples, color_from); }
     float render_shutter_dev(float color_fa, float geo_open, float geo_close, int samples, int color_from = 1)
-    {
-        float ms = 0;
-        check(vm_render_shutter_dev(f_, color_fa, geo_open, geo_close, samples, color_from, &ms));
-        return ms;
-    }
+    { return timed(vm_render_shutter_dev, color_fa, geo_open, geo_close, samples, color_from); }
     // the layers through the same shutter: (h, w, channels) floats
     std::vector<float> render_shutter_layers(float color_fa, float geo_open, float geo_close, int samples, int color_from = 1)
-    {
-        std::vector<float> out((size_t)w_ * h_ * (channels_ ? channels_ : 1));
-        check(vm_render_shutter_layers(f_, color_fa, geo_open, geo_close, samples, color_from, out.data(), 0));
-        return out;
-    }
+    { return rendered<float>(layer_floats(), vm_render_shutter_layers, color_fa, geo_open, geo_close, samples, color_from); }
     float render_shutter_layers_dev(float color_fa, float geo_open, float geo_close, int samples, int color_from = 1)
-    {
-        float ms = 0;
-        check(vm_render_shutter_layers_dev(f_, color_fa, geo_open, geo_close, samples, color_from, &ms));
-        return ms;
-    }
+    { return timed(vm_render_shutter_layers_dev, color_fa, geo_open, geo_close, samples, color_from); }
     // motion blur under the schedule (vm_render_transition_shutter): the mean over `samples` (1..64) times between t_open
     // and t_close, the geometry schedule ramped at each of them, the colour schedule once at t_color
     std::vector<unsigned char> render_transition_shutter(float t_open, float t_close, int samples, float t_color,
                                                          int ease = VM_EASE_LINEAR, int color_from = 1)
-    {
-        std::vector<unsigned char> out((size_t)w_ * h_ * 3);
-        check(vm_render_transition_shutter(f_, t_open, t_close, samples, t_color, ease, color_from, out.data(), 0));
-        return out;
-    }
+    { return rendered<unsigned char>(rgb_bytes(), vm_render_transition_shutter, t_open, t_close, samples, t_color, ease, color_from); }
     float render_transition_shutter_dev(float t_open, float t_close, int samples, float t_color, int ease = VM_EASE_LINEAR,
                                         int color_from = 1)
-    {
-        float ms = 0;
-        check(vm_render_transition_shutter_dev(f_, t_open, t_close, samples, t_color, ease, color_from, &ms));
-        return ms;
-    }
+    { return timed(vm_render_transition_shutter_dev, t_open, t_close, samples, t_color, ease, color_from); }
     // the layers through the same shutter and schedule: (h, w, channels) floats
     std::vector<float> render_transition_shutter_layers(float t_open, float t_close, int samples, float t_color,
                                                         int ease = VM_EASE_LINEAR, int color_from = 1)
-    {
-        std::vector<float> out((size_t)w_ * h_ * (channels_ ? channels_ : 1));
-        check(vm_render_transition_shutter_layers(f_, t_open, t_close, samples, t_color, ease, color_from, out.data(), 0));
-        return out;
-    }
+    { return rendered<float>(layer_floats(), vm_render_transition_shutter_layers, t_open, t_close, samples, t_color, ease, color_from); }
     float render_transition_shutter_layers_dev(float t_open, float t_close, int samples, float t_color, int ease = VM_EASE_LINEAR,
                                                int color_from = 1)
-    {
-        float ms = 0;
-        check(vm_render_transition_shutter_layers_dev(f_, t_open, t_close, samples, t_color, ease, color_from, &ms));
-        return ms;
-    }
+    { return timed(vm_render_transition_shutter_layers_dev, t_open, t_close, samples, t_color, ease, color_from); }
     // any viewport of the morph at any size, supersampled (vm_render_viewport): every pixel of the vp.out_w x vp.out_h grid
     // the mean of vp.nx x vp.ny chains of render.cu:16-60, taken in float32 before the one rounding: (out_h, out_w, 3) bytes
     std::vector<unsigned char> render_viewport(const Viewport &vp, float color_fa, float geo_fa, int color_from = 1)
-    {
-        std::vector<unsigned char> out(viewport_pixels(vp) * 3);
-        check(vm_render_viewport(f_, &vp, color_fa, geo_fa, color_from, out.data(), 0));
-        return out;
-    }
+    { return rendered<unsigned char>(rgb_bytes(&vp), vm_render_viewport, &vp, color_fa, geo_fa, color_from); }
     float render_viewport_dev(const Viewport &vp, float color_fa, float geo_fa, int color_from = 1)
-    {
-        float ms = 0;
-        check(vm_render_viewport_dev(f_, &vp, color_fa, geo_fa, color_from, &ms));
-        return ms;
-    }
+    { return timed(vm_render_viewport_dev, &vp, color_fa, geo_fa, color_from); }
     // the layers through the same viewport: (out_h, out_w, channels) floats
     std::vector<float> render_viewport_layers(const Viewport &vp, float color_fa, float geo_fa, int color_from = 1)
-    {
-        std::vector<float> out(viewport_pixels(vp) * (channels_ ? channels_ : 1));
-        check(vm_render_viewport_layers(f_, &vp, color_fa, geo_fa, color_from, out.data(), 0));
-        return out;
-    }
+    { return rendered<float>(layer_floats(&vp), vm_render_viewport_layers, &vp, color_fa, geo_fa, color_from); }
     float render_viewport_layers_dev(const Viewport &vp, float color_fa, float geo_fa, int color_from = 1)
-    {
-        float ms = 0;
-        check(vm_render_viewport_layers_dev(f_, &vp, color_fa, geo_fa, color_from, &ms));
-        return ms;
-    }
+    { return timed(vm_render_viewport_layers_dev, &vp, color_fa, geo_fa, color_from); }
     // a viewport over a shutter (vm_render_viewport_shutter): every output pixel the mean of its vp.nx x vp.ny chains at
     // each of `samples` times between geo_open and geo_close; samples * vp.nx * vp.ny may be 256 at most
     std::vector<unsigned char> render_viewport_shutter(const Viewport &vp, float color_fa, float geo_open, float geo_close,
                                                        int samples, int color_from = 1)
-    {
-        std::vector<unsigned char> out(viewport_pixels(vp) * 3);
-        check(vm_render_viewport_shutter(f_, &vp, color_fa, geo_open, geo_close, samples, color_from, out.data(), 0));
-        return out;
-    }
+    { return rendered<unsigned char>(rgb_bytes(&vp), vm_render_viewport_shutter, &vp, color_fa, geo_open, geo_close, samples, color_from); }
     float render_viewport_shutter_dev(const Viewport &vp, float color_fa, float geo_open, float geo_close, int samples,
                                       int color_from = 1)
-    {
-        float ms = 0;
-        check(vm_render_viewport_shutter_dev(f_, &vp, color_fa, geo_open, geo_close, samples, color_from, &ms));
-        return ms;
-    }
+    { return timed(vm_render_viewport_shutter_dev, &vp, color_fa, geo_open, geo_close, samples, color_from); }
     // the layers through the same viewport over the same shutter: (out_h, out_w, channels) floats
     std::vector<float> render_viewport_shutter_layers(const Viewport &vp, float color_fa, float geo_open, float geo_close,
                                                       int samples, int color_from = 1)
-    {
-        std::vector<float> out(viewport_pixels(vp) * (channels_ ? channels_ : 1));
-        check(vm_render_viewport_shutter_layers(f_, &vp, color_fa, geo_open, geo_close, samples, color_from, out.data(), 0));
-        return out;
-    }
+    { return rendered<float>(layer_floats(&vp), vm_render_viewport_shutter_layers, &vp, color_fa, geo_open, geo_close, samples, color_from); }
     float render_viewport_shutter_layers_dev(const Viewport &vp, float color_fa, float geo_open, float geo_close, int samples,
                                              int color_from = 1)
-    {
-        float ms = 0;
-        check(vm_render_viewport_shutter_layers_dev(f_, &vp, color_fa, geo_open, geo_close, samples, color_from, &ms));
-        return ms;
-    }
+    { return timed(vm_render_viewport_shutter_layers_dev, &vp, color_fa, geo_open, geo_close, samples, color_from); }
     // a viewport over a shutter under the schedule (vm_render_viewport_transition_shutter): the geometry schedule ramped at
     // each of `samples` times between t_open and t_close, the colour schedule once at t_color
     std::vector<unsigned char> render_viewport_transition_shutter(const Viewport &vp, float t_open, float t_close, int samples,
                                                                   float t_color, int ease = VM_EASE_LINEAR, int color_from = 1)
-    {
-        std::vector<unsigned char> out(viewport_pixels(vp) * 3);
-        check(vm_render_viewport_transition_shutter(f_, &vp, t_open, t_close, samples, t_color, ease, color_from, out.data(), 0));
-        return out;
-    }
+    { return rendered<unsigned char>(rgb_bytes(&vp), vm_render_viewport_transition_shutter, &vp, t_open, t_close, samples, t_color, ease, color_from); }
     float render_viewport_transition_shutter_dev(const Viewport &vp, float t_open, float t_close, int samples, float t_color,
                                                  int ease = VM_EASE_LINEAR, int color_from = 1)
-    {
-        float ms = 0;
-        check(vm_render_viewport_transition_shutter_dev(f_, &vp, t_open, t_close, samples, t_color, ease, color_from, &ms));
-        return ms;
-    }
+    { return timed(vm_render_viewport_transition_shutter_dev, &vp, t_open, t_close, samples, t_color, ease, color_from); }
     // the layers through the same viewport, shutter and schedule: (out_h, out_w, channels) floats
     std::vector<float> render_viewport_transition_shutter_layers(const Viewport &vp, float t_open, float t_close, int samples,
                                                                  float t_color, int ease = VM_EASE_LINEAR, int color_from = 1)
-    {
-        std::vector<float> out(viewport_pixels(vp) * (channels_ ? channels_ : 1));
-        check(vm_render_viewport_transition_shutter_layers(f_, &vp, t_open, t_close, samples, t_color, ease, color_from,
-                                                           out.data(), 0));
-        return out;
-    }
+    { return rendered<float>(layer_floats(&vp), vm_render_viewport_transition_shutter_layers, &vp, t_open, t_close, samples, t_color, ease, color_from); }
     float render_viewport_transition_shutter_layers_dev(const Viewport &vp, float t_open, float t_close, int samples,
                                                         float t_color, int ease = VM_EASE_LINEAR, int color_from = 1)
-    {
-        float ms = 0;
-        check(vm_render_viewport_transition_shutter_layers_dev(f_, &vp, t_open, t_close, samples, t_color, ease, color_from, &ms));
-        return ms;
-    }
+    { return timed(vm_render_viewport_transition_shutter_layers_dev, &vp, t_open, t_close, samples, t_color, ease, color_from); }
     // a viewport under the schedule at the one instant t: one sample, t_open == t_close == t_color == t
     std::vector<unsigned char> render_viewport_transition(const Viewport &vp, float t, int ease = VM_EASE_LINEAR, int color_from = 1)
     {
@@ -341,12 +232,29 @@ public:
     vm_frame *handle() const { return f_; }
 
 private:
-    // the pixels of a viewport's output (one for a viewport the library will refuse)
-    static size_t viewport_pixels(const vm_viewport &vp)
+    // a render call that downloads, call(f_, args..., out, pitch): `count` elements, tight
+    template <class T, class Call, class... Args> std::vector<T> rendered(size_t count, Call call, Args... args)
     {
-        const bool ok = vp.out_w >= 1 && vp.out_w <= 32768 && vp.out_h >= 1 && vp.out_h <= 32768;
-        return ok ? (size_t)vp.out_w * vp.out_h : 1;
+        std::vector<T> out(count);
+        check(call(f_, args..., out.data(), 0));
+        return out;
     }
+    // ... and its _dev twin, call(f_, args..., elapsed_ms): the launch's milliseconds
+    template <class Call, class... Args> float timed(Call call, Args... args)
+    {
+        float ms = 0;
+        check(call(f_, args..., &ms));
+        return ms;
+    }
+    // the pixels of the frame, or of a viewport's output (one for a viewport the library will refuse)
+    size_t pixels(const vm_viewport *vp) const
+    {
+        if (!vp) return (size_t)w_ * h_;
+        const bool ok = vp->out_w >= 1 && vp->out_w <= 32768 && vp->out_h >= 1 && vp->out_h <= 32768;
+        return ok ? (size_t)vp->out_w * vp->out_h : 1;
+    }
+    size_t rgb_bytes(const vm_viewport *vp = nullptr) const { return pixels(vp) * 3; }
+    size_t layer_floats(const vm_viewport *vp = nullptr) const { return pixels(vp) * (channels_ ? channels_ : 1); }
     vm_frame *f_ = nullptr;
     int w_, h_, ex_;
     int channels_ = 0;

@@ -53,13 +53,9 @@ UNITS = [
     ("vm_warp.hip", "vm_warp_kernels.o", ["-ffp-contract=off"]),
     ("vm_warp.cpp", "vm_warp.o", ["-x", "hip"]),
     ("vm_shutter.hip", "vm_shutter_kernels.o", ["-ffp-contract=off"]),
-    ("vm_shutter.cpp", "vm_shutter.o", ["-x", "hip"]),
     ("vm_tshutter.hip", "vm_tshutter_kernels.o", ["-ffp-contract=off"]),
-    ("vm_tshutter.cpp", "vm_tshutter.o", ["-x", "hip"]),
     ("vm_viewport.hip", "vm_viewport_kernels.o", ["-ffp-contract=off"]),
-    ("vm_viewport.cpp", "vm_viewport.o", ["-x", "hip"]),
     ("vm_vshutter.hip", "vm_vshutter_kernels.o", ["-ffp-contract=off"]),
-    ("vm_vshutter.cpp", "vm_vshutter.o", ["-x", "hip"]),
     ("vm_poisson.hip", "vm_poisson.o", ["-ffp-contract=off"]),
     ("vm_mgb.hip", "vm_mgb.o", ["-ffp-contract=fast"]),
     ("vm_pyramid.hip", "vm_pyramid.o", ["-ffp-contract=off"]),
@@ -78,6 +74,7 @@ UNITS = [
     ("vm_sweep_sched.cpp", "vm_sweep_sched.o", ["-x", "hip"]),
     ("vm_host.cpp", "vm_host.o", ["-x", "hip"]),
     ("vm_frame.cpp", "vm_frame.o", ["-x", "hip"]),
+    ("vm_render_calls.cpp", "vm_render_calls.o", ["-x", "hip"]),
     ("vm_poisson_api.cpp", "vm_poisson_api.o", ["-x", "hip"]),
     ("vm_rccl.cpp", "vm_rccl.o", ["-x", "hip"]),
 ]

@@ -226,31 +226,3 @@ extern "C" int vm_upscale_result(vm_pyr *p, int lvl, int w0, int h0, float *out,
     VM_HIP(hipStreamSynchronize(s));
     return VM_OK;
 }
-
-static int render_dev(vm_frame *f, float color_fa, float geo_fa, int color_from, float *ms)
-{
-    if (color_from < 0 || color_from > 2) return vm_fail(VM_E_INVALID, "vm_render_halfway: color_from %d", color_from);
-    return vm_timed_launch(f->ctx, ms, [&] {
-        vm_launch_render(f->out.get(), f->w * 3, f->w, f->h, f->rs, f->ex, color_fa, geo_fa, color_from, f->ext[0].get(),
-                         f->ext[1].get(), f->v.get(), f->u_zero ? nullptr : f->u.get(), f->ctx->stream);
-    });
-}
-
-extern "C" int vm_render_halfway_dev(vm_frame *f, float color_fa, float geo_fa, int color_from, float *ms)
-{
-    VM_ENTER(f);
-    return render_dev(f, color_fa, geo_fa, color_from, ms);
-}
-
-extern "C" int vm_render_halfway(vm_frame *f, float color_fa, float geo_fa, int color_from,
-                                 uint8_t *rgb, int pitch)
-{
-    if (!rgb) return vm_fail(VM_E_INVALID, "vm_render_halfway: output is NULL");
-    VM_ENTER(f);
-    if (int rc = vm_pitch_resolve(__func__, &pitch, 1, (size_t)f->w * 3)) return rc;
-    if (int rc = render_dev(f, color_fa, geo_fa, color_from, nullptr)) return rc;
-    hipStream_t s = f->ctx->stream;
-    if (int rc = vm_copy_pitched(__func__, hipMemcpyDeviceToHost, f->out.get(), (size_t)f->w * 3, rgb, pitch, 1, (size_t)f->w * 3, f->h, s)) return rc;
-    VM_HIP(hipStreamSynchronize(s));
-    return VM_OK;
-}

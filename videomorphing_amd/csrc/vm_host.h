@@ -237,7 +237,8 @@ struct vm_frame {
     VmDev<float> layers;
     int layer_ch = 0;
     size_t layer_off = 0;
-    // what the warp kernels write before it goes to the host (the maps, or the rendered layers), allocated on first use
+    // what the warp kernels write before it goes to the host (the maps of vm_warp.cpp, the output of a render call of
+    // vm_render_calls.cpp), allocated on first use
     VmDev<char> warp_out;
     // the transition schedule (vm_frame_upload_schedule, vm_warp.cpp), allocated on the first upload: the geometry plane and
     // the colour plane of h x rs pairs (t0, t1), then the scratch plane of the same size a call ramps its rates into
@@ -282,9 +283,9 @@ int vm_level_copy_v(vm_ctx *c, vm_level &l, hipMemcpyKind kind, const float *v, 
 int vm_pitch_resolve(const char *fn, int *pitch, size_t unit, size_t row_bytes);
 int vm_copy_pitched(const char *fn, hipMemcpyKind kind, void *dev, size_t dev_pitch_bytes, const void *host, int pitch,
                     size_t unit, size_t row_bytes, int h, hipStream_t s);
-// What every call that takes a vm_viewport checks of it and of its colour source (vm_viewport.cpp; include/vmorph.h's
-// viewport section lists the refusals): VM_OK, or VM_E_INVALID with fn's message.
-int vm_viewport_check(const char *fn, const vm_viewport *vp, int color_from);
+// The three planes of a frame's schedule (vm_warp.cpp, which uploads them; the maps call there and the render calls of
+// vm_render_calls.cpp bind them): geometry, colour, and the scratch plane a call ramps its rates into.
+void vm_frame_schedule_planes(vm_frame *f, const float2 **geo, const float2 **color, float2 **rates);
 // the sweep of one level (vm_sweep_sched.cpp)
 int vm_iteration_cap(float max_iter, int *cap);
 int vm_optimize_levels(vm_ctx *c, vm_level **lv, int n, float max_iter, volatile const int *run_flag,

@@ -1,0 +1,441 @@
+// vm_render_calls.cpp -- the C-ABI of the render calls, every vm_render_* of include/vmorph.h: the launchers of
+// vm_render.hip, vm_warp.hip, vm_shutter.hip, vm_tshutter.hip, vm_viewport.hip and vm_vshutter.hip (the compositor's chain,
+// render.cu:16-60, UI/RenderWidget.cpp:229-266, with their tails) behind ONE host path -- check, bind, launch, download
+// (DESIGN 3.15).  Nothing here changes the frame's v, path, canvases, layers or schedule; the schedule's rate plane and
+// warp_out are a call's scratch.
+#include "vm_host.h"
+#include "vm_warp.h"
+#include "vm_shutter.h"
+#include "vm_tshutter.h"
+#include "vm_viewport.h"
+#include "vm_vshutter.h"
+#include <cmath>
+#include <type_traits>
+
+namespace {
+
+static_assert((int)VM_WARP_CANVAS == (int)VM_SHUTTER_CANVAS, "the launchers name the canvas tail alike");
+enum { VM_VIEWPORT_MAX_SIDE = 32768, VM_VIEWPORT_MAX_SAMPLES = 64 };
+
+// What a call carries and needs (the bits of Call::what).
+enum {
+    VIEWPORT = 1,       // carries a vm_viewport: the output grid is the viewport's, not the frame's
+    SHUTTER = 2,        // carries a sample count
+    SCHEDULED = 4,      // carries an ease and needs the frame's schedule
+    LAYERS = 8,         // renders the frame's layers (floats) instead of its canvases (RGB8)
+    OWN_OUT = 16        // renders into the frame's own `out` (vm_render_halfway*), not into warp_out
+};
+struct Call {
+    const char *fn;     // the entry point, for the messages
+    int what;
+    const vm_viewport *vp;
+    int samples, ease, color_from;
+};
+// ... and where its output goes: to the host (pitch in bytes for RGB8, in floats for layers; 0 = tight) and drained, or
+// left on the device with the launch timed (ms may be NULL)
+struct Dest {
+    bool download;
+    void *host;
+    int pitch;
+    float *ms;
+};
+Dest down(void *out, int pitch) { return Dest{true, out, pitch, nullptr}; }
+Dest left(float *ms) { return Dest{false, nullptr, 0, ms}; }
+
+// ---- the argument checks: VM_OK, or VM_E_INVALID with fn's message
+int check_viewport(const char *fn, const vm_viewport *vp)
+{
+    if (!vp) return vm_fail(VM_E_INVALID, "%s: viewport is NULL", fn);
+    if (!std::isfinite(vp->x0) || !std::isfinite(vp->y0))
+        return vm_fail(VM_E_INVALID, "%s: viewport corner (%g, %g) is not finite", fn, (double)vp->x0, (double)vp->y0);
+    if (!std::isfinite(vp->step_x) || !std::isfinite(vp->step_y) || !(vp->step_x > 0) || !(vp->step_y > 0))
+        return vm_fail(VM_E_INVALID, "%s: viewport step (%g, %g) (finite, > 0)", fn, (double)vp->step_x, (double)vp->step_y);
+    if (vp->out_w < 1 || vp->out_w > VM_VIEWPORT_MAX_SIDE || vp->out_h < 1 || vp->out_h > VM_VIEWPORT_MAX_SIDE)
+        return vm_fail(VM_E_INVALID, "%s: output of %d x %d (1..%d each)", fn, vp->out_w, vp->out_h, (int)VM_VIEWPORT_MAX_SIDE);
+    // (nx alone is bounded first: the product of two ints that passed cannot overflow)
+    if (vp->nx < 1 || vp->ny < 1 || vp->nx > VM_VIEWPORT_MAX_SAMPLES || vp->ny > VM_VIEWPORT_MAX_SAMPLES ||
+        vp->nx * vp->ny > VM_VIEWPORT_MAX_SAMPLES)
+        return vm_fail(VM_E_INVALID, "%s: %d x %d sub-samples (each >= 1, 1..%d together)", fn, vp->nx, vp->ny,
+                       (int)VM_VIEWPORT_MAX_SAMPLES);
+    return VM_OK;
+}
+
+int check_samples(const char *fn, int samples)
+{
+    if (samples < 1 || samples > VM_SHUTTER_MAX_SAMPLES)
+        return vm_fail(VM_E_INVALID, "%s: %d samples (1..%d)", fn, samples, (int)VM_SHUTTER_MAX_SAMPLES);
+    return VM_OK;
+}
+
+// (after the viewport and the samples: the product of three ints that passed cannot overflow)
+int check_chains(const char *fn, int samples, const vm_viewport *vp)
+{
+    if (samples * vp->nx * vp->ny > VM_VSHUTTER_MAX_CHAINS)
+        return vm_fail(VM_E_INVALID, "%s: %d samples of %d x %d sub-samples (at most %d chains per pixel)", fn, samples, vp->nx,
+                       vp->ny, (int)VM_VSHUTTER_MAX_CHAINS);
+    return VM_OK;
+}
+
+int check_ease(const char *fn, int ease)
+{
+    if (ease != VM_EASE_LINEAR && ease != VM_EASE_SMOOTH) return vm_fail(VM_E_INVALID, "%s: ease %d", fn, ease);
+    return VM_OK;
+}
+
+int check_color_from(const char *fn, int color_from)
+{
+    if (color_from < 0 || color_from > 2) return vm_fail(VM_E_INVALID, "%s: color_from %d", fn, color_from);
+    return VM_OK;
+}
+
+// the arguments a call carries, in the one order: viewport, samples, chain cap, ease, color_from
+int check_args(const Call &k)
+{
+    if (k.what & VIEWPORT)
+        if (int rc = check_viewport(k.fn, k.vp)) return rc;
+    if (k.what & SHUTTER)
+        if (int rc = check_samples(k.fn, k.samples)) return rc;
+    if ((k.what & VIEWPORT) && (k.what & SHUTTER))
+        if (int rc = check_chains(k.fn, k.samples, k.vp)) return rc;
+    if (k.what & SCHEDULED)
+        if (int rc = check_ease(k.fn, k.ease)) return rc;
+    return check_color_from(k.fn, k.color_from);
+}
+
+// ---- the frame binders: a launcher's argument struct filled from the frame, field by name
+const float2 *path_of(const vm_frame *f) { return f->u_zero ? nullptr : f->u.get(); }
+
+// the field: its size and pitch, v, and the quadratic path (NULL for a zero path); VmTransition says v / u
+template <class A> void bind_field(A &a, const vm_frame *f)
+{
+    a.w = f->w; a.h = f->h; a.rs = f->rs;
+    if constexpr (std::is_same<A, VmTransition>::value) {
+        a.v = f->v.get(); a.u = path_of(f);
+    } else {
+        a.vf = f->v.get(); a.uf = path_of(f);
+    }
+}
+
+template <class A> void bind_schedule(A &a, vm_frame *f) { vm_frame_schedule_planes(f, &a.sched_geo, &a.sched_color, &a.rates); }
+
+template <class A> void bind_viewport(A &a, const vm_viewport *vp)
+{
+    a.x0 = vp->x0; a.y0 = vp->y0; a.step_x = vp->step_x; a.step_y = vp->step_y;
+    a.out_w = vp->out_w; a.out_h = vp->out_h; a.nx = vp->nx; a.ny = vp->ny;
+}
+
+// the tail: the frame's layers into floats at dev, or its canvases into RGB8 at dev
+template <class A> void bind_tail(A &a, const vm_frame *f, bool layers, void *dev)
+{
+    if (layers) {
+        a.channels = f->layer_ch;
+        a.layer0 = f->layers.get(); a.layer1 = f->layers.get() + f->layer_off; a.out = (float *)dev;
+    } else {
+        a.channels = VM_SHUTTER_CANVAS;
+        a.ext0 = f->ext[0].get(); a.ext1 = f->ext[1].get(); a.ex = f->ex; a.rgb = (uint8_t *)dev;
+    }
+}
+
+// ---- the driver: every render call after its handle guard.  NULL output (a call that downloads) -> the arguments ->
+// the frame's state, "no schedule" then "no layers" -> the pitch -> the device buffer reserved, launch(dev, stream) --
+// timed for a call that leaves its output there --, and for one that downloads the rows copied out and the stream drained.
+template <class L> int render_call(vm_frame *f, const Call &k, const Dest &d, L launch)
+{
+    if (d.download && !d.host) return vm_fail(VM_E_INVALID, "%s: output is NULL", k.fn);
+    if (int rc = check_args(k)) return rc;
+    if ((k.what & SCHEDULED) && !f->has_sched)
+        return vm_fail(VM_E_STATE, "%s: the frame holds no schedule (vm_frame_upload_schedule)", k.fn);
+    const bool layers = (k.what & LAYERS) != 0;
+    if (layers && !f->layer_ch) return vm_fail(VM_E_STATE, "%s: the frame holds no layers (vm_frame_upload_layers)", k.fn);
+    // the output grid, and one tight row of it in bytes
+    const int out_w = (k.what & VIEWPORT) ? k.vp->out_w : f->w, out_h = (k.what & VIEWPORT) ? k.vp->out_h : f->h;
+    const size_t unit = layers ? 4 : 1, row = (size_t)out_w * (layers ? (size_t)f->layer_ch * 4 : 3);
+    int pitch = d.pitch;
+    if (d.download)
+        if (int rc = vm_pitch_resolve(k.fn, &pitch, unit, row)) return rc;
+    vm_ctx *c = f->ctx;
+    void *dev = f->out.get();
+    if (!(k.what & OWN_OUT)) {
+        if (int rc = f->warp_out.reserve(row * (size_t)out_h, c->stream)) return rc;
+        dev = f->warp_out.get();
+    }
+    if (int rc = vm_timed_launch(c, d.ms, [&] { launch(dev, c->stream); })) return rc;
+    if (!d.download) return VM_OK;
+    if (int rc = vm_copy_pitched(k.fn, hipMemcpyDeviceToHost, dev, row, d.host, pitch, unit, row, out_h, c->stream)) return rc;
+    VM_HIP(hipStreamSynchronize(c->stream));
+    return VM_OK;
+}
+
+// ---- the families: a call's arguments into its launcher's
+int halfway(vm_frame *f, const char *fn, float color_fa, float geo_fa, int color_from, const Dest &d)
+{
+    return render_call(f, Call{fn, OWN_OUT, nullptr, 0, 0, color_from}, d, [&](void *dev, hipStream_t s) {
+        vm_launch_render((uint8_t *)dev, f->w * 3, f->w, f->h, f->rs, f->ex, color_fa, geo_fa, color_from, f->ext[0].get(),
+                         f->ext[1].get(), f->v.get(), path_of(f), s);
+    });
+}
+
+int layers(vm_frame *f, const char *fn, float color_fa, float geo_fa, int color_from, const Dest &d)
+{
+    return render_call(f, Call{fn, LAYERS, nullptr, 0, 0, color_from}, d, [&](void *dev, hipStream_t s) {
+        vm_launch_warp(f->w, f->h, f->rs, color_fa, geo_fa, color_from, f->v.get(), path_of(f), nullptr, nullptr, nullptr, nullptr,
+                       f->layer_ch, f->layers.get(), f->layers.get() + f->layer_off, (float *)dev, s);
+    });
+}
+
+int transition(vm_frame *f, const char *fn, int tail, float t, int ease, int color_from, const Dest &d)
+{
+    return render_call(f, Call{fn, SCHEDULED | tail, nullptr, 0, ease, color_from}, d, [&](void *dev, hipStream_t s) {
+        VmTransition T{};
+        bind_field(T, f); bind_schedule(T, f); bind_tail(T, f, tail == LAYERS, dev);
+        T.t = t; T.ease = ease; T.color_from = color_from;
+        vm_launch_transition(T, s);
+    });
+}
+
+int shutter(vm_frame *f, const char *fn, int tail, float color_fa, float geo_open, float geo_close, int samples, int color_from,
+            const Dest &d)
+{
+    return render_call(f, Call{fn, SHUTTER | tail, nullptr, samples, 0, color_from}, d, [&](void *dev, hipStream_t s) {
+        VmShutter S{};
+        bind_field(S, f); bind_tail(S, f, tail == LAYERS, dev);
+        S.color_fa = color_fa; S.geo_open = geo_open; S.geo_close = geo_close;
+        S.samples = samples; S.color_from = color_from;
+        vm_launch_shutter(S, s);
+    });
+}
+
+int tshutter(vm_frame *f, const char *fn, int tail, float t_open, float t_close, int samples, float t_color, int ease,
+             int color_from, const Dest &d)
+{
+    return render_call(f, Call{fn, SHUTTER | SCHEDULED | tail, nullptr, samples, ease, color_from}, d, [&](void *dev, hipStream_t s) {
+        VmTShutter S{};
+        bind_field(S, f); bind_schedule(S, f); bind_tail(S, f, tail == LAYERS, dev);
+        S.t_open = t_open; S.t_close = t_close; S.t_color = t_color;
+        S.samples = samples; S.ease = ease; S.color_from = color_from;
+        vm_launch_tshutter(S, s);
+    });
+}
+
+int viewport(vm_frame *f, const char *fn, int tail, const vm_viewport *vp, float color_fa, float geo_fa, int color_from,
+             const Dest &d)
+{
+    return render_call(f, Call{fn, VIEWPORT | tail, vp, 0, 0, color_from}, d, [&](void *dev, hipStream_t s) {
+        VmViewport V{};
+        bind_field(V, f); bind_viewport(V, vp); bind_tail(V, f, tail == LAYERS, dev);
+        V.color_fa = color_fa; V.geo_fa = geo_fa; V.color_from = color_from;
+        vm_launch_viewport(V, s);
+    });
+}
+
+// the uniform family (sched == 0: t_open / t_close are geo_open / geo_close, the schedule planes stay NULL, t_color and
+// ease are not read) or the scheduled one (sched == SCHEDULED: color_fa is not read)
+int vshutter(vm_frame *f, const char *fn, int sched, int tail, const vm_viewport *vp, float color_fa, float t_open, float t_close,
+             int samples, float t_color, int ease, int color_from, const Dest &d)
+{
+    return render_call(f, Call{fn, VIEWPORT | SHUTTER | sched | tail, vp, samples, ease, color_from}, d, [&](void *dev, hipStream_t s) {
+        VmVShutter S{};
+        bind_field(S, f); bind_viewport(S, vp); bind_tail(S, f, tail == LAYERS, dev);
+        if (sched) bind_schedule(S, f);
+        S.color_fa = color_fa; S.t_open = t_open; S.t_close = t_close; S.t_color = t_color;
+        S.samples = samples; S.ease = ease; S.color_from = color_from;
+        vm_launch_vshutter(S, s);
+    });
+}
+
+} // namespace
+
+// ---- the entry points: the handle guard under the call's own name, then its family
+extern "C" int vm_render_halfway(vm_frame *f, float color_fa, float geo_fa, int color_from, uint8_t *rgb, int pitch)
+{
+    VM_ENTER(f);
+    return halfway(f, __func__, color_fa, geo_fa, color_from, down(rgb, pitch));
+}
+
+extern "C" int vm_render_halfway_dev(vm_frame *f, float color_fa, float geo_fa, int color_from, float *ms)
+{
+    VM_ENTER(f);
+    return halfway(f, __func__, color_fa, geo_fa, color_from, left(ms));
+}
+
+extern "C" int vm_render_layers(vm_frame *f, float color_fa, float geo_fa, int color_from, float *out, int pitch_floats)
+{
+    VM_ENTER(f);
+    return layers(f, __func__, color_fa, geo_fa, color_from, down(out, pitch_floats));
+}
+
+extern "C" int vm_render_layers_dev(vm_frame *f, float color_fa, float geo_fa, int color_from, float *elapsed_ms)
+{
+    VM_ENTER(f);
+    return layers(f, __func__, color_fa, geo_fa, color_from, left(elapsed_ms));
+}
+
+extern "C" int vm_render_transition(vm_frame *f, float t, int ease, int color_from, uint8_t *rgb_out, int pitch_bytes)
+{
+    VM_ENTER(f);
+    return transition(f, __func__, 0, t, ease, color_from, down(rgb_out, pitch_bytes));
+}
+
+extern "C" int vm_render_transition_dev(vm_frame *f, float t, int ease, int color_from, float *elapsed_ms)
+{
+    VM_ENTER(f);
+    return transition(f, __func__, 0, t, ease, color_from, left(elapsed_ms));
+}
+
+extern "C" int vm_render_transition_layers(vm_frame *f, float t, int ease, int color_from, float *out, int pitch_floats)
+{
+    VM_ENTER(f);
+    return transition(f, __func__, LAYERS, t, ease, color_from, down(out, pitch_floats));
+}
+
+extern "C" int vm_render_transition_layers_dev(vm_frame *f, float t, int ease, int color_from, float *elapsed_ms)
+{
+    VM_ENTER(f);
+    return transition(f, __func__, LAYERS, t, ease, color_from, left(elapsed_ms));
+}
+
+extern "C" int vm_render_shutter(vm_frame *f, float color_fa, float geo_open, float geo_close, int samples, int color_from,
+                                 uint8_t *rgb_out, int pitch_bytes)
+{
+    VM_ENTER(f);
+    return shutter(f, __func__, 0, color_fa, geo_open, geo_close, samples, color_from, down(rgb_out, pitch_bytes));
+}
+
+extern "C" int vm_render_shutter_dev(vm_frame *f, float color_fa, float geo_open, float geo_close, int samples, int color_from,
+                                     float *elapsed_ms)
+{
+    VM_ENTER(f);
+    return shutter(f, __func__, 0, color_fa, geo_open, geo_close, samples, color_from, left(elapsed_ms));
+}
+
+extern "C" int vm_render_shutter_layers(vm_frame *f, float color_fa, float geo_open, float geo_close, int samples, int color_from,
+                                        float *out, int pitch_floats)
+{
+    VM_ENTER(f);
+    return shutter(f, __func__, LAYERS, color_fa, geo_open, geo_close, samples, color_from, down(out, pitch_floats));
+}
+
+extern "C" int vm_render_shutter_layers_dev(vm_frame *f, float color_fa, float geo_open, float geo_close, int samples,
+                                            int color_from, float *elapsed_ms)
+{
+    VM_ENTER(f);
+    return shutter(f, __func__, LAYERS, color_fa, geo_open, geo_close, samples, color_from, left(elapsed_ms));
+}
+
+extern "C" int vm_render_transition_shutter(vm_frame *f, float t_open, float t_close, int samples, float t_color, int ease,
+                                            int color_from, uint8_t *rgb_out, int pitch_bytes)
+{
+    VM_ENTER(f);
+    return tshutter(f, __func__, 0, t_open, t_close, samples, t_color, ease, color_from, down(rgb_out, pitch_bytes));
+}
+
+extern "C" int vm_render_transition_shutter_dev(vm_frame *f, float t_open, float t_close, int samples, float t_color, int ease,
+                                                int color_from, float *elapsed_ms)
+{
+    VM_ENTER(f);
+    return tshutter(f, __func__, 0, t_open, t_close, samples, t_color, ease, color_from, left(elapsed_ms));
+}
+
+extern "C" int vm_render_transition_shutter_layers(vm_frame *f, float t_open, float t_close, int samples, float t_color, int ease,
+                                                   int color_from, float *out, int pitch_floats)
+{
+    VM_ENTER(f);
+    return tshutter(f, __func__, LAYERS, t_open, t_close, samples, t_color, ease, color_from, down(out, pitch_floats));
+}
+
+extern "C" int vm_render_transition_shutter_layers_dev(vm_frame *f, float t_open, float t_close, int samples, float t_color,
+                                                       int ease, int color_from, float *elapsed_ms)
+{
+    VM_ENTER(f);
+    return tshutter(f, __func__, LAYERS, t_open, t_close, samples, t_color, ease, color_from, left(elapsed_ms));
+}
+
+extern "C" int vm_render_viewport(vm_frame *f, const vm_viewport *vp, float color_fa, float geo_fa, int color_from,
+                                  uint8_t *rgb_out, int pitch_bytes)
+{
+    VM_ENTER(f);
+    return viewport(f, __func__, 0, vp, color_fa, geo_fa, color_from, down(rgb_out, pitch_bytes));
+}
+
+extern "C" int vm_render_viewport_dev(vm_frame *f, const vm_viewport *vp, float color_fa, float geo_fa, int color_from,
+                                      float *elapsed_ms)
+{
+    VM_ENTER(f);
+    return viewport(f, __func__, 0, vp, color_fa, geo_fa, color_from, left(elapsed_ms));
+}
+
+extern "C" int vm_render_viewport_layers(vm_frame *f, const vm_viewport *vp, float color_fa, float geo_fa, int color_from,
+                                         float *out, int pitch_floats)
+{
+    VM_ENTER(f);
+    return viewport(f, __func__, LAYERS, vp, color_fa, geo_fa, color_from, down(out, pitch_floats));
+}
+
+extern "C" int vm_render_viewport_layers_dev(vm_frame *f, const vm_viewport *vp, float color_fa, float geo_fa, int color_from,
+                                             float *elapsed_ms)
+{
+    VM_ENTER(f);
+    return viewport(f, __func__, LAYERS, vp, color_fa, geo_fa, color_from, left(elapsed_ms));
+}
+
+extern "C" int vm_render_viewport_shutter(vm_frame *f, const vm_viewport *vp, float color_fa, float geo_open, float geo_close,
+                                          int samples, int color_from, uint8_t *rgb_out, int pitch_bytes)
+{
+    VM_ENTER(f);
+    return vshutter(f, __func__, 0, 0, vp, color_fa, geo_open, geo_close, samples, 0.0f, VM_EASE_LINEAR, color_from,
+                    down(rgb_out, pitch_bytes));
+}
+
+extern "C" int vm_render_viewport_shutter_dev(vm_frame *f, const vm_viewport *vp, float color_fa, float geo_open, float geo_close,
+                                              int samples, int color_from, float *elapsed_ms)
+{
+    VM_ENTER(f);
+    return vshutter(f, __func__, 0, 0, vp, color_fa, geo_open, geo_close, samples, 0.0f, VM_EASE_LINEAR, color_from, left(elapsed_ms));
+}
+
+extern "C" int vm_render_viewport_shutter_layers(vm_frame *f, const vm_viewport *vp, float color_fa, float geo_open,
+                                                 float geo_close, int samples, int color_from, float *out, int pitch_floats)
+{
+    VM_ENTER(f);
+    return vshutter(f, __func__, 0, LAYERS, vp, color_fa, geo_open, geo_close, samples, 0.0f, VM_EASE_LINEAR, color_from,
+                    down(out, pitch_floats));
+}
+
+extern "C" int vm_render_viewport_shutter_layers_dev(vm_frame *f, const vm_viewport *vp, float color_fa, float geo_open,
+                                                     float geo_close, int samples, int color_from, float *elapsed_ms)
+{
+    VM_ENTER(f);
+    return vshutter(f, __func__, 0, LAYERS, vp, color_fa, geo_open, geo_close, samples, 0.0f, VM_EASE_LINEAR, color_from,
+                    left(elapsed_ms));
+}
+
+extern "C" int vm_render_viewport_transition_shutter(vm_frame *f, const vm_viewport *vp, float t_open, float t_close, int samples,
+                                                     float t_color, int ease, int color_from, uint8_t *rgb_out, int pitch_bytes)
+{
+    VM_ENTER(f);
+    return vshutter(f, __func__, SCHEDULED, 0, vp, 0.0f, t_open, t_close, samples, t_color, ease, color_from, down(rgb_out, pitch_bytes));
+}
+
+extern "C" int vm_render_viewport_transition_shutter_dev(vm_frame *f, const vm_viewport *vp, float t_open, float t_close,
+                                                         int samples, float t_color, int ease, int color_from, float *elapsed_ms)
+{
+    VM_ENTER(f);
+    return vshutter(f, __func__, SCHEDULED, 0, vp, 0.0f, t_open, t_close, samples, t_color, ease, color_from, left(elapsed_ms));
+}
+
+extern "C" int vm_render_viewport_transition_shutter_layers(vm_frame *f, const vm_viewport *vp, float t_open, float t_close,
+                                                            int samples, float t_color, int ease, int color_from, float *out,
+                                                            int pitch_floats)
+{
+    VM_ENTER(f);
+    return vshutter(f, __func__, SCHEDULED, LAYERS, vp, 0.0f, t_open, t_close, samples, t_color, ease, color_from,
+                    down(out, pitch_floats));
+}
+
+extern "C" int vm_render_viewport_transition_shutter_layers_dev(vm_frame *f, const vm_viewport *vp, float t_open, float t_close,
+                                                                int samples, float t_color, int ease, int color_from,
+                                                                float *elapsed_ms)
+{
+    VM_ENTER(f);
+    return vshutter(f, __func__, SCHEDULED, LAYERS, vp, 0.0f, t_open, t_close, samples, t_color, ease, color_from, left(elapsed_ms));
+}

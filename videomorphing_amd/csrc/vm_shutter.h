@@ -1,4 +1,4 @@
-// vm_shutter.h -- the launcher of vm_shutter.hip, called from vm_shutter.cpp.
+// vm_shutter.h -- the launcher of vm_shutter.hip, called from vm_render_calls.cpp.
 #ifndef VM_SHUTTER_H
 #define VM_SHUTTER_H
 

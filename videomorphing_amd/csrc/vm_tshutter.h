@@ -1,4 +1,4 @@
-// vm_tshutter.h -- the launcher of vm_tshutter.hip, called from vm_tshutter.cpp.
+// vm_tshutter.h -- the launcher of vm_tshutter.hip, called from vm_render_calls.cpp.
 #ifndef VM_TSHUTTER_H
 #define VM_TSHUTTER_H
 

@@ -1,4 +1,4 @@
-// vm_viewport.h -- the launcher of vm_viewport.hip, called from vm_viewport.cpp.
+// vm_viewport.h -- the launcher of vm_viewport.hip, called from vm_render_calls.cpp.
 #ifndef VM_VIEWPORT_H
 #define VM_VIEWPORT_H
 

@@ -1,4 +1,4 @@
-// vm_vshutter.h -- the launcher of vm_vshutter.hip, called from vm_vshutter.cpp.
+// vm_vshutter.h -- the launcher of vm_vshutter.hip, called from vm_render_calls.cpp.
 #ifndef VM_VSHUTTER_H
 #define VM_VSHUTTER_H
 

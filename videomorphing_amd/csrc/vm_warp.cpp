@@ -1,6 +1,7 @@
-// vm_warp.cpp -- the C-ABI around vm_warp.hip: the sampling maps of the compositor's fixed point (render.cu:16-60,
-// UI/RenderWidget.cpp:229-266) and float layers carried through it, uniformly or under a transition schedule.  Nothing
-// here changes the frame's v, path or canvases.
+// vm_warp.cpp -- what a frame holds for the warp kernels and what it answers about its fixed point: the layer and
+// schedule uploads, and the sampling maps of the compositor's chain (render.cu:16-60, UI/RenderWidget.cpp:229-266),
+// uniformly or under a transition schedule.  The render calls are vm_render_calls.cpp's.  The maps calls change nothing
+// of the frame's v, path or canvases.
 #include "vm_host.h"
 #include "vm_warp.h"
 
@@ -60,39 +61,6 @@ extern "C" int vm_frame_upload_layers(vm_frame *f, int channels, const float *la
     return VM_OK;
 }
 
-static int layers_dev(vm_frame *f, const char *fn, float color_fa, float geo_fa, int color_from, float *ms)
-{
-    if (color_from < 0 || color_from > 2) return vm_fail(VM_E_INVALID, "%s: color_from %d", fn, color_from);
-    if (!f->layer_ch) return vm_fail(VM_E_STATE, "%s: the frame holds no layers (vm_frame_upload_layers)", fn);
-    vm_ctx *c = f->ctx;
-    if (int rc = f->warp_out.reserve((size_t)f->w * f->h * f->layer_ch * 4, c->stream)) return rc;
-    return vm_timed_launch(c, ms, [&] {
-        vm_launch_warp(f->w, f->h, f->rs, color_fa, geo_fa, color_from, f->v.get(), path_of(f), nullptr, nullptr, nullptr, nullptr,
-                       f->layer_ch, f->layers.get(), f->layers.get() + f->layer_off, (float *)f->warp_out.get(), c->stream);
-    });
-}
-
-extern "C" int vm_render_layers_dev(vm_frame *f, float color_fa, float geo_fa, int color_from, float *elapsed_ms)
-{
-    VM_ENTER(f);
-    return layers_dev(f, __func__, color_fa, geo_fa, color_from, elapsed_ms);
-}
-
-extern "C" int vm_render_layers(vm_frame *f, float color_fa, float geo_fa, int color_from, float *out, int pitch_floats)
-{
-    VM_ENTER(f);
-    if (!out) return vm_fail(VM_E_INVALID, "%s: output is NULL", __func__);
-    if (color_from < 0 || color_from > 2) return vm_fail(VM_E_INVALID, "%s: color_from %d", __func__, color_from);
-    if (!f->layer_ch) return vm_fail(VM_E_STATE, "%s: the frame holds no layers (vm_frame_upload_layers)", __func__);
-    const size_t row = (size_t)f->w * f->layer_ch * 4;
-    if (int rc = vm_pitch_resolve(__func__, &pitch_floats, 4, row)) return rc;
-    if (int rc = layers_dev(f, __func__, color_fa, geo_fa, color_from, nullptr)) return rc;
-    hipStream_t s = f->ctx->stream;
-    if (int rc = vm_copy_pitched(__func__, hipMemcpyDeviceToHost, f->warp_out.get(), row, out, pitch_floats, 4, row, f->h, s)) return rc;
-    VM_HIP(hipStreamSynchronize(s));
-    return VM_OK;
-}
-
 // ---------------------------------------------------------------------------
 // transition control: the schedule lives in the frame, every call ramps it at its own time
 extern "C" int vm_frame_upload_schedule(vm_frame *f, const float *geo_t0t1, const float *color_t0t1, int pitch_floats)
@@ -127,77 +95,11 @@ extern "C" int vm_frame_clear_schedule(vm_frame *f)
     return VM_OK;
 }
 
-// what every transition call checks, and the arguments they share
-static int transition_args(vm_frame *f, const char *fn, float t, int ease, int color_from, VmTransition *T)
+// the three planes of the frame's schedule: geometry, colour, and the scratch plane a call ramps its rates into
+void vm_frame_schedule_planes(vm_frame *f, const float2 **geo, const float2 **color, float2 **rates)
 {
-    if (ease != VM_EASE_LINEAR && ease != VM_EASE_SMOOTH) return vm_fail(VM_E_INVALID, "%s: ease %d", fn, ease);
-    if (color_from < 0 || color_from > 2) return vm_fail(VM_E_INVALID, "%s: color_from %d", fn, color_from);
-    if (!f->has_sched) return vm_fail(VM_E_STATE, "%s: the frame holds no schedule (vm_frame_upload_schedule)", fn);
     const size_t plane = (size_t)f->rs * f->h;
-    *T = VmTransition{};
-    T->w = f->w; T->h = f->h; T->rs = f->rs;
-    T->t = t; T->ease = ease; T->color_from = color_from;
-    T->v = f->v.get(); T->u = path_of(f);
-    T->sched_geo = f->sched.get(); T->sched_color = f->sched.get() + plane; T->rates = f->sched.get() + 2 * plane;
-    return VM_OK;
-}
-
-// the launch of the canvas tail (layers == false) or the layer tail into warp_out, timed if ms is given
-static int transition_dev(vm_frame *f, const char *fn, float t, int ease, int color_from, bool layers, float *ms)
-{
-    VmTransition T;
-    if (int rc = transition_args(f, fn, t, ease, color_from, &T)) return rc;
-    if (layers && !f->layer_ch) return vm_fail(VM_E_STATE, "%s: the frame holds no layers (vm_frame_upload_layers)", fn);
-    vm_ctx *c = f->ctx;
-    if (int rc = f->warp_out.reserve((size_t)f->w * f->h * (layers ? (size_t)f->layer_ch * 4 : 3), c->stream)) return rc;
-    if (layers) {
-        T.channels = f->layer_ch;
-        T.layer0 = f->layers.get(); T.layer1 = f->layers.get() + f->layer_off; T.out = (float *)f->warp_out.get();
-    } else {
-        T.channels = VM_WARP_CANVAS;
-        T.ext0 = f->ext[0].get(); T.ext1 = f->ext[1].get(); T.ex = f->ex; T.rgb = (uint8_t *)f->warp_out.get();
-    }
-    return vm_timed_launch(c, ms, [&] { vm_launch_transition(T, c->stream); });
-}
-
-extern "C" int vm_render_transition_dev(vm_frame *f, float t, int ease, int color_from, float *elapsed_ms)
-{
-    VM_ENTER(f);
-    return transition_dev(f, __func__, t, ease, color_from, false, elapsed_ms);
-}
-
-extern "C" int vm_render_transition_layers_dev(vm_frame *f, float t, int ease, int color_from, float *elapsed_ms)
-{
-    VM_ENTER(f);
-    return transition_dev(f, __func__, t, ease, color_from, true, elapsed_ms);
-}
-
-extern "C" int vm_render_transition(vm_frame *f, float t, int ease, int color_from, uint8_t *rgb_out, int pitch_bytes)
-{
-    VM_ENTER(f);
-    if (!rgb_out) return vm_fail(VM_E_INVALID, "%s: output is NULL", __func__);
-    const size_t row = (size_t)f->w * 3;
-    if (int rc = vm_pitch_resolve(__func__, &pitch_bytes, 1, row)) return rc;
-    if (int rc = transition_dev(f, __func__, t, ease, color_from, false, nullptr)) return rc;
-    hipStream_t s = f->ctx->stream;
-    if (int rc = vm_copy_pitched(__func__, hipMemcpyDeviceToHost, f->warp_out.get(), row, rgb_out, pitch_bytes, 1, row, f->h, s)) return rc;
-    VM_HIP(hipStreamSynchronize(s));
-    return VM_OK;
-}
-
-extern "C" int vm_render_transition_layers(vm_frame *f, float t, int ease, int color_from, float *out, int pitch_floats)
-{
-    VM_ENTER(f);
-    if (!out) return vm_fail(VM_E_INVALID, "%s: output is NULL", __func__);
-    // (before the pitch is judged: its row depends on the layers)
-    if (!f->layer_ch) return vm_fail(VM_E_STATE, "%s: the frame holds no layers (vm_frame_upload_layers)", __func__);
-    const size_t row = (size_t)f->w * f->layer_ch * 4;
-    if (int rc = vm_pitch_resolve(__func__, &pitch_floats, 4, row)) return rc;
-    if (int rc = transition_dev(f, __func__, t, ease, color_from, true, nullptr)) return rc;
-    hipStream_t s = f->ctx->stream;
-    if (int rc = vm_copy_pitched(__func__, hipMemcpyDeviceToHost, f->warp_out.get(), row, out, pitch_floats, 4, row, f->h, s)) return rc;
-    VM_HIP(hipStreamSynchronize(s));
-    return VM_OK;
+    *geo = f->sched.get(); *color = f->sched.get() + plane; *rates = f->sched.get() + 2 * plane;
 }
 
 extern "C" int vm_frame_transition_maps(vm_frame *f, float t, int ease, float *map0_xy, float *map1_xy, float *resid, uint8_t *flags,
@@ -205,8 +107,13 @@ extern "C" int vm_frame_transition_maps(vm_frame *f, float t, int ease, float *m
 {
     VM_ENTER(f);
     if (!map0_xy && !map1_xy && !resid && !flags && !rates_gk) return vm_fail(VM_E_INVALID, "%s: every output is NULL", __func__);
-    VmTransition T;
-    if (int rc = transition_args(f, __func__, t, ease, 0, &T)) return rc;
+    if (ease != VM_EASE_LINEAR && ease != VM_EASE_SMOOTH) return vm_fail(VM_E_INVALID, "%s: ease %d", __func__, ease);
+    if (!f->has_sched) return vm_fail(VM_E_STATE, "%s: the frame holds no schedule (vm_frame_upload_schedule)", __func__);
+    VmTransition T{};
+    T.w = f->w; T.h = f->h; T.rs = f->rs;
+    T.t = t; T.ease = ease;
+    T.v = f->v.get(); T.u = path_of(f);
+    vm_frame_schedule_planes(f, &T.sched_geo, &T.sched_color, &T.rates);
     hipStream_t s = f->ctx->stream;
     const size_t n = (size_t)f->w * f->h;
     void *const host[5] = {map0_xy, map1_xy, resid, flags, rates_gk};

@@ -1,4 +1,5 @@
-// vm_warp.h -- the launchers of vm_warp.hip, called from vm_warp.cpp, and the switch between the chain's two forms.
+// vm_warp.h -- the launchers of vm_warp.hip, called from vm_warp.cpp (the maps) and vm_render_calls.cpp, and the switch
+// between the chain's two forms.
 #ifndef VM_WARP_H
 #define VM_WARP_H
 

@@ -584,17 +584,31 @@ class Frame(object):
         capi.check(self._L.vm_frame_download_ext(self._h, side, out.ctypes.data))
         return out
 
-    def render_halfway(self, color_fa, geo_fa, color_from):
-        """render_halfway_image, render.cu:62-96 -> (h, w, 3) uint8."""
-        out = np.zeros((self.h, self.w, 3), dtype=np.uint8)
-        capi.check(self._L.vm_render_halfway(self._h, color_fa, geo_fa, color_from,
-                                             out.ctypes.data, 0))
+    def _render(self, name, args, grid, layers, vp=None):
+        """one downloading vm_render_* call (after the handle: the viewport, if the call takes one, then args) into a host
+        array over grid = (rows, columns): uint8 RGB, or float32 with the channels the layers were uploaded in"""
+        if layers:
+            shape = getattr(self, "_layer_shape", (self.h, self.w))       # (no upload: the call answers VM_E_STATE)
+            out = np.empty(tuple(grid) + tuple(shape[2:]), dtype=np.float32)
+        else:
+            out = np.zeros(tuple(grid) + (3,), dtype=np.uint8)
+        head = () if vp is None else (C.byref(vp),)
+        capi.check(getattr(self._L, name)(self._h, *head, *args, out.ctypes.data, 0))
         return out
 
-    def render_halfway_dev(self, color_fa, geo_fa, color_from):
+    def _render_dev(self, name, args, vp=None):
+        """the same call's _dev twin: the output stays on the device, the launch's milliseconds come back"""
         ms = C.c_float(0)
-        capi.check(self._L.vm_render_halfway_dev(self._h, color_fa, geo_fa, color_from, C.byref(ms)))
+        head = () if vp is None else (C.byref(vp),)
+        capi.check(getattr(self._L, name)(self._h, *head, *args, C.byref(ms)))
         return ms.value
+
+    def render_halfway(self, color_fa, geo_fa, color_from):
+        """render_halfway_image, render.cu:62-96 -> (h, w, 3) uint8."""
+        return self._render("vm_render_halfway", (color_fa, geo_fa, color_from), (self.h, self.w), False)
+
+    def render_halfway_dev(self, color_fa, geo_fa, color_from):
+        return self._render_dev("vm_render_halfway_dev", (color_fa, geo_fa, color_from))
 
     def sampling_maps(self, geo_fa):
         """where every output pixel of render_halfway at geo_fa samples image 0 and image 1, and how well that is
@@ -619,15 +633,10 @@ class Frame(object):
 
     def render_layers(self, color_fa, geo_fa, color_from):
         """the uploaded layers through the morph (vm_render_layers): float32 of the shape they were uploaded in"""
-        shape = getattr(self, "_layer_shape", (self.h, self.w))       # (no upload: the call answers VM_E_STATE)
-        out = np.empty(shape, dtype=np.float32)
-        capi.check(self._L.vm_render_layers(self._h, color_fa, geo_fa, color_from, out.ctypes.data, 0))
-        return out
+        return self._render("vm_render_layers", (color_fa, geo_fa, color_from), (self.h, self.w), True)
 
     def render_layers_dev(self, color_fa, geo_fa, color_from):
-        ms = C.c_float(0)
-        capi.check(self._L.vm_render_layers_dev(self._h, color_fa, geo_fa, color_from, C.byref(ms)))
-        return ms.value
+        return self._render_dev("vm_render_layers_dev", (color_fa, geo_fa, color_from))
 
     def upload_schedule(self, geo=None, color=None):
         """the transition schedule (vm_frame_upload_schedule): (h, w, 2) float32 planes of (t0, t1) in the halfway
@@ -648,27 +657,18 @@ class Frame(object):
 
     def render_transition(self, t, ease=capi.EASE_LINEAR, color_from=1):
         """render_halfway under the schedule at time t (vm_render_transition) -> (h, w, 3) uint8"""
-        out = np.zeros((self.h, self.w, 3), dtype=np.uint8)
-        capi.check(self._L.vm_render_transition(self._h, float(t), int(ease), int(color_from), out.ctypes.data, 0))
-        return out
+        return self._render("vm_render_transition", (float(t), int(ease), int(color_from)), (self.h, self.w), False)
 
     def render_transition_dev(self, t, ease=capi.EASE_LINEAR, color_from=1):
-        ms = C.c_float(0)
-        capi.check(self._L.vm_render_transition_dev(self._h, float(t), int(ease), int(color_from), C.byref(ms)))
-        return ms.value
+        return self._render_dev("vm_render_transition_dev", (float(t), int(ease), int(color_from)))
 
     def render_transition_layers(self, t, ease=capi.EASE_LINEAR, color_from=1):
         """the uploaded layers under the schedule at time t (vm_render_transition_layers): float32 of the shape they
         were uploaded in"""
-        shape = getattr(self, "_layer_shape", (self.h, self.w))       # (no upload: the call answers VM_E_STATE)
-        out = np.empty(shape, dtype=np.float32)
-        capi.check(self._L.vm_render_transition_layers(self._h, float(t), int(ease), int(color_from), out.ctypes.data, 0))
-        return out
+        return self._render("vm_render_transition_layers", (float(t), int(ease), int(color_from)), (self.h, self.w), True)
 
     def render_transition_layers_dev(self, t, ease=capi.EASE_LINEAR, color_from=1):
-        ms = C.c_float(0)
-        capi.check(self._L.vm_render_transition_layers_dev(self._h, float(t), int(ease), int(color_from), C.byref(ms)))
-        return ms.value
+        return self._render_dev("vm_render_transition_layers_dev", (float(t), int(ease), int(color_from)))
 
     def transition_maps(self, t, ease=capi.EASE_LINEAR):
         """sampling_maps under the schedule at time t (vm_frame_transition_maps): (map0, map1, resid, flags, rates) --
@@ -682,34 +682,27 @@ class Frame(object):
                                                     resid.ctypes.data, flags.ctypes.data, rates.ctypes.data))
         return m0, m1, resid, flags, rates
 
+    @staticmethod
+    def _shutter_args(color_fa, geo_open, geo_close, samples, color_from):
+        return (float(color_fa), float(geo_open), float(geo_close), int(samples), int(color_from))
+
     def render_shutter(self, color_fa, geo_open, geo_close, samples, color_from=1):
         """render_halfway with motion blur (vm_render_shutter): the mean over `samples` (1..64) times between geo_open
         and geo_close, each clamped to [0, 1], taken in float32 before the one rounding -> (h, w, 3) uint8"""
-        out = np.zeros((self.h, self.w, 3), dtype=np.uint8)
-        capi.check(self._L.vm_render_shutter(self._h, float(color_fa), float(geo_open), float(geo_close), int(samples),
-                                             int(color_from), out.ctypes.data, 0))
-        return out
+        args = self._shutter_args(color_fa, geo_open, geo_close, samples, color_from)
+        return self._render("vm_render_shutter", args, (self.h, self.w), False)
 
     def render_shutter_dev(self, color_fa, geo_open, geo_close, samples, color_from=1):
-        ms = C.c_float(0)
-        capi.check(self._L.vm_render_shutter_dev(self._h, float(color_fa), float(geo_open), float(geo_close), int(samples),
-                                                 int(color_from), C.byref(ms)))
-        return ms.value
+        return self._render_dev("vm_render_shutter_dev", self._shutter_args(color_fa, geo_open, geo_close, samples, color_from))
 
     def render_shutter_layers(self, color_fa, geo_open, geo_close, samples, color_from=1):
         """the uploaded layers through the same shutter (vm_render_shutter_layers): float32 of the shape they were
         uploaded in -- a matte blurs exactly as its plate does"""
-        shape = getattr(self, "_layer_shape", (self.h, self.w))       # (no upload: the call answers VM_E_STATE)
-        out = np.empty(shape, dtype=np.float32)
-        capi.check(self._L.vm_render_shutter_layers(self._h, float(color_fa), float(geo_open), float(geo_close), int(samples),
-                                                    int(color_from), out.ctypes.data, 0))
-        return out
+        args = self._shutter_args(color_fa, geo_open, geo_close, samples, color_from)
+        return self._render("vm_render_shutter_layers", args, (self.h, self.w), True)
 
     def render_shutter_layers_dev(self, color_fa, geo_open, geo_close, samples, color_from=1):
-        ms = C.c_float(0)
-        capi.check(self._L.vm_render_shutter_layers_dev(self._h, float(color_fa), float(geo_open), float(geo_close),
-                                                        int(samples), int(color_from), C.byref(ms)))
-        return ms.value
+        return self._render_dev("vm_render_shutter_layers_dev", self._shutter_args(color_fa, geo_open, geo_close, samples, color_from))
 
     @staticmethod
     def _viewport_grid(s):
@@ -722,68 +715,48 @@ class Frame(object):
         of the morph at any size, every output pixel the mean of vp.nx x vp.ny chains taken in float32 before the one
         rounding -> (vp.out_h, vp.out_w, 3) uint8.  The library checks the viewport (VmError, VM_E_INVALID)."""
         s = vp.struct()
-        out = np.zeros(self._viewport_grid(s) + (3,), dtype=np.uint8)
-        capi.check(self._L.vm_render_viewport(self._h, C.byref(s), float(color_fa), float(geo_fa), int(color_from),
-                                              out.ctypes.data, 0))
-        return out
+        return self._render("vm_render_viewport", (float(color_fa), float(geo_fa), int(color_from)), self._viewport_grid(s), False, s)
 
     def render_viewport_dev(self, vp, color_fa, geo_fa, color_from=1):
-        ms, s = C.c_float(0), vp.struct()
-        capi.check(self._L.vm_render_viewport_dev(self._h, C.byref(s), float(color_fa), float(geo_fa), int(color_from), C.byref(ms)))
-        return ms.value
+        return self._render_dev("vm_render_viewport_dev", (float(color_fa), float(geo_fa), int(color_from)), vp.struct())
 
     def render_viewport_layers(self, vp, color_fa, geo_fa, color_from=1):
         """the uploaded layers through the same viewport (vm_render_viewport_layers): float32 (vp.out_h, vp.out_w) or
         (vp.out_h, vp.out_w, C) as they were uploaded -- a matte is filtered exactly as its plate is"""
         s = vp.struct()
-        shape = getattr(self, "_layer_shape", (self.h, self.w))       # (no upload: the call answers VM_E_STATE)
-        out = np.empty(self._viewport_grid(s) + tuple(shape[2:]), dtype=np.float32)
-        capi.check(self._L.vm_render_viewport_layers(self._h, C.byref(s), float(color_fa), float(geo_fa), int(color_from),
-                                                     out.ctypes.data, 0))
-        return out
+        return self._render("vm_render_viewport_layers", (float(color_fa), float(geo_fa), int(color_from)), self._viewport_grid(s), True, s)
 
     def render_viewport_layers_dev(self, vp, color_fa, geo_fa, color_from=1):
-        ms, s = C.c_float(0), vp.struct()
-        capi.check(self._L.vm_render_viewport_layers_dev(self._h, C.byref(s), float(color_fa), float(geo_fa), int(color_from),
-                                                         C.byref(ms)))
-        return ms.value
-
-    def _viewport_shutter(self, name, s, args, layers):
-        """one vm_render_viewport_[transition_]shutter[_layers] call into a host array of the viewport's grid"""
-        if layers:
-            shape = getattr(self, "_layer_shape", (self.h, self.w))       # (no upload: the call answers VM_E_STATE)
-            out = np.empty(self._viewport_grid(s) + tuple(shape[2:]), dtype=np.float32)
-        else:
-            out = np.zeros(self._viewport_grid(s) + (3,), dtype=np.uint8)
-        capi.check(getattr(self._L, name)(self._h, C.byref(s), *args, out.ctypes.data, 0))
-        return out
-
-    def _viewport_shutter_dev(self, name, s, args):
-        ms = C.c_float(0)
-        capi.check(getattr(self._L, name)(self._h, C.byref(s), *args, C.byref(ms)))
-        return ms.value
+        return self._render_dev("vm_render_viewport_layers_dev", (float(color_fa), float(geo_fa), int(color_from)), vp.struct())
 
     def render_viewport_shutter(self, vp, color_fa, geo_open, geo_close, samples, color_from=1):
         """render_viewport with motion blur (vm_render_viewport_shutter): every output pixel the mean of its vp.nx x vp.ny
         chains at each of `samples` (1..64) times between geo_open and geo_close, each clamped to [0, 1], taken in float32
         before the one rounding -> (vp.out_h, vp.out_w, 3) uint8.  samples * vp.nx * vp.ny may be 256 at most; the library
         checks that and the viewport (VmError, VM_E_INVALID)."""
-        args = (float(color_fa), float(geo_open), float(geo_close), int(samples), int(color_from))
-        return self._viewport_shutter("vm_render_viewport_shutter", vp.struct(), args, False)
+        s, args = vp.struct(), self._shutter_args(color_fa, geo_open, geo_close, samples, color_from)
+        return self._render("vm_render_viewport_shutter", args, self._viewport_grid(s), False, s)
 
     def render_viewport_shutter_dev(self, vp, color_fa, geo_open, geo_close, samples, color_from=1):
-        args = (float(color_fa), float(geo_open), float(geo_close), int(samples), int(color_from))
-        return self._viewport_shutter_dev("vm_render_viewport_shutter_dev", vp.struct(), args)
+        args = self._shutter_args(color_fa, geo_open, geo_close, samples, color_from)
+        return self._render_dev("vm_render_viewport_shutter_dev", args, vp.struct())
 
     def render_viewport_shutter_layers(self, vp, color_fa, geo_open, geo_close, samples, color_from=1):
         """the uploaded layers through the same viewport over the same shutter (vm_render_viewport_shutter_layers):
         float32 (vp.out_h, vp.out_w) or (vp.out_h, vp.out_w, C) as they were uploaded"""
-        args = (float(color_fa), float(geo_open), float(geo_close), int(samples), int(color_from))
-        return self._viewport_shutter("vm_render_viewport_shutter_layers", vp.struct(), args, True)
+        s, args = vp.struct(), self._shutter_args(color_fa, geo_open, geo_close, samples, color_from)
+        return self._render("vm_render_viewport_shutter_layers", args, self._viewport_grid(s), True, s)
 
     def render_viewport_shutter_layers_dev(self, vp, color_fa, geo_open, geo_close, samples, color_from=1):
-        args = (float(color_fa), float(geo_open), float(geo_close), int(samples), int(color_from))
-        return self._viewport_shutter_dev("vm_render_viewport_shutter_layers_dev", vp.struct(), args)
+        args = self._shutter_args(color_fa, geo_open, geo_close, samples, color_from)
+        return self._render_dev("vm_render_viewport_shutter_layers_dev", args, vp.struct())
+
+    @staticmethod
+    def _shutter_color_time(t_open, t_close, t_color):
+        """t_color of the transition shutter calls; None: the float32 midpoint (t_open + t_close) * 0.5, formed here"""
+        if t_color is not None:
+            return float(t_color)
+        return float((np.float32(t_open) + np.float32(t_close)) * np.float32(0.5))
 
     def _scheduled_args(self, t_open, t_close, samples, t_color, ease, color_from):
         tc = self._shutter_color_time(t_open, t_close, t_color)
@@ -794,69 +767,49 @@ class Frame(object):
         ramped at each of `samples` times between t_open and t_close, the colour schedule once at t_color (None: the
         float32 midpoint, formed on the host), from the vp.nx x vp.ny sub-sample points of every output pixel ->
         (vp.out_h, vp.out_w, 3) uint8"""
-        args = self._scheduled_args(t_open, t_close, samples, t_color, ease, color_from)
-        return self._viewport_shutter("vm_render_viewport_transition_shutter", vp.struct(), args, False)
+        s, args = vp.struct(), self._scheduled_args(t_open, t_close, samples, t_color, ease, color_from)
+        return self._render("vm_render_viewport_transition_shutter", args, self._viewport_grid(s), False, s)
 
     def render_viewport_transition_shutter_dev(self, vp, t_open, t_close, samples, t_color=None, ease=capi.EASE_LINEAR, color_from=1):
         args = self._scheduled_args(t_open, t_close, samples, t_color, ease, color_from)
-        return self._viewport_shutter_dev("vm_render_viewport_transition_shutter_dev", vp.struct(), args)
+        return self._render_dev("vm_render_viewport_transition_shutter_dev", args, vp.struct())
 
     def render_viewport_transition_shutter_layers(self, vp, t_open, t_close, samples, t_color=None, ease=capi.EASE_LINEAR,
                                                   color_from=1):
         """the uploaded layers through the same viewport, shutter and rates (vm_render_viewport_transition_shutter_layers)"""
-        args = self._scheduled_args(t_open, t_close, samples, t_color, ease, color_from)
-        return self._viewport_shutter("vm_render_viewport_transition_shutter_layers", vp.struct(), args, True)
+        s, args = vp.struct(), self._scheduled_args(t_open, t_close, samples, t_color, ease, color_from)
+        return self._render("vm_render_viewport_transition_shutter_layers", args, self._viewport_grid(s), True, s)
 
     def render_viewport_transition_shutter_layers_dev(self, vp, t_open, t_close, samples, t_color=None, ease=capi.EASE_LINEAR,
                                                       color_from=1):
         args = self._scheduled_args(t_open, t_close, samples, t_color, ease, color_from)
-        return self._viewport_shutter_dev("vm_render_viewport_transition_shutter_layers_dev", vp.struct(), args)
+        return self._render_dev("vm_render_viewport_transition_shutter_layers_dev", args, vp.struct())
 
     def render_viewport_transition(self, vp, t, ease=capi.EASE_LINEAR, color_from=1):
         """render_transition through a viewport: the frame under its schedule at the one instant t, which is
         render_viewport_transition_shutter with samples = 1 and t_open == t_close == t_color == t"""
         return self.render_viewport_transition_shutter(vp, t, t, 1, t, ease, color_from)
 
-    @staticmethod
-    def _shutter_color_time(t_open, t_close, t_color):
-        """t_color of the transition shutter calls; None: the float32 midpoint (t_open + t_close) * 0.5, formed here"""
-        if t_color is not None:
-            return float(t_color)
-        return float((np.float32(t_open) + np.float32(t_close)) * np.float32(0.5))
-
     def render_transition_shutter(self, t_open, t_close, samples, t_color=None, ease=capi.EASE_LINEAR, color_from=1):
         """render_transition with motion blur (vm_render_transition_shutter): the mean over `samples` (1..64) times
         between t_open and t_close, the geometry schedule ramped at each of them, the colour schedule once at t_color
         (None: the float32 midpoint (t_open + t_close) * 0.5, formed on the host) -> (h, w, 3) uint8"""
-        out = np.zeros((self.h, self.w, 3), dtype=np.uint8)
-        tc = self._shutter_color_time(t_open, t_close, t_color)
-        capi.check(self._L.vm_render_transition_shutter(self._h, float(t_open), float(t_close), int(samples), tc, int(ease),
-                                                        int(color_from), out.ctypes.data, 0))
-        return out
+        args = self._scheduled_args(t_open, t_close, samples, t_color, ease, color_from)
+        return self._render("vm_render_transition_shutter", args, (self.h, self.w), False)
 
     def render_transition_shutter_dev(self, t_open, t_close, samples, t_color=None, ease=capi.EASE_LINEAR, color_from=1):
-        ms = C.c_float(0)
-        tc = self._shutter_color_time(t_open, t_close, t_color)
-        capi.check(self._L.vm_render_transition_shutter_dev(self._h, float(t_open), float(t_close), int(samples), tc, int(ease),
-                                                            int(color_from), C.byref(ms)))
-        return ms.value
+        args = self._scheduled_args(t_open, t_close, samples, t_color, ease, color_from)
+        return self._render_dev("vm_render_transition_shutter_dev", args)
 
     def render_transition_shutter_layers(self, t_open, t_close, samples, t_color=None, ease=capi.EASE_LINEAR, color_from=1):
         """the uploaded layers through the same shutter under the schedule (vm_render_transition_shutter_layers): float32
         of the shape they were uploaded in; t_color None: the float32 midpoint, as above"""
-        shape = getattr(self, "_layer_shape", (self.h, self.w))       # (no upload: the call answers VM_E_STATE)
-        out = np.empty(shape, dtype=np.float32)
-        tc = self._shutter_color_time(t_open, t_close, t_color)
-        capi.check(self._L.vm_render_transition_shutter_layers(self._h, float(t_open), float(t_close), int(samples), tc, int(ease),
-                                                               int(color_from), out.ctypes.data, 0))
-        return out
+        args = self._scheduled_args(t_open, t_close, samples, t_color, ease, color_from)
+        return self._render("vm_render_transition_shutter_layers", args, (self.h, self.w), True)
 
     def render_transition_shutter_layers_dev(self, t_open, t_close, samples, t_color=None, ease=capi.EASE_LINEAR, color_from=1):
-        ms = C.c_float(0)
-        tc = self._shutter_color_time(t_open, t_close, t_color)
-        capi.check(self._L.vm_render_transition_shutter_layers_dev(self._h, float(t_open), float(t_close), int(samples), tc,
-                                                                   int(ease), int(color_from), C.byref(ms)))
-        return ms.value
+        args = self._scheduled_args(t_open, t_close, samples, t_color, ease, color_from)
+        return self._render_dev("vm_render_transition_shutter_layers_dev", args)
 
     def quadratic_path(self, tol=1e-4, max_it=200):
         """CQuadraticPath::optimize for this frame's v (QuadraticPath.cpp:24-223); the result
