@@ -13,7 +13,8 @@ import numpy as np
 import pytest
 
 import warp_ref
-from videomorphing_amd import capi, morph, synth
+from render_cases import field as _field, rgb_pair as _rgb, same_bits as _same
+from videomorphing_amd import capi, morph
 
 pytestmark = pytest.mark.gpu
 
@@ -27,36 +28,12 @@ shapes = pytest.mark.parametrize("w,h,ex", SHAPES)
 
 
 @functools.lru_cache(maxsize=None)
-def _field(w, h, kind, with_path):
-    rng = np.random.RandomState(41)
-    v = warp_ref.field(kind, w, h, rng)
-    u = warp_ref.path(w, h, rng) if with_path else None
-    for a in (v, u):
-        if a is not None:
-            a.setflags(write=False)
-    return v, u
-
-
-@functools.lru_cache(maxsize=None)
 def _ref_maps(w, h, kind, with_path, geo):
     """the statement's maps: computed once, shared, never written"""
     out = warp_ref.sampling_maps(*_field(w, h, kind, with_path), geo)
     for a in out:
         a.setflags(write=False)
     return out
-
-
-@functools.lru_cache(maxsize=None)
-def _rgb(w, h):
-    return synth.make_rgb_pair(w, h)
-
-
-def _same(got, want):
-    """bit for bit, a NaN for a NaN"""
-    if got.dtype != np.float32:
-        return got.dtype == want.dtype and np.array_equal(got, want)
-    ng, nw = np.isnan(got), np.isnan(want)
-    return got.shape == want.shape and np.array_equal(ng, nw) and np.array_equal(got.view(np.uint32)[~ng], want.view(np.uint32)[~nw])
 
 
 def _frame(gpu_ctx, w, h, ex, kind, with_path, canvases=True):

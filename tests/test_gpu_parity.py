@@ -458,7 +458,8 @@ def test_render_plain_kernel_agrees(gpu_ctx):
     """the plain gather kernel (VM_RENDER=plain -- also the path of fields of 4 GiB and more, which the window
     kernel's 32-bit texel offsets do not reach) renders the same bytes as the window kernel: a child process with
     the switch set hashes four frames of a 640x360 pair with a rough path, this process hashes its own"""
-    import hashlib, subprocess, sys, textwrap
+    import textwrap
+    from render_cases import hashes_under_render_mode
     prog = textwrap.dedent("""
         import hashlib, sys
         import numpy as np
@@ -477,15 +478,7 @@ def test_render_plain_kernel_agrees(gpu_ctx):
                 hh.update(fr.render_halfway(0.4, geo, 1).tobytes())
         print("HASH", hh.hexdigest())
     """) % ROOT
-    def run(mode):
-        env = dict(os.environ)
-        env.pop("VM_RENDER", None)
-        if mode:
-            env["VM_RENDER"] = mode
-        r = subprocess.run([sys.executable, "-c", prog], env=env, capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stderr[-2000:]
-        return [l for l in r.stdout.splitlines() if l.startswith("HASH")][0]
-    assert run("plain") == run(None)
+    assert hashes_under_render_mode(prog, "plain")[0] == hashes_under_render_mode(prog, None)[0]
 
 
 def test_render_identity(gpu_ctx):

@@ -11,16 +11,14 @@ neither by C nor by numpy."""
 import ctypes as C
 import functools
 import os
-import subprocess
-import sys
 import textwrap
 
 import numpy as np
 import pytest
 
 import transit_ref
-import warp_ref
-from videomorphing_amd import capi, morph, synth, transition
+from render_cases import field as _field, hashes_under_render_mode, layers as _layers, rgb_pair as _rgb, same_bits as _same
+from videomorphing_amd import capi, morph, transition
 
 pytestmark = pytest.mark.gpu
 
@@ -33,17 +31,6 @@ TIMES = (0.0, 0.3, 0.5, 0.7, 1.0)
 EASES = (capi.EASE_LINEAR, capi.EASE_SMOOTH)
 cases = pytest.mark.parametrize("with_path", [False, True])
 shapes = pytest.mark.parametrize("w,h,ex", SHAPES)
-
-
-@functools.lru_cache(maxsize=None)
-def _field(w, h, kind, with_path):
-    rng = np.random.RandomState(41)
-    v = warp_ref.field(kind, w, h, rng)
-    u = warp_ref.path(w, h, rng) if with_path else None
-    for a in (v, u):
-        if a is not None:
-            a.setflags(write=False)
-    return v, u
 
 
 @functools.lru_cache(maxsize=None)
@@ -77,19 +64,6 @@ def _ref(w, h, kind, with_path, name, t, ease):
     return out
 
 
-@functools.lru_cache(maxsize=None)
-def _rgb(w, h):
-    return synth.make_rgb_pair(w, h)
-
-
-def _same(got, want):
-    """bit for bit, a NaN for a NaN"""
-    if got.dtype != np.float32:
-        return got.dtype == want.dtype and np.array_equal(got, want)
-    ng, nw = np.isnan(got), np.isnan(want)
-    return got.shape == want.shape and np.array_equal(ng, nw) and np.array_equal(got.view(np.uint32)[~ng], want.view(np.uint32)[~nw])
-
-
 def _founded(m0, m1):
     """where a byte is defined: both sampling positions finite"""
     return np.isfinite(m0).all(-1) & np.isfinite(m1).all(-1)
@@ -101,15 +75,6 @@ def _frame(gpu_ctx, w, h, ex, kind, with_path):
     rgb0, rgb1 = _rgb(w, h)
     fr.upload(morph.make_extended(rgb0, ex), morph.make_extended(rgb1, ex), v, u)
     return fr
-
-
-def _layers(w, h, c, seed):
-    """values of both signs over twelve orders of magnitude, +-1e6 among them"""
-    rng = np.random.RandomState(seed)
-    a = (rng.randn(h, w, c) * 10.0 ** rng.randint(-6, 6, (h, w, c))).astype(f32)
-    a[rng.rand(h, w, c) < 0.05] = f32(1e6)
-    a[rng.rand(h, w, c) < 0.05] = f32(-1e6)
-    return a[..., 0] if c == 1 else a
 
 
 @shapes
@@ -254,15 +219,7 @@ def test_plain_form_agrees(gpu_ctx):
     """the plain gather kernels (VM_RENDER=plain -- also the path of fields of 4 GiB and more) give the window kernels'
     bits: a fresh child process with the switch set hashes the maps, the bytes and the layers of two scheduled calls
     with and without a path, another one hashes the window form's"""
-    def run(mode):
-        env = dict(os.environ)
-        env.pop("VM_RENDER", None)
-        if mode:
-            env["VM_RENDER"] = mode
-        r = subprocess.run([sys.executable, "-c", _PROG], env=env, capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stderr[-2000:]
-        return [l for l in r.stdout.splitlines() if l.startswith("HASH")][0]
-    assert run("plain") == run(None)
+    assert hashes_under_render_mode(_PROG, "plain")[0] == hashes_under_render_mode(_PROG, None)[0]
 
 
 def test_state_and_errors(gpu_ctx):

@@ -12,18 +12,15 @@ output can afford -- (1, 1) always, (2, 2) or (3, 2) beside it, (8, 8) on output
 longer than a few seconds.  RGB8 bytes are compared where every sample's two positions are finite: what a NaN becomes as
 a byte is defined neither by C nor by numpy."""
 import ctypes as C
-import functools
 import os
-import subprocess
-import sys
 import textwrap
 
 import numpy as np
 import pytest
 
 import viewport_ref
-import warp_ref
-from videomorphing_amd import capi, morph, synth
+from render_cases import field as _field, frame as _frame, hashes_under_render_mode, layers as _layers, same_bits as _same
+from videomorphing_amd import capi, morph
 from videomorphing_amd.viewport import Viewport
 
 pytestmark = pytest.mark.gpu
@@ -59,46 +56,6 @@ def viewports(w, h, ex):
 
 NAMES = sorted(viewports(203, 77, 9))
 EVERY = [(w, h, ex, name) for w, h, ex in SHAPES for name in sorted(viewports(w, h, ex))]
-
-
-@functools.lru_cache(maxsize=None)
-def _field(w, h, kind, with_path):
-    rng = np.random.RandomState(41)
-    v = warp_ref.field(kind, w, h, rng)
-    u = warp_ref.path(w, h, rng) if with_path else None
-    for a in (v, u):
-        if a is not None:
-            a.setflags(write=False)
-    return v, u
-
-
-@functools.lru_cache(maxsize=None)
-def _rgb(w, h):
-    return synth.make_rgb_pair(w, h)
-
-
-def _same(got, want):
-    """bit for bit, a NaN for a NaN"""
-    if got.dtype != np.float32:
-        return got.dtype == want.dtype and np.array_equal(got, want)
-    ng, nw = np.isnan(got), np.isnan(want)
-    return got.shape == want.shape and np.array_equal(ng, nw) and np.array_equal(got.view(np.uint32)[~ng], want.view(np.uint32)[~nw])
-
-
-def _frame(gpu_ctx, w, h, ex, v, u):
-    fr = morph.Frame(gpu_ctx, w, h, ex)
-    rgb0, rgb1 = _rgb(w, h)
-    fr.upload(morph.make_extended(rgb0, ex), morph.make_extended(rgb1, ex), v, u)
-    return fr
-
-
-def _layers(w, h, c, seed):
-    """values of both signs over twelve orders of magnitude, +-1e6 among them"""
-    rng = np.random.RandomState(seed)
-    a = (rng.randn(h, w, c) * 10.0 ** rng.randint(-6, 6, (h, w, c))).astype(f32)
-    a[rng.rand(h, w, c) < 0.05] = f32(1e6)
-    a[rng.rand(h, w, c) < 0.05] = f32(-1e6)
-    return a[..., 0] if c == 1 else a
 
 
 @shapes
@@ -218,15 +175,7 @@ def test_plain_form_agrees(gpu_ctx):
     hashes, case by case, the bytes and the layers of 1, 3 and 4 channels (a NaN for a NaN, bit for bit elsewhere) under
     every viewport and sample grid of this file, on three shapes and the four fields, with and without a path; another
     one hashes the window form's"""
-    def run(mode):
-        env = dict(os.environ)
-        env.pop("VM_RENDER", None)
-        if mode:
-            env["VM_RENDER"] = mode
-        r = subprocess.run([sys.executable, "-c", _PROG], env=env, capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stderr[-2000:]
-        return [l for l in r.stdout.splitlines() if l.startswith("HASH")]
-    plain, window = run("plain"), run(None)
+    plain, window = hashes_under_render_mode(_PROG, "plain"), hashes_under_render_mode(_PROG, None)
     assert len(window) == 24
     assert plain == window, [a for a, b in zip(plain, window) if a != b]
 

@@ -15,8 +15,6 @@ numpy): everywhere for the three finite fields, which the test asserts."""
 import ctypes as C
 import functools
 import os
-import subprocess
-import sys
 import textwrap
 
 import numpy as np
@@ -25,9 +23,9 @@ import pytest
 import transit_ref
 import viewport_ref
 import vshutter_ref as VS
-import warp_ref
+from render_cases import field as _field, frame, hashes_under_render_mode, layers as _layers, same_bits as _same
 from test_gpu_viewport import viewports
-from videomorphing_amd import capi, morph, synth, transition
+from videomorphing_amd import capi, morph, transition
 from videomorphing_amd.viewport import Viewport
 
 pytestmark = pytest.mark.gpu
@@ -60,17 +58,6 @@ names = pytest.mark.parametrize("name", NAMES)
 
 
 @functools.lru_cache(maxsize=None)
-def _field(w, h, kind, with_path):
-    rng = np.random.RandomState(41)
-    v = warp_ref.field(kind, w, h, rng)
-    u = warp_ref.path(w, h, rng) if with_path else None
-    for a in (v, u):
-        if a is not None:
-            a.setflags(write=False)
-    return v, u
-
-
-@functools.lru_cache(maxsize=None)
 def _schedule(w, h, which):
     """(geometry, colour) of the transition tests: a wipe with a radial colour, two halves, a radial one with a wipe"""
     out = {"wipe": lambda: (transition.wipe(w, h), transition.radial(w, h)),
@@ -82,35 +69,8 @@ def _schedule(w, h, which):
     return out
 
 
-@functools.lru_cache(maxsize=None)
-def _rgb(w, h):
-    return synth.make_rgb_pair(w, h)
-
-
-def _same(got, want):
-    """bit for bit, a NaN for a NaN"""
-    if got.dtype != np.float32:
-        return got.dtype == want.dtype and np.array_equal(got, want)
-    ng, nw = np.isnan(got), np.isnan(want)
-    return got.shape == want.shape and np.array_equal(ng, nw) and np.array_equal(got.view(np.uint32)[~ng], want.view(np.uint32)[~nw])
-
-
 def _frame(gpu_ctx, w, h, ex, v, u, which=None):
-    fr = morph.Frame(gpu_ctx, w, h, ex)
-    rgb0, rgb1 = _rgb(w, h)
-    fr.upload(morph.make_extended(rgb0, ex), morph.make_extended(rgb1, ex), v, u)
-    if which:
-        fr.upload_schedule(*_schedule(w, h, which))
-    return fr
-
-
-def _layers(w, h, c, seed):
-    """values of both signs over twelve orders of magnitude, +-1e6 among them"""
-    rng = np.random.RandomState(seed)
-    a = (rng.randn(h, w, c) * 10.0 ** rng.randint(-6, 6, (h, w, c))).astype(f32)
-    a[rng.rand(h, w, c) < 0.05] = f32(1e6)
-    a[rng.rand(h, w, c) < 0.05] = f32(-1e6)
-    return a[..., 0] if c == 1 else a
+    return frame(gpu_ctx, w, h, ex, v, u, _schedule(w, h, which) if which else None)
 
 
 def _viewport(w, h, ex, name, grid):
@@ -314,15 +274,7 @@ def test_plain_form_agrees(gpu_ctx):
     hashes, case by case, the bytes and the layers of 1, 3 and 4 channels (a NaN for a NaN, bit for bit elsewhere) of both
     families under every viewport and combination of this file, on three shapes and the four fields, with and without a
     path; another one hashes the window form's"""
-    def run(mode):
-        env = dict(os.environ)
-        env.pop("VM_RENDER", None)
-        if mode:
-            env["VM_RENDER"] = mode
-        r = subprocess.run([sys.executable, "-c", _PROG], env=env, capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stderr[-2000:]
-        return [l for l in r.stdout.splitlines() if l.startswith("HASH")]
-    plain, window = run("plain"), run(None)
+    plain, window = hashes_under_render_mode(_PROG, "plain"), hashes_under_render_mode(_PROG, None)
     assert len(window) == 24
     assert plain == window, [a for a, b in zip(plain, window) if a != b]
 

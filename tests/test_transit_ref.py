@@ -2,26 +2,15 @@
 (tests/warp_ref.py), without a GPU: under the schedule (0, 1) with the linear ease it IS the uniform chain, bit for bit;
 two half frames scheduled one after the other equal the two uniform extremes away from their seam; the ramp's corner
 cases are what include/vmorph.h says; a rate tap of a constant plane is that constant to the bit."""
-import functools
 
 import numpy as np
 import pytest
 
 import transit_ref as T
+from render_cases import field as _field
 import warp_ref as R
 
 f32 = np.float32
-
-
-@functools.lru_cache(maxsize=None)
-def _field(w, h, kind, with_path):
-    rng = np.random.RandomState(41)
-    v = R.field(kind, w, h, rng)
-    u = R.path(w, h, rng) if with_path else None
-    for a in (v, u):
-        if a is not None:
-            a.setflags(write=False)
-    return v, u
 
 
 def _bits(a):

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import shutter_ref
+from render_cases import same_bits as _same
 import transit_ref
 import transit_shutter_ref as TS
 import warp_ref
@@ -34,14 +35,6 @@ def _case(w, h, ex, kind, with_path):
     e0, e1 = morph.make_extended(rgb0, ex), morph.make_extended(rgb1, ex)
     l0, l1 = rgb0.astype(f32) / f32(3), rgb1.astype(f32) / f32(7)
     return v, u, e0, e1, l0, l1
-
-
-def _same(got, want):
-    """bit for bit, a NaN for a NaN"""
-    if got.dtype != np.float32:
-        return got.dtype == want.dtype and np.array_equal(got, want)
-    ng, nw = np.isnan(got), np.isnan(want)
-    return got.shape == want.shape and np.array_equal(ng, nw) and np.array_equal(got.view(np.uint32)[~ng], want.view(np.uint32)[~nw])
 
 
 @shapes

@@ -5,15 +5,10 @@ less per CU than the uniform shutter), two without.  What the sample loop holds 
 (per_sample() in vm_shutter_tail.h is there for that), so a compiler that decides otherwise shows here and not in a
 timing.  The unit is cross-compiled with the build's own flags (no GPU) and the compiler's resource remarks are read;
 nothing is run."""
-import os
-import re
-import subprocess
-
 import pytest
 
-from videomorphing_amd import build
+from kernel_resources import unit_usage
 
-SRC = os.path.join(build.CSRC, "vm_tshutter.hip")
 LDS_PER_CU = 160 * 1024         # bytes
 WAVE_SLOTS = 32                 # per CU, four SIMDs
 WAVES_PER_WORKGROUP = 512 // 64
@@ -23,22 +18,7 @@ REGISTER_FILE, GRANULE = 512, 8     # VGPRs + AGPRs per lane and SIMD; the alloc
 @pytest.fixture(scope="module")
 def usage(tmp_path_factory):
     """{kernel: {"VGPRs": n, "ScratchSize [bytes/lane]": n, ...}} of every kernel of the unit"""
-    obj = str(tmp_path_factory.mktemp("tshres") / "vm_tshutter.o")
-    extra = [e for s, _, e in build.UNITS if s == "vm_tshutter.hip"][0]
-    r = subprocess.run([build._hipcc()] + build.COMMON + extra + ["-Rpass-analysis=kernel-resource-usage", "-c", SRC, "-o", obj],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    out, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark: (?:Function Name: (\S+)|\s+([A-Za-z][^:]*): (\d+))", line)
-        if not m:
-            continue
-        if m.group(1):
-            name = m.group(1)
-            out[name] = {}
-        elif name:
-            out[name][m.group(2).strip()] = int(m.group(3))
-    return out
+    return unit_usage("vm_tshutter.hip", tmp_path_factory.mktemp("tshres"))
 
 
 def _split(usage):

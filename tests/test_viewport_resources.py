@@ -4,37 +4,15 @@ every kernel of the unit free of scratch.  How many registers the sample loop ta
 out of it (per_sample() in the unit is there for that), so a compiler that decides otherwise shows here and not in a
 timing.  The unit is cross-compiled with the build's own flags (no GPU) and the compiler's resource remarks are read;
 nothing is run."""
-import os
-import re
-import subprocess
-
 import pytest
 
-from videomorphing_amd import build
-
-SRC = os.path.join(build.CSRC, "vm_viewport.hip")
+from kernel_resources import unit_usage
 
 
 @pytest.fixture(scope="module")
 def usage(tmp_path_factory):
     """{kernel: {"VGPRs": n, "ScratchSize [bytes/lane]": n, ...}} of every kernel of the unit"""
-    obj = str(tmp_path_factory.mktemp("vpres") / "vm_viewport.o")
-    extra = [e for s, _, e in build.UNITS if s == "vm_viewport.hip"][0]
-    assert "-ffp-contract=off" in extra
-    r = subprocess.run([build._hipcc()] + build.COMMON + extra + ["-Rpass-analysis=kernel-resource-usage", "-c", SRC, "-o", obj],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    out, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark: (?:Function Name: (\S+)|\s+([A-Za-z][^:]*): (\d+))", line)
-        if not m:
-            continue
-        if m.group(1):
-            name = m.group(1)
-            out[name] = {}
-        elif name:
-            out[name][m.group(2).strip()] = int(m.group(3))
-    return out
+    return unit_usage("vm_viewport.hip", tmp_path_factory.mktemp("vpres"))
 
 
 def test_every_instantiation_is_there_and_none_spills(usage):

@@ -5,11 +5,11 @@ import numpy as np
 import pytest
 
 import shutter_ref
+from render_cases import field as _field, same_bits as _same
 import transit_ref
 import transit_shutter_ref as TS
 import viewport_ref
 import vshutter_ref as VS
-import warp_ref
 from videomorphing_amd import transition
 from videomorphing_amd.viewport import Viewport
 
@@ -22,11 +22,6 @@ kinds = pytest.mark.parametrize("kind", KINDS)
 cases = pytest.mark.parametrize("with_path", [False, True])
 
 
-def _field(w, h, kind, with_path):
-    rng = np.random.RandomState(41)
-    return warp_ref.field(kind, w, h, rng), (warp_ref.path(w, h, rng) if with_path else None)
-
-
 def _canvases(w, h, ex):
     rng = np.random.RandomState(5)
     return [rng.randint(0, 256, (h + 2 * ex, w + 2 * ex, 4)).astype(np.uint8) for _ in range(2)]
@@ -36,15 +31,6 @@ def _layers(w, h, c, seed):
     rng = np.random.RandomState(seed)
     a = (rng.randn(h, w, c) * 10.0 ** rng.randint(-6, 6, (h, w, c))).astype(f32)
     return a[..., 0] if c == 1 else a
-
-
-def _same(a, b):
-    """bit for bit, a NaN for a NaN"""
-    a, b = np.asarray(a), np.asarray(b)
-    if a.dtype != np.float32:
-        return a.dtype == b.dtype and np.array_equal(a, b)
-    na, nb = np.isnan(a), np.isnan(b)
-    return a.shape == b.shape and np.array_equal(na, nb) and np.array_equal(a.view(np.uint32)[~na], b.view(np.uint32)[~nb])
 
 
 def _same_maps(got, want):

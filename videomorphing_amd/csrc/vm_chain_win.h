@@ -21,7 +21,7 @@
 //   VM_CHAIN_WIN_STAGE_FIELD     whether a staging copies v and u, workgroup-uniform (default: true; vm_tshutter.hip stages
 //                                the rates at every sample, v and u only where the window has moved)
 // A kernel whose output grid is not the field's (vm_viewport.hip: x, y, tiles_x and ntiles then count OUTPUT pixels and
-// tiles, w, h and rs stay the field's) defines
+// tiles, w, h and rs stay the field's) defines, by including vm_viewport_win.h,
 //   VM_CHAIN_WIN_Q_X, _Q_Y           the point q of the halfway domain the chain of output pixel (x, y) starts from
 //                                    (default: (float)x, (float)y, the pixel's centre)
 //   VM_CHAIN_WIN_ORIGIN_X, _Y        the field cell the tile's footprint begins at, from which the window is placed

@@ -15,7 +15,7 @@
 //   Algorithm/MatchingThread.cpp:22-136.
 #include "vm_internal.h"
 #include "vm_chain.h"
-#include "vm_warp.h"     // vm_render_window_form only (vm_internal.h is part of the sweep profile's source fingerprint)
+#include "vm_chain_launch.h"    // (and vm_warp.h for vm_render_window_form: vm_internal.h is part of the sweep profile's source fingerprint)
 #include <cstdlib>
 #include <cstring>
 
@@ -121,15 +121,15 @@ __global__ __launch_bounds__(256) void k_blend_v(float2 *__restrict__ dst, int d
 void vm_launch_blend_v(float2 *dst, int dpitch, const float2 *a, const float2 *b, int spitch, int w0, int h0,
                        float alpha, float beta, hipStream_t s)
 {
-    dim3 blk(64, 4), g((w0 + 63) / 64, (h0 + 3) / 4);
-    hipLaunchKernelGGL(k_blend_v, g, blk, 0, s, dst, dpitch, a, b, spitch, w0, h0, alpha, beta);
+    const Grid G = plain_grid(w0, h0);
+    hipLaunchKernelGGL(k_blend_v, G.g, G.b, 0, s, dst, dpitch, a, b, spitch, w0, h0, alpha, beta);
 }
 
 void vm_launch_upscale(float2 *dst, int w0, int h0, int dpitch, const float2 *v, int w, int h,
                        int rs, hipStream_t s)
 {
-    dim3 b(64, 4), g((w0 + 63) / 64, (h0 + 3) / 4);
-    hipLaunchKernelGGL(k_upscale, g, b, 0, s, dst, w0, h0, dpitch, v, w, h, rs);
+    const Grid G = plain_grid(w0, h0);
+    hipLaunchKernelGGL(k_upscale, G.g, G.b, 0, s, dst, w0, h0, dpitch, v, w, h, rs);
 }
 
 // a kernel that only takes time: one wave reading the constant 100 MHz counter until `ticks` have passed
@@ -156,18 +156,18 @@ void vm_launch_render(uint8_t *out, int out_pitch, int w, int h, int rs, int ex,
                       const float2 *v, const float2 *u, hipStream_t s)
 {
     if (!vm_render_window_form(rs, h)) {
-        dim3 b(64, 4), g((w + 63) / 64, (h + 3) / 4);
-        hipLaunchKernelGGL(k_render, g, b, 0, s, out, out_pitch, w, h, rs, ex, color_fa, geo_fa, color_from, ext0, ext1, v, u);
+        const Grid G = plain_grid(w, h);
+        hipLaunchKernelGGL(k_render, G.g, G.b, 0, s, out, out_pitch, w, h, rs, ex, color_fa, geo_fa, color_from, ext0, ext1, v, u);
         return;
     }
-    const int tiles_x = (w + RW - 1) / RW, ntiles = tiles_x * ((h + RH - 1) / RH);
+    struct { int tiles_x, ntiles; } T;
+    const Grid G = window_grid(T, w, h);
     const uint64_t cw = (uint64_t)w + 2 * (uint64_t)ex, ch = (uint64_t)h + 2 * (uint64_t)ex;
     const bool lean_canvas = cw * ch * 4ull < (1ull << 32) && cw < (1u << 24) && ch < (1u << 24);   // 32-bit texel offsets, 24-bit rows
-    dim3 b(RW, RH), g(((ntiles + 7) / 8) * 8);
     if (u)
-        hipLaunchKernelGGL(k_render_win<true>, g, b, 0, s, out, out_pitch, w, h, rs, ex, color_fa, geo_fa, color_from, ext0,
-                           ext1, v, u, tiles_x, ntiles, lean_canvas);
+        hipLaunchKernelGGL(k_render_win<true>, G.g, G.b, 0, s, out, out_pitch, w, h, rs, ex, color_fa, geo_fa, color_from, ext0,
+                           ext1, v, u, T.tiles_x, T.ntiles, lean_canvas);
     else
-        hipLaunchKernelGGL(k_render_win<false>, g, b, 0, s, out, out_pitch, w, h, rs, ex, color_fa, geo_fa, color_from, ext0,
-                           ext1, v, u, tiles_x, ntiles, lean_canvas);
+        hipLaunchKernelGGL(k_render_win<false>, G.g, G.b, 0, s, out, out_pitch, w, h, rs, ex, color_fa, geo_fa, color_from, ext0,
+                           ext1, v, u, T.tiles_x, T.ntiles, lean_canvas);
 }

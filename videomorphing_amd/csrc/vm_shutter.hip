@@ -18,8 +18,8 @@
 // window holds exact texels, the bits cannot change -- which is the usual case for a short shutter (VM_SHUTTER_SKIP=0
 // restages always: the A/B of profiles/shutter.md).
 #include "vm_chain.h"
+#include "vm_chain_launch.h"
 #include "vm_shutter_tail.h"
-#include "vm_warp.h"     // vm_render_window_form
 
 #ifndef VM_SHUTTER_SKIP
 #define VM_SHUTTER_SKIP 1
@@ -29,12 +29,6 @@ namespace {
 
 using namespace vm_chain;
 
-__device__ __forceinline__ float sample_time(float open, float close, int s, float n)
-{
-    const float f = sample_fraction(s, n);
-    return fminf(fmaxf(open + (close - open) * f, 0.0f), 1.0f);
-}
-
 // the plain form: one pixel per thread, every tap a global gather
 template <int C> __global__ __launch_bounds__(256) void k_shutter(const VmShutter A)
 {
@@ -43,7 +37,7 @@ template <int C> __global__ __launch_bounds__(256) void k_shutter(const VmShutte
     int x = 0, y = 0;
     for (int s = 0; s < A.samples; ++s) {
         Landing L;
-        if (!chain_plain<false>(A.w, A.h, A.rs, sample_time(A.geo_open, A.geo_close, s, n), A.vf, A.uf, nullptr, x, y, L))
+        if (!chain_plain<false>(A.w, A.h, A.rs, sample_time<true>(A.geo_open, A.geo_close, s, n), A.vf, A.uf, nullptr, x, y, L))
             return;
         add_sample<C>(A, L, per_sample(A.color_fa), acc);
     }
@@ -52,6 +46,7 @@ template <int C> __global__ __launch_bounds__(256) void k_shutter(const VmShutte
 
 // whether sample s stages the window at (ox, oy), for the whole workgroup: not if the sample before left it there; the
 // barrier before a restaging is taken here (every tap of the sample before has been served)
+// (not restage<false> of vm_shutter_tail.h: its `moved`, formed before the early return, moves all ten window kernels)
 __device__ __forceinline__ bool restage(int s, int ox, int oy, int &at_x, int &at_y)
 {
     ox = __builtin_amdgcn_readfirstlane(ox); oy = __builtin_amdgcn_readfirstlane(oy);
@@ -80,7 +75,7 @@ template <bool HAS_U, int C> __global__ __launch_bounds__(RW * RH) void k_shutte
         const int w = per_sample(A.w), h = per_sample(A.h), tiles_x = per_sample(A.tiles_x);
         const float n = (float)per_sample(A.samples);
         // (geo_open alone: close - open is then formed per sample, and close is read from its scalar register)
-        const float geo_fa = sample_time(per_sample(A.geo_open), A.geo_close, s, n);
+        const float geo_fa = sample_time<true>(per_sample(A.geo_open), A.geo_close, s, n);
 #include "vm_chain_win.h"
         add_sample<C>(A, L, per_sample(A.color_fa), acc);
         if (s == A.samples - 1)
@@ -90,32 +85,13 @@ template <bool HAS_U, int C> __global__ __launch_bounds__(RW * RH) void k_shutte
 #undef VM_CHAIN_WIN_NO_PIXEL
 #undef VM_CHAIN_WIN_STAGE
 
-template <int C> void launch(VmShutter &A, hipStream_t s)
-{
-    if (!vm_render_window_form(A.rs, A.h)) {
-        dim3 b(64, 4), g((A.w + 63) / 64, (A.h + 3) / 4);
-        hipLaunchKernelGGL((k_shutter<C>), g, b, 0, s, A);
-        return;
-    }
-    A.tiles_x = (A.w + RW - 1) / RW;
-    A.ntiles = A.tiles_x * ((A.h + RH - 1) / RH);
-    dim3 b(RW, RH), g(((A.ntiles + 7) / 8) * 8);
-    if (A.uf)
-        hipLaunchKernelGGL((k_shutter_win<true, C>), g, b, 0, s, A);
-    else
-        hipLaunchKernelGGL((k_shutter_win<false, C>), g, b, 0, s, A);
-}
-
 } // namespace
 
 void vm_launch_shutter(const VmShutter &S, hipStream_t s)
 {
     VmShutter A = S;
-    switch (A.channels) {
-    case 1: launch<1>(A, s); break;
-    case 2: launch<2>(A, s); break;
-    case 3: launch<3>(A, s); break;
-    case 4: launch<4>(A, s); break;
-    default: launch<CANVAS>(A, s); break;
-    }
+    for_channels(A.channels, [&](auto c) {
+        constexpr int C = decltype(c)::value;
+        launch_form(vm_render_window_form(A.rs, A.h), A.w, A.h, A, k_shutter<C>, k_shutter_win<true, C>, k_shutter_win<false, C>, s);
+    });
 }

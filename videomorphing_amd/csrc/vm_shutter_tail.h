@@ -1,6 +1,7 @@
-// vm_shutter_tail.h -- what the sample loops of a shutter share, for vm_shutter.hip and
-// vm_tshutter.hip: the fraction of the exposure at which sample s stands, the sum of the samples' colours in registers
-// with the uniform tails' taps, and the one store of their mean.
+// vm_shutter_tail.h -- what the sample loops share, for vm_shutter.hip, vm_tshutter.hip,
+// vm_viewport.hip and vm_vshutter.hip: the fraction of the exposure at which sample s stands, the sum of the samples'
+// colours in registers with the uniform tails' taps, and the one store of their mean; for the three shutters also the
+// time of sample s and the rule by which the window form restages its window from one time to the next.
 #ifndef VM_SHUTTER_TAIL_H
 #define VM_SHUTTER_TAIL_H
 
@@ -15,6 +16,30 @@ template <int C> constexpr int NACC = C == CANVAS ? 3 : C;      // accumulators 
 
 // f = ((float)s + 0.5f) / (float)N, correctly rounded
 __device__ __forceinline__ float sample_fraction(int s, float n) { return __fdiv_rn((float)s + 0.5f, n); }
+
+// t_s = open + (close - open) * f.  CLAMP: to [0, 1], where it is the chain's geo_fa (a shutter across t = 0 or 1 holds
+// still outside); not where ramp clamps per texel (a shutter under a schedule)
+template <bool CLAMP> __device__ __forceinline__ float sample_time(float open, float close, int s, float n)
+{
+    const float t = open + (close - open) * sample_fraction(s, n);
+    return CLAMP ? fminf(fmaxf(t, 0.0f), 1.0f) : t;
+}
+
+// Whether time sample s stages the window at (ox, oy), for the whole workgroup, behind a barrier from the second sample on
+// (every tap of the sample before has been served).  `moved`: whether the sample before left the window elsewhere.  Not
+// ALWAYS (a uniform shutter): no restaging where it has not moved -- the window holds exact texels, the bits cannot
+// change.  ALWAYS (under a schedule, for the rates): `moved` says whether v and u are staged with them.
+template <bool ALWAYS> __device__ __forceinline__ bool restage(int s, int ox, int oy, int &at_x, int &at_y, bool &moved)
+{
+    ox = __builtin_amdgcn_readfirstlane(ox); oy = __builtin_amdgcn_readfirstlane(oy);
+    moved = !(s && ox == at_x && oy == at_y);
+    if (!ALWAYS && !moved)
+        return false;
+    if (s)
+        __syncthreads();
+    at_x = ox; at_y = oy;
+    return true;
+}
 
 // A uniform value the sample loop takes from its scalar register anew in every round.  Hoisted out of the loop, what is
 // derived from it -- (float)w, (float)N, 1 - color_fa, the tile's pixel, the first tap's indices and weights: some twenty

@@ -22,21 +22,16 @@
 //
 // The window form restages (G, K) at every sample -- G_s has changed even where the window has not moved -- after a
 // barrier from the second sample on (every tap of the sample before has been served; a thread without a pixel stays in
-// the loop for it), and v and u only where the window's origin has moved, as vm_shutter.hip does.
+// the loop for it), and v and u only where the window's origin has moved (restage<true> of vm_shutter_tail.h).
 #include "vm_chain.h"
+#include "vm_chain_launch.h"
 #include "vm_ramp.h"
 #include "vm_shutter_tail.h"
 #include "vm_tshutter.h"
-#include "vm_warp.h"     // vm_render_window_form, vm_launch_rates
 
 namespace {
 
 using namespace vm_chain;
-
-__device__ __forceinline__ float sample_time(float open, float close, int s, float n)
-{
-    return open + (close - open) * sample_fraction(s, n);
-}
 
 // the plain form: one pixel per thread, every tap a global gather, every rate texel ramped where it is read
 template <int C> __global__ __launch_bounds__(256) void k_tblur(const VmTShutter A)
@@ -45,7 +40,7 @@ template <int C> __global__ __launch_bounds__(256) void k_tblur(const VmTShutter
     float acc[NACC<C>] = {};
     int x = 0, y = 0;
     for (int s = 0; s < A.samples; ++s) {
-        const Ramped rates{A.sched_geo, A.rates, sample_time(A.t_open, A.t_close, s, n), A.ease};
+        const Ramped rates{A.sched_geo, A.rates, sample_time<false>(A.t_open, A.t_close, s, n), A.ease};
         Landing L;
         if (!chain_plain<true>(A.w, A.h, A.rs, 0.0f, A.vf, A.uf, rates, x, y, L))
             return;
@@ -54,24 +49,11 @@ template <int C> __global__ __launch_bounds__(256) void k_tblur(const VmTShutter
     store_mean<C>(A, x, y, acc, n);
 }
 
-// Sample s stages its rates at (ox, oy) always, for the whole workgroup, behind a barrier from the second sample on
-// (every tap of the sample before has been served); `moved`: whether v and u are staged with them -- not if the sample
-// before left the window there.
-__device__ __forceinline__ bool restage(int s, int ox, int oy, int &at_x, int &at_y, bool &moved)
-{
-    ox = __builtin_amdgcn_readfirstlane(ox); oy = __builtin_amdgcn_readfirstlane(oy);
-    moved = !(s && ox == at_x && oy == at_y);
-    if (s)
-        __syncthreads();
-    at_x = ox; at_y = oy;
-    return true;
-}
-
 // the window form.  The chain's statements stand in the sample loop, as in k_shutter_win: a thread without a pixel goes
 // on to the next sample's barriers, only the workgroup past the last tile leaves, and the one store stands behind the
 // last sample inside the loop.
 #define VM_CHAIN_WIN_NO_PIXEL continue
-#define VM_CHAIN_WIN_STAGE(ox, oy) restage(s, ox, oy, at_x, at_y, moved)
+#define VM_CHAIN_WIN_STAGE(ox, oy) restage<true>(s, ox, oy, at_x, at_y, moved)
 #define VM_CHAIN_WIN_STAGE_FIELD moved
 template <bool HAS_U, int C> __global__ __launch_bounds__(RW * RH) void k_tblur_win(const VmTShutter A)
 {
@@ -85,7 +67,7 @@ template <bool HAS_U, int C> __global__ __launch_bounds__(RW * RH) void k_tblur_
     for (int s = 0; s < A.samples; ++s) {
         const int w = per_sample(A.w), h = per_sample(A.h), tiles_x = per_sample(A.tiles_x);
         const float n = (float)per_sample(A.samples);
-        const Ramped rates{A.sched_geo, A.rates, sample_time(per_sample(A.t_open), A.t_close, s, n), A.ease};
+        const Ramped rates{A.sched_geo, A.rates, sample_time<false>(per_sample(A.t_open), A.t_close, s, n), A.ease};
 #include "vm_chain_win.h"
         add_sample<C>(A, L, L.k, acc);
         if (s == A.samples - 1)
@@ -96,38 +78,14 @@ template <bool HAS_U, int C> __global__ __launch_bounds__(RW * RH) void k_tblur_
 #undef VM_CHAIN_WIN_STAGE
 #undef VM_CHAIN_WIN_STAGE_FIELD
 
-template <int C> void launch(VmTShutter &A, hipStream_t s)
-{
-    if (!vm_render_window_form(A.rs, A.h)) {
-        dim3 b(64, 4), g((A.w + 63) / 64, (A.h + 3) / 4);
-        hipLaunchKernelGGL((k_tblur<C>), g, b, 0, s, A);
-        return;
-    }
-    A.tiles_x = (A.w + RW - 1) / RW;
-    A.ntiles = A.tiles_x * ((A.h + RH - 1) / RH);
-    dim3 b(RW, RH), g(((A.ntiles + 7) / 8) * 8);
-    if (A.uf)
-        hipLaunchKernelGGL((k_tblur_win<true, C>), g, b, 0, s, A);
-    else
-        hipLaunchKernelGGL((k_tblur_win<false, C>), g, b, 0, s, A);
-}
-
 } // namespace
 
 void vm_launch_tshutter(const VmTShutter &S, hipStream_t s)
 {
     VmTShutter A = S;
-    // K into the .y of the rate plane (its .x, the geometry at t_color, is not read)
-    VmTransition T{};
-    T.w = A.w; T.h = A.h; T.rs = A.rs;
-    T.t = A.t_color; T.ease = A.ease;
-    T.sched_geo = A.sched_geo; T.sched_color = A.sched_color; T.rates = A.rates;
-    vm_launch_rates(T, s);
-    switch (A.channels) {
-    case 1: launch<1>(A, s); break;
-    case 2: launch<2>(A, s); break;
-    case 3: launch<3>(A, s); break;
-    case 4: launch<4>(A, s); break;
-    default: launch<CANVAS>(A, s); break;
-    }
+    launch_colour_rates(A, s);
+    for_channels(A.channels, [&](auto c) {
+        constexpr int C = decltype(c)::value;
+        launch_form(vm_render_window_form(A.rs, A.h), A.w, A.h, A, k_tblur<C>, k_tblur_win<true, C>, k_tblur_win<false, C>, s);
+    });
 }

@@ -19,29 +19,14 @@
 // tile taps it, and no barrier follows the first.  A tap outside the window takes the global path, so the placement
 // cannot change a bit.  Larger steps (a proxy, a thumbnail) run the plain form.
 #include "vm_chain.h"
+#include "vm_chain_launch.h"
 #include "vm_shutter_tail.h"
 #include "vm_viewport.h"
-#include "vm_warp.h"     // vm_render_window_form
+#include "vm_viewport_win.h"        // sample_q, cell_at, Out, next_sub, and the hooks of the window form
 
 namespace {
 
 using namespace vm_chain;
-
-// q of sub-sample i of n along one axis of output pixel X: the viewport's corner c0 and step
-__device__ __forceinline__ float sample_q(float c0, float step, int X, int i, float n)
-{
-    return (c0 + ((float)X + sample_fraction(i, n)) * step) - 0.5f;
-}
-
-// the field cell nearest output edge `edge` (a tile's centre) along one axis; a corner far outside the field is cut off
-// where the cell still is an int (the window then holds the field's clamped edge, or nothing useful)
-__device__ __forceinline__ int cell_at(float c0, float step, int edge)
-{
-    return (int)rintf(__builtin_amdgcn_fmed3f((c0 + (float)edge * step) - 0.5f, -1e6f, 1e6f));
-}
-
-// where store_mean puts pixel (x, y): the tight output grid
-struct Out { int w; uint8_t *rgb; float *out; };
 
 // the plain form: one output pixel per thread, every tap a global gather; any step
 template <int C> __global__ __launch_bounds__(256) void k_viewport(const VmViewport A)
@@ -66,13 +51,6 @@ template <int C> __global__ __launch_bounds__(256) void k_viewport(const VmViewp
 // after it tap what is there.  x, y, tiles_x and ntiles count output pixels and tiles; (x, y) belong to the chain's
 // statements, so the one store stands behind the last sample inside the loop.
 #define VM_CHAIN_WIN_STAGE(ox, oy) (s == 0)
-#define VM_CHAIN_WIN_Q_X sample_q(per_sample(A.x0), per_sample(A.step_x), x, si, (float)per_sample(A.nx))
-#define VM_CHAIN_WIN_Q_Y sample_q(per_sample(A.y0), per_sample(A.step_y), y, sj, (float)per_sample(A.ny))
-#define VM_CHAIN_WIN_ORIGIN_X (cell_at(A.x0, A.step_x, bx + RW / 2) - RW / 2)
-#define VM_CHAIN_WIN_ORIGIN_Y (cell_at(A.y0, A.step_y, by + RH / 2) - RH / 2)
-#define VM_CHAIN_WIN_CENTRE_X min(max(cell_at(A.x0, A.step_x, bx + RW / 2), 0), wm1)
-#define VM_CHAIN_WIN_CENTRE_Y min(max(cell_at(A.y0, A.step_y, by + RH / 2), 0), hm1)
-#define VM_CHAIN_WIN_OUTSIDE x >= per_sample(A.out_w) || y >= per_sample(A.out_h)
 template <bool HAS_U, int C> __global__ __launch_bounds__(RW * RH) void k_viewport_win(const VmViewport A)
 {
     constexpr bool RATES = false;       // (a viewport under a transition schedule or over a shutter is vm_vshutter.hip)
@@ -89,48 +67,22 @@ template <bool HAS_U, int C> __global__ __launch_bounds__(RW * RH) void k_viewpo
         add_sample<C>(A, L, per_sample(A.color_fa), acc);
         if (s == samples - 1)
             store_mean<C>(Out{A.out_w, A.rgb, A.out}, x, y, acc, (float)per_sample(samples));
-        if (++si == A.nx) {
+        if (++si == A.nx) {     // (not next_sub of vm_viewport_win.h: behind a function call all ten window kernels move)
             si = 0;
             ++sj;
         }
     }
 }
 #undef VM_CHAIN_WIN_STAGE
-#undef VM_CHAIN_WIN_Q_X
-#undef VM_CHAIN_WIN_Q_Y
-#undef VM_CHAIN_WIN_ORIGIN_X
-#undef VM_CHAIN_WIN_ORIGIN_Y
-#undef VM_CHAIN_WIN_CENTRE_X
-#undef VM_CHAIN_WIN_CENTRE_Y
-#undef VM_CHAIN_WIN_OUTSIDE
-
-template <int C> void launch(VmViewport &A, hipStream_t s)
-{
-    // (!(step <= 1) rather than step > 1: anything the host let through that is no step up to 1 is plain)
-    if (!vm_render_window_form(A.rs, A.h) || !(A.step_x <= 1.0f) || !(A.step_y <= 1.0f)) {
-        dim3 b(64, 4), g((A.out_w + 63) / 64, (A.out_h + 3) / 4);
-        hipLaunchKernelGGL((k_viewport<C>), g, b, 0, s, A);
-        return;
-    }
-    A.tiles_x = (A.out_w + RW - 1) / RW;
-    A.ntiles = A.tiles_x * ((A.out_h + RH - 1) / RH);
-    dim3 b(RW, RH), g(((A.ntiles + 7) / 8) * 8);
-    if (A.uf)
-        hipLaunchKernelGGL((k_viewport_win<true, C>), g, b, 0, s, A);
-    else
-        hipLaunchKernelGGL((k_viewport_win<false, C>), g, b, 0, s, A);
-}
+#include "vm_viewport_win.h"        // (the hooks leave)
 
 } // namespace
 
 void vm_launch_viewport(const VmViewport &V, hipStream_t s)
 {
     VmViewport A = V;
-    switch (A.channels) {
-    case 1: launch<1>(A, s); break;
-    case 2: launch<2>(A, s); break;
-    case 3: launch<3>(A, s); break;
-    case 4: launch<4>(A, s); break;
-    default: launch<CANVAS>(A, s); break;
-    }
+    for_channels(A.channels, [&](auto c) {
+        constexpr int C = decltype(c)::value;
+        launch_form(viewport_window_form(A), A.out_w, A.out_h, A, k_viewport<C>, k_viewport_win<true, C>, k_viewport_win<false, C>, s);
+    });
 }

@@ -20,28 +20,22 @@
 // layers.  With T = 1 that is vm_viewport.hip's result, with {0, 0, 1, 1, w, h, 1, 1} vm_shutter.hip's or vm_tshutter.hip's,
 // bit for bit.
 //
-// The window form runs for steps up to 1, as in vm_viewport.hip.  Its window belongs to the tile AND to the time sample:
+// The window form runs for steps up to 1, as in vm_viewport.hip (viewport_window_form, vm_chain_launch.h).  Its window belongs to the tile AND to the time sample:
 // sub-sample 0 of a time sample alone may stage, by the shutters' rules -- a barrier before a restaging from the second
 // time sample on (every tap of every sub-sample of the time before has been served); uniform: no restaging where the
 // origin has not moved; scheduled: (G, K) at every time sample, v and u only where the origin has moved -- and the
 // sub-samples after it tap what is there, with no barrier.  A thread without a pixel stays in both loops for the
 // barriers of the time samples to come; only the workgroup past the last tile leaves.
 #include "vm_chain.h"
+#include "vm_chain_launch.h"
 #include "vm_ramp.h"
-#include "vm_shutter_tail.h"
+#include "vm_shutter_tail.h"        // sample_time, restage
+#include "vm_viewport_win.h"        // sample_q, cell_at, Out, next_sub, and the hooks of the window form
 #include "vm_vshutter.h"
-#include "vm_warp.h"     // vm_render_window_form, vm_launch_rates
 
 namespace {
 
 using namespace vm_chain;
-
-// t_tau: clamped where it is the chain's geo_fa (vm_shutter.hip), not where ramp clamps per texel (vm_tshutter.hip)
-template <bool RATES> __device__ __forceinline__ float sample_time(float open, float close, int ts, float n)
-{
-    const float t = open + (close - open) * sample_fraction(ts, n);
-    return RATES ? t : fminf(fmaxf(t, 0.0f), 1.0f);
-}
 
 // what the chain takes in the place of its rate plane at time t: the geometry schedule ramped where it is read, or nothing
 template <bool RATES> __device__ __forceinline__ auto rates_at_time(const VmVShutter &A, float t)
@@ -52,22 +46,6 @@ template <bool RATES> __device__ __forceinline__ auto rates_at_time(const VmVShu
         return (const float2 *)nullptr;
 }
 
-// q of sub-sample i of n along one axis of output pixel X: the viewport's corner c0 and step (vm_viewport.hip's)
-__device__ __forceinline__ float sample_q(float c0, float step, int X, int i, float n)
-{
-    return (c0 + ((float)X + sample_fraction(i, n)) * step) - 0.5f;
-}
-
-// the field cell nearest output edge `edge` (a tile's centre) along one axis; a corner far outside the field is cut off
-// where the cell still is an int (vm_viewport.hip's)
-__device__ __forceinline__ int cell_at(float c0, float step, int edge)
-{
-    return (int)rintf(__builtin_amdgcn_fmed3f((c0 + (float)edge * step) - 0.5f, -1e6f, 1e6f));
-}
-
-// where store_mean puts pixel (x, y): the tight output grid
-struct Out { int w; uint8_t *rgb; float *out; };
-
 // the plain form: one output pixel per thread, every tap a global gather, every rate texel ramped where it is read; any step
 template <int C, bool RATES> __global__ __launch_bounds__(256) void k_vblur(const VmVShutter A)
 {
@@ -77,7 +55,7 @@ template <int C, bool RATES> __global__ __launch_bounds__(256) void k_vblur(cons
     const float nt = (float)A.samples, nx = (float)A.nx, ny = (float)A.ny;
     float acc[NACC<C>] = {};
     for (int ts = 0; ts < A.samples; ++ts) {
-        const float t = sample_time<RATES>(A.t_open, A.t_close, ts, nt);
+        const float t = sample_time<!RATES>(A.t_open, A.t_close, ts, nt);     // clamped where it is the chain's geo_fa
         const auto rates = rates_at_time<RATES>(A, t);
         for (int j = 0; j < A.ny; ++j)
             for (int i = 0; i < A.nx; ++i) {
@@ -90,44 +68,14 @@ template <int C, bool RATES> __global__ __launch_bounds__(256) void k_vblur(cons
     store_mean<C>(Out{A.out_w, A.rgb, A.out}, x, y, acc, (float)(A.samples * A.nx * A.ny));
 }
 
-// Whether sub-sample 0 of time sample ts stages the window at (ox, oy), for the whole workgroup, behind a barrier from the
-// second time sample on (every tap of the time before has been served).  Uniform: not if the time before left the window
-// there.  Scheduled: always, for the rates; `moved`: whether v and u are staged with them.
-template <bool RATES> __device__ __forceinline__ bool restage(int ts, int ox, int oy, int &at_x, int &at_y, bool &moved)
-{
-    ox = __builtin_amdgcn_readfirstlane(ox); oy = __builtin_amdgcn_readfirstlane(oy);
-    moved = !(ts && ox == at_x && oy == at_y);
-    if (!RATES && !moved)
-        return false;
-    if (ts)
-        __syncthreads();
-    at_x = ox; at_y = oy;
-    return true;
-}
-
-// the next sub-sample s = sj * nx + si
-__device__ __forceinline__ void next_sub(int &si, int &sj, int nx)
-{
-    if (++si == nx) {
-        si = 0;
-        ++sj;
-    }
-}
-
-// the window form.  The chain's statements stand in the inner loop with the shutters' hooks and the viewport's: a thread
+// the window form.  The chain's statements stand in the inner loop with the shutters' hooks and the viewport's
+// (vm_viewport_win.h); sub-sample 0 of a time sample alone may stage, by restage<RATES> of vm_shutter_tail.h: a thread
 // without a pixel goes on through both loops (the counters are kept in the loop's own increment, which `continue` reaches)
 // to the barriers of the time samples to come, only the workgroup past the last tile leaves, and the one store stands
 // behind the last sample inside the loop.  x, y, tiles_x and ntiles count output pixels and tiles.
 #define VM_CHAIN_WIN_NO_PIXEL continue
 #define VM_CHAIN_WIN_STAGE(ox, oy) (s == 0 && restage<RATES>(ts, ox, oy, at_x, at_y, moved))
 #define VM_CHAIN_WIN_STAGE_FIELD moved
-#define VM_CHAIN_WIN_Q_X sample_q(per_sample(A.x0), per_sample(A.step_x), x, si, (float)per_sample(A.nx))
-#define VM_CHAIN_WIN_Q_Y sample_q(per_sample(A.y0), per_sample(A.step_y), y, sj, (float)per_sample(A.ny))
-#define VM_CHAIN_WIN_ORIGIN_X (cell_at(A.x0, A.step_x, bx + RW / 2) - RW / 2)
-#define VM_CHAIN_WIN_ORIGIN_Y (cell_at(A.y0, A.step_y, by + RH / 2) - RH / 2)
-#define VM_CHAIN_WIN_CENTRE_X min(max(cell_at(A.x0, A.step_x, bx + RW / 2), 0), wm1)
-#define VM_CHAIN_WIN_CENTRE_Y min(max(cell_at(A.y0, A.step_y, by + RH / 2), 0), hm1)
-#define VM_CHAIN_WIN_OUTSIDE x >= per_sample(A.out_w) || y >= per_sample(A.out_h)
 template <bool HAS_U, int C, bool RATES> __global__ __launch_bounds__(RW * RH) void k_vblur_win(const VmVShutter A)
 {
     const int rs = A.rs, ntiles = A.ntiles;
@@ -140,7 +88,7 @@ template <bool HAS_U, int C, bool RATES> __global__ __launch_bounds__(RW * RH) v
         int si = 0, sj = 0;
         for (int s = 0; s < subs; ++s, next_sub(si, sj, A.nx)) {
             const int w = per_sample(A.w), h = per_sample(A.h), tiles_x = per_sample(A.tiles_x);
-            const float t = sample_time<RATES>(per_sample(A.t_open), A.t_close, ts, (float)per_sample(A.samples));
+            const float t = sample_time<!RATES>(per_sample(A.t_open), A.t_close, ts, (float)per_sample(A.samples));
             const float geo_fa = RATES ? 0.0f : t;      // (under RATES every round takes its own g)
             const auto rates = rates_at_time<RATES>(A, t);
 #include "vm_chain_win.h"
@@ -153,40 +101,14 @@ template <bool HAS_U, int C, bool RATES> __global__ __launch_bounds__(RW * RH) v
 #undef VM_CHAIN_WIN_NO_PIXEL
 #undef VM_CHAIN_WIN_STAGE
 #undef VM_CHAIN_WIN_STAGE_FIELD
-#undef VM_CHAIN_WIN_Q_X
-#undef VM_CHAIN_WIN_Q_Y
-#undef VM_CHAIN_WIN_ORIGIN_X
-#undef VM_CHAIN_WIN_ORIGIN_Y
-#undef VM_CHAIN_WIN_CENTRE_X
-#undef VM_CHAIN_WIN_CENTRE_Y
-#undef VM_CHAIN_WIN_OUTSIDE
-
-template <int C, bool RATES> void launch(VmVShutter &A, hipStream_t s)
-{
-    // (!(step <= 1) rather than step > 1: anything the host let through that is no step up to 1 is plain)
-    if (!vm_render_window_form(A.rs, A.h) || !(A.step_x <= 1.0f) || !(A.step_y <= 1.0f)) {
-        dim3 b(64, 4), g((A.out_w + 63) / 64, (A.out_h + 3) / 4);
-        hipLaunchKernelGGL((k_vblur<C, RATES>), g, b, 0, s, A);
-        return;
-    }
-    A.tiles_x = (A.out_w + RW - 1) / RW;
-    A.ntiles = A.tiles_x * ((A.out_h + RH - 1) / RH);
-    dim3 b(RW, RH), g(((A.ntiles + 7) / 8) * 8);
-    if (A.uf)
-        hipLaunchKernelGGL((k_vblur_win<true, C, RATES>), g, b, 0, s, A);
-    else
-        hipLaunchKernelGGL((k_vblur_win<false, C, RATES>), g, b, 0, s, A);
-}
+#include "vm_viewport_win.h"        // (the hooks leave)
 
 template <bool RATES> void launch_channels(VmVShutter &A, hipStream_t s)
 {
-    switch (A.channels) {
-    case 1: launch<1, RATES>(A, s); break;
-    case 2: launch<2, RATES>(A, s); break;
-    case 3: launch<3, RATES>(A, s); break;
-    case 4: launch<4, RATES>(A, s); break;
-    default: launch<CANVAS, RATES>(A, s); break;
-    }
+    for_channels(A.channels, [&](auto c) {
+        constexpr int C = decltype(c)::value;
+        launch_form(viewport_window_form(A), A.out_w, A.out_h, A, k_vblur<C, RATES>, k_vblur_win<true, C, RATES>, k_vblur_win<false, C, RATES>, s);
+    });
 }
 
 } // namespace
@@ -198,11 +120,6 @@ void vm_launch_vshutter(const VmVShutter &S, hipStream_t s)
         launch_channels<false>(A, s);
         return;
     }
-    // K into the .y of the rate plane (its .x, the geometry at t_color, is not read)
-    VmTransition T{};
-    T.w = A.w; T.h = A.h; T.rs = A.rs;
-    T.t = A.t_color; T.ease = A.ease;
-    T.sched_geo = A.sched_geo; T.sched_color = A.sched_color; T.rates = A.rates;
-    vm_launch_rates(T, s);
+    launch_colour_rates(A, s);
     launch_channels<true>(A, s);
 }

@@ -24,6 +24,7 @@
 // in the tail.  The window form stages (G, K) in a third LDS window beside v and u; nothing of the rates is left in
 // the uniform instantiations (RATES == false).  A third tail, CANVAS, is the renderer's own: RGB8 from the extended canvases.
 #include "vm_chain.h"
+#include "vm_chain_launch.h"
 #include "vm_layer_tap.h"
 #include "vm_ramp.h"
 #include "vm_warp.h"
@@ -133,34 +134,13 @@ template <bool HAS_U, int C, bool RATES> __global__ __launch_bounds__(RW * RH) v
     warp_tail<C, RATES>(A, x, y, L);
 }
 
-template <int C, bool RATES> void launch(VmWarpArgs &A, bool window, hipStream_t s)
-{
-    if (!window) {
-        dim3 b(64, 4), g((A.w + 63) / 64, (A.h + 3) / 4);
-        hipLaunchKernelGGL((k_warp<C, RATES>), g, b, 0, s, A);
-        return;
-    }
-    A.tiles_x = (A.w + RW - 1) / RW;
-    A.ntiles = A.tiles_x * ((A.h + RH - 1) / RH);
-    dim3 b(RW, RH), g(((A.ntiles + 7) / 8) * 8);
-    if (A.uf)
-        hipLaunchKernelGGL((k_warp_win<true, C, RATES>), g, b, 0, s, A);
-    else
-        hipLaunchKernelGGL((k_warp_win<false, C, RATES>), g, b, 0, s, A);
-}
-
+// (the canvas tail exists under RATES only: the uniform renderer is vm_render.hip)
 template <bool RATES> void launch_tail(VmWarpArgs &A, int channels, bool window, hipStream_t s)
 {
-    switch (channels) {
-    case 0: launch<0, RATES>(A, window, s); break;
-    case 1: launch<1, RATES>(A, window, s); break;
-    case 2: launch<2, RATES>(A, window, s); break;
-    case 3: launch<3, RATES>(A, window, s); break;
-    case 4: launch<4, RATES>(A, window, s); break;
-    default:
-        if constexpr (RATES) launch<CANVAS, RATES>(A, window, s);
-        break;
-    }
+    for_channels<true, RATES>(channels, [&](auto c) {
+        constexpr int C = decltype(c)::value;
+        launch_form(window, A.w, A.h, A, k_warp<C, RATES>, k_warp_win<true, C, RATES>, k_warp_win<false, C, RATES>, s);
+    });
 }
 
 } // namespace
@@ -181,8 +161,8 @@ void vm_launch_warp(int w, int h, int rs, float color_fa, float geo_fa, int colo
 
 void vm_launch_rates(const VmTransition &T, hipStream_t s)
 {
-    dim3 b(64, 4), g((T.w + 63) / 64, (T.h + 3) / 4);
-    hipLaunchKernelGGL(k_rates, g, b, 0, s, T.rates, T.sched_geo, T.sched_color, T.w, T.h, T.rs, T.t, T.ease);
+    const Grid G = plain_grid(T.w, T.h);
+    hipLaunchKernelGGL(k_rates, G.g, G.b, 0, s, T.rates, T.sched_geo, T.sched_color, T.w, T.h, T.rs, T.t, T.ease);
 }
 
 void vm_launch_transition(const VmTransition &T, hipStream_t s)
