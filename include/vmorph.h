@@ -466,12 +466,38 @@ int  vm_frame_sampling_maps(vm_frame *f, float geo_fa, float *map0_xy, float *ma
 int  vm_frame_upload_layers(vm_frame *f, int channels, const float *layer0, const float *layer1, int pitch_floats);
 /* The layers through the morph (the chain of render.cu:16-60, UI/RenderWidget.cpp:229-266): layer k is sampled at
  * (mapk.x + 0.5f, mapk.y + 0.5f) with the field taps' bilinear expression, per channel (1-a)(1-b) t00 + a(1-b) t10 +
- * (1-a)b t01 + ab t11 from left to right, indices clamped to the layer: no Poisson extension, the edge texel repeats
- * (flags of vm_frame_sampling_maps tell where).  color_from 0: c0, 2: c1, 1: c0 * (1 - color_fa) + c1 * color_fa in float32.
+ * (1-a)b t01 + ab t11 from left to right, indices clamped to the layer: the edge texel repeats (flags of
+ * vm_frame_sampling_maps tell where) unless the layers have been extended (vm_frame_extend_layers, below).  color_from 0: c0, 2: c1, 1: c0 * (1 - color_fa) + c1 * color_fa in float32.
  * out: (h, w, channels) floats, pitch in floats (0 = tight).  VM_E_STATE on a frame that holds no layers. */
 int  vm_render_layers(vm_frame *f, float color_fa, float geo_fa, int color_from, float *out, int pitch_floats);
 /* same (render.cu:16-60, UI/RenderWidget.cpp:229-266), output left on the device (for timing) */
 int  vm_render_layers_dev(vm_frame *f, float color_fa, float geo_fa, int color_from, float *elapsed_ms);
+/* ---- the layers past the image edge -----------------------------------------
+ * The layers extended as the canvases are (PoissonExt.cpp:49-362): per side a (ch, cw, channels) float32 canvas, cw = w +
+ * 2 ex, ch = h + 2 ex, the tight layer at (ex, ex); every cell outside the image filled by following the halfway field
+ * into the OTHER side's tight layer (the RGB fill's chain; the bilinear value unrounded; a landing point outside
+ * [0, w) x [0, h) leaves a hole); then the screened Poisson system of the RGB path on the image's outermost ring and the
+ * cells outside it, holes starting from 0, per group of up to three channels through the solver of vm_poisson_extend_frames
+ * (both sides of a group one batch; vm_set_reduction applies).  The solution is pasted as it is, neither clamped nor
+ * rounded; the cells inside the ring keep their bits.  From then on EVERY layer render call of this header samples the
+ * canvases at ((map + ex) + 0.5f) -- the renderer's own + ex + 0.5f -- instead of the tight layers at (map + 0.5f); flags and
+ * the maps keep their meaning.  iters / rel_res: two entries per channel group ((channels + 2) / 3 groups), side 1 then side
+ * 2; either may be NULL.  A group whose right-hand side is all zeros (an empty matte) extends to zeros without a solve
+ * (0 iterations).  VM_E_STATE without layers or with ex == 0; VM_E_INVALID for tol <= 0 or max_it < 1; VM_E_NUMERIC for a
+ * residual above tol or a right-hand side that is not finite -- the frame then renders its tight layers.  v, the path, the
+ * RGB canvases and the schedule are not touched.  vm_frame_upload_layers drops the extension (extend again);
+ * vm_frame_set_v_* and vm_frame_upload leave it as it is, as they leave the RGB canvases. */
+int  vm_frame_extend_layers(vm_frame *f, float tol, int max_it, int *iters, float *rel_res, float *elapsed_ms);
+/* the extended layer of side 1 or 2 (PoissonExt.cpp:49-362): (ch, cw, channels) floats, pitch in floats (0 = tight).
+ * VM_E_STATE on a frame whose layers are not extended. */
+int  vm_frame_download_layers_ext(vm_frame *f, int side, float *out, int pitch_floats);
+/* back to the tight layers (the canvases of PoissonExt.cpp:49-362 stay allocated); a no-op on a frame without extension */
+int  vm_frame_drop_layer_extension(vm_frame *f);
+/* Diagnostic: what the extension of one side (PoissonExt.cpp:49-362) solves, before any solve -- the filled canvas
+ * (ch, cw, channels) floats, `valid` (ch, cw) bytes (1: the cell holds a value, 0: a hole), the type map (ch, cw) bytes (2
+ * outside the image, 1 its outermost ring, 0 inside) and the right-hand side (ch, cw, channels) floats.  Any output may be
+ * NULL.  Works on buffers of its own: the frame, extended or not, is not changed.  VM_E_STATE without layers. */
+int  vm_dbg_layers_prepare(vm_frame *f, int side, float *filled, uint8_t *valid, uint8_t *type, float *rhs);
 /* ---- transition control: where the morph happens when ---------------------
  * The calls above take one geo_fa and one color_fa for the whole frame.  A frame may instead hold a SCHEDULE: two planes
  * of w x h float pairs (t0, t1) in the halfway domain (the domain of v), one for the geometry and one for the colour.  A

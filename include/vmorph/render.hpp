@@ -117,6 +117,24 @@ public:
         check(vm_frame_upload_layers(f_, channels, layer0, layer1, pitch_floats));
         channels_ = channels;
     }
+    // the layers extended past the image edge as the canvases are (vm_frame_extend_layers; PoissonExt.cpp:49-362): from then
+    // on every layer render call samples the extension instead of repeating the edge texel; a new upload_layers drops it.
+    // Returns the iterations of every system: side 1 then side 2 per group of up to three channels
+    std::vector<int> extend_layers(float tol = 1e-5f, int max_it = 20000)
+    {
+        std::vector<int> it(2 * ((channels_ + 2) / 3 > 0 ? (channels_ + 2) / 3 : 1), 0);
+        check(vm_frame_extend_layers(f_, tol, max_it, it.data(), nullptr, nullptr));
+        return it;
+    }
+    // the extended layer of side 1 or 2: (h + 2 ex, w + 2 ex, channels) floats
+    std::vector<float> download_layers_ext(int side)
+    {
+        std::vector<float> out((size_t)(w_ + 2 * ex_) * (h_ + 2 * ex_) * (channels_ > 0 ? channels_ : 1));
+        check(vm_frame_download_layers_ext(f_, side, out.data(), 0));
+        return out;
+    }
+    // back to the tight layers
+    void drop_layer_extension() { check(vm_frame_drop_layer_extension(f_)); }
     // the layers through the morph: (h, w, channels) floats
     std::vector<float> render_layers(float color_fa, float geo_fa, int color_from)
     { return rendered<float>(layer_floats(), vm_render_layers, color_fa, geo_fa, color_from); }

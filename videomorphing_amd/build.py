@@ -57,6 +57,7 @@ UNITS = [
     ("vm_viewport.hip", "vm_viewport_kernels.o", ["-ffp-contract=off"]),
     ("vm_vshutter.hip", "vm_vshutter_kernels.o", ["-ffp-contract=off"]),
     ("vm_poisson.hip", "vm_poisson.o", ["-ffp-contract=off"]),
+    ("vm_layer_ext.hip", "vm_layer_ext.o", ["-ffp-contract=off"]),
     ("vm_mgb.hip", "vm_mgb.o", ["-ffp-contract=fast"]),
     ("vm_pyramid.hip", "vm_pyramid.o", ["-ffp-contract=off"]),
     ("vm_temporal.hip", "vm_temporal.o", ["-ffp-contract=off"]),

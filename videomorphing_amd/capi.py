@@ -65,6 +65,7 @@ SYMBOLS = [
     "vm_render_viewport_shutter_layers_dev",
     "vm_render_viewport_transition_shutter", "vm_render_viewport_transition_shutter_dev",
     "vm_render_viewport_transition_shutter_layers", "vm_render_viewport_transition_shutter_layers_dev",
+    "vm_frame_extend_layers", "vm_frame_download_layers_ext", "vm_frame_drop_layer_extension", "vm_dbg_layers_prepare",
 ]
 
 
@@ -263,6 +264,10 @@ def load():
         "vm_video_error_image": [vp, i, i, i, f, i, i, vp, i],
         "vm_frame_sampling_maps": [vp, f, vp, vp, vp, vp],
         "vm_frame_upload_layers": [vp, i, vp, vp, i],
+        "vm_frame_extend_layers": [vp, f, i, C.POINTER(i), C.POINTER(f), C.POINTER(f)],
+        "vm_frame_download_layers_ext": [vp, i, vp, i],
+        "vm_frame_drop_layer_extension": [vp],
+        "vm_dbg_layers_prepare": [vp, i, vp, vp, vp, vp],
         "vm_render_layers": [vp, f, f, i, vp, i],
         "vm_render_layers_dev": [vp, f, f, i, C.POINTER(f)],
         "vm_frame_upload_schedule": [vp, vp, vp, i],

@@ -237,6 +237,16 @@ struct vm_frame {
     VmDev<float> layers;
     int layer_ch = 0;
     size_t layer_off = 0;
+    // ... and their Poisson extension (vm_frame_extend_layers, vm_poisson_api.cpp), allocated on the first call: two
+    // (ch, cw, layer_ch) canvases with the image at (ex, ex), the second at lext_off floats; the byte planes that tell
+    // where a canvas cell holds a value (two of cw x ch); one word per system and channel group, raised by a right-hand
+    // side that is not all zeros.  layer_ext: the render calls sample the canvases instead of the tight layers; a new
+    // upload of layers drops it
+    VmDev<float> lext;
+    VmDev<uint8_t> lext_valid;
+    VmDev<int> lext_nz;
+    size_t lext_off = 0;
+    bool layer_ext = false;
     // what the warp kernels write before it goes to the host (the maps of vm_warp.cpp, the output of a render call of
     // vm_render_calls.cpp), allocated on first use
     VmDev<char> warp_out;

@@ -5,6 +5,7 @@
 #include "vm_host.h"
 #include "vm_mgb.h"
 #include "vm_poisson.h"
+#include "vm_layer_ext.h"
 
 #include <cstring>
 #include <mutex>
@@ -421,6 +422,170 @@ extern "C" int vm_poisson_extend_frames(vm_frame *const *frames, int n, float to
     if (R.rel[at] > tol)
         return vm_fail(VM_E_NUMERIC, "vm_poisson_extend_frames: residual %.3g after %d iterations on side %d of frame %d (tol %.3g)",
                        R.rel[at], R.its[at], at % 2 + 1, at / 2, (double)tol);
+    return VM_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The same extension for the frame's float layers (vm_layer_ext.hip): the geometric type map, the fill from the
+// other side's tight layer, and per group of up to three channels the RGB path's system through the same batched solver.
+
+namespace {
+
+int layer_groups(int channels) { return (channels + 2) / 3; }
+
+// One side's workspace (pws2[side - 1], as mgb_system carves it) with the layers' type map, and its canvas and valid plane
+// at ext / valid: the tight layer pasted, every outside cell filled from the other side's tight layer.  All enqueued.
+int layer_prepare(vm_frame *f, int side, float *ext, uint8_t *valid, MgbWork &W)
+{
+    hipStream_t s = f->ctx->stream;
+    if (int rc = f->pws2[side - 1].reserve(mgb_bytes(f->cw, f->ch))) return rc;
+    mgb_carve(W, f->cw, f->ch, f->pws2[side - 1].get());
+    const float *tight[2] = {f->layers.get(), f->layers.get() + f->layer_off};
+    vm_layer_ext_launch_canvas(ext, valid, tight[side - 1], f->layer_ch, f->w, f->h, f->ex, s);
+    vm_layer_ext_launch_type(W.type, f->w, f->h, f->ex, s);
+    // the other side is the original tight layer (PoissonExt.cpp:54-57), the sign the side's (:104-137)
+    vm_layer_ext_launch_fill(ext, valid, W.type, tight[side == 1 ? 1 : 0], f->v.get(), f->layer_ch, f->w, f->h, f->rs, f->ex,
+                             side == 1 ? 1 : -1, s);
+    VM_HIP(hipGetLastError());
+    return VM_OK;
+}
+
+// room for the frame's two canvases, their valid planes and the groups' words
+int layer_ext_reserve(vm_frame *f)
+{
+    hipStream_t s = f->ctx->stream;
+    const size_t cells = (size_t)f->cw * f->ch, one = cells * f->layer_ch;
+    f->lext_off = vm_align256(one * 4) / 4;
+    if (int rc = f->lext.reserve(f->lext_off + one, s)) return rc;
+    if (int rc = f->lext_valid.reserve(2 * cells, s)) return rc;
+    return f->lext_nz.reserve(4, s);
+}
+
+// Both sides of every channel group, group by group on the frame's two workspaces: a batch of two systems per group, less
+// those whose right-hand side is all zeros -- the system is positive definite, their solution is zero, and the solver
+// (whose residual is relative to the right-hand side) is not asked.  its / rels: side 1 then side 2 of each group.
+int layer_solve(vm_frame *f, float tol, int max_it, int *its, double *rels)
+{
+    vm_ctx *c = f->ctx;
+    hipStream_t s = c->stream;
+    const int C = f->layer_ch, cw = f->cw, ch = f->ch;
+    const size_t cells = (size_t)cw * ch;
+    float *ext[2] = {f->lext.get(), f->lext.get() + f->lext_off};
+    uint8_t *valid[2] = {f->lext_valid.get(), f->lext_valid.get() + cells};
+    std::vector<MgbWork> W(2);
+    for (int k = 0; k < 2; ++k)
+        if (int rc = layer_prepare(f, k + 1, ext[k], valid[k], W[k])) return rc;
+    const int ng = layer_groups(C);
+    for (int g = 0; g < ng; ++g) {
+        const int c0 = 3 * g, n = std::min(3, C - c0);
+        int *nz_dev = f->lext_nz.get();
+        VM_HIP(hipMemsetAsync(nz_dev, 0, 2 * sizeof(int), s));
+        for (int k = 0; k < 2; ++k)
+            vm_layer_ext_launch_setup(ext[k], valid[k], W[k].type, W[k].S.lv[0].b, W[k].S.X, nz_dev + k, cw, ch, C, c0, n, s);
+        VM_HIP(hipGetLastError());
+        int nz[2] = {0, 0};
+        VM_HIP(hipMemcpyAsync(nz, nz_dev, sizeof(nz), hipMemcpyDeviceToHost, s));
+        VM_HIP(hipStreamSynchronize(s));
+        std::vector<MgbWork> live;
+        int at[2], nlive = 0;
+        for (int k = 0; k < 2; ++k) {
+            its[2 * g + k] = 0;
+            rels[2 * g + k] = 0;
+            if (nz[k]) { live.push_back(W[k]); at[nlive++] = k; }
+            else VM_HIP(hipMemsetAsync(W[k].S.X, 0, cells * sizeof(VmV3), s));
+        }
+        if (nlive) {
+            int li[2];
+            double lr[2];
+            if (int rc = mgb_solve(c, live, nlive, tol, max_it, li, lr)) return rc;
+            for (int j = 0; j < nlive; ++j) { its[2 * g + at[j]] = li[j]; rels[2 * g + at[j]] = lr[j]; }
+        }
+        for (int k = 0; k < 2; ++k)
+            vm_layer_ext_launch_paste(ext[k], valid[k], W[k].type, W[k].S.X, cw, ch, C, c0, n, g == ng - 1, s);
+        VM_HIP(hipGetLastError());
+    }
+    return VM_OK;
+}
+
+} // namespace
+
+// The frame's layers extended past the image edge as its canvases are (PoissonExt.cpp:49-362): from then on every layer
+// render call samples the (ch, cw, C) canvases.  iters / rel_res: two entries per channel group, side 1 then side 2.  A failed
+// call leaves the frame with its tight layers.
+extern "C" int vm_frame_extend_layers(vm_frame *f, float tol, int max_it, int *iters, float *rel_res, float *elapsed_ms)
+{
+    VM_ENTER_LOCKED(f);
+    if (!f->layer_ch) return vm_fail(VM_E_STATE, "%s: the frame holds no layers (vm_frame_upload_layers)", __func__);
+    if (f->ex == 0) return vm_fail(VM_E_STATE, "%s: the frame has no extension (ex == 0)", __func__);
+    if (!(tol > 0) || max_it < 1) return vm_fail(VM_E_INVALID, "%s: bad argument", __func__);
+    vm_ctx *c = f->ctx;
+    f->layer_ext = false;
+    if (int rc = layer_ext_reserve(f)) return rc;
+    const int n = 2 * layer_groups(f->layer_ch);
+    MgbResult R;
+    auto solve = [&](int *its, double *rel) { return layer_solve(f, tol, max_it, its, rel); };
+    if (int rc = mgb_timed(c, n, solve, iters, rel_res, elapsed_ms, R)) return rc;
+    const int at = R.worst;
+    if (R.rel[at] > tol)
+        return vm_fail(VM_E_NUMERIC, "%s: residual %.3g after %d iterations on side %d of channel group %d (tol %.3g)", __func__,
+                       R.rel[at], R.its[at], at % 2 + 1, at / 2, (double)tol);
+    f->layer_ext = true;
+    return VM_OK;
+}
+
+extern "C" int vm_frame_download_layers_ext(vm_frame *f, int side, float *out, int pitch_floats)
+{
+    if (!out || (side != 1 && side != 2)) return vm_fail(VM_E_INVALID, "%s: bad argument", __func__);
+    VM_ENTER(f);
+    if (!f->layer_ext) return vm_fail(VM_E_STATE, "%s: the frame's layers are not extended (vm_frame_extend_layers)", __func__);
+    hipStream_t s = f->ctx->stream;
+    const size_t row = (size_t)f->cw * f->layer_ch * 4;
+    if (int rc = vm_copy_pitched(__func__, hipMemcpyDeviceToHost, f->lext.get() + (side - 1) * f->lext_off, row, out, pitch_floats, 4, row,
+                                 f->ch, s)) return rc;
+    VM_HIP(hipStreamSynchronize(s));
+    return VM_OK;
+}
+
+extern "C" int vm_frame_drop_layer_extension(vm_frame *f)
+{
+    VM_ENTER(f);
+    f->layer_ext = false;
+    return VM_OK;
+}
+
+// One side's canvas as the solve would find it -- filled, with its valid plane, type map and the right-hand side
+// (ch, cw, C) of every channel group -- from buffers of the call's own: the frame's extension, if it holds one, is not
+// touched (the workspace is the solver's scratch).
+extern "C" int vm_dbg_layers_prepare(vm_frame *f, int side, float *filled, uint8_t *valid, uint8_t *type, float *rhs)
+{
+    if (side != 1 && side != 2) return vm_fail(VM_E_INVALID, "%s: side %d", __func__, side);
+    VM_ENTER_LOCKED(f);
+    if (!f->layer_ch) return vm_fail(VM_E_STATE, "%s: the frame holds no layers (vm_frame_upload_layers)", __func__);
+    hipStream_t s = f->ctx->stream;
+    const int C = f->layer_ch;
+    const size_t cells = (size_t)f->cw * f->ch;
+    VmDev<float> ext;
+    VmDev<uint8_t> val;
+    VmDev<int> nz;
+    if (int rc = ext.reserve(cells * C)) return rc;
+    if (int rc = val.reserve(cells)) return rc;
+    if (int rc = nz.reserve(1)) return rc;
+    MgbWork W;
+    if (int rc = layer_prepare(f, side, ext.get(), val.get(), W)) return rc;
+    if (filled) VM_HIP(hipMemcpyAsync(filled, ext.get(), cells * C * 4, hipMemcpyDeviceToHost, s));
+    if (valid) VM_HIP(hipMemcpyAsync(valid, val.get(), cells, hipMemcpyDeviceToHost, s));
+    if (type) VM_HIP(hipMemcpyAsync(type, W.type, cells, hipMemcpyDeviceToHost, s));
+    std::vector<float> b3(rhs ? cells * 3 : 0);
+    for (int g = 0; rhs && g < layer_groups(C); ++g) {
+        const int c0 = 3 * g, n = std::min(3, C - c0);
+        vm_layer_ext_launch_setup(ext.get(), val.get(), W.type, W.S.lv[0].b, W.S.X, nz.get(), f->cw, f->ch, C, c0, n, s);
+        VM_HIP(hipGetLastError());
+        VM_HIP(hipMemcpyAsync(b3.data(), W.S.lv[0].b, cells * sizeof(VmV3), hipMemcpyDeviceToHost, s));
+        VM_HIP(hipStreamSynchronize(s));
+        for (size_t i = 0; i < cells; ++i)
+            for (int k = 0; k < n; ++k) rhs[i * C + c0 + k] = b3[3 * i + k];
+    }
+    VM_HIP(hipStreamSynchronize(s));        // (the call's buffers are freed on return)
     return VM_OK;
 }
 

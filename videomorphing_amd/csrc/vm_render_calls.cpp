@@ -124,12 +124,20 @@ template <class A> void bind_viewport(A &a, const vm_viewport *vp)
     a.out_w = vp->out_w; a.out_h = vp->out_h; a.nx = vp->nx; a.ny = vp->ny;
 }
 
-// the tail: the frame's layers into floats at dev, or its canvases into RGB8 at dev
+// the tail: the frame's layers into floats at dev, or its canvases into RGB8 at dev.  The layers are the extended ones
+// when the frame holds them (vm_frame_extend_layers): the canvas grid, the image at (ex, ex) -- the renderer's own + ex
 template <class A> void bind_tail(A &a, const vm_frame *f, bool layers, void *dev)
 {
     if (layers) {
         a.channels = f->layer_ch;
-        a.layer0 = f->layers.get(); a.layer1 = f->layers.get() + f->layer_off; a.out = (float *)dev;
+        a.out = (float *)dev;
+        if (f->layer_ext) {
+            a.layer0 = f->lext.get(); a.layer1 = f->lext.get() + f->lext_off;
+            a.lw = f->cw; a.lh = f->ch; a.lexf = (float)f->ex;
+        } else {
+            a.layer0 = f->layers.get(); a.layer1 = f->layers.get() + f->layer_off;
+            a.lw = f->w; a.lh = f->h; a.lexf = 0.0f;
+        }
     } else {
         a.channels = VM_SHUTTER_CANVAS;
         a.ext0 = f->ext[0].get(); a.ext1 = f->ext[1].get(); a.ex = f->ex; a.rgb = (uint8_t *)dev;
@@ -178,8 +186,10 @@ int halfway(vm_frame *f, const char *fn, float color_fa, float geo_fa, int color
 int layers(vm_frame *f, const char *fn, float color_fa, float geo_fa, int color_from, const Dest &d)
 {
     return render_call(f, Call{fn, LAYERS, nullptr, 0, 0, color_from}, d, [&](void *dev, hipStream_t s) {
+        VmTransition T{};               // (the binder's target only: the uniform launcher takes the tail field by field)
+        bind_tail(T, f, true, dev);
         vm_launch_warp(f->w, f->h, f->rs, color_fa, geo_fa, color_from, f->v.get(), path_of(f), nullptr, nullptr, nullptr, nullptr,
-                       f->layer_ch, f->layers.get(), f->layers.get() + f->layer_off, (float *)dev, s);
+                       T.channels, T.layer0, T.layer1, T.lw, T.lh, T.lexf, T.out, s);
     });
 }
 

@@ -52,7 +52,8 @@ template <class T> __device__ __forceinline__ T per_sample(T v)
 }
 
 // acc += c_s: the uniform tails' taps and blend on the Landing of sample s, by the sample's colour fraction (the call's one
-// color_fa, or the k the chain left under a schedule).  Args: w, h, color_from, and ext0 / ext1 / ex or layer0 / layer1
+// color_fa, or the k the chain left under a schedule).  Args: w, h, color_from, and ext0 / ext1 / ex or layer0 / layer1 with
+// their grid lw / lh and the image's place in it, lexf
 template <int C, class Args> __device__ __forceinline__ void add_sample(const Args &A, const Landing &L, float color_fa, float (&acc)[NACC<C>])
 {
     const float m0x = L.px - L.v.x, m0y = L.py - L.v.y;
@@ -73,13 +74,15 @@ template <int C, class Args> __device__ __forceinline__ void add_sample(const Ar
         }
         acc[0] = acc[0] + c.x; acc[1] = acc[1] + c.y; acc[2] = acc[2] + c.z;
     } else {
+        const int lw = A.lw, lh = A.lh;
+        const float lexf = A.lexf;
         Texel<C> r;
         if (A.color_from == 0) {
-            r = tap_layer<C>(A.layer0, A.w, A.h, m0x + 0.5f, m0y + 0.5f);
+            r = tap_layer<C>(A.layer0, lw, lh, (m0x + lexf) + 0.5f, (m0y + lexf) + 0.5f);
         } else if (A.color_from == 2) {
-            r = tap_layer<C>(A.layer1, A.w, A.h, m1x + 0.5f, m1y + 0.5f);
+            r = tap_layer<C>(A.layer1, lw, lh, (m1x + lexf) + 0.5f, (m1y + lexf) + 0.5f);
         } else {
-            Texel<C> c0 = tap_layer<C>(A.layer0, A.w, A.h, m0x + 0.5f, m0y + 0.5f);
+            Texel<C> c0 = tap_layer<C>(A.layer0, lw, lh, (m0x + lexf) + 0.5f, (m0y + lexf) + 0.5f);
             // 3 and 4 channels: side 1 is tapped after side 0's texels are summed (side 1's position passes through a
             // statement that stands behind the one side 0's sums pass through), or eight texels of C registers are live
             // at once: 55 / 56 registers instead of 70 / 72
@@ -90,7 +93,7 @@ template <int C, class Args> __device__ __forceinline__ void add_sample(const Ar
                     asm volatile("" : "+v"(c0.c[k]));
                 asm volatile("" : "+v"(n1x), "+v"(n1y));
             }
-            const Texel<C> c1 = tap_layer<C>(A.layer1, A.w, A.h, n1x + 0.5f, n1y + 0.5f);
+            const Texel<C> c1 = tap_layer<C>(A.layer1, lw, lh, (n1x + lexf) + 0.5f, (n1y + lexf) + 0.5f);
 #pragma unroll
             for (int k = 0; k < C; ++k)
                 r.c[k] = c0.c[k] * (1 - color_fa) + c1.c[k] * color_fa;

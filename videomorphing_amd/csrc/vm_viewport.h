@@ -21,6 +21,8 @@ struct VmViewport {
     const float2 *vf, *uf;
     int channels;
     const float *layer0, *layer1;
+    int lw, lh;             // the layers' grid and where the image starts in it: w, h, 0 tight; cw, ch, ex extended
+    float lexf;             // (vm_frame_extend_layers)
     float *out;
     const uchar4 *ext0, *ext1;
     int ex;

@@ -34,10 +34,11 @@ template <int C> __global__ __launch_bounds__(256) void k_viewport(const VmViewp
     const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
     if (x >= A.out_w || y >= A.out_h)
         return;
-    const float nx = (float)A.nx, ny = (float)A.ny;
     float acc[NACC<C>] = {};
     for (int j = 0; j < A.ny; ++j)
         for (int i = 0; i < A.nx; ++i) {
+            // (the layer tails: not held in vector registers across the chain -- their taps have a grid of their own to hold)
+            const float nx = (float)(C == CANVAS ? A.nx : per_sample(A.nx)), ny = (float)(C == CANVAS ? A.ny : per_sample(A.ny));
             Landing L;
             chain_plain_from<false>(A.w, A.h, A.rs, A.geo_fa, A.vf, A.uf, nullptr, sample_q(A.x0, A.step_x, x, i, nx),
                                     sample_q(A.y0, A.step_y, y, j, ny), L);

@@ -32,6 +32,8 @@ struct VmVShutter {
     float2 *rates;
     int channels;
     const float *layer0, *layer1;
+    int lw, lh;             // the layers' grid and where the image starts in it: w, h, 0 tight; cw, ch, ex extended
+    float lexf;             // (vm_frame_extend_layers)
     float *out;
     const uchar4 *ext0, *ext1;
     int ex;

@@ -37,7 +37,7 @@ extern "C" int vm_frame_sampling_maps(vm_frame *f, float geo_fa, float *map0_xy,
     const size_t bytes[4] = {n * 8, n * 8, n * 4, n};
     return maps_call(f, host, bytes, s, [&](void *const *dev) {
         vm_launch_warp(f->w, f->h, f->rs, 0.0f, geo_fa, 0, f->v.get(), path_of(f), (float2 *)dev[0], (float2 *)dev[1], (float *)dev[2],
-                       (uint8_t *)dev[3], 0, nullptr, nullptr, nullptr, s);
+                       (uint8_t *)dev[3], 0, nullptr, nullptr, 0, 0, 0.0f, nullptr, s);
     });
 }
 
@@ -50,6 +50,7 @@ extern "C" int vm_frame_upload_layers(vm_frame *f, int channels, const float *la
     if (int rc = vm_pitch_resolve(__func__, &pitch_floats, 4, row)) return rc;
     hipStream_t s = f->ctx->stream;
     const size_t off = vm_align256(one * 4) / 4;
+    f->layer_ext = false;               // the extension was the old layers': tight again until vm_frame_extend_layers
     if (int rc = f->layers.reserve(off + one, s)) { f->layer_ch = 0; return rc; }
     f->layer_ch = 0;                    // until both copies are in
     const float *src[2] = {layer0, layer1};

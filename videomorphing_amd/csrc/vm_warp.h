@@ -13,10 +13,11 @@
 bool vm_render_window_form(int rs, int h);
 
 // The renderer's chain with other tails.  channels == 0: the sampling maps into map0 / map1 / resid / flags (tight (h, w);
-// any may be NULL); 1..4: the two tight (h, w, channels) layers through the morph into out.
+// any may be NULL); 1..4: the two tight (lh, lw, channels) layers through the morph into out, the image
+// at (lexf, lexf) of them: (h, w) and 0, or the extended (ch, cw) and ex (vm_frame_extend_layers).
 void vm_launch_warp(int w, int h, int rs, float color_fa, float geo_fa, int color_from, const float2 *v, const float2 *u,
                     float2 *map0, float2 *map1, float *resid, uint8_t *flags, int channels, const float *layer0,
-                    const float *layer1, float *out, hipStream_t s);
+                    const float *layer1, int lw, int lh, float lexf, float *out, hipStream_t s);
 
 // The same chain under a transition schedule (vm_warp.hip): geo_fa / color_fa are per-texel rates ramped from
 // the schedule planes (h x rs pairs (t0, t1), geometry and colour) at time t with `ease`, by a pre-pass, into `rates`,
@@ -36,6 +37,8 @@ struct VmTransition {
     uint8_t *flags;
     float2 *rates_out;
     const float *layer0, *layer1;
+    int lw, lh;             // the layers' grid and where the image starts in it: w, h, 0 tight; cw, ch, ex extended
+    float lexf;             // (vm_frame_extend_layers)
     float *out;
     const uchar4 *ext0, *ext1;
     int ex;

@@ -11,8 +11,8 @@
 //   map0 = (px - v.x, py - v.y), map1 = (px + v.x, py + v.y)       image pixels, pixel centre i is i
 //   resid = fmaxf(|px20 - px19|, |py20 - py19|)                    the move of the last round
 //   flags bit 0 / 1: map0 / map1 within [0, w - 1] x [0, h - 1]    (a NaN fails the comparisons)
-// A layer is sampled at (map + 0.5f) with tap2's expression and clamps on the w x h layer: no Poisson extension, the
-// edge texel repeats.  Tails: the maps kernel four coalesced stores per pixel, the layer kernel 2 x 4 texel gathers of
+// A layer is sampled at ((map + lexf) + 0.5f) with tap2's expression and clamps on the lw x lh layer: tight (lexf = 0), where
+// the edge texel repeats, or Poisson-extended as the canvases are (vm_layer_ext.hip; lexf = ex).  Tails: the maps kernel four coalesced stores per pixel, the layer kernel 2 x 4 texel gathers of
 // C floats (8-byte texels for C = 2, 16-byte for C = 4, three dwords for C = 3: texels stay tight) and one store.
 //
 // TRANSITION CONTROL (RATES).  The scalar geo_fa / color_fa become per-texel rates in the halfway domain: a
@@ -45,8 +45,10 @@ struct VmWarpArgs {
     float2 *map0, *map1;
     float *resid;
     uint8_t *flags;
-    // the layer tail (C >= 1): tight (h, w, C)
+    // the layer tail (C >= 1): tight (lh, lw, C), the image at (lexf, lexf) -- (h, w, C) at 0, or the extended (ch, cw, C) at ex
     const float *layer0, *layer1;
+    int lw, lh;
+    float lexf;
     float *out;
     int tiles_x, ntiles;
     // transition control (RATES): the call's (G, K) plane, ramped by k_rates, of the field's pitch; the maps tail's (g, k)
@@ -100,12 +102,12 @@ template <int C, bool RATES> __device__ __forceinline__ void warp_tail(const VmW
     } else {
         Texel<C> r;
         if (A.color_from == 0) {
-            r = tap_layer<C>(A.layer0, A.w, A.h, m0x + 0.5f, m0y + 0.5f);
+            r = tap_layer<C>(A.layer0, A.lw, A.lh, (m0x + A.lexf) + 0.5f, (m0y + A.lexf) + 0.5f);
         } else if (A.color_from == 2) {
-            r = tap_layer<C>(A.layer1, A.w, A.h, m1x + 0.5f, m1y + 0.5f);
+            r = tap_layer<C>(A.layer1, A.lw, A.lh, (m1x + A.lexf) + 0.5f, (m1y + A.lexf) + 0.5f);
         } else {
-            const Texel<C> c0 = tap_layer<C>(A.layer0, A.w, A.h, m0x + 0.5f, m0y + 0.5f);
-            const Texel<C> c1 = tap_layer<C>(A.layer1, A.w, A.h, m1x + 0.5f, m1y + 0.5f);
+            const Texel<C> c0 = tap_layer<C>(A.layer0, A.lw, A.lh, (m0x + A.lexf) + 0.5f, (m0y + A.lexf) + 0.5f);
+            const Texel<C> c1 = tap_layer<C>(A.layer1, A.lw, A.lh, (m1x + A.lexf) + 0.5f, (m1y + A.lexf) + 0.5f);
 #pragma unroll
             for (int k = 0; k < C; ++k)
                 r.c[k] = c0.c[k] * (1 - color_fa) + c1.c[k] * color_fa;
@@ -148,7 +150,7 @@ template <bool RATES> void launch_tail(VmWarpArgs &A, int channels, bool window,
 // channels == 0: the maps into map0 / map1 / resid / flags (tight, any may be NULL); 1..4: the layers into out
 void vm_launch_warp(int w, int h, int rs, float color_fa, float geo_fa, int color_from, const float2 *v, const float2 *u,
                     float2 *map0, float2 *map1, float *resid, uint8_t *flags, int channels, const float *layer0,
-                    const float *layer1, float *out, hipStream_t s)
+                    const float *layer1, int lw, int lh, float lexf, float *out, hipStream_t s)
 {
     VmWarpArgs A{};
     A.w = w; A.h = h; A.rs = rs;
@@ -156,6 +158,7 @@ void vm_launch_warp(int w, int h, int rs, float color_fa, float geo_fa, int colo
     A.vf = v; A.uf = u;
     A.map0 = map0; A.map1 = map1; A.resid = resid; A.flags = flags;
     A.layer0 = layer0; A.layer1 = layer1; A.out = out;
+    A.lw = lw; A.lh = lh; A.lexf = lexf;
     launch_tail<false>(A, channels, vm_render_window_form(rs, h), s);
 }
 
@@ -174,6 +177,7 @@ void vm_launch_transition(const VmTransition &T, hipStream_t s)
     A.rates = T.rates;
     A.map0 = T.map0; A.map1 = T.map1; A.resid = T.resid; A.flags = T.flags; A.rates_out = T.rates_out;
     A.layer0 = T.layer0; A.layer1 = T.layer1; A.out = T.out;
+    A.lw = T.lw; A.lh = T.lh; A.lexf = T.lexf;
     A.ext0 = T.ext0; A.ext1 = T.ext1; A.ex = T.ex; A.rgb = T.rgb;
     vm_launch_rates(T, s);
     launch_tail<true>(A, T.channels, vm_render_window_form(T.rs, T.h), s);

@@ -631,6 +631,41 @@ class Frame(object):
         self._layer_shape = a0.shape
         capi.check(self._L.vm_frame_upload_layers(self._h, 1 if a0.ndim == 2 else a0.shape[2], a0.ctypes.data, a1.ctypes.data, 0))
 
+    def extend_layers(self, tol=1e-5, max_it=20000):
+        """the uploaded layers extended past the image edge as the canvases are (vm_frame_extend_layers;
+        PoissonExt.cpp:49-362): from then on every layer render call samples the extension instead of repeating the
+        edge texel.  A new upload_layers drops it.  Returns ([((iters, rel) side 1, (iters, rel) side 2) per group of up
+        to three channels], elapsed ms)."""
+        shape = getattr(self, "_layer_shape", (self.h, self.w))           # (no upload: the call answers VM_E_STATE)
+        n = ((shape[2] if len(shape) == 3 else 1) + 2) // 3
+        it, rr, ms = (C.c_int * (2 * n))(), (C.c_float * (2 * n))(), C.c_float(0)
+        capi.check(self._L.vm_frame_extend_layers(self._h, float(tol), int(max_it), it, rr, C.byref(ms)))
+        return [((it[2 * g], rr[2 * g]), (it[2 * g + 1], rr[2 * g + 1])) for g in range(n)], ms.value
+
+    def download_layers_ext(self, side):
+        """the extended layer of side 1 or 2 (vm_frame_download_layers_ext): float32 (h + 2 ex, w + 2 ex) with the
+        channels the layers were uploaded in"""
+        shape = getattr(self, "_layer_shape", (self.h, self.w))
+        out = np.empty((self.h + 2 * self.ex, self.w + 2 * self.ex) + tuple(shape[2:]), dtype=np.float32)
+        capi.check(self._L.vm_frame_download_layers_ext(self._h, int(side), out.ctypes.data, 0))
+        return out
+
+    def drop_layer_extension(self):
+        """back to the tight layers (vm_frame_drop_layer_extension)"""
+        capi.check(self._L.vm_frame_drop_layer_extension(self._h))
+
+    def layers_prepare(self, side):
+        """diagnostic (vm_dbg_layers_prepare): what the extension of one side solves, before any solve -- (filled canvas,
+        valid, type map, right-hand side); the frame is not changed"""
+        shape = getattr(self, "_layer_shape", (self.h, self.w))
+        grid = (self.h + 2 * self.ex, self.w + 2 * self.ex)
+        filled = np.empty(grid + tuple(shape[2:]), dtype=np.float32)
+        rhs = np.empty_like(filled)
+        valid, typ = np.empty(grid, dtype=np.uint8), np.empty(grid, dtype=np.uint8)
+        capi.check(self._L.vm_dbg_layers_prepare(self._h, int(side), filled.ctypes.data, valid.ctypes.data, typ.ctypes.data,
+                                                 rhs.ctypes.data))
+        return filled, valid, typ, rhs
+
     def render_layers(self, color_fa, geo_fa, color_from):
         """the uploaded layers through the morph (vm_render_layers): float32 of the shape they were uploaded in"""
         return self._render("vm_render_layers", (color_fa, geo_fa, color_from), (self.h, self.w), True)
