@@ -544,6 +544,55 @@ int  vm_render_transition_layers_dev(vm_frame *f, float t, int ease, int color_f
  * (VM_E_INVALID). */
 int  vm_frame_transition_maps(vm_frame *f, float t, int ease, float *map0_xy, float *map1_xy, float *resid, uint8_t *flags,
                               float *rates_gk);
+/* ---- points and motion vectors through the morph ---------------------------
+ * The maps above go from the pixel grid of one output frame to image 0 and image 1.  The carry calls take any position of
+ * an output frame and return that position at other times of the morph: markers, roto shapes and mesh vertices drawn on
+ * every frame, a motion-vector pass, the gap a constraint is left with.  For a start point q = (x, y) of the output frame
+ * at geo_fa = from_fa (pixel centre i is i, as in the maps), in float32, in this order, without contraction:
+ *   the chain of kernel_render_halfway_image (Algorithm/render.cu:16-60; UI/RenderWidget.cpp:229-266) from q: p = q,
+ *   V = tap(v, p), U = tap(u, p); 20 rounds: p = (q - s1 V) - s2 U, V = 0.8 tap(v, p) + (1 - 0.8) V, U likewise (U = 0
+ *   without a path), with s1 = 2 from_fa - 1, s2 = 4 from_fa - 4 from_fa from_fa.  After round 20:
+ *   halfway = (px, py);  pos0 = (px - V.x, py - V.y);  pos1 = (px + V.x, py + V.y): the point in the halfway domain, in
+ *     image 0 and in image 1;
+ *   resid = fmaxf(|px20 - px19|, |py20 - py19|);  flags: bit 0 set when pos0 is inside the image, bit 1 when pos1 is (the
+ *     comparisons of vm_frame_sampling_maps);
+ *   for every to-time g = to_fa[k]:  s1 = 2 g - 1;  s2 = 4 g - 4 g g;
+ *     out[k] = ((px + s1 V.x) + s2 U.x, (py + s1 V.y) + s2 U.y)      (the s2 term is added without a path too, U = 0).
+ * Image 0 is time 0 and image 1 is time 1: "from image 0", "from image 1" and "from a rendered frame" are one call with
+ * another from-time.  Neither from_fa nor the to-times are clamped.  Under a schedule (the _transition forms; the section
+ * above) the chain runs with g = tapr(G, p), G the geometry plane ramped at t_from, and the rate of a to-time t_k is the
+ * same tap at p of round 20 -- the four schedule texels and fractions of tap_at(px + 0.5f, py + 0.5f) -- with the ramp
+ * taken at t_k: g_k = lerp(ramp(s00, t_k), ramp(s10, t_k), ramp(s01, t_k), ramp(s11, t_k)); then s1, s2 and out[k] as
+ * above.  The colour plane plays no part.  With the schedule (0, 1), VM_EASE_LINEAR and all times in [0, 1] every output
+ * has the bits of the uniform call.  The property that a point carried from s to t and back returns holds where the
+ * field is invertible and the chain has settled (resid).
+ * Outputs: out_xy (nt, n, 2) floats; halfway_xy, pos0_xy, pos1_xy (n, 2) floats; resid n floats; flags n bytes.  Any output
+ * may be NULL, not all of them; elapsed_ms (the launch, by events) may be NULL.  The calls refuse in the order of the
+ * render calls: the handle; every output NULL, a NULL pts_xy or a NULL times array; the arguments -- n outside 1..2^26, nt outside
+ * 1..64 (the dense calls: 1..16), a from-time or a to-time that is not finite, an ease outside the two (all
+ * VM_E_INVALID); the state -- no schedule for the _transition forms (VM_E_STATE).  The points are not scanned: a NaN, an
+ * infinite or a huge coordinate goes through the chain's clamps like a NaN of the field and comes out as the statement
+ * says.  The frame is not changed. */
+int  vm_frame_carry_points(vm_frame *f, float from_fa, const float *pts_xy, int n, const float *to_fa, int nt,
+                           float *out_xy, float *halfway_xy, float *pos0_xy, float *pos1_xy, float *resid, uint8_t *flags,
+                           float *elapsed_ms);
+/* same under the frame's schedule (render.cu:16-60, UI/RenderWidget.cpp:229-266): the from-time and the to-times are
+ * times of the schedule */
+int  vm_frame_carry_points_transition(vm_frame *f, float t_from, int ease, const float *pts_xy, int n, const float *t_to,
+                                      int nt, float *out_xy, float *halfway_xy, float *pos0_xy, float *pos1_xy, float *resid,
+                                      uint8_t *flags, float *elapsed_ms);
+/* The motion maps (render.cu:16-60, UI/RenderWidget.cpp:229-266): the carry call from the w x h pixel centres of the
+ * output frame at from_fa -- "output pixel at time s to its position at time t", a motion-vector pass once the pixel's own
+ * position is subtracted.  out_xy (nt, h, w, 2) floats, resid (h, w) floats, flags (h, w) bytes; any may be NULL, not all
+ * three.  nt in 1..16.  For the to-times {0, 1} out is map0 / map1 of vm_frame_sampling_maps at geo_fa = from_fa. */
+int  vm_frame_motion_maps(vm_frame *f, float from_fa, const float *to_fa, int nt, float *out_xy, float *resid, uint8_t *flags);
+/* same (render.cu:16-60, UI/RenderWidget.cpp:229-266), all three outputs left on the device (for timing) */
+int  vm_frame_motion_maps_dev(vm_frame *f, float from_fa, const float *to_fa, int nt, float *elapsed_ms);
+/* the motion maps under the frame's schedule (render.cu:16-60, UI/RenderWidget.cpp:229-266) */
+int  vm_frame_transition_motion_maps(vm_frame *f, float t_from, int ease, const float *t_to, int nt, float *out_xy,
+                                     float *resid, uint8_t *flags);
+/* same (render.cu:16-60, UI/RenderWidget.cpp:229-266), all three outputs left on the device (for timing) */
+int  vm_frame_transition_motion_maps_dev(vm_frame *f, float t_from, int ease, const float *t_to, int nt, float *elapsed_ms);
 /* ---- motion blur: the morph integrated over a shutter ----------------------
  * A frame rendered at one instant is sharp however fast its content moves; a sequence of them strobes.  A shutter call
  * walks the chain of kernel_render_halfway_image (Algorithm/render.cu:16-60) at N = samples times per output pixel, in one

@@ -5,6 +5,8 @@
 #ifndef VMORPH_RENDER_HPP
 #define VMORPH_RENDER_HPP
 
+#include <cmath>
+
 #include "pyramid.hpp"
 
 namespace vmorph {
@@ -247,9 +249,86 @@ public:
         return m;
     }
 
+    // ---- points and motion vectors through the morph (vm_frame_carry_points, ...; image 0 is time 0, image 1 time 1)
+    // n points (x, y) of the output frame at the from-time carried to nt to-times
+    struct Carried {
+        std::vector<float> out;                     // (nt, n, 2): the position at every to-time
+        std::vector<float> halfway, pos0, pos1;     // (n, 2): in the halfway domain, in image 0, in image 1
+        std::vector<float> resid;                   // n: the move of the chain's last round
+        std::vector<unsigned char> flags;           // n: bit 0 / 1: pos0 / pos1 inside the image
+    };
+    Carried carry_points(const std::vector<float> &points_xy, float from_fa, const std::vector<float> &to_fa)
+    {
+        Carried c = carried(points_xy.size() / 2, to_fa.size());
+        check(vm_frame_carry_points(f_, from_fa, points_xy.data(), (int)(points_xy.size() / 2), to_fa.data(), (int)to_fa.size(),
+                                    c.out.data(), c.halfway.data(), c.pos0.data(), c.pos1.data(), c.resid.data(), c.flags.data(), nullptr));
+        return c;
+    }
+    Carried carry_points_transition(const std::vector<float> &points_xy, float t_from, const std::vector<float> &t_to,
+                                    int ease = VM_EASE_LINEAR)
+    {
+        Carried c = carried(points_xy.size() / 2, t_to.size());
+        check(vm_frame_carry_points_transition(f_, t_from, ease, points_xy.data(), (int)(points_xy.size() / 2), t_to.data(),
+                                               (int)t_to.size(), c.out.data(), c.halfway.data(), c.pos0.data(), c.pos1.data(),
+                                               c.resid.data(), c.flags.data(), nullptr));
+        return c;
+    }
+    // the same from every pixel centre of the output frame: out (nt, h, w, 2), resid and flags (h, w); out[k] minus the
+    // pixel's own position is the motion-vector pass to time to_fa[k] (at most 16 to-times)
+    struct MotionMaps {
+        std::vector<float> out, resid;
+        std::vector<unsigned char> flags;
+    };
+    MotionMaps motion_maps(float from_fa, const std::vector<float> &to_fa)
+    {
+        const size_t n = (size_t)w_ * h_;
+        MotionMaps m{std::vector<float>(2 * n * to_fa.size()), std::vector<float>(n), std::vector<unsigned char>(n)};
+        check(vm_frame_motion_maps(f_, from_fa, to_fa.data(), (int)to_fa.size(), m.out.data(), m.resid.data(), m.flags.data()));
+        return m;
+    }
+    float motion_maps_dev(float from_fa, const std::vector<float> &to_fa)
+    { return timed(vm_frame_motion_maps_dev, from_fa, to_fa.data(), (int)to_fa.size()); }
+    MotionMaps transition_motion_maps(float t_from, const std::vector<float> &t_to, int ease = VM_EASE_LINEAR)
+    {
+        const size_t n = (size_t)w_ * h_;
+        MotionMaps m{std::vector<float>(2 * n * t_to.size()), std::vector<float>(n), std::vector<unsigned char>(n)};
+        check(vm_frame_transition_motion_maps(f_, t_from, ease, t_to.data(), (int)t_to.size(), m.out.data(), m.resid.data(),
+                                              m.flags.data()));
+        return m;
+    }
+    float transition_motion_maps_dev(float t_from, const std::vector<float> &t_to, int ease = VM_EASE_LINEAR)
+    { return timed(vm_frame_transition_motion_maps_dev, t_from, ease, t_to.data(), (int)t_to.size()); }
+    // how well each constraint is met, in pixels: (lx, ly) carried from image 0 gives pos1, compared with (rx, ry);
+    // (rx, ry) carried from image 1 gives pos0, compared with (lx, ly)
+    struct ConstraintGaps {
+        std::vector<float> gap01, gap10;            // |pos1(l) - r|, |pos0(r) - l|
+        std::vector<float> resid01, resid10;        // the resid of either carry: a gap beside a large one means little
+    };
+    ConstraintGaps constraint_gaps(const std::vector<vm_constraint> &cons)
+    {
+        if (cons.empty()) return ConstraintGaps{};
+        std::vector<float> l, r;
+        for (const vm_constraint &c : cons) {
+            l.push_back(c.lx); l.push_back(c.ly);
+            r.push_back(c.rx); r.push_back(c.ry);
+        }
+        const Carried a = carry_points(l, 0.0f, {1.0f}), b = carry_points(r, 1.0f, {0.0f});
+        ConstraintGaps g{{}, {}, a.resid, b.resid};
+        for (size_t i = 0; i < cons.size(); ++i) {
+            g.gap01.push_back(std::hypot(a.pos1[2 * i] - r[2 * i], a.pos1[2 * i + 1] - r[2 * i + 1]));
+            g.gap10.push_back(std::hypot(b.pos0[2 * i] - l[2 * i], b.pos0[2 * i + 1] - l[2 * i + 1]));
+        }
+        return g;
+    }
+
     vm_frame *handle() const { return f_; }
 
 private:
+    static Carried carried(size_t n, size_t nt)
+    {
+        return Carried{std::vector<float>(2 * n * nt), std::vector<float>(2 * n), std::vector<float>(2 * n), std::vector<float>(2 * n),
+                       std::vector<float>(n), std::vector<unsigned char>(n)};
+    }
     // a render call that downloads, call(f_, args..., out, pitch): `count` elements, tight
     template <class T, class Call, class... Args> std::vector<T> rendered(size_t count, Call call, Args... args)
     {

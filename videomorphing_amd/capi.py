@@ -66,6 +66,8 @@ SYMBOLS = [
     "vm_render_viewport_transition_shutter", "vm_render_viewport_transition_shutter_dev",
     "vm_render_viewport_transition_shutter_layers", "vm_render_viewport_transition_shutter_layers_dev",
     "vm_frame_extend_layers", "vm_frame_download_layers_ext", "vm_frame_drop_layer_extension", "vm_dbg_layers_prepare",
+    "vm_frame_carry_points", "vm_frame_carry_points_transition", "vm_frame_motion_maps", "vm_frame_motion_maps_dev",
+    "vm_frame_transition_motion_maps", "vm_frame_transition_motion_maps_dev",
 ]
 
 
@@ -297,6 +299,12 @@ def load():
         "vm_render_viewport_transition_shutter_dev": [vp, C.POINTER(ViewportStruct), f, f, i, f, i, i, C.POINTER(f)],
         "vm_render_viewport_transition_shutter_layers": [vp, C.POINTER(ViewportStruct), f, f, i, f, i, i, vp, i],
         "vm_render_viewport_transition_shutter_layers_dev": [vp, C.POINTER(ViewportStruct), f, f, i, f, i, i, C.POINTER(f)],
+        "vm_frame_carry_points": [vp, f, vp, i, vp, i, vp, vp, vp, vp, vp, vp, C.POINTER(f)],
+        "vm_frame_carry_points_transition": [vp, f, i, vp, i, vp, i, vp, vp, vp, vp, vp, vp, C.POINTER(f)],
+        "vm_frame_motion_maps": [vp, f, vp, i, vp, vp, vp],
+        "vm_frame_motion_maps_dev": [vp, f, vp, i, C.POINTER(f)],
+        "vm_frame_transition_motion_maps": [vp, f, i, vp, i, vp, vp, vp],
+        "vm_frame_transition_motion_maps_dev": [vp, f, i, vp, i, C.POINTER(f)],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

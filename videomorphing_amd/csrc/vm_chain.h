@@ -1,6 +1,6 @@
 // vm_chain.h -- the compositor's fixed-point chain (kernel_render_halfway_image, Algorithm/render.cu:16-60), stated once
 // for the units that walk it: vm_render.hip (RGB8 from the extended canvases), vm_warp.hip (sampling maps, float
-// layers, transition control), vm_shutter.hip (both tails over the sample times of a shutter), vm_tshutter.hip (the same under a schedule) and vm_viewport.hip (both tails from the sub-sample points of a viewport), vm_vshutter.hip (a viewport over either shutter).  A kernel walks the window form (the product path: taps served from an LDS window;
+// layers, transition control), vm_shutter.hip (both tails over the sample times of a shutter), vm_tshutter.hip (the same under a schedule) and vm_viewport.hip (both tails from the sub-sample points of a viewport), vm_vshutter.hip (a viewport over either shutter), vm_carry.hip (the landing carried to other times).  A kernel walks the window form (the product path: taps served from an LDS window;
 // vm_chain_win.h, included in the kernel's body) or calls chain_plain (VM_RENDER=plain, and fields of 4 GiB and more),
 // returns if the chain gave its thread no pixel, and runs its own tail on the Landing.  Everything is float32 in tap2's
 // expressions and order; the units are compiled with -ffp-contract=off.  Every function here is inlined into the kernel
@@ -32,6 +32,7 @@ struct Landing {
     float lx, ly;       // p of round 19
     float2 v;
     float g, k;         // RATES: the rates at p of round 20
+    float2 u;           // the damped path (zero without one): read by vm_carry.hip only, dead in every other tail
 };
 
 __device__ __forceinline__ int med3_i32(int a, int b, int c)     // median = clamp of a to [b, c] when b <= c
@@ -137,7 +138,7 @@ __device__ __forceinline__ bool chain_plain(int w, int h, int rs, float geo_fa, 
         }
         if constexpr (RATES) gk = tapr(rates, w, h, rs, L.px + 0.5f, L.py + 0.5f);
     }
-    L.v = v;
+    L.v = v; L.u = u;
     L.g = gk.x; L.k = gk.y;
     return true;
 }
@@ -176,7 +177,7 @@ __device__ __forceinline__ void chain_plain_from(int w, int h, int rs, float geo
         }
         if constexpr (RATES) gk = tapr(rates, w, h, rs, L.px + 0.5f, L.py + 0.5f);
     }
-    L.v = v;
+    L.v = v; L.u = u;
     L.g = gk.x; L.k = gk.y;
 }
 

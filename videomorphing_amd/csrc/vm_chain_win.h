@@ -1,5 +1,5 @@
 // vm_chain_win.h -- the window form of the compositor's chain (vm_chain.h), stated once as the statements a window kernel
-// includes at the top of its body -- k_render_win (vm_render.hip) and k_warp_win (vm_warp.hip) -- or of its sample loop's
+// includes at the top of its body -- k_render_win (vm_render.hip), k_warp_win (vm_warp.hip) and k_motion_win (vm_carry.hip) -- or of its sample loop's
 // (k_shutter_win, vm_shutter.hip; k_tblur_win, vm_tshutter.hip; k_viewport_win, vm_viewport.hip; k_vblur_win,
 // vm_vshutter.hip, with the hooks of all three).  It is no function because
 // the compiler lays a kernel out differently once this body sits behind any function boundary, a lambda included (the
@@ -190,6 +190,6 @@
                 u.y = alpha * tu.y + (1 - alpha) * u.y;
             }
         }
-        L.px = px; L.py = py; L.lx = lx; L.ly = ly; L.v = v;
+        L.px = px; L.py = py; L.lx = lx; L.ly = ly; L.v = v; L.u = u;
         L.g = g; L.k = lerp2(k00, k10, k01, k11, ka, kb);
     }

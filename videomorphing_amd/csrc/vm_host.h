@@ -254,6 +254,8 @@ struct vm_frame {
     // the colour plane of h x rs pairs (t0, t1), then the scratch plane of the same size a call ramps its rates into
     VmDev<float2> sched;
     bool has_sched = false;
+    // the start points of a carry call (vm_frame_carry_points, vm_render_calls.cpp), grown on demand
+    VmDev<float2> carry_pts;
 };
 
 // The one destroy path of the objects that live on a context's device (pyramid, video, frame, sync).  With the device

@@ -1,14 +1,15 @@
 // vm_render_calls.cpp -- the C-ABI of the render calls, every vm_render_* of include/vmorph.h: the launchers of
 // vm_render.hip, vm_warp.hip, vm_shutter.hip, vm_tshutter.hip, vm_viewport.hip and vm_vshutter.hip (the compositor's chain,
 // render.cu:16-60, UI/RenderWidget.cpp:229-266, with their tails) behind ONE host path -- check, bind, launch, download
-// (DESIGN 3.15).  Nothing here changes the frame's v, path, canvases, layers or schedule; the schedule's rate plane and
-// warp_out are a call's scratch.
+//  -- and the carry calls of vm_carry.hip on the same helpers.  Nothing here changes the frame's
+// v, path, canvases, layers or schedule; the schedule's rate plane, warp_out and carry_pts are a call's scratch.
 #include "vm_host.h"
 #include "vm_warp.h"
 #include "vm_shutter.h"
 #include "vm_tshutter.h"
 #include "vm_viewport.h"
 #include "vm_vshutter.h"
+#include "vm_carry.h"
 #include <cmath>
 #include <type_traits>
 
@@ -253,6 +254,73 @@ int vshutter(vm_frame *f, const char *fn, int sched, int tail, const vm_viewport
     });
 }
 
+// ---- the carry calls (vm_carry.hip): the same path -- check, bind, launch, download -- with up to six
+// optional outputs in the place of one pitched image.  `what`: POINTS (pts / n are the start points; without it the start
+// points are the frame's pixel grid) and SCHEDULED.  host: out, halfway, pos0, pos1, resid, flags.  A call that leaves its
+// output on the device (the dense _dev twins) writes what the dense call can give -- out, resid, flags -- and downloads
+// nothing.  NULL outputs and arrays -> the arguments (n, nt, the times, ease) -> the frame's state -> the outputs one after
+// the other in warp_out (256-byte aligned each), the points uploaded into carry_pts, the launch, the copies out, drained.
+enum { POINTS = 32 };
+
+int carry(vm_frame *f, const char *fn, int what, const float *pts, int n, float from, int ease, const float *to, int nt,
+          void *const (&host)[6], const Dest &d)
+{
+    const bool points = (what & POINTS) != 0;
+    bool want[6];
+    bool any = false;
+    for (int k = 0; k < 6; ++k) {
+        want[k] = d.download ? host[k] != nullptr : (k == 0 || k >= 4);
+        any = any || want[k];
+    }
+    if (!any) return vm_fail(VM_E_INVALID, "%s: every output is NULL", fn);
+    if (points && !pts) return vm_fail(VM_E_INVALID, "%s: the points are NULL", fn);
+    if (!to) return vm_fail(VM_E_INVALID, "%s: the to-times are NULL", fn);
+    if (points && (n < 1 || n > VM_CARRY_MAX_POINTS))
+        return vm_fail(VM_E_INVALID, "%s: %d points (1..%d)", fn, n, (int)VM_CARRY_MAX_POINTS);
+    const int max_nt = points ? VM_CARRY_MAX_TIMES : VM_CARRY_MAX_DENSE_TIMES;
+    if (nt < 1 || nt > max_nt) return vm_fail(VM_E_INVALID, "%s: %d to-times (1..%d)", fn, nt, max_nt);
+    if (!std::isfinite(from)) return vm_fail(VM_E_INVALID, "%s: the from-time %g is not finite", fn, (double)from);
+    for (int k = 0; k < nt; ++k)
+        if (!std::isfinite(to[k])) return vm_fail(VM_E_INVALID, "%s: to-time %d, %g, is not finite", fn, k, (double)to[k]);
+    if (what & SCHEDULED)
+        if (int rc = check_ease(fn, ease)) return rc;
+    if ((what & SCHEDULED) && !f->has_sched)
+        return vm_fail(VM_E_STATE, "%s: the frame holds no schedule (vm_frame_upload_schedule)", fn);
+    vm_ctx *c = f->ctx;
+    hipStream_t s = c->stream;
+    const size_t N = points ? (size_t)n : (size_t)f->w * f->h;
+    const size_t bytes[6] = {(size_t)nt * N * 8, N * 8, N * 8, N * 8, N * 4, N};
+    size_t off[6], total = 0;
+    for (int k = 0; k < 6; ++k) {
+        off[k] = total;
+        if (want[k]) total += vm_align256(bytes[k]);
+    }
+    if (int rc = f->warp_out.reserve(total, s)) return rc;
+    if (points)
+        if (int rc = f->carry_pts.reserve(N, s)) return rc;
+    void *dev[6];
+    for (int k = 0; k < 6; ++k) dev[k] = want[k] ? f->warp_out.get() + off[k] : nullptr;
+    VmCarry C{};
+    bind_field(C, f);
+    if (what & SCHEDULED) bind_schedule(C, f);
+    C.from = from; C.ease = ease;
+    C.pts = f->carry_pts.get(); C.n = n;
+    C.out = (float2 *)dev[0]; C.halfway = (float2 *)dev[1]; C.pos0 = (float2 *)dev[2]; C.pos1 = (float2 *)dev[3];
+    C.resid = (float *)dev[4]; C.flags = (uint8_t *)dev[5];
+    C.nt = nt;
+    for (int k = 0; k < nt; ++k) C.to[k] = to[k];
+    if (points) VM_HIP(hipMemcpyAsync(f->carry_pts.get(), pts, N * 8, hipMemcpyHostToDevice, s));
+    if (int rc = vm_timed_launch(c, d.ms, [&] { points ? vm_launch_carry_points(C, s) : vm_launch_motion_maps(C, s); })) return rc;
+    if (!d.download) return VM_OK;
+    for (int k = 0; k < 6; ++k)
+        if (host[k]) VM_HIP(hipMemcpyAsync(host[k], dev[k], bytes[k], hipMemcpyDeviceToHost, s));
+    VM_HIP(hipStreamSynchronize(s));    // the host buffers belong to the caller
+    return VM_OK;
+}
+
+// the points call downloads and may be timed too; the dense calls do one or the other
+Dest down_timed(float *ms) { return Dest{true, nullptr, 0, ms}; }
+
 } // namespace
 
 // ---- the entry points: the handle guard under the call's own name, then its family
@@ -448,4 +516,54 @@ extern "C" int vm_render_viewport_transition_shutter_layers_dev(vm_frame *f, con
 {
     VM_ENTER(f);
     return vshutter(f, __func__, SCHEDULED, LAYERS, vp, 0.0f, t_open, t_close, samples, t_color, ease, color_from, left(elapsed_ms));
+}
+
+// ---- points and motion vectors through the morph (vm_carry.hip)
+extern "C" int vm_frame_carry_points(vm_frame *f, float from_fa, const float *pts_xy, int n, const float *to_fa, int nt,
+                                     float *out_xy, float *halfway_xy, float *pos0_xy, float *pos1_xy, float *resid,
+                                     uint8_t *flags, float *elapsed_ms)
+{
+    VM_ENTER(f);
+    void *const host[6] = {out_xy, halfway_xy, pos0_xy, pos1_xy, resid, flags};
+    return carry(f, __func__, POINTS, pts_xy, n, from_fa, VM_EASE_LINEAR, to_fa, nt, host, down_timed(elapsed_ms));
+}
+
+extern "C" int vm_frame_carry_points_transition(vm_frame *f, float t_from, int ease, const float *pts_xy, int n,
+                                                const float *t_to, int nt, float *out_xy, float *halfway_xy, float *pos0_xy,
+                                                float *pos1_xy, float *resid, uint8_t *flags, float *elapsed_ms)
+{
+    VM_ENTER(f);
+    void *const host[6] = {out_xy, halfway_xy, pos0_xy, pos1_xy, resid, flags};
+    return carry(f, __func__, POINTS | SCHEDULED, pts_xy, n, t_from, ease, t_to, nt, host, down_timed(elapsed_ms));
+}
+
+extern "C" int vm_frame_motion_maps(vm_frame *f, float from_fa, const float *to_fa, int nt, float *out_xy, float *resid,
+                                    uint8_t *flags)
+{
+    VM_ENTER(f);
+    void *const host[6] = {out_xy, nullptr, nullptr, nullptr, resid, flags};
+    return carry(f, __func__, 0, nullptr, 0, from_fa, VM_EASE_LINEAR, to_fa, nt, host, down_timed(nullptr));
+}
+
+extern "C" int vm_frame_motion_maps_dev(vm_frame *f, float from_fa, const float *to_fa, int nt, float *elapsed_ms)
+{
+    VM_ENTER(f);
+    void *const host[6] = {};
+    return carry(f, __func__, 0, nullptr, 0, from_fa, VM_EASE_LINEAR, to_fa, nt, host, left(elapsed_ms));
+}
+
+extern "C" int vm_frame_transition_motion_maps(vm_frame *f, float t_from, int ease, const float *t_to, int nt, float *out_xy,
+                                               float *resid, uint8_t *flags)
+{
+    VM_ENTER(f);
+    void *const host[6] = {out_xy, nullptr, nullptr, nullptr, resid, flags};
+    return carry(f, __func__, SCHEDULED, nullptr, 0, t_from, ease, t_to, nt, host, down_timed(nullptr));
+}
+
+extern "C" int vm_frame_transition_motion_maps_dev(vm_frame *f, float t_from, int ease, const float *t_to, int nt,
+                                                   float *elapsed_ms)
+{
+    VM_ENTER(f);
+    void *const host[6] = {};
+    return carry(f, __func__, SCHEDULED, nullptr, 0, t_from, ease, t_to, nt, host, left(elapsed_ms));
 }

@@ -717,6 +717,82 @@ class Frame(object):
                                                     resid.ctypes.data, flags.ctypes.data, rates.ctypes.data))
         return m0, m1, resid, flags, rates
 
+    def _carry(self, name, head, points, times, want=None, timed=False):
+        """one vm_frame_carry_points* call: points (n, 2) (or (2,)) float32 of the output frame at the from-time, carried to
+        `times` -> (out (nt, n, 2), halfway, pos0, pos1 (n, 2), resid (n,) float32, flags (n,) uint8); `want` names the
+        outputs to ask for (the others come back None); timed: the launch's milliseconds are appended"""
+        pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 2)
+        to = np.ascontiguousarray(np.atleast_1d(times), dtype=np.float32)
+        n, nt = len(pts), len(to)
+        names = ("out", "halfway", "pos0", "pos1", "resid", "flags")
+        shapes = ((nt, n, 2), (n, 2), (n, 2), (n, 2), (n,), (n,))
+        outs = [np.empty(s, dtype=np.uint8 if k == "flags" else np.float32) if want is None or k in want else None
+                for k, s in zip(names, shapes)]
+        ms = C.c_float(0)
+        capi.check(getattr(self._L, name)(self._h, *head, pts.ctypes.data, n, to.ctypes.data, nt,
+                                          *[None if a is None else a.ctypes.data for a in outs], C.byref(ms) if timed else None))
+        return tuple(outs) + ((ms.value,) if timed else ())
+
+    def carry_points(self, points, from_fa, to_fa, want=None, timed=False):
+        """where the points (n, 2) of the output frame at geo_fa = from_fa lie at every time of to_fa
+        (vm_frame_carry_points; image 0 is time 0, image 1 time 1, pixel centre i is i): (out (nt, n, 2), halfway, pos0,
+        pos1 (n, 2), resid (n,), flags (n,)) -- the position at each to-time, in the halfway domain, in image 0 and in
+        image 1, the move of the chain's last round, bit 0 / 1: pos0 / pos1 inside the image"""
+        return self._carry("vm_frame_carry_points", (float(from_fa),), points, to_fa, want, timed)
+
+    def carry_points_transition(self, points, t_from, t_to, ease=capi.EASE_LINEAR, want=None, timed=False):
+        """carry_points under the schedule (vm_frame_carry_points_transition): the from-time and the to-times are times
+        of the schedule"""
+        return self._carry("vm_frame_carry_points_transition", (float(t_from), int(ease)), points, t_to, want, timed)
+
+    def _motion(self, name, head, times, want):
+        to = np.ascontiguousarray(np.atleast_1d(times), dtype=np.float32)
+        names = ("out", "resid", "flags")
+        shapes = ((len(to), self.h, self.w, 2), (self.h, self.w), (self.h, self.w))
+        outs = [np.empty(s, dtype=np.uint8 if k == "flags" else np.float32) if want is None or k in want else None
+                for k, s in zip(names, shapes)]
+        capi.check(getattr(self._L, name)(self._h, *head, to.ctypes.data, len(to),
+                                          *[None if a is None else a.ctypes.data for a in outs]))
+        return tuple(outs)
+
+    def _motion_dev(self, name, head, times):
+        to = np.ascontiguousarray(np.atleast_1d(times), dtype=np.float32)
+        ms = C.c_float(0)
+        capi.check(getattr(self._L, name)(self._h, *head, to.ctypes.data, len(to), C.byref(ms)))
+        return ms.value
+
+    def motion_maps(self, from_fa, to_fa, want=None):
+        """carry_points from every pixel centre of the output frame at from_fa (vm_frame_motion_maps): (out
+        (nt, h, w, 2), resid (h, w), flags (h, w)); out[k] minus the pixel grid is the motion-vector pass to time
+        to_fa[k].  At most 16 to-times."""
+        return self._motion("vm_frame_motion_maps", (float(from_fa),), to_fa, want)
+
+    def motion_maps_dev(self, from_fa, to_fa):
+        return self._motion_dev("vm_frame_motion_maps_dev", (float(from_fa),), to_fa)
+
+    def transition_motion_maps(self, t_from, t_to, ease=capi.EASE_LINEAR, want=None):
+        """motion_maps under the schedule (vm_frame_transition_motion_maps)"""
+        return self._motion("vm_frame_transition_motion_maps", (float(t_from), int(ease)), t_to, want)
+
+    def transition_motion_maps_dev(self, t_from, t_to, ease=capi.EASE_LINEAR):
+        return self._motion_dev("vm_frame_transition_motion_maps_dev", (float(t_from), int(ease)), t_to)
+
+    def constraint_gaps(self, constraints):
+        """how well each constraint is met, in pixels: rows (lx, ly, rx, ry[, weight]) or capi.Constraint items.  (lx, ly)
+        carried from image 0 gives pos1, compared with (rx, ry); (rx, ry) carried from image 1 gives pos0, compared with
+        (lx, ly) -> (gap01, gap10, resid01, resid10), one float32 per row each (a resid that is not small says the chain
+        had not settled there, and the gap beside it means little); no constraints: four empty arrays"""
+        if len(constraints) and isinstance(constraints[0], capi.Constraint):
+            constraints = [(c.lx, c.ly, c.rx, c.ry) for c in constraints]
+        if not len(constraints):
+            return tuple(np.empty(0, np.float32) for _ in range(4))
+        c = np.asarray(constraints, dtype=np.float32).reshape(len(constraints), -1)[:, :4]
+        _, _, _, p1, r01, _ = self.carry_points(c[:, 0:2], 0.0, [1.0], want=("pos1", "resid"))
+        _, _, p0, _, r10, _ = self.carry_points(c[:, 2:4], 1.0, [0.0], want=("pos0", "resid"))
+        gap01 = np.hypot(p1[:, 0] - c[:, 2], p1[:, 1] - c[:, 3])
+        gap10 = np.hypot(p0[:, 0] - c[:, 0], p0[:, 1] - c[:, 1])
+        return gap01, gap10, r01, r10
+
     @staticmethod
     def _shutter_args(color_fa, geo_open, geo_close, samples, color_from):
         return (float(color_fa), float(geo_open), float(geo_close), int(samples), int(color_from))
