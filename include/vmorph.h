@@ -438,9 +438,10 @@ int  vm_host_register(void *ptr, uint64_t bytes);
 int  vm_host_unregister(void *ptr);
 /* ... and frame `frame` of vm_video_result (above), computed on the device */
 int  vm_frame_set_v_from_video(vm_frame *f, vm_video *v, int lvl, int frame);
-/* The render calls -- every vm_render_* from here to the viewports over a shutter, and each one's _dev twin -- refuse in
+/* The render calls -- every vm_render_* from here to the viewports over a shutter, the vm_frame_render_viewport_filtered*
+ * among them, and each one's _dev twin -- refuse in
  * one order: the handle (VM_E_INVALID); a NULL output of a call that downloads (VM_E_INVALID); the arguments -- viewport,
- * samples, samples * nx * ny, ease, color_from (VM_E_INVALID); the frame's state -- no schedule, then no layers
+ * samples, samples * nx * ny, ease, filter, color_from (VM_E_INVALID); the frame's state -- no schedule, then no layers
  * (VM_E_STATE); a pitch below the row (VM_E_INVALID).  Of two faults at once the earlier one answers. */
 /* render_halfway_image, Algorithm/render.cu:62-96 (UI/RenderWidget.h:52-57);
  * rgb_out: h rows of w RGB8 pixels, pitch in bytes (0 = tight) */
@@ -703,6 +704,58 @@ int  vm_render_viewport_layers(vm_frame *f, const vm_viewport *vp, float color_f
 /* same (render.cu:16-60, UI/RenderWidget.cpp:229-266), output left on the device (for timing) */
 int  vm_render_viewport_layers_dev(vm_frame *f, const vm_viewport *vp, float color_fa, float geo_fa, int color_from,
                                    float *elapsed_ms);
+/* ---- viewports through a cubic filter ----------
+ * A viewport call taps its colour, at the end of its chain, with four texels: a 2.5x zoom magnifies the plate through a
+ * bilinear kernel, which is soft and shows its diamond pattern along edges (supersampling does not help: under
+ * magnification it averages more bilinear values).  The calls of this section take the viewport section's arguments,
+ * outputs and refusals, and a filter for the taps that read picture content -- a canvas, a layer: */
+#define VM_FILTER_BILINEAR    0
+#define VM_FILTER_CATMULL_ROM 1   /* B = 0,   C = 1/2: interpolating */
+#define VM_FILTER_MITCHELL    2   /* B = 1/3, C = 1/3 */
+#define VM_FILTER_BSPLINE     3   /* B = 1,   C = 0: never overshoots, blurs */
+/* Everything is as the viewport section states it: q, the chain, (map0, map1)_s = (p - V, p + V), the blend by color_from /
+ * color_fa, acc = acc + c_s in sample order, acc / (float)N.  The one exception is the tap that reads a canvas or a layer;
+ * the chain's own taps of the field stay bilinear (it taps a smooth vector field, and its bits are the reference's).
+ * A cubic tap reads a W x H image at (x, y).  These are the coordinates that the bilinear tap takes: the canvases'
+ * + ex + 0.5f, the layers' (+ lexf) + 0.5f.  It works in float32, without contraction, in this order:
+ *   xb = x - 0.5f;  fi = floorf(xb);  a = xb - fi;  fi = fminf(fmaxf(fi, -2.0f), (float)W + 1.0f);  i = (int)fi
+ *   columns  c_k = clamp(i + k, 0, W - 1),  k = -1, 0, 1, 2                 (rows r_m from y, b, H likewise)
+ *   inner(d) = ((p3 * d + p2) * d) * d + p0            outer(d) = ((q3 * d + q2) * d + q1) * d + q0
+ *   wx_-1 = outer(1.0f + a)   wx_0 = inner(a)   wx_1 = inner(1.0f - a)   wx_2 = outer(2.0f - a)     (wy from b likewise)
+ *   row_m = ((wx_-1 * t(c_-1, r_m) + wx_0 * t(c_0, r_m)) + wx_1 * t(c_1, r_m)) + wx_2 * t(c_2, r_m)
+ *   value = ((wy_-1 * row_-1 + wy_0 * row_0) + wy_1 * row_1) + wy_2 * row_2
+ * The value is per channel, and uchar -> float is exact.  No tap reads outside the image whatever x is -- NaN, +-inf, 1e30:
+ * the float clamp before the conversion guarantees it.  The coefficients are one host table per filter, each (float)(n / d)
+ * with n, d doubles:
+ *   filter        p3    p2    p0    q3     q2    q1     q0
+ *   Catmull-Rom   3/2   -5/2  1     -1/2   5/2   -4     2
+ *   Mitchell      7/6   -2    8/9   -7/18  2     -10/3  16/9
+ *   B-spline      1/2   -1    2/3   -1/6   1     -2     4/3
+ * Cubic filters overshoot: a 0 / 255 step tapped at a = 0.25 gives 272.93 and -17.93 under Catmull-Rom, 260.98 and -5.98
+ * under Mitchell.  The RGB8 result is (uint8)((double)fminf(fmaxf(acc / (float)N, 0.0f), 255.0f) + 0.5); samples are not
+ * clamped one by one.  Layers are returned UNCLAMPED: a matte may leave [0, 1]; that is the filter's answer, and the caller
+ * decides what to do with it.  Extended layers (vm_frame_extend_layers) are tapped on their extended grid, as every layer
+ * call taps them.  VM_FILTER_BILINEAR is the viewport call itself, bit for bit (the same kernel).  Every call of this
+ * section answers VM_E_INVALID for whatever the viewport section refuses and for a filter outside 0..3, VM_E_STATE for a
+ * layer call on a frame without layers, and leaves the frame (v, path, canvases, layers, schedule) unchanged after a refusal
+ * as after a render.  Not in this section, deliberately: filtered forms of the shutter, transition and viewport-shutter
+ * families (they take this tail as a choice later), filtered sampling maps, any change to the chain's own taps, and a
+ * prefilter for the B-spline (which therefore smooths: it does not interpolate). */
+/* vm_render_viewport through a filter (render.cu:16-60, UI/RenderWidget.cpp:229-266): RGB8 from the Poisson-extended
+ * canvases, clamped to [0, 255] before the rounding.  rgb_out: out_h rows of out_w RGB8 pixels, pitch in bytes (0 = tight). */
+int  vm_frame_render_viewport_filtered(vm_frame *f, const vm_viewport *vp, int filter, float color_fa, float geo_fa,
+                                       int color_from, uint8_t *rgb_out, int pitch_bytes);
+/* same (render.cu:16-60, UI/RenderWidget.cpp:229-266), output left on the device (for timing) */
+int  vm_frame_render_viewport_filtered_dev(vm_frame *f, const vm_viewport *vp, int filter, float color_fa, float geo_fa,
+                                           int color_from, float *elapsed_ms);
+/* vm_render_viewport_layers through a filter (render.cu:16-60, UI/RenderWidget.cpp:229-266): the layers of
+ * vm_frame_upload_layers, unclamped.  out: (out_h, out_w, channels) floats, pitch in floats (0 = tight).  VM_E_STATE on a
+ * frame that holds no layers. */
+int  vm_frame_render_viewport_filtered_layers(vm_frame *f, const vm_viewport *vp, int filter, float color_fa, float geo_fa,
+                                              int color_from, float *out, int pitch_floats);
+/* same (render.cu:16-60, UI/RenderWidget.cpp:229-266), output left on the device (for timing) */
+int  vm_frame_render_viewport_filtered_layers_dev(vm_frame *f, const vm_viewport *vp, int filter, float color_fa, float geo_fa,
+                                                  int color_from, float *elapsed_ms);
 /* ---- viewports over a shutter, uniformly and under a transition schedule ----
  * The viewport section composed with the two motion-blur sections: a viewer that zooms into a motion-blurred frame, a
  * half-size proxy of a wipe, a delivery at another size with a shutter, an overscan render of a frame that holds a

@@ -54,6 +54,14 @@ struct Viewport : vm_viewport {
     }
 };
 
+// the filter of the last taps of a filtered viewport call (VM_FILTER_*): the taps that read a canvas or a layer
+enum class Filter : int {
+    Bilinear = VM_FILTER_BILINEAR,          // the viewport call itself
+    CatmullRom = VM_FILTER_CATMULL_ROM,     // B = 0, C = 1/2: interpolating
+    Mitchell = VM_FILTER_MITCHELL,          // B = 1/3, C = 1/3
+    BSpline = VM_FILTER_BSPLINE             // B = 1, C = 0: never overshoots, blurs
+};
+
 class Frame {
 public:
     Frame(Context &ctx, int w, int h, int ex) : w_(w), h_(h), ex_(ex) { check(vm_frame_create(ctx.handle(), w, h, ex, &f_)); }
@@ -199,6 +207,17 @@ public:
     { return rendered<float>(layer_floats(&vp), vm_render_viewport_layers, &vp, color_fa, geo_fa, color_from); }
     float render_viewport_layers_dev(const Viewport &vp, float color_fa, float geo_fa, int color_from = 1)
     { return timed(vm_render_viewport_layers_dev, &vp, color_fa, geo_fa, color_from); }
+    // a viewport through a cubic filter (vm_frame_render_viewport_filtered): the taps that read the canvases take 4 x 4 texels,
+    // the mean is clamped to [0, 255] before the rounding; Filter::Bilinear is render_viewport, bit for bit
+    std::vector<unsigned char> render_viewport_filtered(const Viewport &vp, Filter filter, float color_fa, float geo_fa, int color_from = 1)
+    { return rendered<unsigned char>(rgb_bytes(&vp), vm_frame_render_viewport_filtered, &vp, (int)filter, color_fa, geo_fa, color_from); }
+    float render_viewport_filtered_dev(const Viewport &vp, Filter filter, float color_fa, float geo_fa, int color_from = 1)
+    { return timed(vm_frame_render_viewport_filtered_dev, &vp, (int)filter, color_fa, geo_fa, color_from); }
+    // the layers through the same viewport and filter: (out_h, out_w, channels) floats, NOT clamped (a matte may leave [0, 1])
+    std::vector<float> render_viewport_filtered_layers(const Viewport &vp, Filter filter, float color_fa, float geo_fa, int color_from = 1)
+    { return rendered<float>(layer_floats(&vp), vm_frame_render_viewport_filtered_layers, &vp, (int)filter, color_fa, geo_fa, color_from); }
+    float render_viewport_filtered_layers_dev(const Viewport &vp, Filter filter, float color_fa, float geo_fa, int color_from = 1)
+    { return timed(vm_frame_render_viewport_filtered_layers_dev, &vp, (int)filter, color_fa, geo_fa, color_from); }
     // a viewport over a shutter (vm_render_viewport_shutter): every output pixel the mean of its vp.nx x vp.ny chains at
     // each of `samples` times between geo_open and geo_close; samples * vp.nx * vp.ny may be 256 at most
     std::vector<unsigned char> render_viewport_shutter(const Viewport &vp, float color_fa, float geo_open, float geo_close,

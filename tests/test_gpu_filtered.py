@@ -1,0 +1,383 @@
+"""The filtered viewport kernels (videomorphing_amd/csrc/vm_filter.hip) behind vm_frame_render_viewport_filtered[_layers]: with
+VM_FILTER_BILINEAR the viewport calls' bits; with Catmull-Rom, Mitchell and the cubic B-spline the float32 statement of
+tests/filter_ref.py, byte for byte and bit for bit, under zooms, shifts, enlargements, reductions (the plain form), overscan,
+viewports outside the field and outputs smaller than a tile; the ties that need no statement (texel centres, the clamp);
+extended layers; the plain form against the window form; the refusals.
+
+Shapes: 5x3 -- every 4 x 4 footprint clamps on at least one side, and three rows under a four-row footprint always repeat
+one --, 33x7 one tile and one pixel wide, 203x77 several tiles with window and global taps.  The statement walks the chain
+once per sample in numpy (about 6 us per output pixel and sample) and the maps are shared by the three filters, so every
+viewport carries (1, 1) and one of (2, 2) / (3, 2), and no case runs longer than a few seconds."""
+import ctypes as C
+import itertools
+import os
+import textwrap
+
+import numpy as np
+import pytest
+
+import filter_ref
+import viewport_ref
+from filter_ref import BILINEAR, BSPLINE, CATMULL_ROM, CUBIC, MITCHELL
+from render_cases import field as _field, frame as _frame, hashes_under_render_mode, layers as _layers, same_bits as _same
+from videomorphing_amd import capi, morph, transition
+from videomorphing_amd.viewport import Viewport
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+f32 = np.float32
+SHAPES = [(5, 3, 2), (33, 7, 3), (203, 77, 9)]
+KINDS = ["smooth", "large", "outside", "nan"]
+cases = pytest.mark.parametrize("with_path", [False, True])
+shapes = pytest.mark.parametrize("w,h,ex", SHAPES)
+kinds = pytest.mark.parametrize("kind", KINDS)
+
+
+def viewports(w, h, ex):
+    """{name: (x0, y0, step_x, step_y, out_w, out_h, sample grids)} for a w x h field: tests/test_gpu_viewport.py's table
+    with (1, 1) and one more grid each"""
+    vps = {
+        "zoom": (10.25, 3.5, 0.4, 0.4, 64, 40, ((1, 1), (3, 2))),                   # 2.5x at a fractional origin, 2 x 3 tiles
+        "shift": (0.5, 0.5, 1.0, 1.0, w, h, ((1, 1), (2, 2))),                      # every tap half way between texels
+        "double": (0.0, 0.0, 0.5, 0.5, 2 * w, 2 * h, ((1, 1), (2, 2)) if w * h < 3000 else ((1, 1),)),
+        "half": (0.0, 0.0, 2.0, 2.0, (w + 1) // 2, (h + 1) // 2, ((1, 1), (2, 2))),          # the plain form
+        "aniso": (-2.5, 1.25, 0.75, 1.5, w, (h + 1) // 2, ((1, 1), (3, 2))),        # one axis in reach of the window: plain
+        "overscan": (-float(ex), -float(ex), 1.0, 1.0, w + 2 * ex, h + 2 * ex, ((1, 1), (2, 2))),
+        "outside": (w + 40.0, -h - 30.0, 1.0, 1.0, 40, 24, ((1, 1), (2, 2))),
+        "pixel": (w / 3.0, h / 2.0, 0.7, 0.7, 1, 1, ((1, 1), (2, 2))),
+        "narrow": (w - 2.75, -1.5, 0.9, 0.3, 5, 24, ((1, 1), (3, 2))),              # narrower than a tile, two tiles high
+    }
+    if w * h < 100:
+        vps["tenfold"] = (0.0, 0.0, 0.1, 0.1, 10 * w, 10 * h, ((1, 1), (3, 2)))    # the whole field under four tiles
+    return vps
+
+
+NAMES = sorted(viewports(203, 77, 9))
+EVERY = [(w, h, ex, name) for w, h, ex in SHAPES for name in sorted(viewports(w, h, ex))]
+
+
+@shapes
+@kinds
+@cases
+def test_the_bilinear_filter_is_the_viewport_call(gpu_ctx, w, h, ex, kind, with_path):
+    """VM_FILTER_BILINEAR: vm_render_viewport's bytes (NaN pixels too: the same kernel) and vm_render_viewport_layers' bits
+    for 1, 3 and 4 channels, every color_from, in the window form and in the plain one"""
+    fr = _frame(gpu_ctx, w, h, ex, *_field(w, h, kind, with_path))
+    vps = [Viewport.identity(w, h), Viewport(10.25, 3.5, 0.4, 0.4, 40, 24, 3, 2), Viewport(0.0, 0.0, 2.0, 2.0, (w + 1) // 2, (h + 1) // 2, 2, 2)]
+    for vp in vps:
+        for cf in (0, 1, 2):
+            out, ref = fr.render_viewport_filtered(vp, BILINEAR, 0.3, 0.3, cf), fr.render_viewport(vp, 0.3, 0.3, cf)
+            assert np.array_equal(out, ref), (vp, cf, int((out != ref).sum()))
+    for c in (1, 3, 4):
+        fr.upload_layers(_layers(w, h, c, 10 + c), _layers(w, h, c, 20 + c))
+        for vp in vps:
+            for cf in (0, 1, 2):
+                out, ref = fr.render_viewport_filtered_layers(vp, BILINEAR, 0.3, 0.3, cf), fr.render_viewport_layers(vp, 0.3, 0.3, cf)
+                assert _same(out, ref), (c, vp, cf, int((out != ref).sum()))
+    fr.close()
+
+
+@pytest.mark.parametrize("w,h,ex,name", EVERY)
+@kinds
+@cases
+def test_filtered_calls_equal_the_statement(gpu_ctx, w, h, ex, name, kind, with_path):
+    """the three cubic filters on one walk of the chain: RGB8 byte for byte wherever every sample's two positions are finite,
+    layers bit for bit, a NaN for a NaN; every color_from under the first sample grid; 1..4 channels in turn over the
+    viewports and the filters"""
+    v, u = _field(w, h, kind, with_path)
+    fr = _frame(gpu_ctx, w, h, ex, v, u)
+    e0, e1 = fr.download_ext(1), fr.download_ext(2)
+    x0, y0, sx, sy, ow, oh, grids = viewports(w, h, ex)[name]
+    at = NAMES.index(name) if name in NAMES else 0
+    for k, (nx, ny) in enumerate(grids):
+        vp = Viewport(x0, y0, sx, sy, ow, oh, nx, ny).validate()
+        maps = viewport_ref.sample_maps(v, u, 0.3, vp.astuple())
+        ok = viewport_ref.founded(maps)
+        assert kind == "nan" or ok.all()
+        cfs = (0, 1, 2) if k == 0 else (1,)
+        for filt in CUBIC:
+            taps = filter_ref.canvas_taps(e0, e1, ex, maps, filt)
+            for cf in cfs:
+                got = fr.render_viewport_filtered(vp, filt, 0.3, 0.3, cf)
+                want = filter_ref.render_viewport_bytes(e0, e1, ex, maps, 0.3, cf, filt, taps)
+                assert got.shape == (oh, ow, 3) and np.array_equal(got[ok], want[ok]), (filt, nx, ny, cf, int((got != want)[ok].sum()))
+            ch = (at + filt + k) % 4 + 1
+            l0, l1 = _layers(w, h, ch, 10 + ch), _layers(w, h, ch, 20 + ch)
+            fr.upload_layers(l0, l1)
+            taps = filter_ref.layer_taps(l0, l1, maps, filt)
+            for cf in cfs:
+                got = fr.render_viewport_filtered_layers(vp, filt, 0.3, 0.3, cf)
+                want = filter_ref.layers_on_maps(l0, l1, maps, 0.3, cf, filt, 0, taps)
+                assert _same(got, want), (filt, ch, nx, ny, cf, int((got != want).sum()))
+    fr.close()
+
+
+@shapes
+@cases
+def test_catmull_rom_on_texel_centres_returns_the_images(gpu_ctx, w, h, ex, with_path):
+    """zero field (with_path: a path of zeros, which keeps the taps of u), the identity viewport: every sample stands on a
+    texel centre, Catmull-Rom's weights are (0, 1, 0, 0), and the bytes are image 0's and image 1's for color_from 0 and 2"""
+    rng = np.random.RandomState(3)
+    rgb = [rng.randint(0, 256, (h, w, 3)).astype(np.uint8) for _ in range(2)]
+    fr = morph.Frame(gpu_ctx, w, h, ex)
+    zero = np.zeros((h, w, 2), f32)
+    fr.upload(morph.make_extended(rgb[0], ex), morph.make_extended(rgb[1], ex), zero, zero if with_path else None)
+    ident = Viewport.identity(w, h)
+    assert np.array_equal(fr.render_viewport_filtered(ident, CATMULL_ROM, 0.3, 0.35, 0), rgb[0])
+    assert np.array_equal(fr.render_viewport_filtered(ident, CATMULL_ROM, 0.3, 0.35, 2), rgb[1])
+    lay = [(a.astype(f32) + f32(1)) * f32(-1.75) for a in rgb]      # (no zeros: +0 + -0 is +0)
+    fr.upload_layers(*lay)
+    assert _same(fr.render_viewport_filtered_layers(ident, CATMULL_ROM, 0.3, 0.35, 0), lay[0])
+    assert _same(fr.render_viewport_filtered_layers(ident, CATMULL_ROM, 0.3, 0.35, 2), lay[1])
+    fr.close()
+
+
+@shapes
+@pytest.mark.parametrize("filt", [CATMULL_ROM, MITCHELL])
+def test_overshoot_is_clamped_in_bytes_and_kept_in_layers(gpu_ctx, w, h, ex, filt):
+    """the overshoot case (a 0 / 255 step, a zero field, every sample a quarter pixel behind a texel): where the statement's
+    unclamped mean leaves [0, 255] -- it does, below and above -- the bytes are 0 and 255, and the same plate as a float
+    layer comes back outside [0, 255] where its own statement is"""
+    rgb, v, vpt = filter_ref.overshoot_case(w, h)
+    vp = Viewport(*vpt)
+    e = morph.make_extended(rgb, ex)
+    fr = morph.Frame(gpu_ctx, w, h, ex)
+    fr.upload(e, e, v, None)
+    maps = viewport_ref.sample_maps(v, None, 0.3, vpt)
+    mean = filter_ref.canvas_mean(e, e, ex, maps, 0.3, 0, filt)
+    assert (mean < 0).any() and (mean > 255).any()
+    got = fr.render_viewport_filtered(vp, filt, 0.3, 0.3, 0)
+    assert np.all(got[mean < 0] == 0) and np.all(got[mean > 255] == 255)
+    assert np.array_equal(got, filter_ref.bytes_of(mean, filt))
+    lay = rgb.astype(f32)
+    fr.upload_layers(lay, lay)
+    want = filter_ref.layers_on_maps(lay, lay, maps, 0.3, 0, filt)
+    assert (want < 0).any() and (want > 255).any()
+    got = fr.render_viewport_filtered_layers(vp, filt, 0.3, 0.3, 0)
+    assert np.all(got[want < 0] < 0) and np.all(got[want > 255] > 255) and _same(got, want)
+    fr.close()
+
+
+@pytest.mark.parametrize("c", [1, 3, 4])
+def test_filtered_layer_calls_sample_the_extension(gpu_ctx, c):
+    """after vm_frame_extend_layers the filtered layer call taps the extended grid: the statement on what
+    vm_frame_download_layers_ext hands out, the image at (ex, ex); after vm_frame_drop_layer_extension the tight layers again"""
+    w, h, ex = 33, 7, 3
+    v, _ = _field(w, h, "outside", False)
+    fr = morph.Frame(gpu_ctx, w, h, ex)
+    fr.upload(None, None, v, None)
+    rng = np.random.RandomState(7)
+    l0, l1 = rng.rand(h, w, c).astype(f32), rng.rand(h, w, c).astype(f32)
+    fr.upload_layers(l0, l1)
+    vps = (Viewport.identity(w, h), Viewport(2.25, 0.5, 0.4, 0.4, 40, 12, 2, 2), Viewport.fit(w, h, w // 2, h // 2).supersampled(2))
+    maps = [viewport_ref.sample_maps(v, None, 0.5, vp.astuple()) for vp in vps]
+
+    def calls():
+        return [fr.render_viewport_filtered_layers(vp, filt, 0.3, 0.5, 1) for vp in vps for filt in CUBIC]
+
+    tight = calls()
+    for got, want in zip(tight, [filter_ref.layers_on_maps(l0, l1, m, 0.3, 1, filt) for m in maps for filt in CUBIC]):
+        assert _same(got, want)
+    fr.extend_layers(1e-6)
+    x0, x1 = fr.download_layers_ext(1), fr.download_layers_ext(2)
+    got = calls()
+    for k, (a, b) in enumerate(zip(got, [filter_ref.layers_on_maps(x0, x1, m, 0.3, 1, filt, ex) for m in maps for filt in CUBIC])):
+        assert _same(a, b), k
+    assert any(not _same(a, b) for a, b in zip(got, tight)), "the field's samples leave the image: the extension shows"
+    fr.drop_layer_extension()
+    assert all(_same(a, b) for a, b in zip(calls(), tight))
+    fr.close()
+
+
+_PROG = textwrap.dedent("""
+    import hashlib, sys
+    import numpy as np
+    sys.path.insert(0, %r)
+    sys.path.insert(0, %r)
+    import warp_ref
+    from test_gpu_filtered import viewports
+    from videomorphing_amd import capi, morph, synth
+    from videomorphing_amd.viewport import Viewport
+    ctx = morph.Context(0, capi.MATH_FAST)
+    for w, h, ex in ((203, 77, 9), (33, 7, 3), (5, 3, 2)):
+        rgb0, rgb1 = synth.make_rgb_pair(w, h)
+        for kind in ("smooth", "large", "outside", "nan"):
+            rng = np.random.RandomState(41)
+            v, u = warp_ref.field(kind, w, h, rng), warp_ref.path(w, h, rng)
+            fr = morph.Frame(ctx, w, h, ex)
+            for path in (None, u):
+                hh = hashlib.sha256()
+                fr.upload(morph.make_extended(rgb0, ex), morph.make_extended(rgb1, ex), v, path)
+                for c in (1, 3, 4):
+                    fr.upload_layers(np.dstack([rgb0, rgb1]).astype(np.float32)[..., :c] / np.float32(3), np.dstack([rgb1, rgb0]).astype(np.float32)[..., :c])
+                    for name, (x0, y0, sx, sy, ow, oh, grids) in sorted(viewports(w, h, ex).items()):
+                        for nx, ny in grids:
+                            vp = Viewport(x0, y0, sx, sy, ow, oh, nx, ny)
+                            for filt in (1, 2, 3):
+                                if c == 1:
+                                    hh.update(fr.render_viewport_filtered(vp, filt, 0.3, 0.3, 1).tobytes())
+                                lay = fr.render_viewport_filtered_layers(vp, filt, 0.3, 0.3, 1)
+                                nan = np.isnan(lay)                 # a NaN for a NaN: its sign and payload are not specified
+                                hh.update(nan.tobytes())
+                                hh.update(np.where(nan, np.float32(0), lay).tobytes())
+                print("HASH", w, h, kind, path is not None, hh.hexdigest())
+            fr.close()
+""") % (ROOT, os.path.join(ROOT, "tests"))
+
+
+def test_plain_form_agrees(gpu_ctx):
+    """the plain gather kernels (VM_RENDER=plain -- also the path of fields of 4 GiB and more, and of steps above 1) give
+    the window kernels' bits, which the tests above hold to the statement: a fresh child process with the switch set
+    hashes, case by case, the bytes and the layers of 1, 3 and 4 channels (a NaN for a NaN, bit for bit elsewhere) under
+    every viewport, sample grid and cubic filter of this file, on the three shapes and the four fields, with and without
+    a path; another one hashes the window form's"""
+    plain, window = hashes_under_render_mode(_PROG, "plain"), hashes_under_render_mode(_PROG, None)
+    assert len(window) == 24
+    assert plain == window, [a for a, b in zip(plain, window) if a != b]
+
+
+def test_state_and_errors(gpu_ctx):
+    """every refusal of the viewport section and a filter outside 0..3 answer VM_E_INVALID on all four calls, a layer call
+    on a frame without layers VM_E_STATE; pitched outputs keep what lies beyond their rows, a positive time, and after
+    every refusal a frame that is what it was: v, the path, the canvases, the layers and the schedule"""
+    w, h, ex = 33, 7, 3
+    v, u = _field(w, h, "smooth", True)
+    sched = tuple(np.ascontiguousarray(a, dtype=f32) for a in (transition.wipe(w, h), transition.radial(w, h)))
+    fr = _frame(gpu_ctx, w, h, ex, v, u, sched)
+    L, hnd = fr._L, fr._h
+    OK, ST, INV = capi.VM_OK, capi.VM_E_STATE, capi.VM_E_INVALID
+    good = Viewport(2.25, 0.5, 0.8, 0.8, 21, 6, 2, 2)
+    ow, oh = good.out_w, good.out_h
+    gs = good.struct()
+    ms = C.c_float(-1.0)
+    big_rgb, big_out = np.zeros((64, 64, 3), np.uint8), np.zeros((64, 64, 2), f32)
+
+    def all_four(s=gs, filt=CATMULL_ROM, cf=1):
+        p = C.byref(s) if s is not None else None
+        return (L.vm_frame_render_viewport_filtered(hnd, p, filt, 0.3, 0.3, cf, big_rgb.ctypes.data, 0),
+                L.vm_frame_render_viewport_filtered_dev(hnd, p, filt, 0.3, 0.3, cf, C.byref(ms)),
+                L.vm_frame_render_viewport_filtered_layers(hnd, p, filt, 0.3, 0.3, cf, big_out.ctypes.data, 0),
+                L.vm_frame_render_viewport_filtered_layers_dev(hnd, p, filt, 0.3, 0.3, cf, C.byref(ms)))
+
+    def state():
+        return (fr.download_v(), fr.download_qpath(), fr.download_ext(1), fr.download_ext(2), fr.render_halfway(0.3, 0.35, 1),
+                fr.render_transition(0.4, capi.EASE_SMOOTH, 1)) + fr.transition_maps(0.4, capi.EASE_SMOOTH)
+
+    def unchanged(before, after):
+        assert len(before) == len(after)
+        for k, (a, b) in enumerate(zip(before, after)):
+            assert _same(a, b), k
+
+    # no layers yet: every filter, the bilinear one too
+    before = state()
+    for filt in (BILINEAR,) + CUBIC:
+        assert all_four(filt=filt) == (OK, OK, ST, ST), filt
+    with pytest.raises(capi.VmError) as e:
+        fr.render_viewport_filtered_layers(good, MITCHELL, 0.3, 0.3)
+    assert e.value.code == ST
+    unchanged(before, state())
+    l0, l1 = _layers(w, h, 2, 1), _layers(w, h, 2, 2)
+    fr.upload_layers(l0, l1)
+    assert all_four() == (OK,) * 4
+    before = state() + (fr.render_layers(0.3, 0.35, 1),)
+
+    def refused(answer, want=(INV,) * 4):
+        assert answer == want
+        unchanged(before, state() + (fr.render_layers(0.3, 0.35, 1),))
+
+    # what the viewport section refuses
+    for bad in viewport_ref.INVALID_VIEWPORTS:
+        refused(all_four(Viewport(*bad).struct()))
+        with pytest.raises(capi.VmError) as e:
+            fr.render_viewport_filtered(Viewport(*bad), CATMULL_ROM, 0.3, 0.3)
+        assert e.value.code == INV
+    refused(all_four(None))
+    for filt in (-1, 4, 1 << 20):
+        refused(all_four(filt=filt))
+    with pytest.raises(capi.VmError) as e:
+        fr.render_viewport_filtered(good, 4, 0.3, 0.3)
+    assert e.value.code == INV
+    for cf in (-1, 3):
+        refused(all_four(cf=cf))
+    # of two faults at once the earlier one answers: the viewport before the filter, the filter before the state
+    assert all_four(Viewport(*viewport_ref.INVALID_VIEWPORTS[0]).struct(), filt=9) == (INV,) * 4
+    # NULL outputs and pitches below the row
+    rgb, out = np.zeros((oh, ow, 3), np.uint8), np.zeros((oh, ow, 2), f32)
+    p = C.byref(gs)
+    for data, pitch in ((None, 0), (rgb.ctypes.data, 3 * ow - 1), (rgb.ctypes.data, -1)):
+        assert L.vm_frame_render_viewport_filtered(hnd, p, MITCHELL, 0.3, 0.3, 1, data, pitch) == INV
+    for data, pitch in ((None, 0), (out.ctypes.data, 2 * ow - 1), (out.ctypes.data, -1)):
+        assert L.vm_frame_render_viewport_filtered_layers(hnd, p, MITCHELL, 0.3, 0.3, 1, data, pitch) == INV
+    unchanged(before, state() + (fr.render_layers(0.3, 0.35, 1),))
+    # the edges of the viewport section are legal (the second one's corner is a million pixels away)
+    for edge in viewport_ref.EDGE_VIEWPORTS:
+        assert fr.render_viewport_filtered(Viewport(*edge), BSPLINE, 0.3, 0.3).shape == (edge[5], edge[4], 3)
+        assert fr.render_viewport_filtered_layers(Viewport(*edge), BSPLINE, 0.3, 0.3).shape == (edge[5], edge[4], 2)
+    # pitched outputs keep what lies beyond their rows
+    big = np.full((oh, 3 * ow + 5), 201, np.uint8)
+    capi.check(L.vm_frame_render_viewport_filtered(hnd, p, MITCHELL, 0.3, 0.3, 1, big.ctypes.data, 3 * ow + 5))
+    assert np.array_equal(big[:, :3 * ow].reshape(oh, ow, 3), fr.render_viewport_filtered(good, MITCHELL, 0.3, 0.3, 1)) and np.all(big[:, 3 * ow:] == 201)
+    bigf = np.full((oh, 2 * ow + 3), f32(-12345.5), f32)
+    capi.check(L.vm_frame_render_viewport_filtered_layers(hnd, p, MITCHELL, 0.3, 0.3, 1, bigf.ctypes.data, 2 * ow + 3))
+    ref = filter_ref.layers_on_maps(l0, l1, viewport_ref.sample_maps(v, u, 0.3, good.astuple()), 0.3, 1, MITCHELL)
+    assert _same(bigf[:, :2 * ow].reshape(oh, ow, 2), ref) and np.all(bigf[:, 2 * ow:] == f32(-12345.5))
+    assert fr.render_viewport_filtered_dev(good, MITCHELL, 0.3, 0.3) > 0 and fr.render_viewport_filtered_layers_dev(good, MITCHELL, 0.3, 0.3) > 0
+    capi.check(L.vm_frame_render_viewport_filtered_dev(hnd, p, MITCHELL, 0.3, 0.3, 1, None))
+    capi.check(L.vm_frame_render_viewport_filtered_layers_dev(hnd, p, MITCHELL, 0.3, 0.3, 1, None))
+    unchanged(before, state() + (fr.render_layers(0.3, 0.35, 1),))
+    fr.close()
+
+
+def test_two_faults_at_once_answer_in_the_render_calls_order(gpu_ctx):
+    """the one order of the render calls (include/vmorph.h) on the four filtered calls, as
+    tests/test_gpu_render_refusals.py holds it for the vm_render_* ones: a NULL output, the arguments -- viewport, filter,
+    color_from --, the frame's state (no layers), the pitch.  Of every pair of faults a call can carry the earlier one
+    answers, with its message under the call's own name; the _dev twin cannot carry a NULL output or a pitch and answers for
+    what is left of the pair"""
+    w, h, ex, ch = 33, 7, 3, 2
+    v, u = _field(w, h, "smooth", True)
+    frames = {False: _frame(gpu_ctx, w, h, ex, v, u), True: _frame(gpu_ctx, w, h, ex, v, u)}
+    frames[True].upload_layers(_layers(w, h, ch, 1), _layers(w, h, ch, 2))
+    L = frames[True]._L
+    OK, ST, INV = capi.VM_OK, capi.VM_E_STATE, capi.VM_E_INVALID
+    good = Viewport(2.25, 0.5, 0.8, 0.8, 21, 6, 2, 2)
+    gs = good.struct()
+    host = np.zeros(64 * 64 * 4, f32)
+    ms = C.c_float(0)
+    # fault -> (its place in the order, the code, what the message says)
+    faults = {"null_output": (0, INV, "output is NULL"), "null_viewport": (1, INV, "viewport is NULL"), "filter": (2, INV, "filter 4"),
+              "color_from": (3, INV, "color_from 3"), "no_layers": (4, ST, "holds no layers"), "pitch": (5, INV, "below the row")}
+
+    def call(name, mine, dev):
+        fr = frames["no_layers" not in mine]
+        args = (None if "null_viewport" in mine else C.byref(gs), 4 if "filter" in mine else MITCHELL, 0.3, 0.35,
+                3 if "color_from" in mine else 1)
+        if dev:
+            rc = getattr(L, name + "_dev")(fr._h, *args, C.byref(ms))
+        else:
+            row = good.out_w * (ch if name.endswith("_layers") else 3)
+            rc = getattr(L, name)(fr._h, *args, None if "null_output" in mine else host.ctypes.data, row - 1 if "pitch" in mine else 0)
+        return rc, L.vm_last_error().decode()
+
+    before = {k: fr.render_halfway(0.3, 0.35, 1) for k, fr in frames.items()}
+    checked = 0
+    for name in ("vm_frame_render_viewport_filtered", "vm_frame_render_viewport_filtered_layers"):
+        can = [f for f in faults if f != "no_layers" or name.endswith("_layers")]
+        assert call(name, (), False)[0] == OK and call(name, (), True)[0] == OK, name
+        for pair in itertools.combinations(can, 2):
+            for dev in (False, True):
+                mine = [f for f in pair if not (dev and f in ("null_output", "pitch"))]
+                rc, msg = call(name, mine, dev)
+                what = (name, pair, dev, msg)
+                checked += 1
+                if not mine:
+                    assert rc == OK, what
+                    continue
+                first = min(mine, key=lambda f: faults[f][0])
+                assert rc == faults[first][1], what
+                assert msg.startswith(name + ("_dev: " if dev else ": ")) and faults[first][2] in msg, what
+    assert checked == 2 * (10 + 15)
+    for k, fr in frames.items():
+        assert np.array_equal(fr.render_halfway(0.3, 0.35, 1), before[k]), k
+        fr.close()

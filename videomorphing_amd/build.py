@@ -56,6 +56,7 @@ UNITS = [
     ("vm_tshutter.hip", "vm_tshutter_kernels.o", ["-ffp-contract=off"]),
     ("vm_viewport.hip", "vm_viewport_kernels.o", ["-ffp-contract=off"]),
     ("vm_vshutter.hip", "vm_vshutter_kernels.o", ["-ffp-contract=off"]),
+    ("vm_filter.hip", "vm_filter_kernels.o", ["-ffp-contract=off"]),
     ("vm_carry.hip", "vm_carry_kernels.o", ["-ffp-contract=off"]),
     ("vm_poisson.hip", "vm_poisson.o", ["-ffp-contract=off"]),
     ("vm_layer_ext.hip", "vm_layer_ext.o", ["-ffp-contract=off"]),

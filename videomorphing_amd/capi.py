@@ -21,6 +21,8 @@ SWEEP_AUTO, SWEEP_TILE, SWEEP_SPLIT, SWEEP_STEP, SWEEP_SPARSE, SWEEP_PASS = 0, 1
 ERR_SSIM, ERR_TPS, ERR_UI, ERR_TEMP, ERR_ALL = 0, 1, 2, 3, 4   # planes / totals of the error view (vm_level_energy, ...)
 ERR_NAMES = ("ssim", "tps", "ui", "temp", "all")
 EASE_LINEAR, EASE_SMOOTH = 0, 1               # the ramp of a transition schedule (vm_render_transition, ...)
+# the filter of the last taps of a filtered viewport call (vm_frame_render_viewport_filtered, ...)
+FILTER_BILINEAR, FILTER_CATMULL_ROM, FILTER_MITCHELL, FILTER_BSPLINE = 0, 1, 2, 3
 
 FIELDS = {  # name -> (id, channels)
     "img0": (0, 1), "img1": (1, 1), "v": (2, 2), "luma": (3, 2), "mean": (4, 2), "var": (5, 2),
@@ -61,6 +63,8 @@ SYMBOLS = [
     "vm_render_transition_shutter", "vm_render_transition_shutter_dev", "vm_render_transition_shutter_layers",
     "vm_render_transition_shutter_layers_dev",
     "vm_render_viewport", "vm_render_viewport_dev", "vm_render_viewport_layers", "vm_render_viewport_layers_dev",
+    "vm_frame_render_viewport_filtered", "vm_frame_render_viewport_filtered_dev", "vm_frame_render_viewport_filtered_layers",
+    "vm_frame_render_viewport_filtered_layers_dev",
     "vm_render_viewport_shutter", "vm_render_viewport_shutter_dev", "vm_render_viewport_shutter_layers",
     "vm_render_viewport_shutter_layers_dev",
     "vm_render_viewport_transition_shutter", "vm_render_viewport_transition_shutter_dev",
@@ -291,6 +295,10 @@ def load():
         "vm_render_viewport_dev": [vp, C.POINTER(ViewportStruct), f, f, i, C.POINTER(f)],
         "vm_render_viewport_layers": [vp, C.POINTER(ViewportStruct), f, f, i, vp, i],
         "vm_render_viewport_layers_dev": [vp, C.POINTER(ViewportStruct), f, f, i, C.POINTER(f)],
+        "vm_frame_render_viewport_filtered": [vp, C.POINTER(ViewportStruct), i, f, f, i, vp, i],
+        "vm_frame_render_viewport_filtered_dev": [vp, C.POINTER(ViewportStruct), i, f, f, i, C.POINTER(f)],
+        "vm_frame_render_viewport_filtered_layers": [vp, C.POINTER(ViewportStruct), i, f, f, i, vp, i],
+        "vm_frame_render_viewport_filtered_layers_dev": [vp, C.POINTER(ViewportStruct), i, f, f, i, C.POINTER(f)],
         "vm_render_viewport_shutter": [vp, C.POINTER(ViewportStruct), f, f, f, i, i, vp, i],
         "vm_render_viewport_shutter_dev": [vp, C.POINTER(ViewportStruct), f, f, f, i, i, C.POINTER(f)],
         "vm_render_viewport_shutter_layers": [vp, C.POINTER(ViewportStruct), f, f, f, i, i, vp, i],

@@ -1,6 +1,6 @@
 // vm_render_calls.cpp -- the C-ABI of the render calls, every vm_render_* of include/vmorph.h: the launchers of
-// vm_render.hip, vm_warp.hip, vm_shutter.hip, vm_tshutter.hip, vm_viewport.hip and vm_vshutter.hip (the compositor's chain,
-// render.cu:16-60, UI/RenderWidget.cpp:229-266, with their tails) behind ONE host path -- check, bind, launch, download
+// vm_render.hip, vm_warp.hip, vm_shutter.hip, vm_tshutter.hip, vm_viewport.hip, vm_vshutter.hip and vm_filter.hip (the
+// compositor's chain, render.cu:16-60, UI/RenderWidget.cpp:229-266, with their tails) behind ONE host path -- check, bind, launch, download
 //  -- and the carry calls of vm_carry.hip on the same helpers.  Nothing here changes the frame's
 // v, path, canvases, layers or schedule; the schedule's rate plane, warp_out and carry_pts are a call's scratch.
 #include "vm_host.h"
@@ -9,6 +9,7 @@
 #include "vm_tshutter.h"
 #include "vm_viewport.h"
 #include "vm_vshutter.h"
+#include "vm_filter.h"
 #include "vm_carry.h"
 #include <cmath>
 #include <type_traits>
@@ -24,13 +25,15 @@ enum {
     SHUTTER = 2,        // carries a sample count
     SCHEDULED = 4,      // carries an ease and needs the frame's schedule
     LAYERS = 8,         // renders the frame's layers (floats) instead of its canvases (RGB8)
-    OWN_OUT = 16        // renders into the frame's own `out` (vm_render_halfway*), not into warp_out
+    OWN_OUT = 16,       // renders into the frame's own `out` (vm_render_halfway*), not into warp_out
+    FILTERED = 64       // carries a filter (32 is the carry calls' POINTS)
 };
 struct Call {
     const char *fn;     // the entry point, for the messages
     int what;
     const vm_viewport *vp;
     int samples, ease, color_from;
+    int filter = VM_FILTER_BILINEAR;
 };
 // ... and where its output goes: to the host (pitch in bytes for RGB8, in floats for layers; 0 = tight) and drained, or
 // left on the device with the launch timed (ms may be NULL)
@@ -83,13 +86,19 @@ int check_ease(const char *fn, int ease)
     return VM_OK;
 }
 
+int check_filter(const char *fn, int filter)
+{
+    if (filter < VM_FILTER_BILINEAR || filter > VM_FILTER_BSPLINE) return vm_fail(VM_E_INVALID, "%s: filter %d", fn, filter);
+    return VM_OK;
+}
+
 int check_color_from(const char *fn, int color_from)
 {
     if (color_from < 0 || color_from > 2) return vm_fail(VM_E_INVALID, "%s: color_from %d", fn, color_from);
     return VM_OK;
 }
 
-// the arguments a call carries, in the one order: viewport, samples, chain cap, ease, color_from
+// the arguments a call carries, in the one order: viewport, samples, chain cap, ease, filter, color_from
 int check_args(const Call &k)
 {
     if (k.what & VIEWPORT)
@@ -100,6 +109,8 @@ int check_args(const Call &k)
         if (int rc = check_chains(k.fn, k.samples, k.vp)) return rc;
     if (k.what & SCHEDULED)
         if (int rc = check_ease(k.fn, k.ease)) return rc;
+    if (k.what & FILTERED)
+        if (int rc = check_filter(k.fn, k.filter)) return rc;
     return check_color_from(k.fn, k.color_from);
 }
 
@@ -236,6 +247,44 @@ int viewport(vm_frame *f, const char *fn, int tail, const vm_viewport *vp, float
         bind_field(V, f); bind_viewport(V, vp); bind_tail(V, f, tail == LAYERS, dev);
         V.color_fa = color_fa; V.geo_fa = geo_fa; V.color_from = color_from;
         vm_launch_viewport(V, s);
+    });
+}
+
+// The cubic filters' coefficients (vm_filter.h): the Mitchell-Netravali family in B and C, each (float)(n / d) of doubles.
+//   inner: p3 = (12 - 9B - 6C) / 6, p2 = (-18 + 12B + 6C) / 6, p0 = (6 - 2B) / 6
+//   outer: q3 = (-B - 6C) / 6, q2 = (6B + 30C) / 6, q1 = (-12B - 48C) / 6, q0 = (8B + 24C) / 6
+VmFiltered cubic_of(int filter)
+{
+    static const double T[3][7][2] = {
+        {{3, 2}, {-5, 2}, {1, 1}, {-1, 2}, {5, 2}, {-4, 1}, {2, 1}},            // Catmull-Rom: B = 0, C = 1/2
+        {{7, 6}, {-2, 1}, {8, 9}, {-7, 18}, {2, 1}, {-10, 3}, {16, 9}},         // Mitchell: B = 1/3, C = 1/3
+        {{1, 2}, {-1, 1}, {2, 3}, {-1, 6}, {1, 1}, {-2, 1}, {4, 3}},            // B-spline: B = 1, C = 0
+    };
+    const double (&t)[7][2] = T[filter - VM_FILTER_CATMULL_ROM];
+    VmFiltered F{};
+    F.p3 = (float)(t[0][0] / t[0][1]); F.p2 = (float)(t[1][0] / t[1][1]); F.p0 = (float)(t[2][0] / t[2][1]);
+    F.q3 = (float)(t[3][0] / t[3][1]); F.q2 = (float)(t[4][0] / t[4][1]); F.q1 = (float)(t[5][0] / t[5][1]);
+    F.q0 = (float)(t[6][0] / t[6][1]);
+    return F;
+}
+
+// a viewport call with a filter on its last taps (vm_filter.hip).  VM_FILTER_BILINEAR is the viewport call
+// itself: the same launcher, hence the same bits
+int filtered(vm_frame *f, const char *fn, int tail, const vm_viewport *vp, int filter, float color_fa, float geo_fa, int color_from,
+             const Dest &d)
+{
+    return render_call(f, Call{fn, VIEWPORT | FILTERED | tail, vp, 0, 0, color_from, filter}, d, [&](void *dev, hipStream_t s) {
+        if (filter == VM_FILTER_BILINEAR) {
+            VmViewport V{};
+            bind_field(V, f); bind_viewport(V, vp); bind_tail(V, f, tail == LAYERS, dev);
+            V.color_fa = color_fa; V.geo_fa = geo_fa; V.color_from = color_from;
+            vm_launch_viewport(V, s);
+            return;
+        }
+        VmFiltered V = cubic_of(filter);
+        bind_field(V, f); bind_viewport(V, vp); bind_tail(V, f, tail == LAYERS, dev);
+        V.color_fa = color_fa; V.geo_fa = geo_fa; V.color_from = color_from;
+        vm_launch_filtered(V, s);
     });
 }
 
@@ -454,6 +503,34 @@ extern "C" int vm_render_viewport_layers_dev(vm_frame *f, const vm_viewport *vp,
 {
     VM_ENTER(f);
     return viewport(f, __func__, LAYERS, vp, color_fa, geo_fa, color_from, left(elapsed_ms));
+}
+
+extern "C" int vm_frame_render_viewport_filtered(vm_frame *f, const vm_viewport *vp, int filter, float color_fa, float geo_fa,
+                                                 int color_from, uint8_t *rgb_out, int pitch_bytes)
+{
+    VM_ENTER(f);
+    return filtered(f, __func__, 0, vp, filter, color_fa, geo_fa, color_from, down(rgb_out, pitch_bytes));
+}
+
+extern "C" int vm_frame_render_viewport_filtered_dev(vm_frame *f, const vm_viewport *vp, int filter, float color_fa, float geo_fa,
+                                                     int color_from, float *elapsed_ms)
+{
+    VM_ENTER(f);
+    return filtered(f, __func__, 0, vp, filter, color_fa, geo_fa, color_from, left(elapsed_ms));
+}
+
+extern "C" int vm_frame_render_viewport_filtered_layers(vm_frame *f, const vm_viewport *vp, int filter, float color_fa, float geo_fa,
+                                                        int color_from, float *out, int pitch_floats)
+{
+    VM_ENTER(f);
+    return filtered(f, __func__, LAYERS, vp, filter, color_fa, geo_fa, color_from, down(out, pitch_floats));
+}
+
+extern "C" int vm_frame_render_viewport_filtered_layers_dev(vm_frame *f, const vm_viewport *vp, int filter, float color_fa, float geo_fa,
+                                                            int color_from, float *elapsed_ms)
+{
+    VM_ENTER(f);
+    return filtered(f, __func__, LAYERS, vp, filter, color_fa, geo_fa, color_from, left(elapsed_ms));
 }
 
 extern "C" int vm_render_viewport_shutter(vm_frame *f, const vm_viewport *vp, float color_fa, float geo_open, float geo_close,

@@ -840,6 +840,27 @@ class Frame(object):
     def render_viewport_layers_dev(self, vp, color_fa, geo_fa, color_from=1):
         return self._render_dev("vm_render_viewport_layers_dev", (float(color_fa), float(geo_fa), int(color_from)), vp.struct())
 
+    def render_viewport_filtered(self, vp, filter, color_fa, geo_fa, color_from=1):
+        """render_viewport with a cubic filter on the taps that read the canvases (vm_frame_render_viewport_filtered; filter: a
+        capi.FILTER_*): Catmull-Rom, Mitchell or the cubic B-spline over 4 x 4 texels, the mean clamped to [0, 255] before
+        the rounding -> (vp.out_h, vp.out_w, 3) uint8.  FILTER_BILINEAR is render_viewport, bit for bit."""
+        s = vp.struct()
+        args = (int(filter), float(color_fa), float(geo_fa), int(color_from))
+        return self._render("vm_frame_render_viewport_filtered", args, self._viewport_grid(s), False, s)
+
+    def render_viewport_filtered_dev(self, vp, filter, color_fa, geo_fa, color_from=1):
+        return self._render_dev("vm_frame_render_viewport_filtered_dev", (int(filter), float(color_fa), float(geo_fa), int(color_from)), vp.struct())
+
+    def render_viewport_filtered_layers(self, vp, filter, color_fa, geo_fa, color_from=1):
+        """the uploaded layers through the same viewport and filter (vm_frame_render_viewport_filtered_layers): float32 as
+        render_viewport_layers gives them, NOT clamped -- a cubic filter overshoots, and a matte may leave [0, 1]"""
+        s = vp.struct()
+        args = (int(filter), float(color_fa), float(geo_fa), int(color_from))
+        return self._render("vm_frame_render_viewport_filtered_layers", args, self._viewport_grid(s), True, s)
+
+    def render_viewport_filtered_layers_dev(self, vp, filter, color_fa, geo_fa, color_from=1):
+        return self._render_dev("vm_frame_render_viewport_filtered_layers_dev", (int(filter), float(color_fa), float(geo_fa), int(color_from)), vp.struct())
+
     def render_viewport_shutter(self, vp, color_fa, geo_open, geo_close, samples, color_from=1):
         """render_viewport with motion blur (vm_render_viewport_shutter): every output pixel the mean of its vp.nx x vp.ny
         chains at each of `samples` (1..64) times between geo_open and geo_close, each clamped to [0, 1], taken in float32
