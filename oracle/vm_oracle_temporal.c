@@ -9,7 +9,15 @@
  * PARITY STATUS: unpinned by reference-run outputs (upsample.cu is CUDA with texture
  * references; nvcc is absent).  Pinned by analytic known-answer tests
  * (tests/test_oracle_kat.py: constant flows translate the field, zero flows reproduce
- * it, hole filling by rows).
+ * it, hole filling by rows) and by an independent numpy statement of the same kernels
+ * written from upsample.cu's text (tests/temporal_ref.py): tests/test_temporal_ref.py
+ * holds this file to it bit for bit -- accumulators, temp.ref, temp.mask and the
+ * in-between page of upsample() -- on every case and shape of tests/temporal_cases.py
+ * (whole-number landings, one- and two-sided holes, rows without weight, thousands of
+ * sources on one target, footprints cut by the frame, taps clamped on every side), and
+ * bounds the fixed-point sums against the exact sums of the same contributions
+ * (n 2^-33 + |S| 2^-24 per pixel).  The device is held to this file on the same cases
+ * by tests/test_gpu_temporal_stages.py.
  *
  * ORDER: temp_ref accumulates with float atomicAdd in an unspecified order
  * (upsample.cu:57-58).  Each contribution is computed in the reference's own float /

@@ -3,7 +3,14 @@ splat / initialize_temp / temporal upsample kernels bit for bit (the 64-bit fixe
 accumulation is order-independent), the flag == true energy term bit for bit in EXACT mode under
 every sweep schedule, whole video solves incl. the middle-page-outward chain bit for bit, FAST
 within its stated tolerance, and the device-side flow pyramid against the oracle's restatement
-of Pyramid::build's flow half."""
+of Pyramid::build's flow half.
+
+Each stage here runs at one shape on smooth flows.  The stages at their edges (whole-number and
+colliding landings, holes, rows without weight, footprints cut by the frame, level sizes around the
+64-wide workgroup), the term under every schedule on drawn levels (w_temp, factor_d, masks,
+constraints, boundary conditions) and a pyramid whose second level is the largest are
+tests/test_gpu_temporal_stages.py; the oracle itself is held to a numpy statement of upsample.cu
+by tests/test_temporal_ref.py (tests/temporal_ref.py, tests/temporal_cases.py)."""
 import ctypes as C
 
 import numpy as np

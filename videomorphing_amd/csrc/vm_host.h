@@ -209,7 +209,7 @@ struct vm_video {
     std::vector<float> factor_d;          // per level (pyramid.cu:470-477); factor_d0 for the placeholder
     float factor_d0 = 1.0f;
     std::vector<std::vector<vm_video_page>> pages;
-    // scratch of the splat (sized for the finest level): fixed-point accumulators, v_cur, weight
+    // scratch of the splat (sized for the largest level with temporal state): fixed-point accumulators, v_cur, weight
     VmDev<long long> acc;
     VmDev<float2> vcur;
     VmDev<float> weight;

@@ -29,6 +29,21 @@ static int check_page(const vm_video *v, int lvl, int page, const char *fn)
     return VM_OK;
 }
 
+// Pixels (pitch x rows) of the temporal scratch -- the splat accumulators, v_cur and weight of the
+// video and every pipeline lane's accumulators: the largest level that carries temporal state (a
+// tslab: all but the coarsest).  vm_video_create admits a level larger than the one before it, and
+// initialize_temp, the temporal half of upsample and video_task clear, splat and finish pitch x rows
+// entries of the level they run on.
+static size_t temporal_scratch_pixels(const vm_video *v)
+{
+    size_t n = 0;
+    for (size_t i = 0; i + 1 < v->pages.size(); ++i) {
+        const vm_level &l = v->pages[i][0].lv;
+        n = std::max(n, (size_t)l.rs * l.h);
+    }
+    return n;
+}
+
 extern "C" int vm_video_create(vm_ctx *c, int nlevels, const int *w, const int *h, const int *d,
                                const int *factor_t, int depth0, vm_video **out)
 {
@@ -97,8 +112,7 @@ extern "C" int vm_video_create(vm_ctx *c, int nlevels, const int *w, const int *
         }
     }
     {
-        const vm_level &l0 = v->pages[0][0].lv;
-        const size_t n = (size_t)l0.rs * l0.h;
+        const size_t n = temporal_scratch_pixels(v);
         int rc = v->acc.reserve(n * 3);
         if (rc == VM_OK) rc = v->vcur.reserve(n);
         if (rc == VM_OK) rc = v->weight.reserve(n);
@@ -448,8 +462,7 @@ extern "C" int vm_video_optimize_level(vm_video *v, int lvl, float max_iter, vol
 static int ensure_lanes(vm_video *v, int n)
 {
     vm_ctx *p = v->ctx;
-    const vm_level &l0 = v->pages[0][0].lv;
-    const size_t np = (size_t)l0.rs * l0.h;
+    const size_t np = temporal_scratch_pixels(v);
     while ((int)v->lanes.size() < n) {
         vm_video_lane ln;
         int rc = vm_ctx_create(p->device, &ln.c);
