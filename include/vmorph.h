@@ -930,8 +930,12 @@ int  vm_sync_result(vm_sync *s, int lvl, int frame, float *vec4);
 int  vm_sync_upload_frame(vm_sync *s, int side, int frame, const uint8_t *rgba, int pitch_bytes);
 int  vm_sync_upload_flow(vm_sync *s, int side, int frame, const float *flow_xy, int pitch_floats);
 /* render_resample_image(out, ..., fa, frame, ...) (render.cu:203-246; caller RenderWidget::
- * RenderStage1, UI/RenderWidget.cpp:205-227) with the field vm_sync_result last produced for
- * this frame (produced from level 1 if none was); rgb_out: h0 rows of pitch_bytes, RGB8 */
+ * RenderStage1, UI/RenderWidget.cpp:205-227) with this frame's field as it stands: the result of
+ * the level vm_sync_result last delivered from, if that level still holds a field, else of level 1
+ * if it holds one, else zero.  Only one frame's result is kept on the device, and every call that
+ * changes a field (load_identity, upsample_level, optimize_level, solve, set_field) drops it, so
+ * the render regenerates it whenever the frame or a field changed; rgb_out: h0 rows of
+ * pitch_bytes, RGB8 */
 int  vm_sync_render(vm_sync *s, float fa, int frame, uint8_t *rgb_out, int pitch_bytes);
 /* the same, result left on the device (timing without the download) */
 int  vm_sync_render_dev(vm_sync *s, float fa, int frame, float *elapsed_ms);

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import oracle
+from sync_cases import _bits, _cons, _level_solve, _params, _set_cons, _smooth
 from videomorphing_amd import capi, morph
 
 
@@ -17,49 +18,6 @@ def test_level_table_equals_the_oracle(vmlib):
     n = C.c_int(0)
     a = (C.c_int * 4)()
     assert vmlib.vm_sync_level_table(0, 10, 10, 8, a, a, a, 4, C.byref(n)) == capi.VM_E_INVALID
-
-
-def _cons(w0, h0, d, n=6, seed=0):
-    rng = np.random.default_rng(seed)
-    out = []
-    for _ in range(n):
-        lx, ly = int(rng.integers(2, w0 - 2)), int(rng.integers(2, h0 - 2))
-        lz = int(rng.integers(0, d))
-        out.append((lx, ly, lz, int(np.clip(lx + rng.integers(-6, 7), 0, w0 - 1)), int(np.clip(ly + rng.integers(-6, 7), 0, h0 - 1)),
-                    int(np.clip(lz + rng.integers(-2, 3), 0, d - 1))))
-    return out
-
-
-def _params(w_ui=100.0, w_tps=0.001, max_iter=20):
-    P = morph.Parameters()
-    P.w_ui, P.w_tps, P.max_iter, P.max_iter_drop_factor = w_ui, w_tps, max_iter, 2.0
-    return P
-
-
-def _set_cons(P, cons):
-    P.lp, P.rp, P.cnt = [], [], []
-    for k, c in enumerate(cons):
-        P.lp.append([morph.Conp(c[0], c[1], c[2])])
-        P.rp.append([morph.Conp(c[3], c[4], c[5])])
-        P.cnt.append([morph.Connect((k, 0), (k, 0))])
-
-
-def _level_solve(ctx, levels, lvl, cons, P, max_iter, init=None):
-    pyr = morph.SyncPyramid(ctx)
-    pyr.build_levels(levels)
-    _set_cons(P, cons)
-    th = morph.SyncThread(P, pyr)
-    th._max_iter = float(max_iter)
-    if init is None:
-        th.load_identity(lvl)
-    else:
-        pyr.set_field(lvl, *init)
-    pr = th.optimize_level(lvl)
-    return pyr.field(lvl), pr, pyr
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 @pytest.mark.gpu
@@ -184,18 +142,6 @@ def test_upsample_level_matches_the_oracle(gpu_ctx, vmlib):
         for z in range(4):
             assert np.array_equal(_bits(got[c][z]), _bits(oracle.sync_upsample(src[c][z], 45, 35, ratios[c]))), (c, z)
     assert vmlib.vm_sync_get_field(pyr._h, 2, None, None, None) == capi.VM_E_STATE  # released, as in the reference
-
-
-def _smooth(shape, seed, amp):
-    rng = np.random.default_rng(seed)
-    coarse = rng.standard_normal((shape[0] // 8 + 2, shape[1] // 8 + 2)).astype(np.float32)
-    yy = np.linspace(0, coarse.shape[0] - 1.001, shape[0])
-    xx = np.linspace(0, coarse.shape[1] - 1.001, shape[1])
-    y0, x0 = yy.astype(int), xx.astype(int)
-    fy, fx = (yy - y0)[:, None], (xx - x0)[None, :]
-    a = coarse[y0][:, x0] * (1 - fy) * (1 - fx) + coarse[y0][:, x0 + 1] * (1 - fy) * fx
-    a = a + coarse[y0 + 1][:, x0] * fy * (1 - fx) + coarse[y0 + 1][:, x0 + 1] * fy * fx
-    return (amp * a).astype(np.float32)
 
 
 @pytest.mark.gpu

@@ -21,7 +21,8 @@ struct vm_sync {
     VmDev<uchar4> video[2];
     VmDev<float2> forw[2];
     VmDev<float4> vec;
-    int vec_frame = -1;
+    int vec_frame = -1;                       // the frame vec holds, -1 once any field changed under it
+    int vec_level = 0;                        // the level vm_sync_result last delivered from (0: none yet)
     VmDev<uint8_t> out;
 };
 
@@ -117,6 +118,7 @@ extern "C" int vm_sync_load_identity(vm_sync *s, int lvl)
 {
     VM_ENTER_LOCKED(s);
     if (int rc = check_level(s, lvl, __func__)) return rc;
+    s->vec_frame = -1;
     s->f[lvl].reset();
     return alloc_field(s, lvl);
 }
@@ -129,6 +131,7 @@ extern "C" int vm_sync_upsample_level(vm_sync *s, int lvl)
     if (int rc = check_level(s, lvl, __func__)) return rc;
     const int pel = lvl + 1;
     if (pel >= (int)s->w.size() || !s->f[pel].get()) return vm_fail(VM_E_STATE, "vm_sync_upsample_level: level %d holds no field", pel);
+    s->vec_frame = -1;
     s->f[lvl].reset();
     if (int rc = alloc_field(s, lvl)) return rc;
     const float ratio[3] = {(float)s->w[lvl] / (float)s->w[pel], (float)s->h[lvl] / (float)s->h[pel], 1.0f};
@@ -207,6 +210,7 @@ extern "C" int vm_sync_optimize_level(vm_sync *s, int lvl, float max_iter, volat
     if (!s->f[lvl].get()) return vm_fail(VM_E_STATE, "vm_sync_optimize_level: level %d holds no field (load_identity / upsample_level)", lvl);
     if (!std::isfinite(max_iter) || max_iter > 1048576.0f) return vm_fail(VM_E_INVALID, "vm_sync_optimize_level: max_iter %g", (double)max_iter);
     const int passes = max_iter < 0 ? 0 : (int)std::floor(max_iter) + 1; // k = 0; while (k <= max_iter) k++
+    s->vec_frame = -1;
     VmSyncGrid g;
     g.w = s->w[lvl]; g.h = s->h[lvl]; g.d = s->d[lvl];
     g.nbx = (g.w + VM_SB_X - 1) / VM_SB_X; g.nby = (g.h + VM_SB_Y - 1) / VM_SB_Y; g.nbz = (g.d + VM_SB_Z - 1) / VM_SB_Z;
@@ -387,6 +391,7 @@ static int refresh_vec(vm_sync *s, int lvl, int frame)
                           s->h[lvl], s->w[0], s->h[0], s->vec.get(), s->ctx->stream);
     VM_HIP(hipGetLastError());
     s->vec_frame = frame;
+    s->vec_level = lvl;
     return VM_OK;
 }
 
@@ -468,8 +473,11 @@ static int render_common(vm_sync *s, float fa, int frame)
         if (!s->video[k].get() || !s->forw[k].get())
             return vm_fail(VM_E_STATE, "vm_sync_render: video %d or its flow was never uploaded", k);
     if (s->vec_frame != frame) {
-        if (s->f[1].get()) {
-            if (int rc = refresh_vec(s, 1, frame)) return rc;
+        // the level the thread last delivered from (update_result delivers every frame of one level), while it
+        // still holds a field; else the finest level
+        const int lvl = (s->vec_level > 0 && s->f[s->vec_level].get()) ? s->vec_level : (s->f[1].get() ? 1 : 0);
+        if (lvl) {
+            if (int rc = refresh_vec(s, lvl, frame)) return rc;
         } else { // Pyramid::build leaves _vector zero until the thread delivers (pyramid.cu:66-69)
             if (int rc = ensure_vec(s)) return rc;
             VM_HIP(hipMemsetAsync(s->vec.get(), 0, (size_t)w0 * h0 * sizeof(float4), s->ctx->stream));
