@@ -222,6 +222,17 @@ int  vm_dbg_pass_placement(vm_ctx *ctx, uint8_t *xcc_of_block, int n);
  * used evaluations, then the bits of the used evaluation points in order (at most 17, the rest 0).  It moves no
  * texture and touches no level state.  Bad arguments: VM_E_INVALID. */
 int  vm_dbg_golden(vm_ctx *ctx, int n, const float *params, float eps, uint32_t *out);
+/* Test hook of the same search's sampling: along a search line the points of the regime are known before any energy
+ * is, and the four octets of each half of the wave sample four of them in one pass (the ladder); a round takes its
+ * lumas from the octet that holds them.  This runs that search text on the energy f(t) = t, under which it walks the
+ * whole ladder from cc down to eps, on two small images (w x h floats each, host; 2 to 64 a side), and returns what
+ * the ladder delivered beside what the one-point taps of the generic loop sample at the same point.  n cases (1 to
+ * 65536) in one launch, a wave each; params per case (8 n floats, host): the pixel (px, py; whole numbers inside the
+ * image), the field value (vx, vy; any float), a direction (gx, gy), cc in [0, 16], one unused; eps in [2^-10, 1].
+ * out, per case 201 words (host): the count of points, then per point in search order (at most 40, the rest 0) the
+ * bits of t, of the ladder's (lx, ly) and of the one-point taps' (lx, ly).  Bad arguments: VM_E_INVALID. */
+int  vm_dbg_ladder(vm_ctx *ctx, int w, int h, const float *img0, const float *img1, int n, const float *params,
+                   float eps, uint32_t *out);
 /* Do the streams of two contexts of one device run side by side?  (The reference has one device context and one stream,
  * UI/MdiEditor.cpp:54-75; a host of this library keeps several: solver streams, compositor lanes.)  The HIP runtime
  * multiplexes a process's streams onto GPU_MAX_HW_QUEUES hardware queues, and two streams on one queue run their kernels

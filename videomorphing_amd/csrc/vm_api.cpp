@@ -300,6 +300,37 @@ extern "C" int vm_dbg_golden(vm_ctx *c, int n, const float *params, float eps, u
     return VM_OK;
 }
 
+extern "C" int vm_dbg_ladder(vm_ctx *c, int w, int h, const float *img0, const float *img1, int n, const float *params,
+                             float eps, uint32_t *out)
+{
+    if (!img0 || !img1 || !params || !out || n < 1 || n > 65536 || w < 2 || h < 2 || w > 64 || h > 64)
+        return vm_fail(VM_E_INVALID, "vm_dbg_ladder: bad argument");
+    if (!(eps >= 1.0f / 1024.0f && eps <= 1.0f)) return vm_fail(VM_E_INVALID, "vm_dbg_ladder: eps %g (2^-10 to 1)", (double)eps);
+    for (int k = 0; k < n; ++k) {
+        const float *q = params + 8 * k;
+        if (!(q[0] >= 0.0f && q[0] <= (float)(w - 1) && q[1] >= 0.0f && q[1] <= (float)(h - 1)))
+            return vm_fail(VM_E_INVALID, "vm_dbg_ladder: pixel of case %d is (%g, %g)", k, (double)q[0], (double)q[1]);
+        if (!(q[6] >= 0.0f && q[6] <= 16.0f)) return vm_fail(VM_E_INVALID, "vm_dbg_ladder: cc of case %d is %g (0 to 16)", k, (double)q[6]);
+    }
+    VM_ENTER_LOCKED(c);
+    VmDev<float> img, in;
+    VmDev<uint32_t> res;
+    const size_t px = (size_t)w * h, words = (size_t)n * VM_DBG_LADDER_WORDS;
+    if (int rc = img.reserve(2 * px)) return rc;
+    if (int rc = in.reserve((size_t)8 * n)) return rc;
+    if (int rc = res.reserve(words)) return rc;
+    hipStream_t s = c->stream;
+    VM_HIP(hipMemcpyAsync(img.get(), img0, px * sizeof(float), hipMemcpyHostToDevice, s));
+    VM_HIP(hipMemcpyAsync(img.get() + px, img1, px * sizeof(float), hipMemcpyHostToDevice, s));
+    VM_HIP(hipMemcpyAsync(in.get(), params, (size_t)8 * n * sizeof(float), hipMemcpyHostToDevice, s));
+    VM_HIP(hipMemsetAsync(res.get(), 0, words * sizeof(uint32_t), s));
+    vm_launch_dbg_ladder_fast(img.get(), w, h, n, in.get(), eps, res.get(), s);
+    VM_HIP(hipGetLastError());
+    VM_HIP(hipMemcpyAsync(out, res.get(), words * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    VM_HIP(hipStreamSynchronize(s));
+    return VM_OK;
+}
+
 extern "C" int vm_set_tuning(vm_ctx *c, int sweep_mode, int threads, int parts)
 {
     if (!c || sweep_mode < VM_SWEEP_AUTO || sweep_mode > VM_SWEEP_PASS || threads < 0 || parts < 0 ||

@@ -132,6 +132,12 @@ VM_DECL_LAUNCHERS(tex8t)  // the same with truncated weights (-DVM_EXACT=5): VM_
 // VM_DBG_GOLDEN_WORDS result words per case (tmin, fmin, n_eval, up to 17 points)
 #define VM_DBG_GOLDEN_WORDS 20
 void vm_launch_dbg_golden_fast(int n, const float *in, float eps, uint32_t *out, hipStream_t s);
+// vm_dbg_ladder (FAST sweeps only): the sampling of that search along its ladder of points, a wave per case;
+// VM_DBG_LADDER_WORDS result words per case (the count of points, then t, the batch's lumas and the one-point taps' per
+// point, up to VM_DBG_LADDER_POINTS of them)
+#define VM_DBG_LADDER_POINTS 40
+#define VM_DBG_LADDER_WORDS (1 + 5 * VM_DBG_LADDER_POINTS)
+void vm_launch_dbg_ladder_fast(const float *img, int w, int h, int n, const float *in, float eps, uint32_t *out, hipStream_t s);
 
 // compositor / result delivery (single arithmetic mode)
 void vm_launch_upscale(float2 *dst, int w0, int h0, int dpitch, const float2 *v, int w, int h,

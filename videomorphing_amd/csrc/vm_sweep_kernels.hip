@@ -932,6 +932,14 @@ __device__ __forceinline__ void taps32_finish(const TapLane &t, float texel, flo
     lx = t.odd ? o : r;
     ly = t.odd ? r : o;
 }
+// The taps of a point are the same in each of the four octets of a group's 32 lanes (a lane's role is sub & 7), so four
+// points whose positions are known together can be sampled in one pass, octet K taking point K.  ladder_take<K>:
+// octet K's value in every lane of its 32 (ds_swizzle, bit-mask mode: lane <- (lane & 7) | 8 K inside 32 lanes).
+template <int K>
+__device__ __forceinline__ float ladder_take(float x)
+{
+    return __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(x), 0x07 | (K << 8)));
+}
 // (the evaluations along the search line: one after the other, the lane's last texel kept)
 __device__ __forceinline__ void taps32(const VmLevelView &L, const TapLane &t, const PixelCtx &c, float vx, float vy,
                                        TexelKeep &keep, float &lx, float &ly)
@@ -1125,36 +1133,94 @@ __device__ __forceinline__ bool decide32(const VmLevelView &L, const VmKParams &
 //     the top; left for good the first time fx < fb.  (A round whose guess fails is the loop's last: the loop test that
 //     follows it is the guess-held test.)  On the 120x68 level of the 1080p pair every search starts here, 98.9 % of
 //     all rounds run here and 5 % of the searches leave (profiles/line_search_regime.md).
+//     The ladder: while the regime lasts the points are b0 R^k, known before any energy is.  The taps of a point are
+//     the same in each of the four octets of a half (tap_lane_make: a lane's role is sub & 7), so octet o samples the
+//     point of round 4 n + o (BATCH_(t): this lane's point; round 0 is the initial pair) and a round takes its lumas
+//     from the octet that holds them (EVALB_(k, t, flo, fhi): EVAL2_ with the lumas of octet k of the last batch).
+//     One sampling pass per four rounds; the multiplies that make the points are the round's own, in its order.  The
+//     loop is unrolled by four so that k is a constant; samples past the search's end are never read.
 //   generic loop: per round the point the search needs now AND the point it needs next if the coming comparison goes
 //     the way this one went.  It continues from the regime loop's state; a is 0 until its first "lower at x" step.
+//     It samples its own points (EVAL2_).
+
+// the point octet `oct` of a half samples in a batch: l0 .. l3 the lower half's four, h0 .. h3 the upper half's
+__device__ __forceinline__ float ladder_pick(bool hi, int oct, float l0, float h0, float l1, float h1, float l2, float h2,
+                                             float l3, float h3)
+{
+    const float p0 = hi ? h0 : l0, p1 = hi ? h1 : l1, p2 = hi ? h2 : l2, p3 = hi ? h3 : l3;
+    const float p01 = (oct & 1) ? p1 : p0, p23 = (oct & 1) ? p3 : p2;
+    return (oct & 2) ? p23 : p01;
+}
+// round K_'s lumas (LX_, LY_) out of the batch (BLX_, BLY_: this octet's own sample).  Octet 0's are taken right after
+// the pass that made them; the others were fetched a round ahead (PLX_, PLY_), so that their swizzles wait under the
+// previous round's 32-lane sum and a consuming round gains no wait of its own.
+#define LADDER_FETCH(K_, BLX_, BLY_, PLX_, PLY_, LX_, LY_)  \
+    {                                                       \
+        if ((K_) == 0) {                                    \
+            (LX_) = ladder_take<0>(BLX_);                   \
+            (LY_) = ladder_take<0>(BLY_);                   \
+        } else {                                            \
+            (LX_) = (PLX_);                                 \
+            (LY_) = (PLY_);                                 \
+        }                                                   \
+        if ((K_) != 3) {                                    \
+            (PLX_) = ladder_take<((K_) + 1) & 3>(BLX_);     \
+            (PLY_) = ladder_take<((K_) + 1) & 3>(BLY_);     \
+        }                                                   \
+    }
 #define GOLDEN64_NO_TRACE(T_)
-#define GOLDEN64(EVAL2_, TRACE_, CC_, EPS_, HI_, NEVAL_, TMIN_, FMIN_)                                                 \
+#define GOLDEN64_NO_BATCH(T_)
+// one round of the regime loop; its lumas sit in octet K_ of the batch
+#define GOLDEN64_REGIME_ROUND(EVALB_, TRACE_, K_, CC_, EPS_, HI_, NEVAL_)                                              \
+    {                                                                                                                  \
+        const float xn = b * R, xn2 = xn * R;                                                                          \
+        float f1, f2;                                                                                                  \
+        EVALB_(K_, (HI_) ? xn2 : xn, f1, f2);                                                                          \
+        TRACE_(xn)                                                                                                     \
+        /* after the step (cc, x, b) <- (x, b, xn), (fx, fb) <- (fb, f1): does the search go on, the same way? */      \
+        const bool held = x > (EPS_) && !(fb < f1);                                                                    \
+        if (held) { /* the guess held: f2 is the next step's evaluation, two shifts in one */                          \
+            TRACE_(xn2)                                                                                                \
+        }                                                                                                              \
+        (NEVAL_) += held ? 2 : 1;                                                                                      \
+        (CC_) = held ? b : x;                                                                                          \
+        x = held ? xn : b;                                                                                             \
+        b = held ? xn2 : xn;                                                                                           \
+        fx = held ? f1 : fb;                                                                                           \
+        fb = held ? f2 : f1;                                                                                           \
+    }
+#define GOLDEN64(EVAL2_, BATCH_, EVALB_, TRACE_, CC_, EPS_, HI_, OCT_, NEVAL_, TMIN_, FMIN_)                           \
     {                                                                                                                  \
         const float R = 0.618033989f, C = 1.0f - R;                                                                    \
         float a = 0;                                                                                                   \
         float b = (CC_) * C, x = b * R + (CC_) * C;                                                                    \
         float fb, fx;                                                                                                  \
-        EVAL2_((HI_) ? x : b, fb, fx);                                                                                 \
+        { /* the first batch: the initial pair and the points of the regime loop's rounds 1 to 3 */                    \
+            const float q1 = b * R, q2 = q1 * R, q3 = q2 * R, q4 = q3 * R, q5 = q4 * R, q6 = q5 * R;                   \
+            BATCH_(ladder_pick((HI_), (OCT_), b, x, q1, q2, q3, q4, q5, q6))                                           \
+        }                                                                                                              \
+        EVALB_(0, (HI_) ? x : b, fb, fx);                                                                              \
         TRACE_(b)                                                                                                      \
         TRACE_(x)                                                                                                      \
         (NEVAL_) += 2;                                                                                                 \
-        _Pragma("unroll 1") while ((CC_) > (EPS_) && !(fx < fb))                                                       \
-        {                                                                                                              \
-            const float xn = b * R, xn2 = xn * R;                                                                      \
-            float f1, f2;                                                                                              \
-            EVAL2_((HI_) ? xn2 : xn, f1, f2);                                                                          \
-            TRACE_(xn)                                                                                                 \
-            /* after the step (cc, x, b) <- (x, b, xn), (fx, fb) <- (fb, f1): does the search go on, the same way? */  \
-            const bool held = x > (EPS_) && !(fb < f1);                                                                \
-            if (held) { /* the guess held: f2 is the next step's evaluation, two shifts in one */                      \
-                TRACE_(xn2)                                                                                            \
+        _Pragma("unroll 1") for (;;) { /* the regime loop, a batch per trip */                                         \
+            if (!((CC_) > (EPS_) && !(fx < fb)))                                                                       \
+                break;                                                                                                 \
+            GOLDEN64_REGIME_ROUND(EVALB_, TRACE_, 1, CC_, EPS_, HI_, NEVAL_)                                           \
+            if (!((CC_) > (EPS_) && !(fx < fb)))                                                                       \
+                break;                                                                                                 \
+            GOLDEN64_REGIME_ROUND(EVALB_, TRACE_, 2, CC_, EPS_, HI_, NEVAL_)                                           \
+            if (!((CC_) > (EPS_) && !(fx < fb)))                                                                       \
+                break;                                                                                                 \
+            GOLDEN64_REGIME_ROUND(EVALB_, TRACE_, 3, CC_, EPS_, HI_, NEVAL_)                                           \
+            if (!((CC_) > (EPS_) && !(fx < fb)))                                                                       \
+                break;                                                                                                 \
+            { /* the next batch: the points of the coming four rounds, should every guess hold */                      \
+                const float q1 = b * R, q2 = q1 * R, q3 = q2 * R, q4 = q3 * R, q5 = q4 * R, q6 = q5 * R, q7 = q6 * R,  \
+                            q8 = q7 * R;                                                                               \
+                BATCH_(ladder_pick((HI_), (OCT_), q1, q2, q3, q4, q5, q6, q7, q8))                                     \
             }                                                                                                          \
-            (NEVAL_) += held ? 2 : 1;                                                                                  \
-            (CC_) = held ? b : x;                                                                                      \
-            x = held ? xn : b;                                                                                         \
-            b = held ? xn2 : xn;                                                                                       \
-            fx = held ? f1 : fb;                                                                                       \
-            fb = held ? f2 : f1;                                                                                       \
+            GOLDEN64_REGIME_ROUND(EVALB_, TRACE_, 0, CC_, EPS_, HI_, NEVAL_)                                           \
         }                                                                                                              \
         _Pragma("unroll 1") for (;;)                                                                                   \
         {                                                                                                              \
@@ -1218,13 +1284,17 @@ __device__ __forceinline__ bool decide32(const VmLevelView &L, const VmKParams &
 // multiplies and the shifts of (cc, x, b) and (fx, fb), without the selects on the comparison and on the guess -- the
 // regime loop, 114-117 instructions a round against 130 / 139.  The first time the energy at x is the lower one the
 // search falls into the generic loop with its state as it stands, and stays there.
+// In the regime loop the points are known ahead, and the taps of a point are the same in each octet of a half: one
+// sampling pass serves four rounds, a round's lumas come from the octet that holds them (the ladder, GOLDEN64 above;
+// about 80 instructions in a round that consumes, profiles/line_search_ladder.md).  LADDER = false: every round samples
+// its own point, as the generic loop does (the TILE kernels: their tightest form would spill one register more).
 // (Round 4 tried FOUR points per round -- the wave's four 16-lane rows, two window neighbours per lane, the two
 // 16-lane trees of the 32-lane sum side by side: the gradient in one round, two golden-section steps per round
 // for certain and a third under the same guess; bit-identical, all schedule-equality tests green.  Measured: no
 // gain -- PASS 11.37 vs 11.15 us per phase, STEP 14.5 vs 14.1 (tools/dev_pass.py).  A round then costs ~255
 // instructions (two SSIM terms, two trees, 12 v_readlane broadcasts, the bookkeeping of a three-step speculation)
 // against ~150 here for ~2.7 instead of ~1.9 steps: 94 against 79 instructions per step of the search.  Removed.)
-template <bool INTERIOR, class Ring>
+template <bool INTERIOR, bool LADDER = true, class Ring>
 __device__ __forceinline__ bool decide64(const VmLevelView &L, const VmKParams &P, const Nb1 &nb, const Ring &ring,
                                          const PixelCtx &c, int sub, bool hi, float2 &step, float2 &luma,
                                          uint32_t &n_eval)
@@ -1291,9 +1361,30 @@ __device__ __forceinline__ bool decide64(const VmLevelView &L, const VmKParams &
             f_ = fmaf(WT, (fabsf(nvx_ - c.tref.x) + fabsf(nvy_ - c.tref.y)) - T0, f_); \
         halves(f_, (FLO_), (FHI_));                                                    \
     }
+    // the ladder: this lane's octet samples its point of the batch (the lane's own taps, as ELINE2 makes them) ...
+    float blx, bly; // the lumas at this octet's point
+    float plx, ply; // the coming round's, fetched a round ahead (LADDER_FETCH; round 0 of a batch sets them first)
+#define LADDER2(T_)                                                                             \
+    if (LADDER)                                                                                 \
+        taps32(L, tl, c, fmaf(gx, (T_), c.v.x), fmaf(gy, (T_), c.v.y), keep, blx, bly);
+    // ... and ELINE2 with the lumas of octet K_ of the batch; T_ is the point they were sampled at
+#define ELINE2B(K_, T_, FLO_, FHI_)                                                    \
+    {                                                                                  \
+        const float nvx_ = fmaf(gx, (T_), c.v.x), nvy_ = fmaf(gy, (T_), c.v.y);        \
+        if (LADDER)                                                                    \
+            LADDER_FETCH(K_, blx, bly, plx, ply, lx, ly)                               \
+        else                                                                           \
+            taps32(L, tl, c, nvx_, nvy_, keep, lx, ly);                                \
+        float f_ = fmaf(WS, change32<INTERIOR>(P, nb, c, lx, ly), (T_) * fmaf(Q2, (T_), Q1)); \
+        if (has_temp)                                                                  \
+            f_ = fmaf(WT, (fabsf(nvx_ - c.tref.x) + fabsf(nvy_ - c.tref.y)) - T0, f_); \
+        halves(f_, (FLO_), (FHI_));                                                    \
+    }
     float tmin, fmin;
-    GOLDEN64(ELINE2, GOLDEN64_NO_TRACE, cc, P.eps, hi, n_eval, tmin, fmin)
+    GOLDEN64(ELINE2, LADDER2, ELINE2B, GOLDEN64_NO_TRACE, cc, P.eps, hi, sub >> 3, n_eval, tmin, fmin)
 #undef ELINE2
+#undef ELINE2B
+#undef LADDER2
     if (!(fmin < 0))
         return false;
     step = make_float2(gx * tmin, gy * tmin);
@@ -1702,11 +1793,11 @@ __device__ __forceinline__ bool tile_sweep(TileLds &S, const VmLevelView &L, con
                         uint32_t n_eval = 0;
                         if (wave_interior) {
                             nb1_load<true>(nb, L, src, c, sub);
-                            ok = wide ? decide64<true>(L, P, nb, RingGlobal{L.v}, c, sub, (tid & 32) != 0, step, luma, n_eval)
+                            ok = wide ? decide64<true, false>(L, P, nb, RingGlobal{L.v}, c, sub, (tid & 32) != 0, step, luma, n_eval)
                                       : decide32<true>(L, P, nb, RingGlobal{L.v}, c, sub, step, luma, n_eval);
                         } else {
                             nb1_load<false>(nb, L, src, c, sub);
-                            ok = wide ? decide64<false>(L, P, nb, RingGlobal{L.v}, c, sub, (tid & 32) != 0, step, luma, n_eval)
+                            ok = wide ? decide64<false, false>(L, P, nb, RingGlobal{L.v}, c, sub, (tid & 32) != 0, step, luma, n_eval)
                                       : decide32<false>(L, P, nb, RingGlobal{L.v}, c, sub, step, luma, n_eval);
                         }
                         if (writer)
@@ -4247,8 +4338,10 @@ __global__ __launch_bounds__(64) void SUF(k_dbg_golden)(const float *__restrict_
             o[3 + n_pt] = __float_as_uint(T_);                  \
         ++n_pt;                                                 \
     }
+#define EGOLDENB(K_, T_, FLO_, FHI_) EGOLDEN(T_, FLO_, FHI_) // no taps: nothing to batch
     float tmin, fmin;
-    GOLDEN64(EGOLDEN, TGOLDEN, cc, eps, hi, n_eval, tmin, fmin)
+    GOLDEN64(EGOLDEN, GOLDEN64_NO_BATCH, EGOLDENB, TGOLDEN, cc, eps, hi, 0, n_eval, tmin, fmin)
+#undef EGOLDENB
 #undef EGOLDEN
 #undef TGOLDEN
     if (threadIdx.x == 0) {
@@ -4256,6 +4349,81 @@ __global__ __launch_bounds__(64) void SUF(k_dbg_golden)(const float *__restrict_
         o[1] = __float_as_uint(fmin);
         o[2] = n_eval;
     }
+}
+
+// vm_dbg_ladder: the sampling of decide64's search on its own, one wave per case.  The search is GOLDEN64 with the
+// ladder's hooks as decide64 gives them (the batch by this octet's taps32, a round's lumas by LADDER_FETCH); the energy
+// is f(t) = t, under which every guess holds, so the search walks its whole ladder down to eps.  Beside each pair of
+// lumas the batch delivers, the one-point taps32 of the generic loop samples the same point (a TexelKeep of its own).
+// img: two w x h images, one after the other; in: px, py, vx, vy, gx, gy, cc of case k at in[8 k ..]; out, per case
+// VM_DBG_LADDER_WORDS words: the count of points, then per point in search order (the lower half's, then the upper
+// half's of a round) the bits of t, of (lx, ly) by the batch and of (lx, ly) by the one-point taps.
+__global__ __launch_bounds__(64) void SUF(k_dbg_ladder)(const float *__restrict__ img, int w, int h, const float *__restrict__ in,
+                                                        float eps, uint32_t *__restrict__ out)
+{
+    const int k = (int)blockIdx.x;
+    const bool hi = (threadIdx.x & 32) != 0;
+    const int sub = (int)threadIdx.x & 31;
+    const float *q = in + 8 * k;
+    VmLevelView L = {};
+    L.w = w;
+    L.h = h;
+    L.rs = w;
+    L.img0 = img;
+    L.img1 = img + w * h;
+    PixelCtx c = {};
+    c.px = (int)q[0];
+    c.py = (int)q[1];
+    c.v = make_float2(q[2], q[3]);
+    const float gx = q[4], gy = q[5];
+    float cc = q[6];
+    uint32_t *o = out + (size_t)k * VM_DBG_LADDER_WORDS;
+    const TapLane tl = tap_lane_make(L, sub);
+    TexelKeep keep, keep_one;
+    float blx, bly, plx = 0.0f, ply = 0.0f;
+    uint32_t n_eval = 0;
+    int n_pt = 0;
+    // a round's two points: lane 0 of each half writes its own
+#define RLADDER(T_, LX_, LY_)                                                                                   \
+    {                                                                                                           \
+        float ox_, oy_;                                                                                         \
+        taps32(L, tl, c, fmaf(gx, (T_), c.v.x), fmaf(gy, (T_), c.v.y), keep_one, ox_, oy_);                     \
+        const int s_ = n_pt + (hi ? 1 : 0);                                                                     \
+        if (sub == 0 && s_ < VM_DBG_LADDER_POINTS) {                                                            \
+            o[1 + 5 * s_] = __float_as_uint(T_);                                                                \
+            o[2 + 5 * s_] = __float_as_uint(LX_);                                                               \
+            o[3 + 5 * s_] = __float_as_uint(LY_);                                                               \
+            o[4 + 5 * s_] = __float_as_uint(ox_);                                                               \
+            o[5 + 5 * s_] = __float_as_uint(oy_);                                                               \
+        }                                                                                                       \
+        n_pt += 2;                                                                                              \
+    }
+#define BLADDER(T_) taps32(L, tl, c, fmaf(gx, (T_), c.v.x), fmaf(gy, (T_), c.v.y), keep, blx, bly);
+#define ELADDERB(K_, T_, FLO_, FHI_)                     \
+    {                                                    \
+        float lx_, ly_;                                  \
+        LADDER_FETCH(K_, blx, bly, plx, ply, lx_, ly_)   \
+        RLADDER(T_, lx_, ly_)                            \
+        halves((T_), (FLO_), (FHI_));                    \
+    }
+    // (the generic loop's evaluation: under f(t) = t the search never gets there with cc - a > eps)
+#define ELADDER(T_, FLO_, FHI_)                                                              \
+    {                                                                                        \
+        float lx_, ly_;                                                                      \
+        taps32(L, tl, c, fmaf(gx, (T_), c.v.x), fmaf(gy, (T_), c.v.y), keep, lx_, ly_);      \
+        RLADDER(T_, lx_, ly_)                                                                \
+        halves((T_), (FLO_), (FHI_));                                                        \
+    }
+    float tmin, fmin;
+    GOLDEN64(ELADDER, BLADDER, ELADDERB, GOLDEN64_NO_TRACE, cc, eps, hi, sub >> 3, n_eval, tmin, fmin)
+#undef ELADDER
+#undef ELADDERB
+#undef BLADDER
+#undef RLADDER
+    (void)tmin;
+    (void)fmin;
+    if (threadIdx.x == 0)
+        o[0] = (uint32_t)n_pt;
 }
 #endif
 
@@ -4407,5 +4575,11 @@ int SUF(vm_pass_resident_blocks)(int device)
 void vm_launch_dbg_golden_fast(int n, const float *in, float eps, uint32_t *out, hipStream_t s)
 {
     hipLaunchKernelGGL(SUF(k_dbg_golden), dim3(n), dim3(64), 0, s, in, eps, out);
+}
+// vm_dbg_ladder: n ladders in one launch, a wave each (`img`: 2 w h floats, `in`: 8 n floats, `out`: n x
+// VM_DBG_LADDER_WORDS words, device)
+void vm_launch_dbg_ladder_fast(const float *img, int w, int h, int n, const float *in, float eps, uint32_t *out, hipStream_t s)
+{
+    hipLaunchKernelGGL(SUF(k_dbg_ladder), dim3(n), dim3(64), 0, s, img, w, h, in, eps, out);
 }
 #endif
