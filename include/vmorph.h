@@ -450,9 +450,9 @@ int  vm_host_unregister(void *ptr);
 /* ... and frame `frame` of vm_video_result (above), computed on the device */
 int  vm_frame_set_v_from_video(vm_frame *f, vm_video *v, int lvl, int frame);
 /* The render calls -- every vm_render_* from here to the viewports over a shutter, the vm_frame_render_viewport_filtered*
- * among them, and each one's _dev twin -- refuse in
+ * and the vm_frame_render_multiband* among them, and each one's _dev twin -- refuse in
  * one order: the handle (VM_E_INVALID); a NULL output of a call that downloads (VM_E_INVALID); the arguments -- viewport,
- * samples, samples * nx * ny, ease, filter, color_from (VM_E_INVALID); the frame's state -- no schedule, then no layers
+ * samples, samples * nx * ny, bands, ease, filter, color_from (VM_E_INVALID); the frame's state -- no schedule, then no layers
  * (VM_E_STATE); a pitch below the row (VM_E_INVALID).  Of two faults at once the earlier one answers. */
 /* render_halfway_image, Algorithm/render.cu:62-96 (UI/RenderWidget.h:52-57);
  * rgb_out: h rows of w RGB8 pixels, pitch in bytes (0 = tight) */
@@ -767,6 +767,70 @@ int  vm_frame_render_viewport_filtered_layers(vm_frame *f, const vm_viewport *vp
 /* same (render.cu:16-60, UI/RenderWidget.cpp:229-266), output left on the device (for timing) */
 int  vm_frame_render_viewport_filtered_layers_dev(vm_frame *f, const vm_viewport *vp, int filter, float color_fa, float geo_fa,
                                                   int color_from, float *elapsed_ms);
+/* ---- multiband blending: the two plates blended band by band ----------------
+ * Every render call above blends the two warped plates under ONE per-pixel weight, c0 * (1 - k) + c1 * k: a dissolve around
+ * color_fa = 0.5 shows both plates' fine detail at once wherever the correspondence is a pixel off, and the colour seam of a
+ * wipe is as wide as the schedule's ramp at every frequency.  The calls of this section are the multiresolution spline of
+ * Burt and Adelson (1983) on the renderer's chain (kernel_render_halfway_image, Algorithm/render.cu:16-60;
+ * UI/RenderWidget.cpp:229-266): the plates c0, c1 -- exactly what the uniform and the transition calls form before they
+ * blend, RGB from the extended canvases or the layers of vm_frame_upload_layers, tight or extended -- and the colour weight
+ * A (color_fa everywhere, or the per-pixel k of the schedule) are reduced L times; band l of both plates is blended under
+ * the weight of level l, sharpened about 0.5 by sharp[l], and the bands are summed from the coarsest up.  In float32,
+ * without contraction, in this order (fold reflects without repeating the edge sample: -1 -> 1, n -> n - 2):
+ *   reduce, n -> (n + 1) / 2, along x and then along y, t(d) the sample at fold(2 i + d, n):
+ *     (0.0625f * (t(-2) + t(2)) + 0.25f * (t(-1) + t(1))) + 0.375f * t(0)
+ *   expand, m -> n, along x and then along y, i = o / 2, t(d) the sample at fold(i + d, m):
+ *     o even: 0.125f * (t(-1) + t(1)) + 0.75f * t(0)        o odd: 0.5f * (t(0) + t(1))
+ *   G0, G1, M: c0, c1, A reduced 0..L times;  for l = L down to 0:
+ *     m = fminf(fmaxf(0.5f + (M[l] - 0.5f) * sharp[l], 0), 1)
+ *     b0, b1 = G0[l], G1[l] at l == L, else G0[l] - expand(G0[l + 1]), G1[l] - expand(G1[l + 1])
+ *     B = b0 * (1 - m) + b1 * m;   R = B at l == L, else expand(R) + B
+ * Layer calls return R as it is, neither clamped nor rounded; RGB8 calls (uint8)((double)fminf(fmaxf(R, 0), 255) + 0.5): a
+ * sharpened band can overshoot, and a NaN becomes 0.  With sharp = 1 everywhere this is the Burt-Adelson spline with mask A;
+ * with sharp[l] > 1 band l crosses over in the middle 1 / sharp[l] of the transition, so that detail stays single-exposed
+ * except near the midpoint.  A weight of exactly 0 (or 1) gives m = 0 (or 1) on every band: the call reconstructs c0 (c1).
+ * There is no color_from: the calls are the blend.  They refuse in the render calls' order, the arguments being: bands NULL,
+ * levels outside 1..VM_MULTIBAND_MAX_LEVELS, a coarsest level below 2 in either dimension, a sharp entry that is not finite or
+ * below 1, an ease other than the two known (VM_E_INVALID each).  The pyramids are scratch of the frame, allocated on first
+ * use and freed with it; v, the path, the canvases, the layers and the schedule are not changed.  The vm_render_* names are a
+ * closed table; these calls carry the vm_frame_ prefix as the filtered viewport calls do.  Not in this section, deliberately:
+ * multiband forms of the viewport, shutter and filtered families, and bands blended over time. */
+#define VM_MULTIBAND_MAX_LEVELS 8
+typedef struct {
+    int   levels;                               /* L in 1..VM_MULTIBAND_MAX_LEVELS */
+    float sharp[VM_MULTIBAND_MAX_LEVELS + 1];   /* sharp[0..L] are used: band 0 the finest, band L the low-pass residual */
+} vm_bands;
+/* vm_render_halfway with color_from = 1, band by band (render.cu:16-60, UI/RenderWidget.cpp:229-266): RGB8 from the
+ * Poisson-extended canvases.  rgb_out: h rows of w RGB8 pixels, pitch in bytes (0 = tight). */
+int  vm_frame_render_multiband(vm_frame *f, const vm_bands *bands, float color_fa, float geo_fa, uint8_t *rgb_out, int pitch_bytes);
+/* same (render.cu:16-60, UI/RenderWidget.cpp:229-266), output left on the device (for timing) */
+int  vm_frame_render_multiband_dev(vm_frame *f, const vm_bands *bands, float color_fa, float geo_fa, float *elapsed_ms);
+/* vm_render_layers band by band (render.cu:16-60, UI/RenderWidget.cpp:229-266).  out: (h, w, channels) floats, pitch in
+ * floats (0 = tight).  VM_E_STATE on a frame that holds no layers. */
+int  vm_frame_render_multiband_layers(vm_frame *f, const vm_bands *bands, float color_fa, float geo_fa, float *out, int pitch_floats);
+/* same (render.cu:16-60, UI/RenderWidget.cpp:229-266), output left on the device (for timing) */
+int  vm_frame_render_multiband_layers_dev(vm_frame *f, const vm_bands *bands, float color_fa, float geo_fa, float *elapsed_ms);
+/* vm_render_transition band by band (render.cu:16-60, UI/RenderWidget.cpp:229-266): the chain under the geometry schedule,
+ * A the colour rate k of every output pixel.  VM_E_STATE on a frame that holds no schedule. */
+int  vm_frame_render_multiband_transition(vm_frame *f, const vm_bands *bands, float t, int ease, uint8_t *rgb_out, int pitch_bytes);
+/* same (render.cu:16-60, UI/RenderWidget.cpp:229-266), output left on the device (for timing) */
+int  vm_frame_render_multiband_transition_dev(vm_frame *f, const vm_bands *bands, float t, int ease, float *elapsed_ms);
+/* vm_render_transition_layers band by band (render.cu:16-60, UI/RenderWidget.cpp:229-266).  VM_E_STATE on a frame that
+ * holds no schedule, then on one that holds no layers. */
+int  vm_frame_render_multiband_transition_layers(vm_frame *f, const vm_bands *bands, float t, int ease, float *out, int pitch_floats);
+/* same (render.cu:16-60, UI/RenderWidget.cpp:229-266), output left on the device (for timing) */
+int  vm_frame_render_multiband_transition_layers_dev(vm_frame *f, const vm_bands *bands, float t, int ease, float *elapsed_ms);
+/* Diagnostic: one level of what the frame's last multiband call left (the pyramids of render.cu:16-60's two plates; the
+ * reference has no counterpart), for tests that pin the kernels stage by stage.  out: tight (h_l, w_l, C) floats, C = 3
+ * after an RGB8 call, the layers' channels after a layer call; tight (h_l, w_l) floats for the mask.  VM_E_STATE if the frame
+ * has made no multiband call; VM_E_INVALID for a NULL out, an unknown `what`, a level outside 0..L of that call, and for
+ * VM_MB_OUT at level 0 after an RGB8 call (its R is the call's bytes).  VM_MB_OUT at level 0 reads the layer call's own
+ * output buffer: ask before the frame's next render call. */
+#define VM_MB_G0   0   /* Gaussian level of c0 */
+#define VM_MB_G1   1   /* ... of c1 */
+#define VM_MB_MASK 2   /* M[l], before sharpening */
+#define VM_MB_OUT  3   /* R at level l, levels 1..L; level 0 too after a layers call */
+int  vm_dbg_multiband_level(vm_frame *f, int what, int level, float *out);
 /* ---- viewports over a shutter, uniformly and under a transition schedule ----
  * The viewport section composed with the two motion-blur sections: a viewer that zooms into a motion-blurred frame, a
  * half-size proxy of a wipe, a delivery at another size with a shutter, an overscan render of a frame that holds a

@@ -62,6 +62,38 @@ enum class Filter : int {
     BSpline = VM_FILTER_BSPLINE             // B = 1, C = 0: never overshoots, blurs
 };
 
+// the band table of a multiband call (vm_bands): `levels` reductions, one sharpening factor >= 1 per band, band 0 the
+// finest, band `levels` the low-pass residual.  The tables are the Python facade's: computed in double, rounded once
+struct Bands : vm_bands {
+    // the Burt-Adelson spline: every band crosses over with the weight plane of its level as it is
+    static Bands linear(int levels_)
+    {
+        Bands b{};
+        b.levels = levels_;
+        for (int l = 0; l <= VM_MULTIBAND_MAX_LEVELS; ++l) b.sharp[l] = 1.0f;
+        return b;
+    }
+    // detail switches quickly, colour dissolves slowly: finest ^ ((levels - l) / levels) on band l, 1 on the residual
+    static Bands sharpen(int levels_, double finest)
+    {
+        Bands b = linear(levels_);
+        for (int l = 0; l < levels_ && l <= VM_MULTIBAND_MAX_LEVELS; ++l)
+            b.sharp[l] = (float)std::pow(finest, (double)(levels_ - l) / levels_);
+        return b;
+    }
+    // the deepest linear table, of at most `most` levels, whose coarsest level of a w x h frame is still at least 2 x 2
+    // (0 levels for a frame too small to have one: the library refuses it)
+    static Bands for_size(int w, int h, int most = 5)
+    {
+        int levels_ = 0;
+        while (levels_ < most && levels_ < VM_MULTIBAND_MAX_LEVELS && (w + 1) / 2 >= 2 && (h + 1) / 2 >= 2) {
+            w = (w + 1) / 2; h = (h + 1) / 2;
+            ++levels_;
+        }
+        return linear(levels_);
+    }
+};
+
 class Frame {
 public:
     Frame(Context &ctx, int w, int h, int ex) : w_(w), h_(h), ex_(ex) { check(vm_frame_create(ctx.handle(), w, h, ex, &f_)); }
@@ -218,6 +250,38 @@ public:
     { return rendered<float>(layer_floats(&vp), vm_frame_render_viewport_filtered_layers, &vp, (int)filter, color_fa, geo_fa, color_from); }
     float render_viewport_filtered_layers_dev(const Viewport &vp, Filter filter, float color_fa, float geo_fa, int color_from = 1)
     { return timed(vm_frame_render_viewport_filtered_layers_dev, &vp, (int)filter, color_fa, geo_fa, color_from); }
+    // the two plates blended band by band (vm_frame_render_multiband): render_halfway_image with color_from = 1 under the
+    // multiresolution spline of `bands`, clamped to [0, 255] before the rounding: (h, w, 3) bytes
+    std::vector<unsigned char> render_multiband(const Bands &bands, float color_fa, float geo_fa)
+    { return rendered<unsigned char>(rgb_bytes(), vm_frame_render_multiband, &bands, color_fa, geo_fa); }
+    float render_multiband_dev(const Bands &bands, float color_fa, float geo_fa)
+    { return timed(vm_frame_render_multiband_dev, &bands, color_fa, geo_fa); }
+    // the layers under the same bands: (h, w, channels) floats, neither clamped nor rounded
+    std::vector<float> render_multiband_layers(const Bands &bands, float color_fa, float geo_fa)
+    { return rendered<float>(layer_floats(), vm_frame_render_multiband_layers, &bands, color_fa, geo_fa); }
+    float render_multiband_layers_dev(const Bands &bands, float color_fa, float geo_fa)
+    { return timed(vm_frame_render_multiband_layers_dev, &bands, color_fa, geo_fa); }
+    // ... under the schedule at time t: the colour rate k of every output pixel is the weight the bands smooth
+    std::vector<unsigned char> render_multiband_transition(const Bands &bands, float t, int ease = VM_EASE_LINEAR)
+    { return rendered<unsigned char>(rgb_bytes(), vm_frame_render_multiband_transition, &bands, t, ease); }
+    float render_multiband_transition_dev(const Bands &bands, float t, int ease = VM_EASE_LINEAR)
+    { return timed(vm_frame_render_multiband_transition_dev, &bands, t, ease); }
+    std::vector<float> render_multiband_transition_layers(const Bands &bands, float t, int ease = VM_EASE_LINEAR)
+    { return rendered<float>(layer_floats(), vm_frame_render_multiband_transition_layers, &bands, t, ease); }
+    float render_multiband_transition_layers_dev(const Bands &bands, float t, int ease = VM_EASE_LINEAR)
+    { return timed(vm_frame_render_multiband_transition_layers_dev, &bands, t, ease); }
+    // diagnostic: one level of what the last multiband call left (VM_MB_G0, _G1, _MASK, _OUT): tight (h_l, w_l, C) floats,
+    // C = 3 after an RGB8 call; (h_l, w_l) for the mask
+    std::vector<float> multiband_level(int what, int level)
+    {
+        int w = w_, h = h_;
+        for (int l = 0; l < level && l < VM_MULTIBAND_MAX_LEVELS; ++l) {
+            w = (w + 1) / 2; h = (h + 1) / 2;
+        }
+        std::vector<float> out((size_t)w * h * 4);      // (at most four channels: the library knows the last call's)
+        check(vm_dbg_multiband_level(f_, what, level, out.data()));
+        return out;
+    }
     // a viewport over a shutter (vm_render_viewport_shutter): every output pixel the mean of its vp.nx x vp.ny chains at
     // each of `samples` times between geo_open and geo_close; samples * vp.nx * vp.ny may be 256 at most
     std::vector<unsigned char> render_viewport_shutter(const Viewport &vp, float color_fa, float geo_open, float geo_close,

@@ -58,6 +58,7 @@ UNITS = [
     ("vm_vshutter.hip", "vm_vshutter_kernels.o", ["-ffp-contract=off"]),
     ("vm_filter.hip", "vm_filter_kernels.o", ["-ffp-contract=off"]),
     ("vm_carry.hip", "vm_carry_kernels.o", ["-ffp-contract=off"]),
+    ("vm_multiband.hip", "vm_multiband_kernels.o", ["-ffp-contract=off"]),
     ("vm_poisson.hip", "vm_poisson.o", ["-ffp-contract=off"]),
     ("vm_layer_ext.hip", "vm_layer_ext.o", ["-ffp-contract=off"]),
     ("vm_mgb.hip", "vm_mgb.o", ["-ffp-contract=fast"]),

@@ -23,6 +23,9 @@ ERR_NAMES = ("ssim", "tps", "ui", "temp", "all")
 EASE_LINEAR, EASE_SMOOTH = 0, 1               # the ramp of a transition schedule (vm_render_transition, ...)
 # the filter of the last taps of a filtered viewport call (vm_frame_render_viewport_filtered, ...)
 FILTER_BILINEAR, FILTER_CATMULL_ROM, FILTER_MITCHELL, FILTER_BSPLINE = 0, 1, 2, 3
+# the multiband calls (vm_frame_render_multiband, ...): the deepest band table, and what vm_dbg_multiband_level reads
+MULTIBAND_MAX_LEVELS = 8
+MB_G0, MB_G1, MB_MASK, MB_OUT = 0, 1, 2, 3
 
 FIELDS = {  # name -> (id, channels)
     "img0": (0, 1), "img1": (1, 1), "v": (2, 2), "luma": (3, 2), "mean": (4, 2), "var": (5, 2),
@@ -65,6 +68,9 @@ SYMBOLS = [
     "vm_render_viewport", "vm_render_viewport_dev", "vm_render_viewport_layers", "vm_render_viewport_layers_dev",
     "vm_frame_render_viewport_filtered", "vm_frame_render_viewport_filtered_dev", "vm_frame_render_viewport_filtered_layers",
     "vm_frame_render_viewport_filtered_layers_dev",
+    "vm_frame_render_multiband", "vm_frame_render_multiband_dev", "vm_frame_render_multiband_layers",
+    "vm_frame_render_multiband_layers_dev", "vm_frame_render_multiband_transition", "vm_frame_render_multiband_transition_dev",
+    "vm_frame_render_multiband_transition_layers", "vm_frame_render_multiband_transition_layers_dev", "vm_dbg_multiband_level",
     "vm_render_viewport_shutter", "vm_render_viewport_shutter_dev", "vm_render_viewport_shutter_layers",
     "vm_render_viewport_shutter_layers_dev",
     "vm_render_viewport_transition_shutter", "vm_render_viewport_transition_shutter_dev",
@@ -96,6 +102,11 @@ class ViewportStruct(C.Structure):
     """vm_viewport (videomorphing_amd.viewport.Viewport builds and checks one)"""
     _fields_ = [("x0", C.c_float), ("y0", C.c_float), ("step_x", C.c_float), ("step_y", C.c_float),
                 ("out_w", C.c_int), ("out_h", C.c_int), ("nx", C.c_int), ("ny", C.c_int)]
+
+
+class BandsStruct(C.Structure):
+    """vm_bands (videomorphing_amd.multiband.Bands builds one)"""
+    _fields_ = [("levels", C.c_int), ("sharp", C.c_float * (MULTIBAND_MAX_LEVELS + 1))]
 
 
 class Progress(C.Structure):
@@ -300,6 +311,15 @@ def load():
         "vm_frame_render_viewport_filtered_dev": [vp, C.POINTER(ViewportStruct), i, f, f, i, C.POINTER(f)],
         "vm_frame_render_viewport_filtered_layers": [vp, C.POINTER(ViewportStruct), i, f, f, i, vp, i],
         "vm_frame_render_viewport_filtered_layers_dev": [vp, C.POINTER(ViewportStruct), i, f, f, i, C.POINTER(f)],
+        "vm_frame_render_multiband": [vp, C.POINTER(BandsStruct), f, f, vp, i],
+        "vm_frame_render_multiband_dev": [vp, C.POINTER(BandsStruct), f, f, C.POINTER(f)],
+        "vm_frame_render_multiband_layers": [vp, C.POINTER(BandsStruct), f, f, vp, i],
+        "vm_frame_render_multiband_layers_dev": [vp, C.POINTER(BandsStruct), f, f, C.POINTER(f)],
+        "vm_frame_render_multiband_transition": [vp, C.POINTER(BandsStruct), f, i, vp, i],
+        "vm_frame_render_multiband_transition_dev": [vp, C.POINTER(BandsStruct), f, i, C.POINTER(f)],
+        "vm_frame_render_multiband_transition_layers": [vp, C.POINTER(BandsStruct), f, i, vp, i],
+        "vm_frame_render_multiband_transition_layers_dev": [vp, C.POINTER(BandsStruct), f, i, C.POINTER(f)],
+        "vm_dbg_multiband_level": [vp, i, i, vp],
         "vm_render_viewport_shutter": [vp, C.POINTER(ViewportStruct), f, f, f, i, i, vp, i],
         "vm_render_viewport_shutter_dev": [vp, C.POINTER(ViewportStruct), f, f, f, i, i, C.POINTER(f)],
         "vm_render_viewport_shutter_layers": [vp, C.POINTER(ViewportStruct), f, f, f, i, i, vp, i],

@@ -1,6 +1,6 @@
 // vm_chain.h -- the compositor's fixed-point chain (kernel_render_halfway_image, Algorithm/render.cu:16-60), stated once
 // for the units that walk it: vm_render.hip (RGB8 from the extended canvases), vm_warp.hip (sampling maps, float
-// layers, transition control), vm_shutter.hip (both tails over the sample times of a shutter), vm_tshutter.hip (the same under a schedule) and vm_viewport.hip (both tails from the sub-sample points of a viewport), vm_vshutter.hip (a viewport over either shutter), vm_carry.hip (the landing carried to other times).  A kernel walks the window form (the product path: taps served from an LDS window;
+// layers, transition control), vm_shutter.hip (both tails over the sample times of a shutter), vm_tshutter.hip (the same under a schedule) and vm_viewport.hip (both tails from the sub-sample points of a viewport), vm_vshutter.hip (a viewport over either shutter), vm_carry.hip (the landing carried to other times), vm_multiband.hip (the two plates kept apart for a blend band by band).  A kernel walks the window form (the product path: taps served from an LDS window;
 // vm_chain_win.h, included in the kernel's body) or calls chain_plain (VM_RENDER=plain, and fields of 4 GiB and more),
 // returns if the chain gave its thread no pixel, and runs its own tail on the Landing.  Everything is float32 in tap2's
 // expressions and order; the units are compiled with -ffp-contract=off.  Every function here is inlined into the kernel

@@ -1,5 +1,5 @@
 // vm_chain_launch.h -- how the units that walk the compositor's chain (vm_chain.h) launch their kernels, stated once for
-// vm_render.hip, vm_warp.hip, vm_shutter.hip, vm_tshutter.hip, vm_viewport.hip, vm_vshutter.hip and vm_carry.hip: the two grids, the
+// vm_render.hip, vm_warp.hip, vm_shutter.hip, vm_tshutter.hip, vm_viewport.hip, vm_vshutter.hip, vm_carry.hip and vm_multiband.hip: the two grids, the
 // choice between the chain's forms, the dispatch on the channel count, the colour pre-pass of a scheduled shutter and the
 // step rule of the viewports.  Host code only.
 #ifndef VM_CHAIN_LAUNCH_H

@@ -256,6 +256,12 @@ struct vm_frame {
     bool has_sched = false;
     // the start points of a carry call (vm_frame_carry_points, vm_render_calls.cpp), grown on demand
     VmDev<float2> carry_pts;
+    // the pyramids of a multiband call (vm_frame_render_multiband, vm_render_calls.cpp; the layout is vm_multiband.h's),
+    // allocated on first use and grown when the channels or the levels ask for more; mb_levels == 0: no call yet.
+    // mb_channels / mb_layers: what the last call blended (vm_dbg_multiband_level)
+    VmDev<float> mb;
+    int mb_levels = 0, mb_channels = 0;
+    bool mb_layers = false;
 };
 
 // The one destroy path of the objects that live on a context's device (pyramid, video, frame, sync).  With the device

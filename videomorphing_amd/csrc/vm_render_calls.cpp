@@ -1,8 +1,9 @@
 // vm_render_calls.cpp -- the C-ABI of the render calls, every vm_render_* of include/vmorph.h: the launchers of
 // vm_render.hip, vm_warp.hip, vm_shutter.hip, vm_tshutter.hip, vm_viewport.hip, vm_vshutter.hip and vm_filter.hip (the
 // compositor's chain, render.cu:16-60, UI/RenderWidget.cpp:229-266, with their tails) behind ONE host path -- check, bind, launch, download
-//  -- and the carry calls of vm_carry.hip on the same helpers.  Nothing here changes the frame's
-// v, path, canvases, layers or schedule; the schedule's rate plane, warp_out and carry_pts are a call's scratch.
+//  -- and the carry calls of vm_carry.hip and the multiband calls of vm_multiband.hip
+// on the same helpers.  Nothing here changes the frame's
+// v, path, canvases, layers or schedule; the schedule's rate plane, warp_out, carry_pts and the pyramids (mb) are a call's scratch.
 #include "vm_host.h"
 #include "vm_warp.h"
 #include "vm_shutter.h"
@@ -11,6 +12,8 @@
 #include "vm_vshutter.h"
 #include "vm_filter.h"
 #include "vm_carry.h"
+#include "vm_multiband.h"
+#include <vector>
 #include <cmath>
 #include <type_traits>
 
@@ -26,7 +29,8 @@ enum {
     SCHEDULED = 4,      // carries an ease and needs the frame's schedule
     LAYERS = 8,         // renders the frame's layers (floats) instead of its canvases (RGB8)
     OWN_OUT = 16,       // renders into the frame's own `out` (vm_render_halfway*), not into warp_out
-    FILTERED = 64       // carries a filter (32 is the carry calls' POINTS)
+    FILTERED = 64,      // carries a filter (32 is the carry calls' POINTS)
+    BANDS = 128         // carries a vm_bands and needs the frame's pyramid scratch
 };
 struct Call {
     const char *fn;     // the entry point, for the messages
@@ -34,6 +38,7 @@ struct Call {
     const vm_viewport *vp;
     int samples, ease, color_from;
     int filter = VM_FILTER_BILINEAR;
+    const vm_bands *bands = nullptr;
 };
 // ... and where its output goes: to the host (pitch in bytes for RGB8, in floats for layers; 0 = tight) and drained, or
 // left on the device with the launch timed (ms may be NULL)
@@ -92,14 +97,32 @@ int check_filter(const char *fn, int filter)
     return VM_OK;
 }
 
+// (w x h: the frame's grid, whose coarsest level the bands must leave at least 2 x 2)
+int check_bands(const char *fn, const vm_bands *b, int w, int h)
+{
+    if (!b) return vm_fail(VM_E_INVALID, "%s: bands is NULL", fn);
+    if (b->levels < 1 || b->levels > VM_MULTIBAND_MAX_LEVELS)
+        return vm_fail(VM_E_INVALID, "%s: %d levels (1..%d)", fn, b->levels, (int)VM_MULTIBAND_MAX_LEVELS);
+    int cw = w, ch = h;
+    for (int l = 0; l < b->levels; ++l) {
+        cw = (cw + 1) / 2; ch = (ch + 1) / 2;
+    }
+    if (cw < 2 || ch < 2)
+        return vm_fail(VM_E_INVALID, "%s: %d levels leave a coarsest level of %d x %d (at least 2 x 2)", fn, b->levels, cw, ch);
+    for (int l = 0; l <= b->levels; ++l)
+        if (!std::isfinite(b->sharp[l]) || !(b->sharp[l] >= 1.0f))
+            return vm_fail(VM_E_INVALID, "%s: sharp[%d] = %g (finite, >= 1)", fn, l, (double)b->sharp[l]);
+    return VM_OK;
+}
+
 int check_color_from(const char *fn, int color_from)
 {
     if (color_from < 0 || color_from > 2) return vm_fail(VM_E_INVALID, "%s: color_from %d", fn, color_from);
     return VM_OK;
 }
 
-// the arguments a call carries, in the one order: viewport, samples, chain cap, ease, filter, color_from
-int check_args(const Call &k)
+// the arguments a call carries, in the one order: viewport, samples, chain cap, bands, ease, filter, color_from
+int check_args(const Call &k, const vm_frame *f)
 {
     if (k.what & VIEWPORT)
         if (int rc = check_viewport(k.fn, k.vp)) return rc;
@@ -107,6 +130,8 @@ int check_args(const Call &k)
         if (int rc = check_samples(k.fn, k.samples)) return rc;
     if ((k.what & VIEWPORT) && (k.what & SHUTTER))
         if (int rc = check_chains(k.fn, k.samples, k.vp)) return rc;
+    if (k.what & BANDS)
+        if (int rc = check_bands(k.fn, k.bands, f->w, f->h)) return rc;
     if (k.what & SCHEDULED)
         if (int rc = check_ease(k.fn, k.ease)) return rc;
     if (k.what & FILTERED)
@@ -162,7 +187,7 @@ template <class A> void bind_tail(A &a, const vm_frame *f, bool layers, void *de
 template <class L> int render_call(vm_frame *f, const Call &k, const Dest &d, L launch)
 {
     if (d.download && !d.host) return vm_fail(VM_E_INVALID, "%s: output is NULL", k.fn);
-    if (int rc = check_args(k)) return rc;
+    if (int rc = check_args(k, f)) return rc;
     if ((k.what & SCHEDULED) && !f->has_sched)
         return vm_fail(VM_E_STATE, "%s: the frame holds no schedule (vm_frame_upload_schedule)", k.fn);
     const bool layers = (k.what & LAYERS) != 0;
@@ -179,6 +204,8 @@ template <class L> int render_call(vm_frame *f, const Call &k, const Dest &d, L 
         if (int rc = f->warp_out.reserve(row * (size_t)out_h, c->stream)) return rc;
         dev = f->warp_out.get();
     }
+    if (k.what & BANDS)
+        if (int rc = f->mb.reserve(vm_mb_layout(f->w, f->h, layers ? f->layer_ch : 3, k.bands->levels).total, c->stream)) return rc;
     if (int rc = vm_timed_launch(c, d.ms, [&] { launch(dev, c->stream); })) return rc;
     if (!d.download) return VM_OK;
     if (int rc = vm_copy_pitched(k.fn, hipMemcpyDeviceToHost, dev, row, d.host, pitch, unit, row, out_h, c->stream)) return rc;
@@ -301,6 +328,28 @@ int vshutter(vm_frame *f, const char *fn, int sched, int tail, const vm_viewport
         S.samples = samples; S.ease = ease; S.color_from = color_from;
         vm_launch_vshutter(S, s);
     });
+}
+
+// a uniform (sched == 0: t and ease are not read) or a transition call (sched == SCHEDULED: color_fa and geo_fa are not
+// read) blended band by band (vm_multiband.hip); the calls are the blend: color_from is 1
+int multiband(vm_frame *f, const char *fn, int sched, int tail, const vm_bands *bands, float color_fa, float geo_fa, float t, int ease,
+              const Dest &d)
+{
+    Call k{fn, BANDS | sched | tail, nullptr, 0, ease, 1};
+    k.bands = bands;
+    const int rc = render_call(f, k, d, [&](void *dev, hipStream_t s) {
+        VmMultiband M{};
+        bind_field(M, f); bind_tail(M, f, tail == LAYERS, dev);
+        if (sched) bind_schedule(M, f);
+        M.color_fa = color_fa; M.geo_fa = geo_fa; M.t = t; M.ease = ease;
+        M.levels = bands->levels;
+        for (int l = 0; l <= bands->levels; ++l) M.sharp[l] = bands->sharp[l];
+        M.ws = f->mb.get();
+        vm_launch_multiband(M, s);
+        // (what vm_dbg_multiband_level reads: set once the launches are enqueued)
+        f->mb_levels = bands->levels; f->mb_channels = tail == LAYERS ? f->layer_ch : 3; f->mb_layers = tail == LAYERS;
+    });
+    return rc;
 }
 
 // ---- the carry calls (vm_carry.hip): the same path -- check, bind, launch, download -- with up to six
@@ -643,4 +692,89 @@ extern "C" int vm_frame_transition_motion_maps_dev(vm_frame *f, float t_from, in
     VM_ENTER(f);
     void *const host[6] = {};
     return carry(f, __func__, SCHEDULED, nullptr, 0, t_from, ease, t_to, nt, host, left(elapsed_ms));
+}
+
+// ---- the two plates blended band by band (vm_multiband.hip)
+extern "C" int vm_frame_render_multiband(vm_frame *f, const vm_bands *bands, float color_fa, float geo_fa, uint8_t *rgb_out,
+                                         int pitch_bytes)
+{
+    VM_ENTER(f);
+    return multiband(f, __func__, 0, 0, bands, color_fa, geo_fa, 0.0f, VM_EASE_LINEAR, down(rgb_out, pitch_bytes));
+}
+
+extern "C" int vm_frame_render_multiband_dev(vm_frame *f, const vm_bands *bands, float color_fa, float geo_fa, float *elapsed_ms)
+{
+    VM_ENTER(f);
+    return multiband(f, __func__, 0, 0, bands, color_fa, geo_fa, 0.0f, VM_EASE_LINEAR, left(elapsed_ms));
+}
+
+extern "C" int vm_frame_render_multiband_layers(vm_frame *f, const vm_bands *bands, float color_fa, float geo_fa, float *out,
+                                                int pitch_floats)
+{
+    VM_ENTER(f);
+    return multiband(f, __func__, 0, LAYERS, bands, color_fa, geo_fa, 0.0f, VM_EASE_LINEAR, down(out, pitch_floats));
+}
+
+extern "C" int vm_frame_render_multiband_layers_dev(vm_frame *f, const vm_bands *bands, float color_fa, float geo_fa,
+                                                    float *elapsed_ms)
+{
+    VM_ENTER(f);
+    return multiband(f, __func__, 0, LAYERS, bands, color_fa, geo_fa, 0.0f, VM_EASE_LINEAR, left(elapsed_ms));
+}
+
+extern "C" int vm_frame_render_multiband_transition(vm_frame *f, const vm_bands *bands, float t, int ease, uint8_t *rgb_out,
+                                                    int pitch_bytes)
+{
+    VM_ENTER(f);
+    return multiband(f, __func__, SCHEDULED, 0, bands, 0.0f, 0.0f, t, ease, down(rgb_out, pitch_bytes));
+}
+
+extern "C" int vm_frame_render_multiband_transition_dev(vm_frame *f, const vm_bands *bands, float t, int ease, float *elapsed_ms)
+{
+    VM_ENTER(f);
+    return multiband(f, __func__, SCHEDULED, 0, bands, 0.0f, 0.0f, t, ease, left(elapsed_ms));
+}
+
+extern "C" int vm_frame_render_multiband_transition_layers(vm_frame *f, const vm_bands *bands, float t, int ease, float *out,
+                                                           int pitch_floats)
+{
+    VM_ENTER(f);
+    return multiband(f, __func__, SCHEDULED, LAYERS, bands, 0.0f, 0.0f, t, ease, down(out, pitch_floats));
+}
+
+extern "C" int vm_frame_render_multiband_transition_layers_dev(vm_frame *f, const vm_bands *bands, float t, int ease,
+                                                               float *elapsed_ms)
+{
+    VM_ENTER(f);
+    return multiband(f, __func__, SCHEDULED, LAYERS, bands, 0.0f, 0.0f, t, ease, left(elapsed_ms));
+}
+
+// one level of what the last multiband call left: the planes gathered into tight (h_l, w_l, C) floats on the host
+extern "C" int vm_dbg_multiband_level(vm_frame *f, int what, int level, float *out)
+{
+    VM_ENTER(f);
+    if (!out) return vm_fail(VM_E_INVALID, "%s: output is NULL", __func__);
+    if (what < VM_MB_G0 || what > VM_MB_OUT) return vm_fail(VM_E_INVALID, "%s: what %d", __func__, what);
+    if (!f->mb_levels) return vm_fail(VM_E_STATE, "%s: the frame has made no multiband call", __func__);
+    if (level < 0 || level > f->mb_levels) return vm_fail(VM_E_INVALID, "%s: level %d (0..%d)", __func__, level, f->mb_levels);
+    if (what == VM_MB_OUT && level == 0 && !f->mb_layers)
+        return vm_fail(VM_E_INVALID, "%s: level 0 of an RGB8 call is the call's bytes", __func__);
+    hipStream_t s = f->ctx->stream;
+    const int C = f->mb_channels;
+    const VmMbLayout Y = vm_mb_layout(f->w, f->h, C, f->mb_levels);
+    const size_t n = (size_t)Y.w[level] * Y.h[level];
+    if (what == VM_MB_OUT && level == 0) {      // the layer call's output, interleaved already
+        VM_HIP(hipMemcpyAsync(out, f->warp_out.get(), n * C * sizeof(float), hipMemcpyDeviceToHost, s));
+        VM_HIP(hipStreamSynchronize(s));
+        return VM_OK;
+    }
+    const int planes = what == VM_MB_MASK ? 1 : C;
+    const float *src = f->mb.get() + (what == VM_MB_OUT ? Y.r[level] : Y.g[level] + (what == VM_MB_G1 ? C : what == VM_MB_MASK ? 2 * C : 0) * Y.stride[level]);
+    std::vector<float> host(n * planes);
+    for (int c = 0; c < planes; ++c)
+        VM_HIP(hipMemcpyAsync(host.data() + c * n, src + c * Y.stride[level], n * sizeof(float), hipMemcpyDeviceToHost, s));
+    VM_HIP(hipStreamSynchronize(s));
+    for (int c = 0; c < planes; ++c)
+        for (size_t i = 0; i < n; ++i) out[i * planes + c] = host[c * n + i];
+    return VM_OK;
 }

@@ -861,6 +861,62 @@ class Frame(object):
     def render_viewport_filtered_layers_dev(self, vp, filter, color_fa, geo_fa, color_from=1):
         return self._render_dev("vm_frame_render_viewport_filtered_layers_dev", (int(filter), float(color_fa), float(geo_fa), int(color_from)), vp.struct())
 
+    def _multiband(self, name, bands, args, layers):
+        """one multiband call or its _dev twin (bands: a videomorphing_amd.multiband.Bands; the library checks it); what the
+        call blended is kept for multiband_level"""
+        s = bands.struct()
+        if name.endswith("_dev"):
+            out = self._render_dev(name, args, s)
+        else:
+            out = self._render(name, args, (self.h, self.w), layers, s)
+        self._mb_tail = tuple(getattr(self, "_layer_shape", (self.h, self.w))[2:]) if layers else (3,)
+        self._mb_layers = layers
+        return out
+
+    def render_multiband(self, bands, color_fa, geo_fa):
+        """render_halfway's blend (color_from = 1) band by band (vm_frame_render_multiband): the two warped plates and the
+        weight color_fa split into bands.levels + 1 frequency bands, every band blended under its level's weight plane
+        sharpened by bands.sharp[l], the sum clamped to [0, 255] before the rounding -> (h, w, 3) uint8"""
+        return self._multiband("vm_frame_render_multiband", bands, (float(color_fa), float(geo_fa)), False)
+
+    def render_multiband_dev(self, bands, color_fa, geo_fa):
+        return self._multiband("vm_frame_render_multiband_dev", bands, (float(color_fa), float(geo_fa)), False)
+
+    def render_multiband_layers(self, bands, color_fa, geo_fa):
+        """the uploaded layers under the same bands (vm_frame_render_multiband_layers): float32 of the shape they were
+        uploaded in, neither clamped nor rounded"""
+        return self._multiband("vm_frame_render_multiband_layers", bands, (float(color_fa), float(geo_fa)), True)
+
+    def render_multiband_layers_dev(self, bands, color_fa, geo_fa):
+        return self._multiband("vm_frame_render_multiband_layers_dev", bands, (float(color_fa), float(geo_fa)), True)
+
+    def render_multiband_transition(self, bands, t, ease=capi.EASE_LINEAR):
+        """render_transition's blend band by band (vm_frame_render_multiband_transition): the colour rate k of every output
+        pixel is the weight the bands smooth, so a wipe's seam is wide in the low frequencies and narrow in the detail"""
+        return self._multiband("vm_frame_render_multiband_transition", bands, (float(t), int(ease)), False)
+
+    def render_multiband_transition_dev(self, bands, t, ease=capi.EASE_LINEAR):
+        return self._multiband("vm_frame_render_multiband_transition_dev", bands, (float(t), int(ease)), False)
+
+    def render_multiband_transition_layers(self, bands, t, ease=capi.EASE_LINEAR):
+        return self._multiband("vm_frame_render_multiband_transition_layers", bands, (float(t), int(ease)), True)
+
+    def render_multiband_transition_layers_dev(self, bands, t, ease=capi.EASE_LINEAR):
+        return self._multiband("vm_frame_render_multiband_transition_layers_dev", bands, (float(t), int(ease)), True)
+
+    def multiband_level(self, what, level):
+        """diagnostic (vm_dbg_multiband_level): one level of what this frame's last multiband call left -- what: capi.MB_G0,
+        MB_G1 (the Gaussian levels of the two plates), MB_MASK (the weight plane before sharpening), MB_OUT (the sum of the
+        bands from the coarsest down to this level; level 0 after a layers call only) -> float32 (h_l, w_l, C), C = 3
+        after an RGB8 call, the layers' shape after a layer call; (h_l, w_l) for the mask"""
+        w, h = self.w, self.h
+        for _ in range(max(0, min(int(level), capi.MULTIBAND_MAX_LEVELS))):
+            w, h = (w + 1) // 2, (h + 1) // 2
+        tail = () if what == capi.MB_MASK else getattr(self, "_mb_tail", (3,))
+        buf = np.empty(h * w * 4, dtype=np.float32)        # (room for four channels whatever the last call blended)
+        capi.check(self._L.vm_dbg_multiband_level(self._h, int(what), int(level), buf.ctypes.data))
+        return buf[:h * w * int(np.prod(tail, dtype=np.int64))].reshape((h, w) + tail).copy()
+
     def render_viewport_shutter(self, vp, color_fa, geo_open, geo_close, samples, color_from=1):
         """render_viewport with motion blur (vm_render_viewport_shutter): every output pixel the mean of its vp.nx x vp.ny
         chains at each of `samples` (1..64) times between geo_open and geo_close, each clamped to [0, 1], taken in float32
