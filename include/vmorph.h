@@ -208,6 +208,12 @@ int  vm_dbg_pass_fallbacks(vm_ctx *ctx);
 int  vm_dbg_sparse_resident(vm_ctx *ctx, int mode);
 /* ... and how many tile visits of this context's solves were served from that LDS copy so far (saturating). */
 int  vm_dbg_sparse_resident_visits(vm_ctx *ctx);
+/* Test hook of the sweep variants (FAST arithmetic): every FAST sweep kernel exists twice, the
+ * general one, which reads from the level whether its pages carry the temporal term, and one compiled without the
+ * term, which the solver launches for levels that carry none -- the same bits.  mode 0 = by the level (default),
+ * 1 = always the general kernels (tests, and timing one against the other inside one library).  Per context; the other
+ * arithmetics have the general kernels only.  Other values: VM_E_INVALID. */
+int  vm_dbg_sweep_variant(vm_ctx *ctx, int mode);
 /* Diagnostic of the PASS schedule: on which XCD (0..7) each of the first `n` (<= 2048)
  * workgroups of the most recent PASS launch ran (workgroup b belongs to tile group
  * (b / 256) * 8 + b % 8; a group whose 32 workgroups report one XCD keeps its tile in one

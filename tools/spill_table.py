@@ -80,9 +80,10 @@ for l in rem.split("\n"):
     m = re.search(r"remark:\s+([A-Za-z][A-Za-z /\[\]]*?): (\d+) \[", l)
     if m and cur:
         usage[cur][m.group(1).strip()] = int(m.group(2))
-print("%-44s %5s %5s %7s %8s %9s %9s %10s %14s %12s" % ("kernel (%s build)" % ("EXACT" if exact else "FAST"), "VGPR", "SGPR", "spilled", "scratch", "scr.loads", "scr.stores",
+# (48 columns: the FAST kernels' two sweep variants differ in the LAST template argument)
+print("%-48s %5s %5s %7s %8s %9s %9s %10s %14s %12s" % ("kernel (%s build)" % ("EXACT" if exact else "FAST"), "VGPR", "SGPR", "spilled", "scratch", "scr.loads", "scr.stores",
                                                   "eval loops", "scratch in them", "SGPR spills"))
 for name, desc, nl, ns, nev, evs, evv, lanes in rows:
     u = usage.get(name, {})
-    print("%-44s %5s %5s %7s %8s %9d %9d %10d %14d %12s" % (name[:44], u.get("VGPRs", "?"), u.get("TotalSGPRs", "?"), u.get("VGPRs Spill", "?"),
+    print("%-48s %5s %5s %7s %8s %9d %9d %10d %14d %12s" % (re.sub(r"^void ", "", name)[:48], u.get("VGPRs", "?"), u.get("TotalSGPRs", "?"), u.get("VGPRs Spill", "?"),
                                                       str(u.get("ScratchSize [bytes/lane]", "?")) + " B", nl, ns, nev, evs, u.get("SGPRs Spill", "?")))

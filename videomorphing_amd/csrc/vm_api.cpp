@@ -116,6 +116,13 @@ extern "C" int vm_ctx_create(int device, vm_ctx **out)
         if (!strcmp(e, "ordered")) reduction = VM_REDUCE_ORDERED;
         else if (strcmp(e, "atomic")) return vm_fail(VM_E_INVALID, "vm_ctx_create: VM_REDUCTION=%s (ordered or atomic)", e);
     }
+    // VM_SWEEP_VARIANT=general|level (development): the sweep variant the context starts with (vm_dbg_sweep_variant), to
+    // time the two variants against each other inside one library
+    int sweep_variant = 0;
+    if (const char *e = getenv("VM_SWEEP_VARIANT")) {
+        if (!strcmp(e, "general")) sweep_variant = 1;
+        else if (strcmp(e, "level")) return vm_fail(VM_E_INVALID, "vm_ctx_create: VM_SWEEP_VARIANT=%s (general or level)", e);
+    }
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev <= 0)
@@ -126,6 +133,7 @@ extern "C" int vm_ctx_create(int device, vm_ctx **out)
     vm_ctx *c = new vm_ctx();
     c->device = device;
     c->reduction = reduction;
+    c->sweep_variant = sweep_variant;
     VM_ON_DEVICE(c);
     c->math_mode = VM_MATH_EXACT;
     c->kp = {10.0f, 1e5f, 0.05f, 100.0f, 0.0f, 0.01f, VM_BCOND_NONE}; // UI/MdiEditor.cpp:131-140
@@ -232,6 +240,14 @@ extern "C" int vm_dbg_sparse_resident(vm_ctx *c, int mode)
     if (!c) return vm_fail(VM_E_INVALID, "vm_dbg_sparse_resident: ctx is NULL");
     if (mode < 0 || mode > 3) return vm_fail(VM_E_INVALID, "vm_dbg_sparse_resident: mode %d (0 automatic, 1 never, 2 re-centre at every commit, 3 give up at the first commit)", mode);
     c->sparse_resident = mode;
+    return VM_OK;
+}
+
+extern "C" int vm_dbg_sweep_variant(vm_ctx *c, int mode)
+{
+    if (!c) return vm_fail(VM_E_INVALID, "vm_dbg_sweep_variant: ctx is NULL");
+    if (mode < 0 || mode > 1) return vm_fail(VM_E_INVALID, "vm_dbg_sweep_variant: mode %d (0 by the level, 1 always the general kernels)", mode);
+    c->sweep_variant = mode;
     return VM_OK;
 }
 

@@ -98,7 +98,7 @@ struct vm_ctx {
     VmDev<uint32_t> pass_bar;
     VmDev<uint32_t> pass_err;
     VmPinned<uint32_t> pass_err_host;
-    int pass_resident[8] = {-1, -1, -1, -1, -1, -1, -1, -1}; // co-resident k_pass workgroups on this device, per arithmetic build (math_mode); -1: not asked yet
+    int pass_resident[16] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1}; // co-resident k_pass workgroups on this device, per arithmetic build and sweep variant (math_mode * 2 + temporal); -1: not asked yet
     VmDev<uint32_t> pass_dbg;        // vm_dbg_pass_xcd: 256 words, XCC id per workgroup of the last launch
     VmDev<char> pass_snap;           // AUTO: the levels' slabs as they stood before the current PASS batch
     bool pass_latched_off = false;   // AUTO: a tile barrier timed out once on this context: STEP from then on
@@ -115,12 +115,14 @@ struct vm_ctx {
     struct SweepGraph {
         int math_mode;
         int n, w, h, cap, fixed_work, threads, dense, order;
+        int temporal; // the sweep variant its kernel nodes were captured with (SweepRun::temporal)
         const void *views, *flags, *stats, *tile_list;
         vm_kern_params kp;
         hipGraphExec_t exec;
     };
     std::vector<SweepGraph> graphs;
     int commit_order = 0;         // vm_set_commit_order (EXACT, diagnostic): order 0..3
+    int sweep_variant = 0;        // vm_dbg_sweep_variant: 0 = by the level (the kernels without the temporal term where no page carries it), 1 = always the general kernels
     int sparse_resident = 0;      // vm_dbg_sparse_resident: 0 = automatic, 1 = never, 2 / 3 = tests (k_sparse, sv_phases)
     unsigned long long sparse_resident_visits = 0; // vm_dbg_sparse_resident_visits: tile visits served from the resident LDS copy
     VmDev<uint32_t> tile_list;       // the listed form of pruned TILE passes over big batches (k_tile_scan): counters, stamps, entries

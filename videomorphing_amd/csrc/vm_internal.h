@@ -87,18 +87,20 @@ struct VmKParams {
                                      const VmKParams &P, const uint32_t *tables, int offx,    \
                                      int offy, uint32_t *flags, uint32_t *stats, int iter_idx,\
                                      int fixed_work, int threads, const int *iter_dev,        \
-                                     int dense, uint32_t *tile_list, hipStream_t s);          \
+                                     int dense, uint32_t *tile_list, int temporal,            \
+                                     hipStream_t s);                                          \
     void vm_launch_next_iter_##SUFFIX(int *iter_dev, int set, int value, hipStream_t s);      \
     void vm_launch_optimize_sparse_##SUFFIX(const VmLevelView *views, int nbatch, int cap, int w, \
                                             int h, const VmKParams &P, const uint32_t *tables, \
                                             uint32_t *flags, uint32_t *stats, int it0, int nit, \
                                             int fixed_work, int threads, int dense, int lds_cap,   \
-                                            int res_mode, hipStream_t s);                      \
+                                            int res_mode, int temporal, hipStream_t s);        \
     void vm_launch_optimize_split_##SUFFIX(const VmLevelView *views, int nbatch, int cap, int w, \
                                            int h, const VmKParams &P, const uint32_t *tables, \
                                            int offx, int offy, int pass, uint32_t *flags,     \
                                            uint32_t *stats, int iter_idx, int fixed_work,     \
-                                           int threads, int parts, hipStream_t s);            \
+                                           int threads, int parts, int temporal,              \
+                                           hipStream_t s);                                    \
     void vm_launch_optimize_step_##SUFFIX(const VmLevelView *views, int nbatch, int cap, int w,  \
                                           int h, const VmKParams &P, const uint32_t *tables,  \
                                           int offx, int offy, int pi, int pj, uint32_t epoch, \
@@ -106,7 +108,7 @@ struct VmKParams {
                                           uint32_t *flags, uint32_t *stats, int iter_idx,     \
                                           int fixed_work, int threads, int parts,             \
                                           uint32_t *slots_cur, const uint32_t *slots_prev,    \
-                                          int prev_iter_idx, hipStream_t s);                  \
+                                          int prev_iter_idx, int temporal, hipStream_t s);    \
     void vm_launch_optimize_pass_##SUFFIX(const VmLevelView *views, int nbatch, int cap, int w,  \
                                           int h, const VmKParams &P, const uint32_t *tables,  \
                                           int offx, int offy, uint32_t epoch0, uint32_t *bar, \
@@ -114,8 +116,8 @@ struct VmKParams {
                                           int fixed_work, uint32_t *slots_cur,                \
                                           const uint32_t *slots_prev, int prev_iter_idx,      \
                                           uint32_t *err, uint32_t *dbg, int decide,           \
-                                          int force_wt, hipStream_t s);                       \
-    int vm_pass_resident_blocks_##SUFFIX(int device);                                         \
+                                          int force_wt, int temporal, hipStream_t s);         \
+    int vm_pass_resident_blocks_##SUFFIX(int device, int temporal);                           \
     void vm_launch_upsample_##SUFFIX(float2 *dst, int dw, int dh, int drs, const float2 *src, \
                                      int sw, int sh, int srs, hipStream_t s);                 \
     void vm_launch_splat_##SUFFIX(const VmLevelView &L, int w0, int h0,                       \

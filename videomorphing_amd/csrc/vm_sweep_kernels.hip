@@ -143,6 +143,19 @@ __device__ __forceinline__ float temp_change(const PixelCtx &c, float dx, float 
     return v_temp;
 }
 
+// The sweep variant.  TEMP = true is the general kernel: whether the level carries the temporal term is read from its
+// view (uniform in the launch).  TEMP = false is the kernel of a launch whose levels carry none (vm_optimize_levels knows
+// it): nothing of the term is compiled -- no reference / mask loads, no weight, no per-evaluation arithmetic, no select.
+// FAST builds both of every sweep kernel (TEMP last in its template list); the other arithmetics the general one only.
+template <bool TEMP>
+__device__ __forceinline__ bool temp_on(const VmLevelView &L) { return TEMP && L.temp_mask != nullptr; }
+#if VM_EXACT
+#define VM_VARIANT_TEMPLATE
+constexpr bool TEMP = true; // the one variant of this arithmetic
+#else
+#define VM_VARIANT_TEMPLATE template <bool TEMP>
+#endif
+
 // commit_pixel_motion (morph.cu:990-1026), the pixel's own part: a pixel that moved by `step` from luma `ol` to `luma`
 // leaves the records rec_a = (d mean, d var) and rec_b = (d cross, step, 0) and gets a new ui.b and v
 __device__ __forceinline__ float4 commit_rec_a(float2 luma, float2 ol) { return make_float4(luma.x - ol.x, luma.y - ol.y, luma.x * luma.x - ol.x * ol.x, luma.y * luma.y - ol.y * ol.y); }
@@ -191,7 +204,7 @@ struct NbCacheT {};
 template <bool INTERIOR, int SMAX, int LF = 0, class Src>
 __device__ __forceinline__ void nb_load(NbCacheT<SMAX> &, const VmLevelView &, const Src &, const PixelCtx &, int, int) {}
 
-template <bool INTERIOR, int SMAX, int LF = 0, class Src>
+template <bool INTERIOR, int SMAX, int LF = 0, bool TEMP = true, class Src>
 __device__ __forceinline__ float energy_change(const VmLevelView &L, const VmKParams &P, const Src &src,
                                                const NbCacheT<SMAX> &, const PixelCtx &c, float dx, float dy, int)
 {
@@ -355,7 +368,7 @@ __device__ __forceinline__ void nb_load(NbCacheT<SMAX> &nb, const VmLevelView &L
     }
 }
 
-template <bool INTERIOR, int SMAX, int LF = 0, class Src>
+template <bool INTERIOR, int SMAX, int LF = 0, bool TEMP = true, class Src>
 __device__ __forceinline__ float energy_change(const VmLevelView &L, const VmKParams &P, const Src &,
                                                const NbCacheT<SMAX> &nb, const PixelCtx &c, float dx, float dy, int Lf_rt)
 {
@@ -404,7 +417,7 @@ __device__ __forceinline__ float energy_change(const VmLevelView &L, const VmKPa
     const float v_tps = fmaf(c.tps_axy, dd, fmaf(c.tps_b.x, dx, c.tps_b.y * dy));
     const float v_ui = fmaf(c.ui_axy, dd, fmaf(c.ui_b.x, dx, c.ui_b.y * dy));
     float e = P.w_ui * v_ui + P.w_ssim * change;
-    if (L.temp_mask) // uniform in the launch
+    if (temp_on<TEMP>(L)) // uniform in the launch
         e = fmaf(P.w_temp * c.tmask * L.factor_d, temp_change(c, dx, dy), e);
     return e * L.inv_wh + P.w_tps * v_tps;
 }
@@ -669,14 +682,14 @@ __device__ __forceinline__ bool decide_with64(const VmLevelView &L, const VmKPar
 }
 
 // one lane (EXACT) or L lanes (FAST dense path) per pixel
-template <bool INTERIOR, int SMAX, int LF = 0, class Src>
+template <bool INTERIOR, int SMAX, int LF = 0, bool TEMP = true, class Src>
 __device__ __forceinline__ bool decide(const VmLevelView &L, const VmKParams &P, const Src &src,
                                        const PixelCtx &c, int sub, int Lf, float2 &step, uint32_t &n_eval)
 {
     NbCacheT<SMAX> nb;
     nb_load<INTERIOR, SMAX, LF>(nb, L, src, c, sub, Lf);
     return decide_with(
-        L, P, c, [&](float dx, float dy) { return energy_change<INTERIOR, SMAX, LF>(L, P, src, nb, c, dx, dy, Lf); },
+        L, P, c, [&](float dx, float dy) { return energy_change<INTERIOR, SMAX, LF, TEMP>(L, P, src, nb, c, dx, dy, Lf); },
         RingGlobal{L.v}, step, n_eval);
 }
 
@@ -1020,13 +1033,13 @@ __device__ __forceinline__ float fover32(const VmLevelView &L, const Ring &ring,
 // the accepted point (what commit_pixel_motion would sample again).  The gradient uses the
 // energy as energy_change (morph.cu:730-761) writes it; along the search line d = g t the
 // quadratic terms collapse to t (Q2 t + Q1).
-template <bool INTERIOR, class Ring>
+template <bool INTERIOR, bool TEMP, class Ring>
 __device__ __forceinline__ bool decide32(const VmLevelView &L, const VmKParams &P, const Nb1 &nb, const Ring &ring,
                                          const PixelCtx &c, int sub, float2 &step, float2 &luma,
                                          uint32_t &n_eval)
 {
     n_eval += 4;
-    const bool has_temp = L.temp_mask != nullptr; // uniform in the launch
+    const bool has_temp = temp_on<TEMP>(L); // uniform in the launch; without TEMP a constant, and WT, T0 and the term's arithmetic go
     const float WT = has_temp ? P.w_temp * c.tmask * L.factor_d * L.inv_wh : 0.0f;
     const TapLane tl = tap_lane_make(L, sub);
     float lx, ly;
@@ -1294,13 +1307,13 @@ __device__ __forceinline__ float ladder_pick(bool hi, int oct, float l0, float h
 // gain -- PASS 11.37 vs 11.15 us per phase, STEP 14.5 vs 14.1 (tools/dev_pass.py).  A round then costs ~255
 // instructions (two SSIM terms, two trees, 12 v_readlane broadcasts, the bookkeeping of a three-step speculation)
 // against ~150 here for ~2.7 instead of ~1.9 steps: 94 against 79 instructions per step of the search.  Removed.)
-template <bool INTERIOR, bool LADDER = true, class Ring>
+template <bool INTERIOR, bool LADDER, bool TEMP, class Ring>
 __device__ __forceinline__ bool decide64(const VmLevelView &L, const VmKParams &P, const Nb1 &nb, const Ring &ring,
                                          const PixelCtx &c, int sub, bool hi, float2 &step, float2 &luma,
                                          uint32_t &n_eval)
 {
     n_eval += 4;
-    const bool has_temp = L.temp_mask != nullptr; // uniform in the launch
+    const bool has_temp = temp_on<TEMP>(L); // uniform in the launch; without TEMP a constant, as in decide32
     const float WT = has_temp ? P.w_temp * c.tmask * L.factor_d * L.inv_wh : 0.0f;
     const TapLane tl = tap_lane_make(L, sub);
     float lx, ly;
@@ -1394,6 +1407,7 @@ __device__ __forceinline__ bool decide64(const VmLevelView &L, const VmKParams &
 #endif
 
 // everything of a pixel that the energy needs besides the window sums
+template <bool TEMP = true>
 __device__ __forceinline__ void ctx_load(PixelCtx &c, const VmLevelView &L, const float *s_tps, int px, int py)
 {
     c.px = px;
@@ -1406,7 +1420,7 @@ __device__ __forceinline__ void ctx_load(PixelCtx &c, const VmLevelView &L, cons
     c.tps_axy = s_tps[(border_class(py, L.h) * 5 + border_class(px, L.w)) * 25 + 12] / 2;
     c.tref = make_float2(0, 0);
     c.tmask = 0.0f;
-    if (L.temp_mask) { // uniform in the launch
+    if (temp_on<TEMP>(L)) { // uniform in the launch
         c.tref = L.temp_ref[c.idx];
         c.tmask = L.temp_mask[c.idx];
     }
@@ -1668,7 +1682,7 @@ __device__ __forceinline__ bool gather_cell(const LdsT &S, const VmLevelView &L,
 // 256 VGPRs (measured: pruned sweeps 5-8 % faster).
 // sp_list / sp_cnt / sp_cap (SPARSE kernel, list kept in LDS): the set words this tile owns are appended to
 // the pass's new word list as they are written back (entries past sp_cap are only counted: overflow).
-template <bool DENSE, int SMAX = VM_SMAX, int MINF = VM_MIN_FANOUT, bool INTV = true>
+template <bool DENSE, int SMAX = VM_SMAX, int MINF = VM_MIN_FANOUT, bool INTV = true, bool TEMP = true>
 __device__ __forceinline__ bool tile_sweep(TileLds &S, const VmLevelView &L, const VmKParams &P,
                                            const uint32_t *__restrict__ tables, bool tables_staged, int ox, int oy,
                                            int tid, int T, bool &improving, uint32_t &st_cand, uint32_t &st_commit,
@@ -1782,7 +1796,7 @@ __device__ __forceinline__ bool tile_sweep(TileLds &S, const VmLevelView &L, con
                     const bool wave_interior = __all(li >= n_act || is_interior(L, px, py));
                     if (li < n_act) {
                         PixelCtx c;
-                        ctx_load(c, L, S.tps, px, py);
+                        ctx_load<TEMP>(c, L, S.tps, px, py);
                         LdsSrc src{&S, (ty * 2 + pi) * VM_HALO_W + (tx * 2 + pj)};
                         c.tps_b = S.tpsb[src.hc + 2 * VM_HALO_W + 2];
                         // (defined on every path, the four search bodies below included: left undefined where a search
@@ -1793,12 +1807,12 @@ __device__ __forceinline__ bool tile_sweep(TileLds &S, const VmLevelView &L, con
                         uint32_t n_eval = 0;
                         if (wave_interior) {
                             nb1_load<true>(nb, L, src, c, sub);
-                            ok = wide ? decide64<true, false>(L, P, nb, RingGlobal{L.v}, c, sub, (tid & 32) != 0, step, luma, n_eval)
-                                      : decide32<true>(L, P, nb, RingGlobal{L.v}, c, sub, step, luma, n_eval);
+                            ok = wide ? decide64<true, false, TEMP>(L, P, nb, RingGlobal{L.v}, c, sub, (tid & 32) != 0, step, luma, n_eval)
+                                      : decide32<true, TEMP>(L, P, nb, RingGlobal{L.v}, c, sub, step, luma, n_eval);
                         } else {
                             nb1_load<false>(nb, L, src, c, sub);
-                            ok = wide ? decide64<false, false>(L, P, nb, RingGlobal{L.v}, c, sub, (tid & 32) != 0, step, luma, n_eval)
-                                      : decide32<false>(L, P, nb, RingGlobal{L.v}, c, sub, step, luma, n_eval);
+                            ok = wide ? decide64<false, false, TEMP>(L, P, nb, RingGlobal{L.v}, c, sub, (tid & 32) != 0, step, luma, n_eval)
+                                      : decide32<false, TEMP>(L, P, nb, RingGlobal{L.v}, c, sub, step, luma, n_eval);
                         }
                         if (writer)
                             atomicAdd(&S.n_eval, n_eval);
@@ -1870,13 +1884,13 @@ __device__ __forceinline__ bool tile_sweep(TileLds &S, const VmLevelView &L, con
                     const bool wave_interior = INTV && __all(li >= n_act || is_interior(L, px, py));
                     if (li < n_act) {
                         PixelCtx c;
-                        ctx_load(c, L, S.tps, px, py);
+                        ctx_load<TEMP>(c, L, S.tps, px, py);
                         LdsSrc src{&S, (ty * 2 + pi) * VM_HALO_W + (tx * 2 + pj)};
                         c.tps_b = S.tpsb[src.hc + 2 * VM_HALO_W + 2];
                         float2 step;
                         uint32_t n_eval = 0;
-                        const bool ok = wave_interior ? decide<true, SMAX, MINF>(L, P, src, c, sub, Lf, step, n_eval)
-                                                      : decide<false, SMAX, MINF>(L, P, src, c, sub, Lf, step, n_eval);
+                        const bool ok = wave_interior ? decide<true, SMAX, MINF, TEMP>(L, P, src, c, sub, Lf, step, n_eval)
+                                                      : decide<false, SMAX, MINF, TEMP>(L, P, src, c, sub, Lf, step, n_eval);
                         if (sub == 0)
                             atomicAdd(&S.n_eval, n_eval);
                         if (ok && sub == 0) {
@@ -1996,7 +2010,7 @@ __device__ __forceinline__ void clock_probe(uint32_t *st, bool exit_stamp)
 // (The same 128-VGPR form as ONE 1024-thread workgroup per tile -- 4 lanes per candidate in a single
 // round, for batches over levels of few tiles -- was measured slower than the 256-VGPR kernel at
 // every batch size: 30 x 120x68 310 vs 280 us per pass, 30 x 240x135 970 vs 905; removed.)
-template <bool DENSE, int SMAX = VM_SMAX, int MINF = VM_MIN_FANOUT, bool INTV = true>
+template <bool DENSE, int SMAX = VM_SMAX, int MINF = VM_MIN_FANOUT, bool INTV = true, bool TEMP = true>
 __global__ __launch_bounds__(VM_SWEEP_T) __attribute__((amdgpu_waves_per_eu(DENSE && SMAX > 7 ? 1 : 4))) void SUF(k_optimize)(const VmLevelView *__restrict__ views, int cap,
                                                         VmKParams P, const uint32_t *__restrict__ tables,
                                                         int offx, int offy, uint32_t *__restrict__ flags,
@@ -2032,7 +2046,7 @@ __global__ __launch_bounds__(VM_SWEEP_T) __attribute__((amdgpu_waves_per_eu(DENS
 
     bool improving = false;
     uint32_t st_cand = 0, st_commit = 0;
-    const bool swept = tile_sweep<DENSE, SMAX, MINF, INTV>(S, L, P, tables, false, ox, oy, tid, T, improving, st_cand, st_commit);
+    const bool swept = tile_sweep<DENSE, SMAX, MINF, INTV, TEMP>(S, L, P, tables, false, ox, oy, tid, T, improving, st_cand, st_commit);
     if (probe)
         clock_probe(stats + iter_idx * VM_STAT_WORDS, true);
     if (!swept)
@@ -2103,6 +2117,7 @@ __global__ __launch_bounds__(256) void SUF(k_tile_scan)(const VmLevelView *__res
 }
 
 #if !VM_EXACT
+template <bool TEMP>
 __global__ __launch_bounds__(VM_SWEEP_T) __attribute__((amdgpu_waves_per_eu(4))) void SUF(k_optimize_listed)(
     const VmLevelView *__restrict__ views, int cap, VmKParams P, const uint32_t *__restrict__ tables, int offx, int offy,
     uint32_t *__restrict__ flags, uint32_t *__restrict__ stats, int iter_idx, const int *__restrict__ iter_dev,
@@ -2129,7 +2144,7 @@ __global__ __launch_bounds__(VM_SWEEP_T) __attribute__((amdgpu_waves_per_eu(4)))
             S.n_eval = 0; // ordered before its first use by the barriers of tile_sweep
         bool improving = false;
         uint32_t st_cand = 0, st_commit = 0;
-        if (tile_sweep<false>(S, L, P, tables, true, ox, oy, tid, T, improving, st_cand, st_commit) && tid == 0) {
+        if (tile_sweep<false, VM_SMAX, VM_MIN_FANOUT, true, TEMP>(S, L, P, tables, true, ox, oy, tid, T, improving, st_cand, st_commit) && tid == 0) {
             uint32_t *const st = stats + ((size_t)z * cap + iter_idx) * VM_STAT_WORDS;
             if (improving)
                 flags[(size_t)z * cap + iter_idx] = 1u; // every writer stores the same 1
@@ -2404,6 +2419,7 @@ __device__ __forceinline__ int sv_kth_slot(const uint32_t *cb, int k)
 // barrier, all mask writes after it.  The per-phase words (counts, candidate and commit bitmaps) exist twice and
 // phases alternate between them: a phase without a mask hit is a single barrier, and the next phase's
 // writers must not run into a wave that has not read this phase's counts yet.
+template <bool TEMP>
 __device__ __forceinline__ bool sv_phases(TileLds &S, SvPix &X, SparseLds &Q, const VmLevelView &L, const VmKParams &P, SvTile &V,
                                           int ox, int oy, int tid, int T, uint32_t &st_cand, uint32_t &st_commit, int res,
                                           bool &left)
@@ -2471,7 +2487,7 @@ __device__ __forceinline__ bool sv_phases(TileLds &S, SvPix &X, SparseLds &Q, co
                         c.tps_axy = S.tps[(border_class(py, L.h) * 5 + border_class(px, L.w)) * 25 + 12] / 2;
                         c.tref = make_float2(0, 0);
                         c.tmask = 0.0f;
-                        if (L.temp_mask) { // uniform in the launch
+                        if (temp_on<TEMP>(L)) { // uniform in the launch
                             c.tref = L.temp_ref[c.idx];
                             c.tmask = L.temp_mask[c.idx];
                         }
@@ -2483,12 +2499,12 @@ __device__ __forceinline__ bool sv_phases(TileLds &S, SvPix &X, SparseLds &Q, co
                         uint32_t n_eval = 0;
                         if (wave_interior) {
                             nb1_load<true>(nb, L, src, c, sub);
-                            ok = wide ? decide64<true>(L, P, nb, ring, c, sub, (tid & 32) != 0, step, luma, n_eval)
-                                      : decide32<true>(L, P, nb, ring, c, sub, step, luma, n_eval);
+                            ok = wide ? decide64<true, true, TEMP>(L, P, nb, ring, c, sub, (tid & 32) != 0, step, luma, n_eval)
+                                      : decide32<true, TEMP>(L, P, nb, ring, c, sub, step, luma, n_eval);
                         } else {
                             nb1_load<false>(nb, L, src, c, sub);
-                            ok = wide ? decide64<false>(L, P, nb, ring, c, sub, (tid & 32) != 0, step, luma, n_eval)
-                                      : decide32<false>(L, P, nb, ring, c, sub, step, luma, n_eval);
+                            ok = wide ? decide64<false, true, TEMP>(L, P, nb, ring, c, sub, (tid & 32) != 0, step, luma, n_eval)
+                                      : decide32<false, TEMP>(L, P, nb, ring, c, sub, step, luma, n_eval);
                         }
                         if (writer) {
                             atomicAdd(&S.n_eval, n_eval);
@@ -2608,7 +2624,7 @@ __device__ __forceinline__ bool sv_phases(TileLds &S, SvPix &X, SparseLds &Q, co
 // tile owns as it writes them back.  Should the list outgrow LDS, the kernel rescans the level into the
 // lists in memory and goes on there (lds_cap = 0 forces that path: tests).
 // res_mode (lean kernel): 0 = resident visits where the set bits fit one tile, 1 = never; 2, 3 = tests (sv_phases)
-template <bool DENSE>
+template <bool DENSE, bool TEMP = true>
 __global__ __launch_bounds__(VM_SWEEP_T) __attribute__((amdgpu_waves_per_eu(1))) void SUF(k_sparse)(
     const VmLevelView *__restrict__ views, int cap, VmKParams P, const uint32_t *__restrict__ tables,
     uint32_t *__restrict__ flags, uint32_t *__restrict__ stats, int it0, int nit, int fixed_work, int lds_cap, int res_mode)
@@ -2823,7 +2839,7 @@ __global__ __launch_bounds__(VM_SWEEP_T) __attribute__((amdgpu_waves_per_eu(1)))
                         if (visited) {
                             bool left = false;
                             st_res += resident ? 1u : 0u;
-                            if (sv_phases(S, X, Q, L, P, V, ox, oy, tid, T, st_cand, st_commit, resident ? (res_mode ? res_mode : 1) : 0, left))
+                            if (sv_phases<TEMP>(S, X, Q, L, P, V, ox, oy, tid, T, st_cand, st_commit, resident ? (res_mode ? res_mode : 1) : 0, left))
                                 improving = true;
                             if (!resident || left) {
                                 const bool listed = !pass_resident && in_lds;
@@ -2833,7 +2849,7 @@ __global__ __launch_bounds__(VM_SWEEP_T) __attribute__((amdgpu_waves_per_eu(1)))
                         }
                     } else
 #endif
-                        visited = tile_sweep<DENSE>(S, L, P, tables, true, ox, oy, tid, T, improving, st_cand, st_commit,
+                        visited = tile_sweep<DENSE, VM_SMAX, VM_MIN_FANOUT, true, TEMP>(S, L, P, tables, true, ox, oy, tid, T, improving, st_cand, st_commit,
                                                     in_lds ? Q.wl[cur ^ 1] : nullptr, Q.wv[cur ^ 1], &Q.nnew, lcap);
                     if (visited) {
                         ++st_tiles;
@@ -2961,6 +2977,7 @@ __global__ __launch_bounds__(VM_SWEEP_T) __attribute__((amdgpu_waves_per_eu(1)))
 //   rec_a = (d mean.x, d mean.y, d var.x, d var.y),  rec_b = (d cross, step.x, step.y, -)
 // valid only for the current epoch (one epoch per phase, so nothing is ever cleared).
 
+VM_VARIANT_TEMPLATE
 __global__ __launch_bounds__(VM_SWEEP_T) void SUF(k_decide)(const VmLevelView *__restrict__ views, int cap, VmKParams P,
                                                       const uint32_t *__restrict__ tables, int offx, int offy,
                                                       int pi, int pj, int parts, uint32_t epoch,
@@ -3024,7 +3041,7 @@ __global__ __launch_bounds__(VM_SWEEP_T) void SUF(k_decide)(const VmLevelView *_
             PixelCtx c;
             c.idx = py * L.rs + px;
             if (!pixel_locked(L, P.bcond, px, py)) {
-                ctx_load(c, L, S.tps, px, py);
+                ctx_load<TEMP>(c, L, S.tps, px, py);
                 c.tps_b = L.tps_b[c.idx];
                 GlbSrc src{&L, (py - 2) * L.rs + (px - 2)};
 #if VM_EXACT
@@ -3037,10 +3054,10 @@ __global__ __launch_bounds__(VM_SWEEP_T) void SUF(k_decide)(const VmLevelView *_
                 bool ok;
                 if (wave_interior) {
                     nb1_load<true>(nb, L, src, c, sub);
-                    ok = decide32<true>(L, P, nb, RingGlobal{L.v}, c, sub, step, luma, n_eval);
+                    ok = decide32<true, TEMP>(L, P, nb, RingGlobal{L.v}, c, sub, step, luma, n_eval);
                 } else {
                     nb1_load<false>(nb, L, src, c, sub);
-                    ok = decide32<false>(L, P, nb, RingGlobal{L.v}, c, sub, step, luma, n_eval);
+                    ok = decide32<false, TEMP>(L, P, nb, RingGlobal{L.v}, c, sub, step, luma, n_eval);
                 }
 #endif
                 if (ok)
@@ -3320,7 +3337,7 @@ __device__ __forceinline__ bool fold_cell(const VmLevelView &L, const float4 *__
     return touched;
 }
 
-template <int T>
+template <int T, bool TEMP = true>
 __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(T / 128))) void SUF(k_step)(const VmLevelView *__restrict__ views, int cap, VmKParams P,
                                                    const uint32_t *__restrict__ tables, int offx, int offy, int pi,
                                                    int pj, int parts, uint32_t epoch, uint32_t pe, int srcbuf,
@@ -3563,7 +3580,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(T / 128))) vo
         c.idx = py * L.rs + px;
         // every lane takes part in the fold (its slot loops are wave-uniform); idle lanes fold
         // the pixel's own cell with no records
-        ctx_load(c, L, S.tps, px, py);
+        ctx_load<TEMP>(c, L, S.tps, px, py);
         // the lane's window cell: sums of copy `src` + the records of the last phase
         const int i = window_row(sub), jj = sub - i * 5;
         const int qx = px + jj - 2, qy = py + i - 2;
@@ -3600,17 +3617,17 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(T / 128))) vo
                 const bool hi = (tid & 32) != 0;
                 if (wave_interior) {
                     nb1_make<true>(nb, L, okc, qx, qy, m, q, cr, val);
-                    ok = decide64<true>(L, P, nb, RingGlobal{L.v}, c, sub, hi, step, luma, n_eval);
+                    ok = decide64<true, true, TEMP>(L, P, nb, RingGlobal{L.v}, c, sub, hi, step, luma, n_eval);
                 } else {
                     nb1_make<false>(nb, L, okc, qx, qy, m, q, cr, val);
-                    ok = decide64<false>(L, P, nb, RingGlobal{L.v}, c, sub, hi, step, luma, n_eval);
+                    ok = decide64<false, true, TEMP>(L, P, nb, RingGlobal{L.v}, c, sub, hi, step, luma, n_eval);
                 }
             } else if (wave_interior) {
                 nb1_make<true>(nb, L, okc, qx, qy, m, q, cr, val);
-                ok = decide32<true>(L, P, nb, RingGlobal{L.v}, c, sub, step, luma, n_eval);
+                ok = decide32<true, TEMP>(L, P, nb, RingGlobal{L.v}, c, sub, step, luma, n_eval);
             } else {
                 nb1_make<false>(nb, L, okc, qx, qy, m, q, cr, val);
-                ok = decide32<false>(L, P, nb, RingGlobal{L.v}, c, sub, step, luma, n_eval);
+                ok = decide32<false, TEMP>(L, P, nb, RingGlobal{L.v}, c, sub, step, luma, n_eval);
             }
 #endif
             if (ok)
@@ -3773,6 +3790,7 @@ __device__ __forceinline__ void pass_sum_slots(uint32_t *stats0, const uint32_t 
     }
 }
 
+VM_VARIANT_TEMPLATE
 __global__ __launch_bounds__(VM_PASS_T) __attribute__((amdgpu_waves_per_eu(2, 2))) void SUF(k_pass)(
     const VmLevelView *__restrict__ views, int cap, VmKParams P, const uint32_t *__restrict__ tables, int offx, int offy,
     uint32_t epoch0, int ngroups, int ntiles, uint32_t *__restrict__ sync, uint32_t *__restrict__ flags,
@@ -4095,7 +4113,7 @@ __global__ __launch_bounds__(VM_PASS_T) __attribute__((amdgpu_waves_per_eu(2, 2)
         float cr = ldo<float>(sbase, os_cross + g4), val = ldo<float>(sbase, os_value + g4);
         c.tref = make_float2(0, 0);
         c.tmask = 0.0f;
-        if (L.temp_mask) { // uniform in the launch
+        if (temp_on<TEMP>(L)) { // uniform in the launch
             c.tref = L.temp_ref[pidx];
             c.tmask = L.temp_mask[pidx];
         }
@@ -4245,10 +4263,10 @@ __global__ __launch_bounds__(VM_PASS_T) __attribute__((amdgpu_waves_per_eu(2, 2)
                 Nb1 nb;
                 if (is_interior(L, px, py)) { // wave-uniform: one pixel per wave
                     nb1_make<true>(nb, L, okc, qx, qy, m, q, cr, val);
-                    ok = decide64<true>(L, P, nb, ring, c, sub, hi, step, luma, n_eval);
+                    ok = decide64<true, true, TEMP>(L, P, nb, ring, c, sub, hi, step, luma, n_eval);
                 } else {
                     nb1_make<false>(nb, L, okc, qx, qy, m, q, cr, val);
-                    ok = decide64<false>(L, P, nb, ring, c, sub, hi, step, luma, n_eval);
+                    ok = decide64<false, true, TEMP>(L, P, nb, ring, c, sub, hi, step, luma, n_eval);
                 }
 #endif
                 if (ok)
@@ -4433,60 +4451,90 @@ __global__ __launch_bounds__(64) void SUF(k_dbg_ladder)(const float *__restrict_
 // launchers
 // `views`: device array of nbatch level views (frame pairs of one batch, same w x h);
 // flags/stats: nbatch rows of `cap` iterations; dense (SweepBatchPlan::tile_form): 0 the lean kernel, 1 the dense
-// one, 2 its 128-VGPR form, 3 the dense one without the interior form -- FAST; the other arithmetics have one kernel
+// one, 2 its 128-VGPR form, 3 the dense one without the interior form -- FAST; the other arithmetics have one kernel.
+// temporal (every sweep launcher): do the levels of the launch carry the temporal term?  FAST launches the kernel
+// compiled without it when they do not (temp_on); the other arithmetics have the general kernels only and ignore it.
+#if VM_EXACT
+#define VM_VARIANT_LAUNCH(TEMPORAL_, KERNEL_, ...) hipLaunchKernelGGL(KERNEL_(true), __VA_ARGS__)
+#else
+#define VM_VARIANT_LAUNCH(TEMPORAL_, KERNEL_, ...)           \
+    do {                                                     \
+        if (TEMPORAL_)                                       \
+            hipLaunchKernelGGL(KERNEL_(true), __VA_ARGS__);  \
+        else                                                 \
+            hipLaunchKernelGGL(KERNEL_(false), __VA_ARGS__); \
+    } while (0)
+#endif
 void SUF(vm_launch_optimize)(const VmLevelView *views, int nbatch, int cap, int w, int h, const VmKParams &P,
                              const uint32_t *tables, int offx, int offy, uint32_t *flags, uint32_t *stats,
                              int iter_idx, int fixed_work, int threads, const int *iter_dev, int dense,
-                             uint32_t *tile_list, hipStream_t s)
+                             uint32_t *tile_list, int temporal, hipStream_t s)
 {
     dim3 b(threads), g((w + VM_PITCH_X - 1) / VM_PITCH_X, (h + VM_PITCH_Y - 1) / VM_PITCH_Y, nbatch);
+    (void)temporal;
+#define K_TILE_(TEMP_) (SUF(k_optimize)<true, VM_SMAX, VM_MIN_FANOUT, true, TEMP_>)
 #if !VM_EXACT
+#define K_LISTED_(TEMP_) (SUF(k_optimize_listed)<TEMP_>)
+#define K_LEAN_(TEMP_) (SUF(k_optimize)<false, VM_SMAX, VM_MIN_FANOUT, true, TEMP_>)
+#define K_TILE128_(TEMP_) (SUF(k_optimize)<true, 7, 4, true, TEMP_>)
+#define K_TILE_NOINT_(TEMP_) (SUF(k_optimize)<true, VM_SMAX, VM_MIN_FANOUT, false, TEMP_>)
     if (!dense && tile_list) { // the listed form of a pruned pass (k_tile_scan)
         const int nwords = ((w + 4) / 5 + 2) * ((h + 4) / 5 + 2), tiles = (int)(g.x * g.y);
         hipLaunchKernelGGL(SUF(k_tile_scan), dim3(std::min((nwords + 255) / 256, 32), 1, nbatch), dim3(256), 0, s, views, cap, offx,
                            offy, flags, iter_idx, fixed_work, iter_dev, tile_list, tiles);
-        hipLaunchKernelGGL(SUF(k_optimize_listed), dim3(std::min(tiles * nbatch, VM_TILE_LIST_GRID)), b, 0, s, views, cap, P, tables,
-                           offx, offy, flags, stats, iter_idx, iter_dev, tile_list, tiles, nbatch);
+        VM_VARIANT_LAUNCH(temporal, K_LISTED_, dim3(std::min(tiles * nbatch, VM_TILE_LIST_GRID)), b, 0, s, views, cap, P, tables,
+                          offx, offy, flags, stats, iter_idx, iter_dev, tile_list, tiles, nbatch);
         return;
     }
     if (!dense) {
-        hipLaunchKernelGGL(SUF(k_optimize)<false>, g, b, 0, s, views, cap, P, tables, offx, offy, flags, stats,
-                           iter_idx, fixed_work, iter_dev);
+        VM_VARIANT_LAUNCH(temporal, K_LEAN_, g, b, 0, s, views, cap, P, tables, offx, offy, flags, stats,
+                          iter_idx, fixed_work, iter_dev);
         return;
     }
     if (dense == 2) { // the 128-VGPR form: two workgroups per CU
-        hipLaunchKernelGGL((SUF(k_optimize)<true, 7, 4>), g, b, 0, s, views, cap, P, tables, offx, offy, flags, stats,
-                           iter_idx, fixed_work, iter_dev);
+        VM_VARIANT_LAUNCH(temporal, K_TILE128_, g, b, 0, s, views, cap, P, tables, offx, offy, flags, stats,
+                          iter_idx, fixed_work, iter_dev);
         return;
     }
     if (dense == 3) { // without the interior form (VM_NOINT_MAX_TILES, vm_sweep_plan.h)
-        hipLaunchKernelGGL((SUF(k_optimize)<true, VM_SMAX, VM_MIN_FANOUT, false>), g, b, 0, s, views, cap, P, tables, offx, offy,
-                           flags, stats, iter_idx, fixed_work, iter_dev);
+        VM_VARIANT_LAUNCH(temporal, K_TILE_NOINT_, g, b, 0, s, views, cap, P, tables, offx, offy,
+                          flags, stats, iter_idx, fixed_work, iter_dev);
         return;
     }
+#undef K_LISTED_
+#undef K_LEAN_
+#undef K_TILE128_
+#undef K_TILE_NOINT_
 #endif
     (void)dense;
-    hipLaunchKernelGGL(SUF(k_optimize)<true>, g, b, 0, s, views, cap, P, tables, offx, offy, flags, stats, iter_idx,
-                       fixed_work, iter_dev);
+    VM_VARIANT_LAUNCH(temporal, K_TILE_, g, b, 0, s, views, cap, P, tables, offx, offy, flags, stats, iter_idx,
+                      fixed_work, iter_dev);
+#undef K_TILE_
 }
 
 // a batch of `nit` iterations of the SPARSE schedule: list scan + one workgroup per pair
 void SUF(vm_launch_optimize_sparse)(const VmLevelView *views, int nbatch, int cap, int w, int h, const VmKParams &P,
                                     const uint32_t *tables, uint32_t *flags, uint32_t *stats, int it0, int nit,
-                                    int fixed_work, int threads, int dense, int lds_cap, int res_mode, hipStream_t s)
+                                    int fixed_work, int threads, int dense, int lds_cap, int res_mode, int temporal,
+                                    hipStream_t s)
 {
+    (void)temporal;
+#define K_SPARSE_(TEMP_) (SUF(k_sparse)<true, TEMP_>)
     const int nwords = ((w + 4) / 5 + 2) * ((h + 4) / 5 + 2);
     hipLaunchKernelGGL(SUF(k_sparse_scan), dim3((nwords + 255) / 256, 1, nbatch), dim3(256), 0, s, views);
 #if !VM_EXACT
     if (!dense) {
-        hipLaunchKernelGGL(SUF(k_sparse)<false>, dim3(1, 1, nbatch), dim3(threads), 0, s, views, cap, P, tables, flags,
-                           stats, it0, nit, fixed_work, lds_cap, res_mode);
+#define K_SPARSE_LEAN_(TEMP_) (SUF(k_sparse)<false, TEMP_>)
+        VM_VARIANT_LAUNCH(temporal, K_SPARSE_LEAN_, dim3(1, 1, nbatch), dim3(threads), 0, s, views, cap, P, tables, flags,
+                          stats, it0, nit, fixed_work, lds_cap, res_mode);
+#undef K_SPARSE_LEAN_
         return;
     }
 #endif
     (void)dense;
-    hipLaunchKernelGGL(SUF(k_sparse)<true>, dim3(1, 1, nbatch), dim3(threads), 0, s, views, cap, P, tables, flags, stats,
-                       it0, nit, fixed_work, lds_cap, res_mode);
+    VM_VARIANT_LAUNCH(temporal, K_SPARSE_, dim3(1, 1, nbatch), dim3(threads), 0, s, views, cap, P, tables, flags, stats,
+                      it0, nit, fixed_work, lds_cap, res_mode);
+#undef K_SPARSE_
 }
 
 // the device iteration counter of graph-replayed sweeps: set it to, or advance it by, `value`
@@ -4499,17 +4547,24 @@ void SUF(vm_launch_next_iter)(int *iter_dev, int set, int value, hipStream_t s)
 void SUF(vm_launch_optimize_split)(const VmLevelView *views, int nbatch, int cap, int w, int h,
                                    const VmKParams &P, const uint32_t *tables, int offx, int offy, int pass,
                                    uint32_t *flags, uint32_t *stats, int iter_idx, int fixed_work, int threads,
-                                   int parts, hipStream_t s)
+                                   int parts, int temporal, hipStream_t s)
 {
+    (void)temporal;
+#if VM_EXACT
+#define K_DECIDE_(TEMP_) SUF(k_decide)
+#else
+#define K_DECIDE_(TEMP_) (SUF(k_decide)<TEMP_>)
+#endif
     const int gx = (w + VM_PITCH_X - 1) / VM_PITCH_X, gy = (h + VM_PITCH_Y - 1) / VM_PITCH_Y;
     for (int pi = 0; pi < 2; ++pi)
         for (int pj = 0; pj < 2; ++pj) {
             const uint32_t epoch = 1u + (uint32_t)((iter_idx * 4 + pass) * 4 + pi * 2 + pj);
-            hipLaunchKernelGGL(SUF(k_decide), dim3(gx * gy * parts, 1, nbatch), dim3(threads), 0, s, views, cap, P,
-                               tables, offx, offy, pi, pj, parts, epoch, flags, stats, iter_idx, fixed_work);
+            VM_VARIANT_LAUNCH(temporal, K_DECIDE_, dim3(gx * gy * parts, 1, nbatch), dim3(threads), 0, s, views, cap, P,
+                              tables, offx, offy, pi, pj, parts, epoch, flags, stats, iter_idx, fixed_work);
             hipLaunchKernelGGL(SUF(k_commit), dim3(gx, gy, nbatch), dim3(1024), 0, s, views, cap, P, tables, offx,
                                offy, pi, pj, epoch, flags, stats, iter_idx, fixed_work);
         }
+#undef K_DECIDE_
 }
 
 // one phase of the STEP schedule: fold of the previous phase's records + line
@@ -4518,30 +4573,41 @@ void SUF(vm_launch_optimize_step)(const VmLevelView *views, int nbatch, int cap,
                                   const uint32_t *tables, int offx, int offy, int pi, int pj, uint32_t epoch,
                                   uint32_t prev_epoch, int src, int decide, uint32_t *flags, uint32_t *stats,
                                   int iter_idx, int fixed_work, int threads, int parts, uint32_t *slots_cur,
-                                  const uint32_t *slots_prev, int prev_iter_idx, hipStream_t s)
+                                  const uint32_t *slots_prev, int prev_iter_idx, int temporal, hipStream_t s)
 {
+    (void)temporal;
+#define K_STEP256_(TEMP_) (SUF(k_step)<256, TEMP_>)
+#define K_STEP512_(TEMP_) (SUF(k_step)<512, TEMP_>)
     const int gx = (w + VM_PITCH_X - 1) / VM_PITCH_X, gy = (h + VM_PITCH_Y - 1) / VM_PITCH_Y;
     const int n_fold = ((w + 63) / 64) * ((h + 15) / 16);
     const int nslot = gx * gy * parts;
     const dim3 grid(n_fold + (decide ? nslot : 0), 1, nbatch);
     if (threads <= 256)
-        hipLaunchKernelGGL(SUF(k_step)<256>, grid, dim3(256), 0, s, views, cap, P, tables, offx, offy, pi, pj, parts,
-                           epoch, prev_epoch, src, n_fold, flags, stats, iter_idx, fixed_work, slots_cur, slots_prev,
-                           prev_iter_idx, nslot);
+        VM_VARIANT_LAUNCH(temporal, K_STEP256_, grid, dim3(256), 0, s, views, cap, P, tables, offx, offy, pi, pj, parts,
+                          epoch, prev_epoch, src, n_fold, flags, stats, iter_idx, fixed_work, slots_cur, slots_prev,
+                          prev_iter_idx, nslot);
     else
-        hipLaunchKernelGGL(SUF(k_step)<512>, grid, dim3(512), 0, s, views, cap, P, tables, offx, offy, pi, pj, parts,
-                           epoch, prev_epoch, src, n_fold, flags, stats, iter_idx, fixed_work, slots_cur, slots_prev,
-                           prev_iter_idx, nslot);
+        VM_VARIANT_LAUNCH(temporal, K_STEP512_, grid, dim3(512), 0, s, views, cap, P, tables, offx, offy, pi, pj, parts,
+                          epoch, prev_epoch, src, n_fold, flags, stats, iter_idx, fixed_work, slots_cur, slots_prev,
+                          prev_iter_idx, nslot);
+#undef K_STEP256_
+#undef K_STEP512_
 }
 
+#if VM_EXACT
+#define K_PASS_(TEMP_) SUF(k_pass)
+#else
+#define K_PASS_(TEMP_) (SUF(k_pass)<TEMP_>)
+#endif
 // one pass of the PASS schedule: four phases of every tile behind tile-local barriers.  `bar`:
 // ngroups zeroed counters of this launch.  decide == 0: only the closing slot fold of a batch.
 void SUF(vm_launch_optimize_pass)(const VmLevelView *views, int nbatch, int cap, int w, int h, const VmKParams &P,
                                   const uint32_t *tables, int offx, int offy, uint32_t epoch0, uint32_t *bar,
                                   uint32_t *flags, uint32_t *stats, int iter_idx, int fixed_work, uint32_t *slots_cur,
                                   const uint32_t *slots_prev, int prev_iter_idx, uint32_t *err, uint32_t *dbg,
-                                  int decide, int force_wt, hipStream_t s)
+                                  int decide, int force_wt, int temporal, hipStream_t s)
 {
+    (void)temporal;
     const int gx = (w + VM_PITCH_X - 1) / VM_PITCH_X, gy = (h + VM_PITCH_Y - 1) / VM_PITCH_Y;
     const int ntiles = gx * gy, ngroups = ntiles * nbatch;
     const int nblocks = (ngroups + 7) / 8 * 256;
@@ -4550,20 +4616,27 @@ void SUF(vm_launch_optimize_pass)(const VmLevelView *views, int nbatch, int cap,
                            force_wt & 4);
         return;
     }
-    hipLaunchKernelGGL(SUF(k_pass), dim3(nblocks), dim3(VM_PASS_T), 0, s, views, cap, P, tables, offx, offy, epoch0, ngroups,
-                       ntiles, bar, flags, stats, iter_idx, fixed_work, slots_cur, slots_prev, prev_iter_idx, nblocks, err,
-                       dbg, force_wt);
+    VM_VARIANT_LAUNCH(temporal, K_PASS_, dim3(nblocks), dim3(VM_PASS_T), 0, s, views, cap, P, tables, offx, offy, epoch0, ngroups,
+                      ntiles, bar, flags, stats, iter_idx, fixed_work, slots_cur, slots_prev, prev_iter_idx, nblocks, err,
+                      dbg, force_wt);
 }
 
 // how many workgroups of k_pass the device holds at once: a tile group's 32 workgroups wait for each other
 // inside a launch, so a 256-workgroup chunk (8 groups) must be co-resident -- an MI355X in its default
-// mode holds 256 (one per CU); a partitioned or smaller device does not, and gets the STEP schedule
-int SUF(vm_pass_resident_blocks)(int device)
+// mode holds 256 (one per CU); a partitioned or smaller device does not, and gets the STEP schedule.  Asked about the
+// variant that will be launched.
+int SUF(vm_pass_resident_blocks)(int device, int temporal)
 {
     hipDeviceProp_t pr;
     int per_cu = 0;
-    if (hipGetDeviceProperties(&pr, device) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, SUF(k_pass), VM_PASS_T, 0) != hipSuccess) {
+    (void)temporal;
+#if VM_EXACT
+    const hipError_t occ = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, SUF(k_pass), VM_PASS_T, 0);
+#else
+    const hipError_t occ = temporal ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, SUF(k_pass)<true>, VM_PASS_T, 0)
+                                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, SUF(k_pass)<false>, VM_PASS_T, 0);
+#endif
+    if (hipGetDeviceProperties(&pr, device) != hipSuccess || occ != hipSuccess) {
         (void)hipGetLastError();
         return 0;
     }

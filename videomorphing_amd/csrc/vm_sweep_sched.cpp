@@ -140,13 +140,13 @@ static const int pass_offs[4][2] = {{0, 0}, {VM_TILE_W, 0}, {0, VM_TILE_H}, {VM_
 // (VM_NO_GRAPH set, or capture/instantiation failed once): the caller launches eagerly.
 #define VM_GRAPH_ITERS 8
 static hipGraphExec_t sweep_graph(vm_ctx *c, int math_mode, int n, int w, int h, int cap, int fixed_work, int threads,
-                                  int dense, uint32_t *tile_list, const VmKParams &P)
+                                  int dense, uint32_t *tile_list, int temporal, const VmKParams &P)
 {
     if (c->use_graphs < 0) c->use_graphs = getenv("VM_NO_GRAPH") ? 0 : 1;
     if (!c->use_graphs) return nullptr;
     for (auto &g : c->graphs)
         if (g.math_mode == math_mode && g.n == n && g.w == w && g.h == h && g.cap == cap && g.fixed_work == fixed_work &&
-            g.threads == threads && g.dense == dense && g.order == c->commit_order && g.views == c->views.get() && g.flags == c->flags.get() && g.stats == c->stats.get() && g.tile_list == tile_list &&
+            g.threads == threads && g.dense == dense && g.temporal == temporal && g.order == c->commit_order && g.views == c->views.get() && g.flags == c->flags.get() && g.stats == c->stats.get() && g.tile_list == tile_list &&
             memcmp(&g.kp, &c->kp, sizeof(c->kp)) == 0)
             return g.exec;
     if (c->iter_dev.reserve(1) != VM_OK) {
@@ -160,7 +160,7 @@ static hipGraphExec_t sweep_graph(vm_ctx *c, int math_mode, int n, int w, int h,
     if (ok) {
         for (int it = 0; it < VM_GRAPH_ITERS; ++it) {
             for (int k = 0; k < 4; ++k) {
-                SL.optimize(c->views.get(), n, cap, w, h, P, c->tables.get(), pass_offs[k][0], pass_offs[k][1], c->flags.get(), c->stats.get(), it, fixed_work, threads, c->iter_dev.get(), dense, tile_list, c->stream);
+                SL.optimize(c->views.get(), n, cap, w, h, P, c->tables.get(), pass_offs[k][0], pass_offs[k][1], c->flags.get(), c->stats.get(), it, fixed_work, threads, c->iter_dev.get(), dense, tile_list, temporal, c->stream);
             }
         }
         SL.next_iter(c->iter_dev.get(), 0, VM_GRAPH_ITERS, c->stream);
@@ -177,7 +177,7 @@ static hipGraphExec_t sweep_graph(vm_ctx *c, int math_mode, int n, int w, int h,
         for (auto &g : c->graphs) hipGraphExecDestroy(g.exec);
         c->graphs.clear();
     }
-    c->graphs.push_back({math_mode, n, w, h, cap, fixed_work, threads, dense, c->commit_order, c->views.get(), c->flags.get(), c->stats.get(), tile_list, c->kp, exec});
+    c->graphs.push_back({math_mode, n, w, h, cap, fixed_work, threads, dense, c->commit_order, temporal, c->views.get(), c->flags.get(), c->stats.get(), tile_list, c->kp, exec});
     return exec;
 }
 
@@ -271,6 +271,7 @@ struct SweepRun {
     vm_ctx *c = nullptr;
     vm_level **lv = nullptr;
     int n = 0, w = 0, h = 0, cap = 1, fixed_work = 0;
+    int temporal = 1; // the sweep variant of every launch of the call: 1 the general kernels, 0 the ones compiled without the temporal term
     size_t rec_bytes = 0; // of a level's record tags
     hipStream_t s = nullptr;
     VmKParams P{};
@@ -313,8 +314,8 @@ static int admit_pass(SweepRun &r)
         want_pass = false;
     }
     if (want_pass) { // a 256-workgroup chunk of the launch must fit the device at once
-        int &res = c->pass_resident[c->math_mode & 7];
-        if (res < 0) res = r.SL->pass_resident(c->device);
+        int &res = c->pass_resident[(c->math_mode & 7) * 2 + r.temporal];
+        if (res < 0) res = r.SL->pass_resident(c->device, r.temporal);
         if (res < 256) {
             if (c->sweep_mode == VM_SWEEP_PASS)
                 return vm_fail(VM_E_STATE, "vm_optimize_level: the PASS schedule needs 256 co-resident workgroups, this device holds %d", res);
@@ -399,7 +400,7 @@ static int enqueue_sparse(SweepRun &r)
     // "as good as none": the list then lives in memory from the first pass it holds two words -- tests)
     r.SL->sparse(
         c->views.get(), r.n, r.cap, r.w, r.h, r.P, c->tables.get(), c->flags.get(), c->stats.get(), r.done, r.nb, r.fixed_work, r.plan.threads, r.b.dense,
-        c->sweep_mode == VM_SWEEP_SPARSE && c->sweep_parts > 0 ? c->sweep_parts : 1 << 20, c->sparse_resident, r.s);
+        c->sweep_mode == VM_SWEEP_SPARSE && c->sweep_parts > 0 ? c->sweep_parts : 1 << 20, c->sparse_resident, r.temporal, r.s);
     r.launches += 2;
     r.small_dense.leave();
     return VM_OK;
@@ -419,7 +420,7 @@ static int enqueue_tile(SweepRun &r)
     const int end = r.done + r.nb;
     int it0 = r.done;
     if (r.nb >= VM_GRAPH_ITERS) {
-        if (hipGraphExec_t ge = sweep_graph(c, c->math_mode, r.n, r.w, r.h, r.cap, r.fixed_work, tile_threads, form, tile_list, r.P)) {
+        if (hipGraphExec_t ge = sweep_graph(c, c->math_mode, r.n, r.w, r.h, r.cap, r.fixed_work, tile_threads, form, tile_list, r.temporal, r.P)) {
             r.SL->next_iter(c->iter_dev.get(), 1, r.done, r.s);
             for (; it0 + VM_GRAPH_ITERS <= end; it0 += VM_GRAPH_ITERS) {
                 VM_HIP(hipGraphLaunch(ge, r.s));
@@ -429,7 +430,7 @@ static int enqueue_tile(SweepRun &r)
     }
     for (int it = it0; it < end; ++it)
         for (int k = 0; k < 4; ++k) {
-            r.SL->optimize(c->views.get(), r.n, r.cap, r.w, r.h, r.P, c->tables.get(), pass_offs[k][0], pass_offs[k][1], c->flags.get(), c->stats.get(), it, r.fixed_work, tile_threads, nullptr, form, tile_list, r.s);
+            r.SL->optimize(c->views.get(), r.n, r.cap, r.w, r.h, r.P, c->tables.get(), pass_offs[k][0], pass_offs[k][1], c->flags.get(), c->stats.get(), it, r.fixed_work, tile_threads, nullptr, form, tile_list, r.temporal, r.s);
             ++r.launches;
         }
     return VM_OK;
@@ -442,7 +443,7 @@ static int enqueue_split(SweepRun &r)
     r.small_dense.leave();
     for (int it = r.done; it < r.done + r.nb; ++it)
         for (int k = 0; k < 4; ++k) {
-            r.SL->split(c->views.get(), r.n, r.cap, r.w, r.h, r.P, c->tables.get(), pass_offs[k][0], pass_offs[k][1], k, c->flags.get(), c->stats.get(), it, r.fixed_work, r.plan.threads, r.plan.parts, r.s);
+            r.SL->split(c->views.get(), r.n, r.cap, r.w, r.h, r.P, c->tables.get(), pass_offs[k][0], pass_offs[k][1], k, c->flags.get(), c->stats.get(), it, r.fixed_work, r.plan.threads, r.plan.parts, r.temporal, r.s);
             r.launches += 8;
         }
     return VM_OK;
@@ -476,7 +477,7 @@ static int enqueue_step(SweepRun &r)
                 r.SL->step(
                     c->views.get(), r.n, r.cap, r.w, r.h, r.P, c->tables.get(), pass_offs[k][0], pass_offs[k][1], ph >> 1, ph & 1, epoch,
                     sb == 0 ? 0u : epoch - 1u, sb & 1, 1, c->flags.get(), c->stats.get(), it, r.fixed_work, threads, parts,
-                    slots[sb & 1], slots[(sb + 1) & 1], sb == 0 ? -1 : slot_iter, r.s);
+                    slots[sb & 1], slots[(sb + 1) & 1], sb == 0 ? -1 : slot_iter, r.temporal, r.s);
                 slot_iter = it;
                 last_epoch = epoch;
             }
@@ -485,7 +486,7 @@ static int enqueue_step(SweepRun &r)
     // fold the last phase's records in place: copy 0 is complete again
     r.SL->step(
         c->views.get(), r.n, r.cap, r.w, r.h, r.P, c->tables.get(), 0, 0, 0, 0, 0u, last_epoch, 2, 0, c->flags.get(), c->stats.get(),
-        r.done + r.nb - 1, r.fixed_work, threads, parts, slots[sb & 1], slots[(sb + 1) & 1], sb == 0 ? -1 : slot_iter, r.s);
+        r.done + r.nb - 1, r.fixed_work, threads, parts, slots[sb & 1], slots[(sb + 1) & 1], sb == 0 ? -1 : slot_iter, r.temporal, r.s);
     ++r.launches;
     return VM_OK;
 }
@@ -517,7 +518,7 @@ static int enqueue_pass(SweepRun &r)
                 c->views.get(), r.n, r.cap, r.w, r.h, r.P, c->tables.get(), pass_offs[k][0], pass_offs[k][1], 1u + (uint32_t)((it * 4 + k) * 4),
                 c->pass_bar.get() + (size_t)((it - r.done) * 4 + k) * pass_groups * VM_PASS_SYNC_WORDS, c->flags.get(), c->stats.get(), it, r.fixed_work,
                 slots[sb & 1], slots[(sb + 1) & 1], sb == 0 ? -1 : slot_iter, c->pass_err.get(),
-                c->pass_dbg.get(), 1, pass_switches, r.s);
+                c->pass_dbg.get(), 1, pass_switches, r.temporal, r.s);
             slot_iter = it;
             ++sb;
             ++r.launches;
@@ -525,7 +526,7 @@ static int enqueue_pass(SweepRun &r)
     if (sb > 0) {
         r.SL->pass(
             c->views.get(), r.n, r.cap, r.w, r.h, r.P, c->tables.get(), 0, 0, 0u, nullptr, c->flags.get(), c->stats.get(), r.done + r.nb - 1, r.fixed_work,
-            nullptr, slots[(sb + 1) & 1], slot_iter, c->pass_err.get(), nullptr, 0, pass_switches, r.s);
+            nullptr, slots[(sb + 1) & 1], slot_iter, c->pass_err.get(), nullptr, 0, pass_switches, r.temporal, r.s);
         ++r.launches;
     }
     return VM_OK;
@@ -693,6 +694,8 @@ int vm_optimize_levels(vm_ctx *c, vm_level **lv, int n, float max_iter, volatile
     r.w = l0.w;
     r.h = l0.h;
     r.fixed_work = fixed_work;
+    // uniform over the batch by the check above; vm_dbg_sweep_variant 1 keeps the general kernels
+    r.temporal = l0.view.temp_mask != nullptr || c->sweep_variant == 1;
     r.rec_bytes = (size_t)l0.rs * l0.h * 4;
     r.s = c->stream;
     r.P = {c->kp.w_ui, c->kp.w_tps, c->kp.w_ssim, c->kp.ssim_clamp, c->kp.eps, c->kp.bcond, c->kp.w_temp, c->commit_order};

@@ -521,6 +521,7 @@ static int ensure_lanes(vm_video *v, int n)
         ln.c->sweep_parts = p->sweep_parts;
         ln.c->commit_order = p->commit_order;
         ln.c->reduction = p->reduction;
+        ln.c->sweep_variant = p->sweep_variant;
         ln.c->sparse_resident = p->sparse_resident;       // the debug switches too: a hook set on the
         ln.c->pass_test_timeout = p->pass_test_timeout;   // video's context acts on the lanes that do its work
     }

@@ -146,6 +146,11 @@ class Context(object):
         after every commit, 3 give residency up at the first commit (vm_dbg_sparse_resident)"""
         capi.check(self._L.vm_dbg_sparse_resident(self._h, int(mode)))
 
+    def set_sweep_variant(self, mode=0):
+        """test hook of the FAST sweep variants: 0 by the level (the kernels compiled without the temporal term where
+        no page carries it), 1 always the general kernels (vm_dbg_sweep_variant)"""
+        capi.check(self._L.vm_dbg_sweep_variant(self._h, int(mode)))
+
     def sparse_resident_visits(self):
         """tile visits of this context's solves served from the resident LDS copy so far (vm_dbg_sparse_resident_visits)"""
         return int(self._L.vm_dbg_sparse_resident_visits(self._h))
