@@ -93,6 +93,26 @@ __device__ __forceinline__ float cell_count(int qy, int h, int qx, int w) { retu
 // group owns window neighbour (px + column - 2, py + row - 2)
 __device__ __forceinline__ int window_row(int k) { return (k * 13) >> 6; }
 
+// development switches of profiles/phase_chain.md (VM_DEFS="-DVM_CHAIN_...=0" builds a library without that part)
+#ifndef VM_CHAIN_BESIDE
+#define VM_CHAIN_BESIDE 1 // decide64: the coming round's lane term beside this round's sum; the gradient's pair of sums
+#endif
+#ifndef VM_CHAIN_SELECTS
+#define VM_CHAIN_SELECTS 1 // the start blocks' border classes as arithmetic
+#endif
+// border_class (vm_morph_common.h) of an in-image coordinate as arithmetic: a level is at least 5 wide and high
+// (vm_pyramid_create), so the classes 0, 1 | 2 | 3, 4 are min(p, clamp(p - dim + 5, 2, 4)).  The compare-and-select
+// form goes through scalar pairs, each select a wait state or two behind its compare.  Outside the image (a position
+// no caller uses: the kernels index S.tps with it only for a pixel that committed) it stays within -inf .. 4.
+__device__ __forceinline__ int border_class_in(int p, int dim)
+{
+#if VM_CHAIN_SELECTS
+    return min(p, min(max(p - dim + 5, 2), 4));
+#else
+    return border_class(p, dim);
+#endif
+}
+
 struct TileLds {
     float2 mean[VM_NCELL], var[VM_NCELL], tpsb[VM_NCELL];
     float cross[VM_NCELL], value[VM_NCELL];
@@ -974,8 +994,11 @@ __device__ __forceinline__ void line_lumas(const VmLevelView &L, const TapLane &
 
 // sum over the window of (stored SSIM value - value with the pixel's lumas replaced by
 // lx, ly): ssim_change (morph.cu:671-728) on 32 lanes
+// (change32_lane: this lane's term of that sum.  The callers that have something to put behind the steps of the 32-lane
+// sum open it themselves: a DPP step that reads what the previous vector instruction wrote waits two states, which a
+// lone wave spends on nothing -- profiles/phase_chain.md)
 template <bool INTERIOR>
-__device__ __forceinline__ float change32(const VmKParams &P, const Nb1 &nb, const PixelCtx &c, float lx, float ly)
+__device__ __forceinline__ float change32_lane(const VmKParams &P, const Nb1 &nb, const PixelCtx &c, float lx, float ly)
 {
     const float dmx = lx - c.old_luma.x, dmy = ly - c.old_luma.y;
     const float dvx = lx * lx - c.old_luma.x * c.old_luma.x;
@@ -994,7 +1017,103 @@ __device__ __forceinline__ float change32(const VmKParams &P, const Nb1 &nb, con
                                     nb.X + dcross, n, P.ssim_clamp);
         acc = valid ? nb.VAL - val : 0.0f;
     }
-    return group_sum(acc, 32);
+    return acc;
+}
+template <bool INTERIOR>
+__device__ __forceinline__ float change32(const VmKParams &P, const Nb1 &nb, const PixelCtx &c, float lx, float ly)
+{
+    return group_sum(change32_lane<INTERIOR>(P, nb, c, lx, ly), 32);
+}
+// nothing crosses: the statements between two of these are scheduled among themselves and stay where they stand
+#define VM_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
+// two independent sums over 32 lanes, step by step side by side: each sum's association order is group_sum's, and a
+// step of one sum stands in a wait state of the other's
+__device__ __forceinline__ void group_sum32_pair(float &x, float &y)
+{
+    VM_SCHED_FENCE();
+    x += dpp_xor1(x);
+    y += dpp_xor1(y);
+    VM_SCHED_FENCE();
+    x += dpp_xor2(x);
+    y += dpp_xor2(y);
+    VM_SCHED_FENCE();
+    x += dpp_half_mirror(x);
+    y += dpp_half_mirror(y);
+    VM_SCHED_FENCE();
+    x += dpp_mirror(x);
+    y += dpp_mirror(y);
+    VM_SCHED_FENCE();
+    const float sx = swz_xor16(x), sy = swz_xor16(y);
+    x += sx;
+    y += sy;
+}
+// change32_lane at (nlx, nly) -- its arithmetic statement by statement, in five parts -- beside the 32-lane sum of
+// `sum` (group_sum's steps in group_sum's order): each DPP step of the sum stands behind a part of the lane's term and
+// waits for nothing, and the sum's swizzle returns under the term's last part.  For a search whose coming point's lumas
+// are known while this point's sum is still to be made (the ladder).  Returns the term of (nlx, nly); `sum` is summed.
+// The forced PASS / STEP / SPLIT cases of tests/test_gpu_phase_chain.py hold the two statements of the term together.
+template <bool INTERIOR>
+__device__ __forceinline__ float change32_lane_beside_sum(const VmKParams &P, const Nb1 &nb, const PixelCtx &c, float nlx,
+                                                          float nly, float &sum)
+{
+    const bool valid = nb.N != 0.0f;
+    const float n = INTERIOR ? 25.0f : (valid ? nb.N : 25.0f);
+    const float in = INTERIOR ? 0.04f : (n == 25.0f ? 0.04f : __builtin_amdgcn_rcpf(n));
+    const float nc2 = n * 58.5225f, nc3 = n * 29.26125f;
+    VM_SCHED_FENCE();
+    const float dmx = nlx - c.old_luma.x, dmy = nly - c.old_luma.y;
+    const float xx = nlx * nlx, yy = nly * nly, xy = nlx * nly;
+    VM_SCHED_FENCE();
+    sum += dpp_xor1(sum);
+    VM_SCHED_FENCE();
+    const float dvx = xx - c.old_luma.x * c.old_luma.x;
+    const float dvy = yy - c.old_luma.y * c.old_luma.y;
+    const float dcross = xy - c.old_luma.x * c.old_luma.y;
+    const float a = window_mean(nb.A, dmx, in), b = window_mean(nb.B, dmy, in);
+    VM_SCHED_FENCE();
+    sum += dpp_xor2(sum);
+    VM_SCHED_FENCE();
+    const float sx2 = nb.VX + dvx, sy2 = nb.VY + dvy, sxy = nb.X + dcross;
+    const float na = n * a, nbb = n * b;
+    const float vx = fmaxf(fmaf(-na, a, sx2), 0.0f);
+    const float vy = fmaxf(fmaf(-nbb, b, sy2), 0.0f);
+    VM_SCHED_FENCE();
+    sum += dpp_half_mirror(sum);
+    VM_SCHED_FENCE();
+    const float cov = fmaf(-na, b, sxy);
+    const float ss = __builtin_amdgcn_sqrtf(vx * vy);
+    VM_SCHED_FENCE();
+    sum += dpp_mirror(sum);
+    const float other = swz_xor16(sum);
+    VM_SCHED_FENCE();
+    const float num = fmaf(2.0f, ss, nc2) * (fabsf(cov) + nc3);
+    const float den = ((vx + vy) + nc2) * (ss + nc3);
+    const float val = fmaxf(fminf(num * __builtin_amdgcn_rcpf(den), 1.0f), P.ssim_clamp);
+    float acc = valid ? nb.VAL - val : 0.0f;
+    // (the term is used only if the search goes on: without this the compiler sinks it behind the test that decides
+    // that, back onto the chain)
+    asm volatile("" : "+v"(acc));
+    VM_SCHED_FENCE();
+    sum += other;
+    return acc;
+}
+// taps32_finish of two independent evaluations, likewise
+__device__ __forceinline__ void taps32_finish_pair(const TapLane &t, float texel0, float wgt0, float texel1, float wgt1,
+                                                   float &lx0, float &ly0, float &lx1, float &ly1)
+{
+    float r0 = texel0 * wgt0, r1 = texel1 * wgt1;
+    VM_SCHED_FENCE();
+    r0 += dpp_xor1(r0);
+    r1 += dpp_xor1(r1);
+    VM_SCHED_FENCE();
+    r0 += dpp_xor2(r0);
+    r1 += dpp_xor2(r1);
+    VM_SCHED_FENCE();
+    const float o0 = dpp_half_mirror(r0), o1 = dpp_half_mirror(r1);
+    lx0 = t.odd ? o0 : r0;
+    ly0 = t.odd ? r0 : o0;
+    lx1 = t.odd ? o1 : r1;
+    ly1 = t.odd ? r1 : o1;
 }
 
 // prevent_foldover (morph.cu:872-883): lane s < 16 tests segment s & 7 of ring s >> 3
@@ -1134,6 +1253,8 @@ __device__ __forceinline__ bool decide32(const VmLevelView &L, const VmKParams &
 // golden_section_search (morph.cu:885-947) on [0, CC_] with the two halves of a wave side by side, stated once for
 // decide64 and for vm_dbg_golden (a macro, not a function: calls change this unit's code generation).
 // EVAL2_(t, flo, fhi): the energy at this half's t; flo / fhi come back as the lower / the upper half's value.
+// EVALR_(k, b, R, hi, xn, xn2, flo, fhi): a regime round's hook -- sets xn = b R and xn2 = xn R and evaluates this half's
+// one with the lumas of octet k (GOLDEN64_ROUND_PLAIN: by EVALB_).
 // TRACE_(t): a point whose evaluation the search USES, in the order decide32 makes them (GOLDEN64_NO_TRACE: nothing).
 // CC_ (the interval's upper end, consumed) and NEVAL_ are lvalues; TMIN_ / FMIN_ receive the final choice.  All values
 // are uniform over the wave, so neither loop diverges.
@@ -1182,13 +1303,20 @@ __device__ __forceinline__ float ladder_pick(bool hi, int oct, float l0, float h
         }                                                   \
     }
 #define GOLDEN64_NO_TRACE(T_)
+// EVALR_ in its plain form: the round's two multiplies, then EVALB_ at this half's point
+#define GOLDEN64_ROUND_PLAIN(EVALB_, K_, B_, R_, HI_, XN_, XN2_, FLO_, FHI_) \
+    {                                                                        \
+        (XN_) = (B_) * (R_);                                                 \
+        (XN2_) = (XN_) * (R_);                                               \
+        EVALB_(K_, (HI_) ? (XN2_) : (XN_), FLO_, FHI_);                      \
+    }
 #define GOLDEN64_NO_BATCH(T_)
 // one round of the regime loop; its lumas sit in octet K_ of the batch
-#define GOLDEN64_REGIME_ROUND(EVALB_, TRACE_, K_, CC_, EPS_, HI_, NEVAL_)                                              \
+#define GOLDEN64_REGIME_ROUND(EVALR_, TRACE_, K_, CC_, EPS_, HI_, NEVAL_)                                              \
     {                                                                                                                  \
-        const float xn = b * R, xn2 = xn * R;                                                                          \
+        float xn, xn2; /* b R and b R R: EVALR_ makes them, where its own instructions leave room */                   \
         float f1, f2;                                                                                                  \
-        EVALB_(K_, (HI_) ? xn2 : xn, f1, f2);                                                                          \
+        EVALR_(K_, b, R, (HI_), xn, xn2, f1, f2);                                                                      \
         TRACE_(xn)                                                                                                     \
         /* after the step (cc, x, b) <- (x, b, xn), (fx, fb) <- (fb, f1): does the search go on, the same way? */      \
         const bool held = x > (EPS_) && !(fb < f1);                                                                    \
@@ -1202,7 +1330,7 @@ __device__ __forceinline__ float ladder_pick(bool hi, int oct, float l0, float h
         fx = held ? f1 : fb;                                                                                           \
         fb = held ? f2 : f1;                                                                                           \
     }
-#define GOLDEN64(EVAL2_, BATCH_, EVALB_, TRACE_, CC_, EPS_, HI_, OCT_, NEVAL_, TMIN_, FMIN_)                           \
+#define GOLDEN64(EVAL2_, BATCH_, EVALB_, EVALR_, TRACE_, CC_, EPS_, HI_, OCT_, NEVAL_, TMIN_, FMIN_)                   \
     {                                                                                                                  \
         const float R = 0.618033989f, C = 1.0f - R;                                                                    \
         float a = 0;                                                                                                   \
@@ -1219,13 +1347,13 @@ __device__ __forceinline__ float ladder_pick(bool hi, int oct, float l0, float h
         _Pragma("unroll 1") for (;;) { /* the regime loop, a batch per trip */                                         \
             if (!((CC_) > (EPS_) && !(fx < fb)))                                                                       \
                 break;                                                                                                 \
-            GOLDEN64_REGIME_ROUND(EVALB_, TRACE_, 1, CC_, EPS_, HI_, NEVAL_)                                           \
+            GOLDEN64_REGIME_ROUND(EVALR_, TRACE_, 1, CC_, EPS_, HI_, NEVAL_)                                           \
             if (!((CC_) > (EPS_) && !(fx < fb)))                                                                       \
                 break;                                                                                                 \
-            GOLDEN64_REGIME_ROUND(EVALB_, TRACE_, 2, CC_, EPS_, HI_, NEVAL_)                                           \
+            GOLDEN64_REGIME_ROUND(EVALR_, TRACE_, 2, CC_, EPS_, HI_, NEVAL_)                                           \
             if (!((CC_) > (EPS_) && !(fx < fb)))                                                                       \
                 break;                                                                                                 \
-            GOLDEN64_REGIME_ROUND(EVALB_, TRACE_, 3, CC_, EPS_, HI_, NEVAL_)                                           \
+            GOLDEN64_REGIME_ROUND(EVALR_, TRACE_, 3, CC_, EPS_, HI_, NEVAL_)                                           \
             if (!((CC_) > (EPS_) && !(fx < fb)))                                                                       \
                 break;                                                                                                 \
             { /* the next batch: the points of the coming four rounds, should every guess hold */                      \
@@ -1233,7 +1361,7 @@ __device__ __forceinline__ float ladder_pick(bool hi, int oct, float l0, float h
                             q8 = q7 * R;                                                                               \
                 BATCH_(ladder_pick((HI_), (OCT_), q1, q2, q3, q4, q5, q6, q7, q8))                                     \
             }                                                                                                          \
-            GOLDEN64_REGIME_ROUND(EVALB_, TRACE_, 0, CC_, EPS_, HI_, NEVAL_)                                           \
+            GOLDEN64_REGIME_ROUND(EVALR_, TRACE_, 0, CC_, EPS_, HI_, NEVAL_)                                           \
         }                                                                                                              \
         _Pragma("unroll 1") for (;;)                                                                                   \
         {                                                                                                              \
@@ -1307,7 +1435,7 @@ __device__ __forceinline__ float ladder_pick(bool hi, int oct, float l0, float h
 // gain -- PASS 11.37 vs 11.15 us per phase, STEP 14.5 vs 14.1 (tools/dev_pass.py).  A round then costs ~255
 // instructions (two SSIM terms, two trees, 12 v_readlane broadcasts, the bookkeeping of a three-step speculation)
 // against ~150 here for ~2.7 instead of ~1.9 steps: 94 against 79 instructions per step of the search.  Removed.)
-template <bool INTERIOR, bool LADDER, bool TEMP, class Ring>
+template <bool INTERIOR, bool LADDER, bool TEMP, bool BESIDE = LADDER && VM_CHAIN_BESIDE, class Ring>
 __device__ __forceinline__ bool decide64(const VmLevelView &L, const VmKParams &P, const Nb1 &nb, const Ring &ring,
                                          const PixelCtx &c, int sub, bool hi, float2 &step, float2 &luma,
                                          uint32_t &n_eval)
@@ -1327,11 +1455,17 @@ __device__ __forceinline__ bool decide64(const VmLevelView &L, const VmKParams &
             const float dx = r == 0 ? sgn * P.eps : 0.0f, dy = r == 0 ? 0.0f : sgn * P.eps;
             taps32_issue(L, tl, c, c.v.x + dx, c.v.y + dy, g_tex[r], g_wgt[r]);
         }
+        // the two evaluations are independent: their quad sums and their 32-lane sums go side by side
+        float g_lx[2], g_ly[2], g_chg[2];
+        taps32_finish_pair(tl, g_tex[0], g_wgt[0], g_tex[1], g_wgt[1], g_lx[0], g_ly[0], g_lx[1], g_ly[1]);
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+            g_chg[r] = change32_lane<INTERIOR>(P, nb, c, g_lx[r], g_ly[r]);
+        group_sum32_pair(g_chg[0], g_chg[1]);
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
             const float dx = r == 0 ? sgn * P.eps : 0.0f, dy = r == 0 ? 0.0f : sgn * P.eps;
-            taps32_finish(tl, g_tex[r], g_wgt[r], lx, ly);
-            const float change = change32<INTERIOR>(P, nb, c, lx, ly);
+            const float change = g_chg[r];
             const float dd = dx * dx + dy * dy;
             const float v_tps = fmaf(c.tps_axy, dd, fmaf(c.tps_b.x, dx, c.tps_b.y * dy));
             const float v_ui = fmaf(c.ui_axy, dd, fmaf(c.ui_b.x, dx, c.ui_b.y * dy));
@@ -1382,7 +1516,9 @@ __device__ __forceinline__ bool decide64(const VmLevelView &L, const VmKParams &
         taps32(L, tl, c, fmaf(gx, (T_), c.v.x), fmaf(gy, (T_), c.v.y), keep, blx, bly);
     // ... and ELINE2 with the lumas of octet K_ of the batch; T_ is the point they were sampled at
 #define ELINE2B(K_, T_, FLO_, FHI_)                                                    \
-    {                                                                                  \
+    if (LADDER && BESIDE)                                                              \
+        ELINE2P(K_, T_, FLO_, FHI_)                                                    \
+    else {                                                                             \
         const float nvx_ = fmaf(gx, (T_), c.v.x), nvy_ = fmaf(gy, (T_), c.v.y);        \
         if (LADDER)                                                                    \
             LADDER_FETCH(K_, blx, bly, plx, ply, lx, ly)                               \
@@ -1393,10 +1529,58 @@ __device__ __forceinline__ bool decide64(const VmLevelView &L, const VmKParams &
             f_ = fmaf(WT, (fabsf(nvx_ - c.tref.x) + fabsf(nvy_ - c.tref.y)) - T0, f_); \
         halves(f_, (FLO_), (FHI_));                                                    \
     }
+    // BESIDE: a round of the ladder is one chain -- the lane's SSIM term, the five steps of the 32-lane sum, the exchange
+    // between the halves -- and on a lone wave every DPP step of the sum waits two states for the step before it, the
+    // last one a whole LDS round trip.  But the lumas of the COMING round sit in the batch already: its lane term does
+    // not need this round's sum, so it is made beside it (change32_lane_beside_sum) and handed on in `sn`.  Octet 0's
+    // round takes its own lumas, the coming round's and the one's after (plx, ply: fetched two rounds ahead now); rounds
+    // 1 and 2 start from `sn`; round 3 is followed by a new batch and sums alone.  The term made for a round that never
+    // runs (the search ended, or fell into the generic loop) is dropped: a few dozen instructions once per search.
+    // Every term and every sum that is USED is the one ELINE2B makes, bit for bit.
+    float sn = 0.0f;
+#define ELINE2P(K_, T_, FLO_, FHI_)                                                    \
+    {                                                                                  \
+        float s_, nlx_, nly_;                                                          \
+        if ((K_) == 0) {                                                               \
+            lx = ladder_take<0>(blx);                                                  \
+            ly = ladder_take<0>(bly);                                                  \
+            nlx_ = ladder_take<1>(blx);                                                \
+            nly_ = ladder_take<1>(bly);                                                \
+            plx = ladder_take<2>(blx);                                                 \
+            ply = ladder_take<2>(bly);                                                 \
+            s_ = change32_lane<INTERIOR>(P, nb, c, lx, ly);                            \
+        } else {                                                                       \
+            s_ = sn;                                                                   \
+            nlx_ = plx;                                                                \
+            nly_ = ply;                                                                \
+            if ((K_) == 1) {                                                           \
+                plx = ladder_take<3>(blx);                                             \
+                ply = ladder_take<3>(bly);                                             \
+            }                                                                          \
+        }                                                                              \
+        const float tq_ = (T_) * fmaf(Q2, (T_), Q1);                                   \
+        float tt_ = 0.0f;                                                              \
+        if (has_temp) {                                                                \
+            const float nvx_ = fmaf(gx, (T_), c.v.x), nvy_ = fmaf(gy, (T_), c.v.y);    \
+            tt_ = (fabsf(nvx_ - c.tref.x) + fabsf(nvy_ - c.tref.y)) - T0;              \
+        }                                                                              \
+        if ((K_) != 3)                                                                 \
+            sn = change32_lane_beside_sum<INTERIOR>(P, nb, c, nlx_, nly_, s_);         \
+        else                                                                           \
+            s_ = group_sum(s_, 32);                                                    \
+        float f_ = fmaf(WS, s_, tq_);                                                  \
+        if (has_temp)                                                                  \
+            f_ = fmaf(WT, tt_, f_);                                                    \
+        halves(f_, (FLO_), (FHI_));                                                    \
+    }
+    // a regime round: its two points (b R, b R R), then this half's evaluation
+#define ELINE2R(K_, B_, R_, HI_, XN_, XN2_, FLO_, FHI_) GOLDEN64_ROUND_PLAIN(ELINE2B, K_, B_, R_, HI_, XN_, XN2_, FLO_, FHI_)
     float tmin, fmin;
-    GOLDEN64(ELINE2, LADDER2, ELINE2B, GOLDEN64_NO_TRACE, cc, P.eps, hi, sub >> 3, n_eval, tmin, fmin)
+    GOLDEN64(ELINE2, LADDER2, ELINE2B, ELINE2R, GOLDEN64_NO_TRACE, cc, P.eps, hi, sub >> 3, n_eval, tmin, fmin)
 #undef ELINE2
+#undef ELINE2R
 #undef ELINE2B
+#undef ELINE2P
 #undef LADDER2
     if (!(fmin < 0))
         return false;
@@ -2484,7 +2668,7 @@ __device__ __forceinline__ bool sv_phases(TileLds &S, SvPix &X, SparseLds &Q, co
                         c.old_luma = X.luma[pc];
                         c.ui_axy = X.uiaxy[pc];
                         c.ui_b = X.uib[pc];
-                        c.tps_axy = S.tps[(border_class(py, L.h) * 5 + border_class(px, L.w)) * 25 + 12] / 2;
+                        c.tps_axy = S.tps[(border_class_in(py, L.h) * 5 + border_class_in(px, L.w)) * 25 + 12] / 2;
                         c.tref = make_float2(0, 0);
                         c.tmask = 0.0f;
                         if (temp_on<TEMP>(L)) { // uniform in the launch
@@ -3329,7 +3513,7 @@ __device__ __forceinline__ bool fold_cell(const VmLevelView &L, const float4 *__
             q.x += ra[k].z;
             q.y += ra[k].w;
             cr += rb[k].x;
-            const float kk = s_tps[(border_class(y, L.h) * 5 + border_class(x, L.w)) * 25 + (4 - dy) * 5 + (4 - dx)];
+            const float kk = s_tps[(border_class_in(y, L.h) * 5 + border_class_in(x, L.w)) * 25 + (4 - dy) * 5 + (4 - dx)];
             tb.x += rb[k].y * kk;
             tb.y += rb[k].z * kk;
         }
@@ -4096,7 +4280,7 @@ __global__ __launch_bounds__(VM_PASS_T) __attribute__((amdgpu_waves_per_eu(2, 2)
         const bool okc = cell_ok && sub < 25; // a window neighbour of the pixel
         const uint32_t gi = (uint32_t)(cell_ok ? mad24(qy, L.rs, qx) : pidx);
         const uint32_t g4 = gi << 2, g8 = gi << 3;
-        const float tps_axy = S.tps[(border_class(spy, L.h) * 5 + border_class(spx, L.w)) * 25 + 12] / 2;
+        const float tps_axy = S.tps[(border_class_in(spy, L.h) * 5 + border_class_in(spx, L.w)) * 25 + 12] / 2;
         __builtin_amdgcn_sched_barrier(0);
         // ---- the loads
         uint32_t mword[2], mcanon[2], mtag[2];
@@ -4163,8 +4347,8 @@ __global__ __launch_bounds__(VM_PASS_T) __attribute__((amdgpu_waves_per_eu(2, 2)
                     win[t] = cell_ok ? ((row << 1) >> (i0 + 1)) & 7u : 0u; // bit a: position (i0 + a, jj); i0 + 1 >= 0
                     if (e0y + 2 * t > 2)
                         win[t] = 0;
-                    bcx[t] = border_class(px + sx0 + 2 * (i0 + t), L.w);
-                    bcy[t] = border_class(py + sy0 + 2 * jj, L.h);
+                    bcx[t] = border_class_in(px + sx0 + 2 * (i0 + t), L.w);
+                    bcy[t] = border_class_in(py + sy0 + 2 * jj, L.h);
                 }
                 if (e0x + 4 > 2) { // the third column is out of reach (e0x = -1)
                     win[0] &= 3u;
@@ -4357,8 +4541,10 @@ __global__ __launch_bounds__(64) void SUF(k_dbg_golden)(const float *__restrict_
         ++n_pt;                                                 \
     }
 #define EGOLDENB(K_, T_, FLO_, FHI_) EGOLDEN(T_, FLO_, FHI_) // no taps: nothing to batch
+#define EGOLDENR(K_, B_, R_, HI_, XN_, XN2_, FLO_, FHI_) GOLDEN64_ROUND_PLAIN(EGOLDENB, K_, B_, R_, HI_, XN_, XN2_, FLO_, FHI_)
     float tmin, fmin;
-    GOLDEN64(EGOLDEN, GOLDEN64_NO_BATCH, EGOLDENB, TGOLDEN, cc, eps, hi, 0, n_eval, tmin, fmin)
+    GOLDEN64(EGOLDEN, GOLDEN64_NO_BATCH, EGOLDENB, EGOLDENR, TGOLDEN, cc, eps, hi, 0, n_eval, tmin, fmin)
+#undef EGOLDENR
 #undef EGOLDENB
 #undef EGOLDEN
 #undef TGOLDEN
@@ -4424,6 +4610,7 @@ __global__ __launch_bounds__(64) void SUF(k_dbg_ladder)(const float *__restrict_
         RLADDER(T_, lx_, ly_)                            \
         halves((T_), (FLO_), (FHI_));                    \
     }
+#define ELADDERR(K_, B_, R_, HI_, XN_, XN2_, FLO_, FHI_) GOLDEN64_ROUND_PLAIN(ELADDERB, K_, B_, R_, HI_, XN_, XN2_, FLO_, FHI_)
     // (the generic loop's evaluation: under f(t) = t the search never gets there with cc - a > eps)
 #define ELADDER(T_, FLO_, FHI_)                                                              \
     {                                                                                        \
@@ -4433,8 +4620,9 @@ __global__ __launch_bounds__(64) void SUF(k_dbg_ladder)(const float *__restrict_
         halves((T_), (FLO_), (FHI_));                                                        \
     }
     float tmin, fmin;
-    GOLDEN64(ELADDER, BLADDER, ELADDERB, GOLDEN64_NO_TRACE, cc, eps, hi, sub >> 3, n_eval, tmin, fmin)
+    GOLDEN64(ELADDER, BLADDER, ELADDERB, ELADDERR, GOLDEN64_NO_TRACE, cc, eps, hi, sub >> 3, n_eval, tmin, fmin)
 #undef ELADDER
+#undef ELADDERR
 #undef ELADDERB
 #undef BLADDER
 #undef RLADDER
