@@ -1,8 +1,9 @@
 """The float32 numpy statement of what videomorphing_amd/csrc/vm_filter.hip computes: the viewport calls of
-tests/viewport_ref.py with a cubic filter on the taps that read picture content -- a canvas, a layer.  The chain, the
-sample points, the blend, the sum in sample order and the division by (float)N are viewport_ref's (this module takes the
-`maps` of viewport_ref.sample_maps); what differs is the tap and, for RGB8, the clamp of the mean to [0, 255] before the
-rounding.  A cubic tap reads a W x H image at (x, y), the coordinates warp_ref.tap takes, in float32, in this order:
+tests/viewport_ref.py with a cubic filter on the taps that read picture content -- a canvas, a layer.  The chain and the
+sample points are viewport_ref's (this module takes the `maps` of viewport_ref.sample_maps); the blend, the sum in sample
+order and the division by (float)N are the tail of tests/chain_ref.py, handed this module's tap; what differs is that tap
+and, for RGB8, the clamp of the mean to [0, 255] before the rounding (chain_ref.bytes_of with clamp).  A cubic tap reads a
+W x H image at (x, y), the coordinates chain_ref.tap takes, in float32, in this order:
 
     xb = x - 0.5f;  fi = floorf(xb);  a = xb - fi;  fi = fminf(fmaxf(fi, -2.0f), (float)W + 1.0f);  i = (int)fi
     columns  c_k = clamp(i + k, 0, W - 1),  k = -1, 0, 1, 2                 (rows r_m from y, b, H likewise)
@@ -15,9 +16,8 @@ Every scalar is a float32 and every expression stands in the kernels' order (the
 tests/test_filter_ref.py pins the statement without a GPU, tests/test_gpu_filtered.py holds the kernels to it bit for bit."""
 import numpy as np
 
-import shutter_ref
-import warp_ref
-from warp_ref import HALF, ONE, f32
+import chain_ref as C
+from chain_ref import HALF, ONE, f32
 
 BILINEAR, CATMULL_ROM, MITCHELL, BSPLINE = 0, 1, 2, 3
 CUBIC = (CATMULL_ROM, MITCHELL, BSPLINE)
@@ -59,9 +59,9 @@ def _axis(n, x):
 
 def tap(img, x, y, filt):
     """the tap of an (h, w, C) float32 image at texture coordinates (x, y) (texel i at i + 0.5) under filter `filt`:
-    warp_ref.tap for BILINEAR, the cubic tap above otherwise"""
+    chain_ref.tap for BILINEAR, the cubic tap above otherwise"""
     if filt == BILINEAR:
-        return warp_ref.tap(img, x, y)
+        return C.tap(img, x, y)
     h, w = img.shape[:2]
     with np.errstate(all="ignore"):
         a, cols = _axis(w, x)
@@ -77,58 +77,38 @@ def tap(img, x, y, filt):
     return value
 
 
+def _tap_under(filt):
+    return lambda img, x, y: tap(img, x, y, filt)
+
+
 def canvas_taps(ext0, ext1, ex, maps, filt):
     """[(c0, c1)] of the samples: the taps of the two canvases at (map + ex) + 0.5, each (out_h, out_w, 3) float32"""
-    e0, e1, exf = ext0[..., :3].astype(f32), ext1[..., :3].astype(f32), f32(ex)
-    with np.errstate(all="ignore"):
-        return [(tap(e0, (m0[..., 0] + exf) + HALF, (m0[..., 1] + exf) + HALF, filt),
-                 tap(e1, (m1[..., 0] + exf) + HALF, (m1[..., 1] + exf) + HALF, filt)) for m0, m1 in maps]
-
-
-def _blended_mean(taps, color_fa, color_from):
-    with np.errstate(all="ignore"):
-        return shutter_ref._mean([warp_ref.blend(c0, c1, color_fa, color_from) for c0, c1 in taps], len(taps))
+    return C.plates(ext0[..., :3], ext1[..., :3], maps, ex, _tap_under(filt))
 
 
 def canvas_mean(ext0, ext1, ex, maps, color_fa, color_from, filt, taps=None):
     """acc / (float)N of the canvas taps on the samples' maps, NOT clamped: (out_h, out_w, 3) float32 (taps: canvas_taps
     of the same arguments, for a test that blends them several ways)"""
-    return _blended_mean(canvas_taps(ext0, ext1, ex, maps, filt) if taps is None else taps, color_fa, color_from)
-
-
-def bytes_of(mean, filt):
-    """the tail: the cubic filters' clamp to [0, 255] (fminf(fmaxf(.)): a NaN becomes 0), + 0.5 in double, truncation"""
-    if filt == BILINEAR:
-        return shutter_ref.bytes_of(mean)
-    with np.errstate(all="ignore"):
-        clamped = np.fmin(np.fmax(mean, f32(0)), f32(255))
-        assert clamped.dtype == f32
-        return (clamped.astype(np.float64) + 0.5).astype(np.uint8)
+    return C.blended_mean(canvas_taps(ext0, ext1, ex, maps, filt) if taps is None else taps, maps, color_fa, color_from)
 
 
 def render_viewport_bytes(ext0, ext1, ex, maps, color_fa, color_from, filt, taps=None):
-    """vm_frame_render_viewport_filtered on the maps of viewport_ref.sample_maps: (out_h, out_w, 3) uint8 (for BILINEAR defined
-    where viewport_ref.founded(maps) holds)"""
-    return bytes_of(canvas_mean(ext0, ext1, ex, maps, color_fa, color_from, filt, taps), filt)
+    """vm_frame_render_viewport_filtered on the maps of viewport_ref.sample_maps: (out_h, out_w, 3) uint8, the cubic filters'
+    mean clamped to [0, 255] first (for BILINEAR defined where chain_ref.founded(maps) holds)"""
+    return C.bytes_of(canvas_mean(ext0, ext1, ex, maps, color_fa, color_from, filt, taps), filt in CUBIC)
 
 
 def layer_taps(layer0, layer1, maps, filt, lex=0):
     """[(c0, c1)] of the samples: the taps of the two layers at (map + lex) + 0.5, each (out_h, out_w, C) float32"""
-    l0, l1 = np.asarray(layer0, dtype=f32), np.asarray(layer1, dtype=f32)
-    if l0.ndim == 2:
-        l0, l1 = l0[..., None], l1[..., None]
-    lexf = f32(lex)
-    with np.errstate(all="ignore"):
-        return [(tap(l0, (m0[..., 0] + lexf) + HALF, (m0[..., 1] + lexf) + HALF, filt),
-                 tap(l1, (m1[..., 0] + lexf) + HALF, (m1[..., 1] + lexf) + HALF, filt)) for m0, m1 in maps]
+    return C.plates(layer0, layer1, maps, lex, _tap_under(filt))
 
 
 def layers_on_maps(layer0, layer1, maps, color_fa, color_from, filt, lex=0, taps=None):
     """vm_frame_render_viewport_filtered_layers on the maps of viewport_ref.sample_maps, unclamped: float32 (out_h, out_w) or
     (out_h, out_w, C) as the layers are.  lex: where the image begins in the layers' grid (0 tight; the frame's ex for what
     vm_frame_download_layers_ext hands out).  taps: layer_taps of the same arguments"""
-    out = _blended_mean(layer_taps(layer0, layer1, maps, filt, lex) if taps is None else taps, color_fa, color_from)
-    return out[..., 0] if np.asarray(layer0).ndim == 2 else out
+    taps = layer_taps(layer0, layer1, maps, filt, lex) if taps is None else taps
+    return C.like(C.blended_mean(taps, maps, color_fa, color_from), layer0)
 
 
 def overshoot_case(w, h):

@@ -12,14 +12,14 @@ boundary extension (CPoissonExt::prepare + poissonExtend, PoissonExt.cpp:49-362)
                g(a, b) = value_a - value_b where both are type 2 and valid, else 0
     solution   A x = b per channel (float64 here: conjugate gradients to 1e-12, or dense); every type > 0 cell takes it
 
-and the render tail on extended layers: warp_ref's tap on the (ch, cw, C) canvas at (map + ex) + 0.5.
+and the render tail on extended layers: the tail of tests/chain_ref.py on the (ch, cw, C) canvas at (map + ex) + 0.5.
 tests/test_layer_ext_ref.py pins the statement without a GPU, tests/test_gpu_layer_ext.py holds the kernels to it."""
 import numpy as np
 
-import warp_ref
+import chain_ref as C
 
 f32 = np.float32
-HALF, ONE = f32(0.5), f32(1)
+ONE = f32(1)
 AL = f32(0.8)
 ROUNDS = 20
 
@@ -208,30 +208,13 @@ def extend(own, other, v, ex, side):
     return np.where((typ > 0)[..., None], x, filled.astype(np.float64)), typ
 
 
-def as3(layer):
-    a = np.asarray(layer, dtype=f32)
-    return a[..., None] if a.ndim == 2 else a
-
-
 def render_layers(ext0, ext1, ex, map0, map1, color_fa, color_from):
-    """the render tail on extended layers (vm_render_layers on an extended frame): warp_ref.tap on the (ch, cw, C)
+    """the render tail on extended layers (vm_render_layers on an extended frame): chain_ref.tap on the (ch, cw, C)
     canvases at (map + ex) + 0.5 -- the renderer's own + ex + 0.5f --, blended.  float32 of the maps' grid x C"""
-    e0, e1, exf = as3(ext0), as3(ext1), f32(ex)
-    with np.errstate(all="ignore"):
-        c0 = warp_ref.tap(e0, (map0[..., 0] + exf) + HALF, (map0[..., 1] + exf) + HALF)
-        c1 = warp_ref.tap(e1, (map1[..., 0] + exf) + HALF, (map1[..., 1] + exf) + HALF)
-        out = warp_ref.blend(c0, c1, color_fa, color_from)
-    assert out.dtype == f32
-    return out
+    return C.blended(ext0, ext1, map0, map1, color_fa, color_from, ex)
 
 
 def layers_on_maps(ext0, ext1, ex, maps, color_fa, color_from):
-    """the sample loops' tail on extended layers (the shutter and viewport families): render_layers for every (map0, map1)
-    of `maps`, summed in float32 in order from +0 and divided by (float)N -- shutter_ref's mean"""
-    with np.errstate(all="ignore"):
-        acc = np.zeros(maps[0][0].shape[:2] + as3(ext0).shape[2:], f32)
-        for m0, m1 in maps:
-            acc = acc + render_layers(ext0, ext1, ex, m0, m1, color_fa, color_from)
-        out = acc / f32(len(maps))
-    assert out.dtype == f32
-    return out
+    """the sample loops' tail on extended layers (the shutter and viewport families): the plates of every (map0, map1) of
+    `maps`, blended, summed in float32 in order from +0 and divided by (float)N -- chain_ref's mean"""
+    return C.sampled_mean(ext0, ext1, maps, color_fa, color_from, ex)

@@ -1,6 +1,6 @@
 """The float32 numpy statement of the multiband render calls (include/vmorph.h): what the kernels of
 videomorphing_amd/csrc/vm_multiband.hip compute.  The two warped plates c0, c1 -- exactly what the render calls' tails form
-before they blend: warp_ref.tap of the canvases' RGB or of the layers at the chain's two sampling positions -- and the
+before they blend: chain_ref.plates of the canvases' RGB or of the layers at the chain's two sampling positions -- and the
 colour weight A (color_fa everywhere, or the plane k of transit_ref.transition_maps) are split into L + 1 frequency bands
 by the 5-tap binomial reduce and expand of Burt and Adelson (1983); band l is blended under the weight plane of level l,
 sharpened about 0.5 by sharp[l] >= 1, and the bands are summed from the coarsest up.  Every scalar is a float32, every
@@ -9,6 +9,7 @@ loses).  tests/test_multiband_ref.py pins the statement without a GPU; tests/tes
 bit for bit, level by level."""
 import numpy as np
 
+import chain_ref as C
 import transit_ref
 import warp_ref
 
@@ -115,35 +116,16 @@ def multiband(c0, c1, A, sharp):
     return stages(c0, c1, A, sharp)[OUT, 0]
 
 
-def bytes_of(R):
-    """the RGB8 tail: (uint8)((double)fminf(fmaxf(R, 0), 255) + 0.5), truncated; a NaN becomes 0"""
-    with np.errstate(all="ignore"):
-        clamped = np.fmin(np.fmax(R, ZERO), f32(255))
-        assert clamped.dtype == f32
-        return (clamped.astype(np.float64) + 0.5).astype(np.uint8)
-
-
 # ---- the plates: what the render calls' tails compute before they blend
 def canvas_plates(ext0, ext1, ex, map0, map1):
-    """warp_ref.tap of the extended canvases' RGB at (map + ex) + 0.5: two (h, w, 3) float32"""
-    exf = f32(ex)
-    with np.errstate(all="ignore"):
-        c0 = warp_ref.tap(ext0[..., :3].astype(f32), (map0[..., 0] + exf) + HALF, (map0[..., 1] + exf) + HALF)
-        c1 = warp_ref.tap(ext1[..., :3].astype(f32), (map1[..., 0] + exf) + HALF, (map1[..., 1] + exf) + HALF)
-    return c0, c1
+    """chain_ref.tap of the extended canvases' RGB at (map + ex) + 0.5: two (h, w, 3) float32"""
+    return C.plates(ext0[..., :3], ext1[..., :3], [(map0, map1)], ex)[0]
 
 
 def layer_plates(layer0, layer1, map0, map1, lex=0):
     """the layers -- tight (lex = 0) or extended, the image at (lex, lex) -- sampled as warp_ref.render_layers samples
     them: two (h, w, C) float32"""
-    l0, l1 = np.asarray(layer0, dtype=f32), np.asarray(layer1, dtype=f32)
-    if l0.ndim == 2:
-        l0, l1 = l0[..., None], l1[..., None]
-    lexf = f32(lex)
-    with np.errstate(all="ignore"):
-        c0 = warp_ref.tap(l0, (map0[..., 0] + lexf) + HALF, (map0[..., 1] + lexf) + HALF)
-        c1 = warp_ref.tap(l1, (map1[..., 0] + lexf) + HALF, (map1[..., 1] + lexf) + HALF)
-    return c0, c1
+    return C.plates(layer0, layer1, [(map0, map1)], lex)[0]
 
 
 def uniform_inputs(v, u, color_fa, geo_fa):
@@ -159,13 +141,13 @@ def scheduled_inputs(v, u, sched_geo, sched_color, t, ease):
 
 
 def render_bytes(ext0, ext1, ex, maps, sharp):
-    """the RGB8 call on maps = (map0, map1, A) -> (h, w, 3) uint8"""
+    """the RGB8 call on maps = (map0, map1, A) -> (h, w, 3) uint8: (uint8)((double)fminf(fmaxf(R, 0), 255) + 0.5),
+    truncated; a NaN becomes 0"""
     c0, c1 = canvas_plates(ext0, ext1, ex, maps[0], maps[1])
-    return bytes_of(multiband(c0, c1, maps[2], sharp))
+    return C.bytes_of(multiband(c0, c1, maps[2], sharp), True)
 
 
 def render_layers(layer0, layer1, maps, sharp, lex=0):
     """the layer call on maps = (map0, map1, A): float32 of the layers' shape (the extended layers': of the image's)"""
     c0, c1 = layer_plates(layer0, layer1, maps[0], maps[1], lex)
-    R = multiband(c0, c1, maps[2], sharp)
-    return R[..., 0] if np.asarray(layer0).ndim == 2 else R
+    return C.like(multiband(c0, c1, maps[2], sharp), layer0)

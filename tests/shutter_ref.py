@@ -1,6 +1,6 @@
 """The float32 numpy statement of what videomorphing_amd/csrc/vm_shutter.hip computes: the compositor's chain
-(tests/warp_ref.py: sampling_maps, tap, blend) walked at the N sample times of a shutter, the samples' colours summed in
-float32 in sample order from +0 and divided by (float)N once.  For s = 0 .. N - 1:
+(tests/warp_ref.py: sampling_maps) walked at the N sample times of a shutter, the samples' colours summed in float32 in
+sample order from +0 and divided by (float)N once (the tail of tests/chain_ref.py).  For s = 0 .. N - 1:
 
     f   = ((float)s + 0.5f) / (float)N
     t_s = fminf(fmaxf(geo_open + (geo_close - geo_open) * f, 0), 1)
@@ -13,6 +13,7 @@ without contraction); numpy's float32 division is IEEE, as the kernels' is.  tes
 statement to warp_ref without a GPU, tests/test_gpu_shutter.py holds the kernels to it bit for bit."""
 import numpy as np
 
+import chain_ref as C
 import warp_ref
 
 f32 = np.float32
@@ -36,60 +37,20 @@ def sample_maps(v, u, geo_open, geo_close, n):
     return [warp_ref.sampling_maps(v, u, t)[:2] for t in sample_times(geo_open, geo_close, n)]
 
 
-def founded(maps):
-    """where every sample's two positions are finite: where an RGB8 byte is defined"""
-    ok = True
-    for m0, m1 in maps:
-        ok = ok & np.isfinite(m0).all(-1) & np.isfinite(m1).all(-1)
-    return ok
-
-
-def _mean(colours, n):
-    with np.errstate(all="ignore"):
-        acc = np.zeros(colours[0].shape, f32)
-        for c in colours:
-            acc = acc + c
-        out = acc / f32(n)
-    assert out.dtype == f32
-    return out
-
-
 def canvas_mean(ext0, ext1, ex, maps, color_fa, color_from):
     """acc / (float)N of the canvas taps on the samples' maps: (h, w, 3) float32"""
-    e0, e1, exf = ext0[..., :3].astype(f32), ext1[..., :3].astype(f32), f32(ex)
-    colours = []
-    with np.errstate(all="ignore"):
-        for m0, m1 in maps:
-            c0 = warp_ref.tap(e0, (m0[..., 0] + exf) + HALF, (m0[..., 1] + exf) + HALF)
-            c1 = warp_ref.tap(e1, (m1[..., 0] + exf) + HALF, (m1[..., 1] + exf) + HALF)
-            colours.append(warp_ref.blend(c0, c1, color_fa, color_from))
-    return _mean(colours, len(maps))
-
-
-def bytes_of(mean):
-    """the statement's tail: + 0.5 in double, truncation"""
-    with np.errstate(all="ignore"):
-        return (mean.astype(np.float64) + 0.5).astype(np.uint8)
+    return C.sampled_mean(ext0[..., :3], ext1[..., :3], maps, color_fa, color_from, ex)
 
 
 def layers_on_maps(layer0, layer1, maps, color_fa, color_from):
-    """the layer result on given sample maps (a test that needs several channel counts walks the chain once)"""
-    l0, l1 = np.asarray(layer0, dtype=f32), np.asarray(layer1, dtype=f32)
-    shape = l0.shape
-    if l0.ndim == 2:
-        l0, l1 = l0[..., None], l1[..., None]
-    colours = []
-    with np.errstate(all="ignore"):
-        for m0, m1 in maps:
-            c0 = warp_ref.tap(l0, m0[..., 0] + HALF, m0[..., 1] + HALF)
-            c1 = warp_ref.tap(l1, m1[..., 0] + HALF, m1[..., 1] + HALF)
-            colours.append(warp_ref.blend(c0, c1, color_fa, color_from))
-    return _mean(colours, len(maps)).reshape(shape)
+    """the layer result on given sample maps, whatever their grid (a test that needs several channel counts walks the
+    chain once): float32 (h, w) or (h, w, C) as the layers are"""
+    return C.like(C.sampled_mean(layer0, layer1, maps, color_fa, color_from), layer0)
 
 
 def render_shutter_bytes(ext0, ext1, ex, v, u, color_fa, geo_open, geo_close, n, color_from):
-    """vm_render_shutter: (h, w, 3) uint8 (defined where founded(sample_maps(...)) holds)"""
-    return bytes_of(canvas_mean(ext0, ext1, ex, sample_maps(v, u, geo_open, geo_close, n), color_fa, color_from))
+    """vm_render_shutter: (h, w, 3) uint8 (defined where chain_ref.founded(sample_maps(...)) holds)"""
+    return C.bytes_of(canvas_mean(ext0, ext1, ex, sample_maps(v, u, geo_open, geo_close, n), color_fa, color_from))
 
 
 def render_shutter_layers(layer0, layer1, v, u, color_fa, geo_open, geo_close, n, color_from):

@@ -14,6 +14,7 @@ import textwrap
 import numpy as np
 import pytest
 
+import chain_ref
 import multiband_ref as MB
 import transit_ref
 from render_cases import field as _field, frame as _frame, hashes_under_render_mode, layers as _layers, rgb_pair, same_bits as _same
@@ -109,7 +110,7 @@ def test_every_level_of_every_stage(gpu_ctx, w, h, L, layer_ch):
     if layer_ch:
         assert _same(out, want[MB.OUT, 0])
     else:
-        assert np.array_equal(out, MB.bytes_of(want[MB.OUT, 0]))
+        assert np.array_equal(out, chain_ref.bytes_of(want[MB.OUT, 0], True))
         with pytest.raises(capi.VmError) as e:
             fr.multiband_level(capi.MB_OUT, 0)
         assert e.value.code == capi.VM_E_INVALID
@@ -160,7 +161,7 @@ def test_the_plate_as_a_float_layer_gives_the_rgb8_calls_bytes(gpu_ctx):
     rgb0, rgb1 = rgb_pair(w, h)
     fr.upload_layers(rgb0.astype(f32), rgb1.astype(f32))
     for bands in (Bands.linear(L), Bands.sharpen(L, 4)):
-        assert np.array_equal(MB.bytes_of(fr.render_multiband_layers(bands, 0.37, GEO)), fr.render_multiband(bands, 0.37, GEO))
+        assert np.array_equal(chain_ref.bytes_of(fr.render_multiband_layers(bands, 0.37, GEO), True), fr.render_multiband(bands, 0.37, GEO))
     fr.close()
 
 

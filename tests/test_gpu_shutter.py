@@ -22,6 +22,7 @@ import textwrap
 import numpy as np
 import pytest
 
+import chain_ref
 import shutter_ref
 from render_cases import field as _field, frame as _frame, hashes_under_render_mode, layers as _layers, rgb_pair as _rgb, same_bits as _same
 import warp_ref
@@ -86,12 +87,12 @@ def test_shutter_calls_equal_the_statement(gpu_ctx, w, h, ex, kind, with_path):
     lay = {c: (_layers(w, h, c, 10 + c), _layers(w, h, c, 20 + c)) for c in (1, 3, 4)}
     for n, (o, c) in EVERY:
         maps = _ref_maps(w, h, kind, with_path, o, c, n)
-        ok = shutter_ref.founded(maps)
+        ok = chain_ref.founded(maps)
         assert kind == "nan" or ok.all()
         cfs = (0, 1, 2) if (n, (o, c)) == EVERY[0] else (1,)
         for cf in cfs:
             got = fr.render_shutter(0.3, o, c, n, cf)
-            want = shutter_ref.bytes_of(shutter_ref.canvas_mean(e0, e1, ex, maps, 0.3, cf))
+            want = chain_ref.bytes_of(shutter_ref.canvas_mean(e0, e1, ex, maps, 0.3, cf))
             assert np.array_equal(got[ok], want[ok]), (n, o, c, cf, int((got != want)[ok].sum()))
         for ch, (l0, l1) in lay.items():
             fr.upload_layers(l0, l1)
@@ -132,7 +133,7 @@ def test_rgb_as_float_layers_rounds_to_the_shutters_bytes(gpu_ctx, w, h, ex, kin
         for cf in ((0, 1, 2) if n == 5 else (1,)):
             lay = fr.render_shutter_layers(0.3, o, c, n, cf)
             assert lay.shape == (h, w, 3) and lay.dtype == np.float32
-            out, ref = shutter_ref.bytes_of(lay), fr.render_shutter(0.3, o, c, n, cf)
+            out, ref = chain_ref.bytes_of(lay), fr.render_shutter(0.3, o, c, n, cf)
             assert np.array_equal(out, ref), (n, o, c, cf, int((out != ref).sum()))
     fr.close()
 

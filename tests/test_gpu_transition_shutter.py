@@ -24,9 +24,9 @@ import textwrap
 import numpy as np
 import pytest
 
+import chain_ref
 import transit_ref
 import transit_shutter_ref as TS
-import shutter_ref
 from render_cases import field as _field, frame, hashes_under_render_mode, layers as _layers, rgb_pair as _rgb, same_bits as _same
 from videomorphing_amd import capi, transition
 
@@ -141,7 +141,7 @@ def _hold_to_the_statement(fr, w, h, ex, kind, with_path, which, stated, floors)
     compared = 0
     for n, (o, c), ease in stated:
         maps = _ref_maps(w, h, kind, with_path, which, ease, o, c, n)
-        ok = TS.founded(maps)
+        ok = chain_ref.founded(maps)
         share = float(ok.mean())
         compared += int(ok.sum())
         print("founded", w, h, kind, with_path, which, n, o, c, ease, share)
@@ -150,7 +150,7 @@ def _hold_to_the_statement(fr, w, h, ex, kind, with_path, which, stated, floors)
         cfs = (0, 1, 2) if (n, (o, c), ease) == stated[0] else (1,)
         for cf in cfs:
             got = fr.render_transition_shutter(o, c, n, T_COLOR, ease, cf)
-            want = shutter_ref.bytes_of(TS.canvas_mean(e0, e1, ex, maps, cf))
+            want = chain_ref.bytes_of(TS.canvas_mean(e0, e1, ex, maps, cf))
             assert np.array_equal(got[ok], want[ok]), (n, o, c, ease, cf, int((got != want)[ok].sum()), int(ok.sum()))
         for ch, (l0, l1) in lay.items():
             fr.upload_layers(l0, l1)

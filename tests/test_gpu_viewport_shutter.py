@@ -20,6 +20,7 @@ import textwrap
 import numpy as np
 import pytest
 
+import chain_ref
 import transit_ref
 import viewport_ref
 import vshutter_ref as VS
@@ -109,7 +110,7 @@ def test_calls_equal_the_statement(gpu_ctx, w, h, ex, name, kind, with_path):
     chans = (1, 2, 3, 4) if at < 2 else ((at % 4) + 1,)
     lay = {c: (_layers(w, h, c, 10 + c), _layers(w, h, c, 20 + c)) for c in chans}
     for k, (family, n, vp, (o, c), ease, maps) in enumerate(every):
-        ok = VS.founded(maps)
+        ok = chain_ref.founded(maps)
         print("founded", w, h, name, kind, with_path, family, n, (vp.nx, vp.ny), o, c, float(ok.mean()))
         assert kind == "nan" or ok.all(), (family, n, o, c)
         cfs = (0, 1, 2) if k < 2 else (1,)

@@ -8,6 +8,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import chain_ref
 import multiband_ref as MB
 import transit_ref
 import warp_ref
@@ -70,7 +71,7 @@ def test_a_weight_of_zero_or_one_returns_the_plate(w, h, L):
 @shapes
 def test_the_table_of_ones_stays_beside_the_plain_blend(w, h, L):
     """the table of ones under a uniform weight a: every band is blended with the same a, so the sum is the plain blend to
-    rounding.  Plates from warp_ref's maps on random canvases.  The statement's prototype deviated from warp_ref.blend by at
+    rounding.  Plates from warp_ref's maps on random canvases.  The statement's prototype deviated from chain_ref.blend by at
     most 4.6e-5 over the six shapes and a in {0.3, 0.5}; the bound is 2e-4, that figure with a fourfold margin for other
     shapes and inputs (on the canvases of this test the deviation is at most 6.1e-5, at 150 x 97).  After the rounding the
     bytes are never more than one level apart."""
@@ -82,12 +83,12 @@ def test_the_table_of_ones_stays_beside_the_plain_blend(w, h, L):
     c0, c1 = MB.canvas_plates(e0, e1, ex, map0, map1)
     for a in (0.3, 0.5):
         got = MB.multiband(c0, c1, np.full((h, w), f32(a)), [1.0] * (L + 1))
-        want = warp_ref.blend(c0, c1, a, 1)
+        want = chain_ref.blend(c0, c1, a, 1)
         worst = float(np.abs(got.astype(np.float64) - want.astype(np.float64)).max())
         print("w %d h %d L %d a %g: deviation %.3g" % (w, h, L, a, worst))
         assert worst <= 2e-4, (a, worst)
         plain = (want.astype(np.float64) + 0.5).astype(np.uint8)
-        assert np.abs(MB.bytes_of(got).astype(int) - plain.astype(int)).max() <= 1
+        assert np.abs(chain_ref.bytes_of(got, True).astype(int) - plain.astype(int)).max() <= 1
 
 
 def test_a_hard_seam_reaches_no_further_than_its_levels():
@@ -101,12 +102,12 @@ def test_a_hard_seam_reaches_no_further_than_its_levels():
     c0, c1 = _integer_plates(w, h, 5)
     flat0, flat1 = np.full((h, w, 1), f32(40)), np.full((h, w, 1), f32(200))
     for sharp in _tables(L):
-        got = MB.bytes_of(MB.multiband(c0, c1, A, sharp))
+        got = chain_ref.bytes_of(MB.multiband(c0, c1, A, sharp), True)
         assert np.array_equal(got[:, :seam - reach + 1], c0[:, :seam - reach + 1].astype(np.uint8)), sharp
         assert np.array_equal(got[:, seam + reach - 1:], c1[:, seam + reach - 1:].astype(np.uint8)), sharp
         differs = np.nonzero((got != np.where(A[..., None] > 0, c1, c0).astype(np.uint8)).any(axis=(0, 2)))[0]
         print("sharp %r: the seam reaches columns %d..%d" % (sharp, differs.min(), differs.max()))
-        row = MB.bytes_of(MB.multiband(flat0, flat1, A, sharp))[h // 2, :, 0].astype(int)
+        row = chain_ref.bytes_of(MB.multiband(flat0, flat1, A, sharp), True)[h // 2, :, 0].astype(int)
         assert row[0] == 40 and row[-1] == 200 and np.all(np.diff(row) >= 0), (sharp, row)
 
 
@@ -132,7 +133,7 @@ def test_a_nan_weight_counts_as_zero_and_a_nan_pixel_becomes_byte_zero():
     R = MB.multiband(c0, c1, A, [1.0, 1.0, 1.0])
     assert np.isfinite(R).all()                     # fmaxf / fminf: the NaN loses on every band
     R[0, 0, 0], R[0, 0, 1], R[0, 0, 2] = np.nan, -3.0, 300.0
-    assert MB.bytes_of(R)[0, 0].tolist() == [0, 0, 255]
+    assert chain_ref.bytes_of(R, True)[0, 0].tolist() == [0, 0, 255]
 
 
 def test_the_bands_helpers():

@@ -6,6 +6,7 @@ cases are what include/vmorph.h says; a rate tap of a constant plane is that con
 import numpy as np
 import pytest
 
+import chain_ref
 import transit_ref as T
 from render_cases import field as _field
 import warp_ref as R
@@ -74,7 +75,7 @@ def test_ramp_corner_cases():
 
 
 def test_rate_tap_of_a_constant_plane_is_the_constant():
-    """the lerp form returns a constant plane's value exactly; the four-weight form of warp_ref.tap does not"""
+    """the lerp form returns a constant plane's value exactly; the four-weight form of chain_ref.tap does not"""
     rng = np.random.RandomState(7)
     w, h = 37, 23
     x = (rng.rand(4000) * (w + 8) - 4).astype(f32)
@@ -82,13 +83,13 @@ def test_rate_tap_of_a_constant_plane_is_the_constant():
     four_weights_differ = False
     for c in (0.2, 0.35, 1.0 / 3.0, 0.8, 1.0, 0.0):
         plane = np.full((h, w), c, f32)
-        assert np.all(T.tapr(plane, x, y).view(np.uint32) == f32(c).view(np.uint32)), c
-        four_weights_differ |= bool(np.any(R.tap(plane[..., None], x, y)[..., 0] != f32(c)))
+        assert np.all(chain_ref.tapr(plane, x, y).view(np.uint32) == f32(c).view(np.uint32)), c
+        four_weights_differ |= bool(np.any(chain_ref.tap(plane[..., None], x, y)[..., 0] != f32(c)))
     assert four_weights_differ
     # and between two texels it is the lerp
     plane = np.zeros((2, 2), f32)
     plane[:, 1] = 1
-    assert T.tapr(plane, np.array([1.25], f32), np.array([1.0], f32))[0] == f32(0.75)
+    assert chain_ref.tapr(plane, np.array([1.25], f32), np.array([1.0], f32))[0] == f32(0.75)
 
 
 def test_schedule_builders():

@@ -9,6 +9,7 @@ import functools
 import numpy as np
 import pytest
 
+import chain_ref
 import shutter_ref
 from render_cases import same_bits as _same
 import transit_ref
@@ -50,10 +51,10 @@ def test_one_sample_is_the_transition_statement(w, h, ex, kind, with_path, ease)
         m0, m1, _, _, rates = transit_ref.transition_maps(v, u, sg, sc, t, ease)
         maps = TS.sample_maps(v, u, sg, sc, t, t, 1, t, ease)
         assert _same(maps[0][0], m0) and _same(maps[0][1], m1) and _same(maps[0][2], rates[..., 1]), t
-        ok = TS.founded(maps)
+        ok = chain_ref.founded(maps)
         assert kind == "nan" or ok.all()
         for cf in (0, 1, 2):
-            got = shutter_ref.bytes_of(TS.canvas_mean(e0, e1, ex, maps, cf))
+            got = chain_ref.bytes_of(TS.canvas_mean(e0, e1, ex, maps, cf))
             want = transit_ref.render_bytes(e0, e1, ex, m0, m1, rates[..., 1], cf)
             assert np.array_equal(got[ok], want[ok]), (t, cf)
             for a, b in ((l0, l1), (l0[..., 0], l1[..., 1])):
@@ -80,11 +81,11 @@ def test_the_uniform_schedule_is_the_shutter_statement(w, h, ex, kind, with_path
                 # (a position that is no number has no fractions, and its k is none either)
                 at = np.isfinite(g0).all(-1) & np.isfinite(g1).all(-1)
                 assert np.all(k[at].view(np.uint32) == f32(tc).view(np.uint32)) and np.all(np.isnan(k[~at]) | (k[~at] == f32(tc)))
-            ok = TS.founded(maps)
+            ok = chain_ref.founded(maps)
             assert kind == "nan" or ok.all()
             for cf in (0, 1, 2):
-                got = shutter_ref.bytes_of(TS.canvas_mean(e0, e1, ex, maps, cf))
-                ref = shutter_ref.bytes_of(shutter_ref.canvas_mean(e0, e1, ex, want, tc, cf))
+                got = chain_ref.bytes_of(TS.canvas_mean(e0, e1, ex, maps, cf))
+                ref = chain_ref.bytes_of(shutter_ref.canvas_mean(e0, e1, ex, want, tc, cf))
                 assert np.array_equal(got[ok], ref[ok]), (n, o, c, tc, cf)
                 got = TS.layers_on_maps(l0, l1, maps, cf)
                 assert _same(got, shutter_ref.layers_on_maps(l0, l1, want, tc, cf)), (n, o, c, tc, cf)

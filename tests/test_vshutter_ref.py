@@ -4,6 +4,7 @@ the schedule (0, 1) with the linear ease the scheduled family is the uniform one
 import numpy as np
 import pytest
 
+import chain_ref
 import shutter_ref
 from render_cases import field as _field, same_bits as _same
 import transit_ref
@@ -54,7 +55,7 @@ def test_one_time_sample_is_the_viewport_statement(w, h, ex, kind, with_path):
             maps = VS.uniform_maps(v, u, g, g, 1, vp.astuple())
             want = viewport_ref.sample_maps(v, u, g, vp.astuple())
             assert _same_maps(maps, want), (vp, g)
-            ok = VS.founded(maps)
+            ok = chain_ref.founded(maps)
             for cf in (0, 1, 2):
                 a = VS.bytes_on_maps(e0, e1, ex, maps, cf, 0.3)
                 b = viewport_ref.render_viewport_bytes(e0, e1, ex, v, u, 0.3, g, cf, vp.astuple(), want)
@@ -76,7 +77,7 @@ def test_the_identity_viewport_is_the_shutter_statements(w, h, ex, kind, with_pa
             maps = VS.uniform_maps(v, u, o, cl, n, ident)
             want = shutter_ref.sample_maps(v, u, o, cl, n)
             assert _same_maps(maps, want), (n, o, cl)
-            ok = VS.founded(maps)
+            ok = chain_ref.founded(maps)
             a = VS.render_viewport_shutter_bytes(e0, e1, ex, v, u, 0.3, o, cl, n, 1, ident)
             assert np.array_equal(a[ok], shutter_ref.render_shutter_bytes(e0, e1, ex, v, u, 0.3, o, cl, n, 1)[ok])
             assert _same(VS.layers_on_maps(l0, l1, maps, 1, 0.3), shutter_ref.layers_on_maps(l0, l1, want, 0.3, 1))
@@ -84,9 +85,9 @@ def test_the_identity_viewport_is_the_shutter_statements(w, h, ex, kind, with_pa
                 maps = VS.scheduled_maps(v, u, sg, sc, o, cl, n, 0.45, ease, ident)
                 want = TS.sample_maps(v, u, sg, sc, o, cl, n, 0.45, ease)
                 assert _same_maps(maps, want), (n, o, cl, ease)
-                ok = VS.founded(maps)
+                ok = chain_ref.founded(maps)
                 a = VS.bytes_on_maps(e0, e1, ex, maps, 1)
-                assert np.array_equal(a[ok], shutter_ref.bytes_of(TS.canvas_mean(e0, e1, ex, want, 1))[ok])
+                assert np.array_equal(a[ok], chain_ref.bytes_of(TS.canvas_mean(e0, e1, ex, want, 1))[ok])
                 assert _same(VS.layers_on_maps(l0, l1, maps, 1), TS.layers_on_maps(l0, l1, want, 1))
 
 
@@ -110,7 +111,7 @@ def test_the_uniform_schedule_is_the_uniform_family(w, h, ex, kind, with_path):
                     there = np.isfinite(m0).all(-1) & np.isfinite(m1).all(-1)
                     assert kind == "nan" or there.all()
                     assert np.array_equal(k[there], np.full(int(there.sum()), f32(tc)))
-                ok = VS.founded(want)
+                ok = chain_ref.founded(want)
                 for cf in (0, 1, 2):
                     assert np.array_equal(VS.bytes_on_maps(e0, e1, ex, got, cf)[ok], VS.bytes_on_maps(e0, e1, ex, want, cf, tc)[ok])
                     assert _same(VS.layers_on_maps(l0, l1, got, cf), VS.layers_on_maps(l0, l1, want, cf, tc))

@@ -9,15 +9,15 @@ output pixel (X, Y) and s = j * nx + i:
     (p, V)_s = the chain from q                    c_s = blend(tap(side 0 at p - V), tap(side 1 at p + V))
     acc = acc + c_s
 
-The chain from q is stated here, in tests/warp_ref.py's expressions (sampling_maps there is the case q = the pixel);
-the taps, the blend, the mean and the rounding to bytes are warp_ref's and shutter_ref's own.  Every scalar is a float32
-and every expression stands in the kernels' order (they are built without contraction).  tests/test_viewport_ref.py pins
+The chain from q is chain_ref.walk (warp_ref.sampling_maps is the case q = the pixel); the taps, the blend, the mean and
+the rounding to bytes are chain_ref's tail, as shutter_ref composes it.  Every scalar is a float32 and every expression
+stands in the kernels' order (they are built without contraction).  tests/test_viewport_ref.py pins
 the statement to warp_ref and the oracle without a GPU, tests/test_gpu_viewport.py holds the kernels to it bit for bit."""
 import numpy as np
 
+import chain_ref as C
 import shutter_ref
-import warp_ref
-from warp_ref import ALPHA, HALF, ITERS, ONE, f32, tap
+from chain_ref import HALF, f32
 
 MAX_SAMPLES = 64
 NAN, INF = float("nan"), float("inf")
@@ -65,24 +65,7 @@ def sample_points(vp):
 def landing(v, u, geo_fa, qx, qy):
     """(map0, map1) of the chain started from the points (qx, qy): warp_ref.sampling_maps with q in the pixel's place (u
     None: the no-path form)"""
-    v = np.ascontiguousarray(v, dtype=f32)
-    h, w = v.shape[:2]
-    u = np.zeros((h, w, 2), f32) if u is None else np.ascontiguousarray(u, dtype=f32)
-    geo = f32(geo_fa)
-    with np.errstate(all="ignore"):
-        s1 = f32(2) * geo - ONE
-        s2 = f32(4) * geo - f32(4) * geo * geo
-        px, py = qx.copy(), qy.copy()
-        V, U = tap(v, px + HALF, py + HALF), tap(u, px + HALF, py + HALF)
-        for _ in range(ITERS):
-            px = (qx - s1 * V[..., 0]) - s2 * U[..., 0]
-            py = (qy - s1 * V[..., 1]) - s2 * U[..., 1]
-            V = ALPHA * tap(v, px + HALF, py + HALF) + (ONE - ALPHA) * V
-            U = ALPHA * tap(u, px + HALF, py + HALF) + (ONE - ALPHA) * U
-        map0 = np.stack([px - V[..., 0], py - V[..., 1]], -1)
-        map1 = np.stack([px + V[..., 0], py + V[..., 1]], -1)
-    assert map0.dtype == f32 and map1.dtype == f32
-    return map0, map1
+    return C.landing(C.walk(v, u, qx, qy, f32(geo_fa)))
 
 
 def sample_maps(v, u, geo_fa, vp):
@@ -90,32 +73,16 @@ def sample_maps(v, u, geo_fa, vp):
     return [landing(v, u, geo_fa, qx, qy) for qx, qy in sample_points(vp)]
 
 
-founded = shutter_ref.founded
+layers_on_maps = shutter_ref.layers_on_maps         # the same tail: its result takes the maps' grid and the layers' form
 
 
 def render_viewport_bytes(ext0, ext1, ex, v, u, color_fa, geo_fa, color_from, vp, maps=None):
-    """vm_render_viewport: (out_h, out_w, 3) uint8 (defined where founded(sample_maps(...)) holds)"""
+    """vm_render_viewport: (out_h, out_w, 3) uint8 (defined where chain_ref.founded(sample_maps(...)) holds)"""
     maps = sample_maps(v, u, geo_fa, vp) if maps is None else maps
-    return shutter_ref.bytes_of(shutter_ref.canvas_mean(ext0, ext1, ex, maps, color_fa, color_from))
+    return C.bytes_of(shutter_ref.canvas_mean(ext0, ext1, ex, maps, color_fa, color_from))
 
 
 def render_viewport_layers(layer0, layer1, v, u, color_fa, geo_fa, color_from, vp, maps=None):
     """vm_render_viewport_layers: float32 (out_h, out_w) or (out_h, out_w, C) as the layers are"""
     maps = sample_maps(v, u, geo_fa, vp) if maps is None else maps
     return layers_on_maps(layer0, layer1, maps, color_fa, color_from)
-
-
-def layers_on_maps(layer0, layer1, maps, color_fa, color_from):
-    """shutter_ref.layers_on_maps on an output grid that is not the layers' (its result takes the layers' shape)"""
-    l0, l1 = np.asarray(layer0, dtype=f32), np.asarray(layer1, dtype=f32)
-    flat = l0.ndim == 2
-    if flat:
-        l0, l1 = l0[..., None], l1[..., None]
-    colours = []
-    with np.errstate(all="ignore"):
-        for m0, m1 in maps:
-            c0 = tap(l0, m0[..., 0] + HALF, m0[..., 1] + HALF)
-            c1 = tap(l1, m1[..., 0] + HALF, m1[..., 1] + HALF)
-            colours.append(warp_ref.blend(c0, c1, color_fa, color_from))
-    out = shutter_ref._mean(colours, len(maps))
-    return out[..., 0] if flat else out

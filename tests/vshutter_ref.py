@@ -1,8 +1,8 @@
 """The float32 numpy statement of what videomorphing_amd/csrc/vm_vshutter.hip computes (include/vmorph.h): a
 viewport of the morph over a shutter, uniformly and under a transition schedule.  Composed from the statements that
-exist -- viewport_ref.sample_points and landing, the shutters' sample_times, transit_ref.ramp and tapr, the taps, the
-blend and the mean of warp_ref and shutter_ref -- and one walk of the chain from q under rate planes.  T = samples,
-N = nx * ny; time sample tau = 0 .. T - 1 is the OUTER loop, sub-sample s = j * nx + i the INNER one, i fastest:
+exist -- viewport_ref.sample_points and landing, the shutters' sample_times, transit_shutter_ref's rate planes and its
+walk from q, and the tail of tests/chain_ref.py.  T = samples, N = nx * ny; time sample tau = 0 .. T - 1 is the OUTER
+loop, sub-sample s = j * nx + i the INNER one, i fastest:
 
     f_tau = ((float)tau + 0.5f) / (float)T
     q     = viewport_ref.sample_points' (qx, qy) for (X, Y, i, j)
@@ -17,42 +17,12 @@ N = nx * ny; time sample tau = 0 .. T - 1 is the OUTER loop, sub-sample s = j * 
 
 A viewport is viewport_ref's tuple.  tests/test_vshutter_ref.py pins the statement to viewport_ref, shutter_ref and
 transit_shutter_ref without a GPU; tests/test_gpu_viewport_shutter.py holds the kernels to it bit for bit."""
-import numpy as np
-
+import chain_ref as C
 import shutter_ref
-import transit_ref
 import transit_shutter_ref as TS
 import viewport_ref
-import warp_ref as R
 
-f32 = np.float32
-HALF, ONE = R.HALF, R.ONE
 MAX_CHAINS = 256        # samples * nx * ny of one call, at most (include/vmorph.h)
-
-
-def walk_from(v, u, G, K, qx, qy):
-    """(map0, map1, k) of the chain started from the points (qx, qy) under the (h, w) rate planes G and K:
-    transit_shutter_ref.walk with q in the pixel's place"""
-    v = np.ascontiguousarray(v, dtype=f32)
-    h, w = v.shape[:2]
-    u = np.zeros((h, w, 2), f32) if u is None else np.ascontiguousarray(u, dtype=f32)
-    with np.errstate(all="ignore"):
-        px, py = qx.copy(), qy.copy()
-        V, U = R.tap(v, px + HALF, py + HALF), R.tap(u, px + HALF, py + HALF)
-        g = transit_ref.tapr(G, px + HALF, py + HALF)
-        for _ in range(R.ITERS):
-            s1 = f32(2) * g - ONE
-            s2 = f32(4) * g - f32(4) * g * g
-            px = (qx - s1 * V[..., 0]) - s2 * U[..., 0]
-            py = (qy - s1 * V[..., 1]) - s2 * U[..., 1]
-            V = R.ALPHA * R.tap(v, px + HALF, py + HALF) + (ONE - R.ALPHA) * V
-            U = R.ALPHA * R.tap(u, px + HALF, py + HALF) + (ONE - R.ALPHA) * U
-            g = transit_ref.tapr(G, px + HALF, py + HALF)
-        k = transit_ref.tapr(K, px + HALF, py + HALF)
-        map0 = np.stack([px - V[..., 0], py - V[..., 1]], -1)
-        map1 = np.stack([px + V[..., 0], py + V[..., 1]], -1)
-    assert map0.dtype == f32 and map1.dtype == f32 and k.dtype == f32
-    return map0, map1, k
 
 
 def _count(n, vp):
@@ -69,76 +39,25 @@ def uniform_maps(v, u, geo_open, geo_close, n, vp):
 def scheduled_maps(v, u, sched_geo, sched_color, t_open, t_close, n, t_color, ease, vp):
     """[(map0, map1, k)] of the T * N samples in loop order (a schedule None: uniform (0, 1))"""
     _count(n, vp)
-    h, w = np.asarray(v).shape[:2]
-    sg, K = TS._plane(sched_geo, w, h), transit_ref.ramp(TS._plane(sched_color, w, h), t_color, ease)
+    Gs, K = TS.planes(v, sched_geo, sched_color, t_open, t_close, n, t_color, ease)
     pts = viewport_ref.sample_points(vp)
-    out = []
-    for t in TS.sample_times(t_open, t_close, n):
-        G = transit_ref.ramp(sg, t, ease)
-        out += [walk_from(v, u, G, K, qx, qy) for qx, qy in pts]
-    return out
-
-
-def founded(maps):
-    """where every sample's two positions are finite: where an RGB8 byte is defined (maps of either family)"""
-    return shutter_ref.founded([m[:2] for m in maps])
-
-
-def _fraction(m, color_fa):
-    """the colour fraction of one sample: its own k under a schedule, the call's color_fa otherwise"""
-    return m[2][..., None] if len(m) == 3 else color_fa
-
-
-def canvas_mean(ext0, ext1, ex, maps, color_from, color_fa=None):
-    """acc / (float)(T * N) of the canvas taps on the samples' maps: (out_h, out_w, 3) float32"""
-    e0, e1, exf = ext0[..., :3].astype(f32), ext1[..., :3].astype(f32), f32(ex)
-    colours = []
-    with np.errstate(all="ignore"):
-        for m in maps:
-            m0, m1 = m[:2]
-            c0 = R.tap(e0, (m0[..., 0] + exf) + HALF, (m0[..., 1] + exf) + HALF)
-            c1 = R.tap(e1, (m1[..., 0] + exf) + HALF, (m1[..., 1] + exf) + HALF)
-            colours.append(R.blend(c0, c1, _fraction(m, color_fa), color_from))
-    return shutter_ref._mean(colours, len(maps))
+    return [TS.walk(v, u, G, K, q) for G in Gs for q in pts]
 
 
 def bytes_on_maps(ext0, ext1, ex, maps, color_from, color_fa=None):
-    """the RGB8 result on given sample maps (defined where founded(maps) holds)"""
-    return shutter_ref.bytes_of(canvas_mean(ext0, ext1, ex, maps, color_from, color_fa))
+    """the RGB8 result on given sample maps of either family (defined where chain_ref.founded(maps) holds); a sample
+    under a schedule is blended with its own k, the others with color_fa"""
+    return C.bytes_of(shutter_ref.canvas_mean(ext0, ext1, ex, maps, color_fa, color_from))
 
 
 def layers_on_maps(layer0, layer1, maps, color_from, color_fa=None):
     """the layer result on given sample maps: float32 (out_h, out_w) or (out_h, out_w, C) as the layers are"""
-    l0, l1 = np.asarray(layer0, dtype=f32), np.asarray(layer1, dtype=f32)
-    flat = l0.ndim == 2
-    if flat:
-        l0, l1 = l0[..., None], l1[..., None]
-    colours = []
-    with np.errstate(all="ignore"):
-        for m in maps:
-            m0, m1 = m[:2]
-            c0 = R.tap(l0, m0[..., 0] + HALF, m0[..., 1] + HALF)
-            c1 = R.tap(l1, m1[..., 0] + HALF, m1[..., 1] + HALF)
-            colours.append(R.blend(c0, c1, _fraction(m, color_fa), color_from))
-    out = shutter_ref._mean(colours, len(maps))
-    return out[..., 0] if flat else out
+    return shutter_ref.layers_on_maps(layer0, layer1, maps, color_fa, color_from)
 
 
 def render_viewport_shutter_bytes(ext0, ext1, ex, v, u, color_fa, geo_open, geo_close, n, color_from, vp):
     """vm_render_viewport_shutter: (out_h, out_w, 3) uint8"""
     return bytes_on_maps(ext0, ext1, ex, uniform_maps(v, u, geo_open, geo_close, n, vp), color_from, color_fa)
-
-
-def render_viewport_shutter_layers(layer0, layer1, v, u, color_fa, geo_open, geo_close, n, color_from, vp):
-    """vm_render_viewport_shutter_layers"""
-    return layers_on_maps(layer0, layer1, uniform_maps(v, u, geo_open, geo_close, n, vp), color_from, color_fa)
-
-
-def render_viewport_transition_shutter_bytes(ext0, ext1, ex, v, u, sched_geo, sched_color, t_open, t_close, n, t_color, ease,
-                                             color_from, vp):
-    """vm_render_viewport_transition_shutter: (out_h, out_w, 3) uint8"""
-    maps = scheduled_maps(v, u, sched_geo, sched_color, t_open, t_close, n, t_color, ease, vp)
-    return bytes_on_maps(ext0, ext1, ex, maps, color_from)
 
 
 def render_viewport_transition_shutter_layers(layer0, layer1, v, u, sched_geo, sched_color, t_open, t_close, n, t_color, ease,
